@@ -2,8 +2,16 @@
 """bench.py -- BPR training triplets/s on synthetic MovieLens-10M-shaped data (BASELINE.json
 configs[1]: ~70k users x ~10k items, k = 128), one process per GPU.
 
-    python bench.py --gpus 1 --steps K --warmup W
+    python bench.py --gpus 1 --steps K --warmup W [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N --steps K --warmup W
+
+A plain run sets up, warms up, times the K steps and prints the line: the headline fields, the headline's `timed_region` and
+`roofline` (its counter bytes replayed from profiles/, nothing measured again), and at N > 1 `epoch_mode`, whose exchange wall
+the headline charges.  Everything else (the legs below: steady state, live counter traffic, CPU baselines, other batch sizes,
+optimisers, shapes and models) runs with --full only; --no-extras / --no-cpu-baseline / --no-live-traffic trim a --full run.
+--dump-outputs DIR: after the timed steps, rank 0 writes what the last timed call hands its caller -- the model tables U, V, b
+and the per-batch losses of that call -- as DIR/<name>.npy (float32; at most 64 MB in all: a table over its share is written as a
+fixed, seeded sample of rows, their row numbers in DIR/<name>_rows.npy as float64).  Same arguments, same inputs: every seed is fixed.
 
 A step = one pass of the hot path over one mini-batch: (u,i,j) draw + batch plan (K1) and the
 loss/gradient/RMSProp update (K2), reference semantics (single/bpr.py:136-147), default batch
@@ -11,7 +19,7 @@ loss/gradient/RMSProp update (K2), reference semantics (single/bpr.py:136-147), 
 before the timed region.  N > 1: users are sharded, item tables replicated, one RCCL all-reduce
 of the item-side state per epoch (every (limit//B)//N steps); weak scaling (K steps per rank).
 
-Prints ONE JSON line (rank 0).  Extra objects beside the contract fields:
+Prints ONE JSON line (rank 0).  Extra objects beside the contract fields (roofline's live `traffic` and every leg below it: --full):
   roofline        dominant kernel (K2) against the HBM roofline: algorithmic bytes per launch
                   (B x (48k+56) B, SURVEY.md §8d) / average launch duration from HIP events;
                   `traffic` = HBM bytes per batch of the headline step measured in THIS run: two rocprofv3 counter
@@ -238,6 +246,7 @@ class Loop:
         self.isync = tdist.ItemSync(eng, names) if world > 1 else None
         self.since = 0                   # batches since the last exchange
         self.exchanges = 0
+        self.last_loss = None            # what the last run_batches call returned: the per-batch losses of its last chunk (device)
 
     def run(self, n):
         done = 0
@@ -246,7 +255,7 @@ class Loop:
                 self.isync.begin()
             m = min(n - done, self.sync_every - self.since)
             ends_epoch = self.isync is not None and self.since + m == self.sync_every        # BPR.train: the exchange follows, then another epoch
-            self.eng.run_batches(self.csr, m, self.B, want_loss=WANT_LOSS, then_exchange=self.sync_every if ends_epoch else 0)
+            self.last_loss = self.eng.run_batches(self.csr, m, self.B, want_loss=WANT_LOSS, then_exchange=self.sync_every if ends_epoch else 0)
             done += m
             self.since += m
             if self.since == self.sync_every:
@@ -703,6 +712,34 @@ def shards_on_one_gpu(r, k, device, B, single_value, limit=10 ** 6, epochs=2):
     return out
 
 
+DUMP_BYTES = 64 * 10 ** 6 - 4096      # --dump-outputs: all files together, .npy headers included
+
+
+def dump_outputs(path, eng, loss):
+    """--dump-outputs: what the timed path hands its caller after its last step -- the model tables (U, V, b as eng.get() reads
+    them) and the per-batch losses the last call returned -- as float32 .npy files.  The bytes not yet written are shared evenly
+    by the tables still to come, smallest first; a table over its share keeps a fixed, seeded sample of rows (sorted row numbers
+    in <name>_rows.npy, float64).  -> {name: shape written}"""
+    os.makedirs(path, exist_ok=True)
+    tables = [('loss', loss), ('b', eng.get('b')[0]), ('V', eng.get('V')[0]), ('U', eng.get('U')[0])]
+    tables = [(n, t.detach().float().cpu().numpy()) for n, t in tables if t is not None]
+    left, wrote = DUMP_BYTES, {}
+    for q, (name, a) in enumerate(tables):
+        share = left // (len(tables) - q) - 256           # room for the headers of <name>.npy and <name>_rows.npy
+        if a.nbytes > share:
+            row = a.nbytes // a.shape[0]
+            rows = np.sort(np.random.Generator(np.random.PCG64(0)).choice(a.shape[0], share // (row + 8), replace=False))
+            np.save(os.path.join(path, name + '_rows.npy'), rows.astype(np.float64))
+            left -= os.path.getsize(os.path.join(path, name + '_rows.npy'))
+            a = a[rows]
+        elif os.path.exists(os.path.join(path, name + '_rows.npy')):
+            os.remove(os.path.join(path, name + '_rows.npy'))     # an earlier run's sample: this run wrote the whole table
+        np.save(os.path.join(path, name + '.npy'), np.ascontiguousarray(a, dtype=np.float32))
+        left -= os.path.getsize(os.path.join(path, name + '.npy'))
+        wrote[name] = list(a.shape)
+    return wrote
+
+
 def summary(out):
     """the numbers VERDICT tracks, compact, as the last key of the line (the driver's record keeps only the tail of stdout)"""
     def leg(key, *path):
@@ -746,6 +783,8 @@ def main():
     ap.add_argument('--no-cpu-baseline', action='store_true')
     ap.add_argument('--no-extras', action='store_true')
     ap.add_argument('--no-live-traffic', action='store_true')       # skip the two rocprofv3 counter passes behind roofline.traffic (~25 s)
+    ap.add_argument('--full', action='store_true')                  # every leg beside the headline (module docstring); a plain run times the headline only
+    ap.add_argument('--dump-outputs', metavar='DIR')                # after the timed steps: the tables and losses of the last step, DIR/<name>.npy
     args = ap.parse_args()
 
     rank = int(os.environ.get('RANK', 0))
@@ -769,13 +808,15 @@ def main():
     sync_every = max(1, (args.epoch_sample_limit // B) // world)       # batches per rank and epoch, as BPR.train deals them (dist.batches_per_rank)
     # the headline: per-launch events only where the launches are long (a run of at least one full chunk)
     wall, step_ms, loop = timed_run(eng, csr, B, args.steps, args.warmup, sync_every, world, per_launch_events=args.steps >= 512)
+    dumped = dump_outputs(args.dump_outputs, eng, loop.last_loss) if (args.dump_outputs and rank == 0) else None
     loop_timed_exchanges = loop.timed_exchanges
     wall = max_over_ranks(wall, device, world)
     raw_wall = wall
     launch_us = step_ms * 1e3 / args.steps
     achieved = B * algorithmic_bytes_per_triplet(k) / (launch_us * 1e-6) / 1e9
-    # whole epochs with K1 of every batch (and, at N > 1, every exchange) inside the timed region: at N = 1 the steady state of the headline
-    em = epoch_mode(eng, csr, B, k, world, device, loop)
+    # whole epochs with K1 of every batch (and, at N > 1, every exchange) inside the timed region: at N = 1 the steady state of the
+    # headline (--full), at N > 1 where the exchange wall the headline charges is measured (every run)
+    em = epoch_mode(eng, csr, B, k, world, device, loop) if (world > 1 or args.full) else {}
     # SURVEY §8d defines the metric with the all-reduce inside the wall.  A short timed window at N > 1 holds fewer exchanges than its
     # share (`--steps 20` of a 488-batch epoch: none), so the headline charges the share that is missing at the exchange wall
     # measured over whole epochs in this same process (epoch_mode.exchange_us: pack + collective + unpack + what the boundary exposes)
@@ -815,17 +856,20 @@ def main():
                                'the pair also spans the host\'s way to that launch: an upper bound of the launch)',
                      'algorithmic_bytes_per_launch': B * algorithmic_bytes_per_triplet(k)},
     }
-    out['epoch_mode'] = em
+    if em:
+        out['epoch_mode'] = em
     out['ranks_on_device'] = int(getattr(eng, 'ranks_on_device', 1))
-    if world == 1:
+    if dumped is not None:
+        out['dump_outputs'] = dumped
+    if world == 1 and em:
         out['steady_state'] = em
-    if rank == 0 and world == 1 and not args.no_extras and not args.no_live_traffic and eng.layout == 'flow':
+    if args.full and rank == 0 and world == 1 and not args.no_extras and not args.no_live_traffic and eng.layout == 'flow':
         t_bytes, t_note = live_traffic(k, B, args.shape)
         out['roofline']['traffic'] = t_bytes
         out['roofline']['traffic_how'] = t_note
         if t_bytes:
             out['roofline']['traffic_over_algorithmic'] = t_bytes / (B * algorithmic_bytes_per_triplet(k))
-    if rank == 0 and world == 1 and not args.no_extras:
+    if args.full and rank == 0 and world == 1 and not args.no_extras:
         # throughput mode: same kernels, batch_size 8192 (fresh tables)
         from single import _engine
         B2 = 8192
@@ -869,7 +913,7 @@ def main():
                         'roofline': {'bound': 'hbm', 'achieved': a3, 'peak': HBM_PEAK_GBS, 'unit': 'GB/s', 'frac': a3 / HBM_PEAK_GBS,
                                      'launch_us': s3 * 1e3 / steps_s, 'algorithmic_bytes_per_triplet': 24 * k + 40, 'traffic': None}}
             del eng3
-    if not args.no_extras:
+    if args.full and not args.no_extras:
         topk = topk_bench(r, k, device, rank, world)
         if rank == 0 and world == 1 and not args.no_cpu_baseline:
             topk['cpu_baseline'] = topk_cpu_baseline(r, k)
@@ -888,7 +932,7 @@ def main():
             out['bpr_netflix_shape'] = netflix_train_bench(k, device)
             if B <= 512:
                 out['shards_on_one_gpu'] = shards_on_one_gpu(r, k, device, B, em['value'], args.epoch_sample_limit)
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline:
         out['cpu_baseline'] = cpu_baseline(r, k, B)
     if rank == 0:
         out['summary'] = summary(out)         # LAST key: the driver keeps the tail of the line

@@ -12,7 +12,7 @@ for B in 8192 65536; do
   for C in "TCC_HIT_sum TCC_MISS_sum" "SQ_WAVE_CYCLES SQ_WAIT_ANY SQ_WAIT_INST_ANY SQ_ACTIVE_INST_ANY" "SQ_BUSY_CYCLES GRBM_GUI_ACTIVE" "SQ_INSTS_VMEM_RD SQ_INSTS_VMEM_WR SQ_INSTS_VALU SQ_WAVES" "TCP_TCC_READ_REQ_sum TCP_TCC_WRITE_REQ_sum"; do
     N=$(echo $C | tr ' ' '_')
     timeout 400 rocprofv3 --kernel-trace --pmc $C --output-format csv -d "$OUT/B${B}_$N" -o b -- \
-        python "$REPO/bench.py" --no-cpu-baseline --no-extras --batch-size $B $ST > /dev/null 2> "$OUT/B${B}_$N.err" < /dev/null
+        python "$REPO/bench.py" --full --no-cpu-baseline --no-extras --batch-size $B $ST > /dev/null 2> "$OUT/B${B}_$N.err" < /dev/null
   done
 done
 find "$OUT" -type f \( -name "*.db" -o -name "*agent_info*" \) -delete

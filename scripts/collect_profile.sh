@@ -14,12 +14,12 @@ OUT=$REPO/gpurun_out/prof_$TAG
 mkdir -p "$OUT"
 cd /tmp && export TMPDIR=/tmp
 timeout 900 rocprofv3 --kernel-trace --stats --output-format csv -d "$OUT/trace" -o bench -- \
-    python "$REPO/bench.py" --no-cpu-baseline > "$OUT/bench_under_rocprof.json" 2> "$OUT/trace.err" < /dev/null
+    python "$REPO/bench.py" --full --no-cpu-baseline > "$OUT/bench_under_rocprof.json" 2> "$OUT/trace.err" < /dev/null
 for C in FETCH_SIZE WRITE_SIZE; do
     timeout 600 rocprofv3 --kernel-trace --pmc $C --output-format csv -d "$OUT/headline_$C" -o b -- \
-        python "$REPO/bench.py" --no-cpu-baseline --no-extras --steps 2048 --warmup 256 > /dev/null 2> "$OUT/headline_$C.err" < /dev/null
+        python "$REPO/bench.py" --full --no-cpu-baseline --no-extras --steps 2048 --warmup 256 > /dev/null 2> "$OUT/headline_$C.err" < /dev/null
     timeout 600 rocprofv3 --kernel-trace --pmc $C --output-format csv -d "$OUT/b8192_$C" -o b -- \
-        python "$REPO/bench.py" --no-cpu-baseline --no-extras --batch-size 8192 --steps 256 --warmup 128 > /dev/null 2> "$OUT/b8192_$C.err" < /dev/null
+        python "$REPO/bench.py" --full --no-cpu-baseline --no-extras --batch-size 8192 --steps 256 --warmup 128 > /dev/null 2> "$OUT/b8192_$C.err" < /dev/null
     timeout 300 rocprofv3 --kernel-trace --pmc $C --output-format csv -d "$OUT/calib_$C" -o c -- \
         python "$REPO/scripts/pmc_calibrate.py" > /dev/null 2> "$OUT/calib_$C.err" < /dev/null
     # round 3: K4's bound-and-refine kernel (ML-10M and Netflix shape), the per-launch kernel at batch 65,536, the VBPR step
@@ -28,7 +28,7 @@ for C in FETCH_SIZE WRITE_SIZE; do
     timeout 600 rocprofv3 --kernel-trace --pmc $C --output-format csv -d "$OUT/topknf_$C" -o b -- \
         python "$REPO/scripts/probe_topk.py" 480189 17770 128 30 > /dev/null 2> "$OUT/topknf_$C.err" < /dev/null
     timeout 600 rocprofv3 --kernel-trace --pmc $C --output-format csv -d "$OUT/b65536_$C" -o b -- \
-        python "$REPO/bench.py" --no-cpu-baseline --no-extras --batch-size 65536 --steps 32 --warmup 16 > /dev/null 2> "$OUT/b65536_$C.err" < /dev/null
+        python "$REPO/bench.py" --full --no-cpu-baseline --no-extras --batch-size 65536 --steps 32 --warmup 16 > /dev/null 2> "$OUT/b65536_$C.err" < /dev/null
     NB=256 timeout 600 rocprofv3 --kernel-trace --pmc $C --output-format csv -d "$OUT/vbpr_$C" -o b -- \
         python "$REPO/scripts/probe_vbpr.py" > /dev/null 2> "$OUT/vbpr_$C.err" < /dev/null
 done

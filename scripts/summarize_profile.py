@@ -46,7 +46,7 @@ known_r, known_w = 541065216, 536870912
 cf = counter('calib', 'FETCH_SIZE', 'calib_rowcopy').Counter_Value.mean()
 cw = counter('calib', 'WRITE_SIZE', 'calib_rowcopy').Counter_Value.mean()
 fr, fw = known_r / (cf * 1024), known_w / (cw * 1024)
-res = {'source': 'rocprofv3 --pmc FETCH_SIZE / --pmc WRITE_SIZE (separate passes, kernel trace only) around `python bench.py --no-cpu-baseline '
+res = {'source': 'rocprofv3 --pmc FETCH_SIZE / --pmc WRITE_SIZE (separate passes, kernel trace only) around `python bench.py --full --no-cpu-baseline '
                  '--no-extras --steps 2048 --warmup 256` (headline: the persistent kernel; with the epoch_mode leg of the same process 11,718 batches of 256) and `... --batch-size 8192 --steps 256 '
                  '--warmup 128` (one launch per batch); corrected by the factors measured with scripts/pmc_calibrate.py (known-byte gather copy); '
                  'bytes = KB * 1024 * factor',

@@ -20,7 +20,8 @@ def _last_json(out):
 
 
 def test_single_gpu_line():
-    out = subprocess.run([sys.executable, os.path.join(ROOT, 'bench.py'), '--gpus', '1', '--steps', '512', '--warmup', '64', '--no-extras'],
+    out = subprocess.run([sys.executable, os.path.join(ROOT, 'bench.py'), '--gpus', '1', '--steps', '512', '--warmup', '64', '--full',
+                          '--no-extras'],
                          capture_output=True, text=True, timeout=600, cwd=ROOT)
     assert out.returncode == 0, out.stderr[-2000:]
     d = _last_json(out.stdout)
@@ -43,8 +44,8 @@ def test_single_gpu_line():
 def test_driver_command_measures_the_steady_state():
     """the round-end driver runs exactly `--gpus 1 --steps 20 --warmup 5`: the 20 timed steps must be the steady state of
     the loop of single/bpr.py:136-147 (plan, buffers and everything else one-off sit outside the timed region), not set-up"""
-    out = subprocess.run([sys.executable, os.path.join(ROOT, 'bench.py'), '--gpus', '1', '--steps', '20', '--warmup', '5', '--no-extras',
-                          '--no-cpu-baseline'], capture_output=True, text=True, timeout=600, cwd=ROOT)
+    out = subprocess.run([sys.executable, os.path.join(ROOT, 'bench.py'), '--gpus', '1', '--steps', '20', '--warmup', '5', '--full',
+                          '--no-extras', '--no-cpu-baseline'], capture_output=True, text=True, timeout=600, cwd=ROOT)
     assert out.returncode == 0, out.stderr[-2000:]
     d = _last_json(out.stdout)
     assert d['steps'] == 20 and d['warmup'] == 5
@@ -56,6 +57,29 @@ def test_driver_command_measures_the_steady_state():
     assert r['launch_us'] <= wall_us * 1.05 and wall_us < 3.0 * r['launch_us'] + 6.0, (r['launch_us'], wall_us)
     assert d['timed_region']['exchanges_inside'] == 0 and len(d['timed_region']['per_batch']) == 2
     assert d['steady_state']['value'] > 85e6 and d['steady_state']['steps'] == 7812, d['steady_state']
+
+
+def test_plain_run_times_the_headline_and_dumps_its_outputs(tmp_path):
+    """without --full the line carries the headline only (no leg of its own runs), and --dump-outputs writes the tables and the
+    losses of the last timed call: float32, the headline's shapes (ML-10M: 69,878 users x 10,380 items, k = 128), 64 MB at most"""
+    out = subprocess.run([sys.executable, os.path.join(ROOT, 'bench.py'), '--gpus', '1', '--steps', '20', '--warmup', '5',
+                          '--dump-outputs', str(tmp_path)], capture_output=True, text=True, timeout=600, cwd=ROOT)
+    assert out.returncode == 0, out.stderr[-2000:]
+    d = _last_json(out.stdout)
+    for key in REQUIRED:
+        assert key in d, key
+    assert d['steps'] == 20 and d['warmup'] == 5 and d['value'] > 15e6
+    assert abs(d['value'] - 20 * 256 / (d['ms_per_step'] * 20 * 1e-3)) / d['value'] < 1e-6
+    for leg in ('epoch_mode', 'steady_state', 'cpu_baseline', 'throughput_mode', 'sgd_mode', 'topk', 'vbpr', 'bpr_netflix_shape', 'shards_on_one_gpu'):
+        assert leg not in d, leg
+    import numpy as np
+    got = {f[:-4]: np.load(str(tmp_path / f)) for f in os.listdir(str(tmp_path))}
+    assert sorted(got) == ['U', 'V', 'b', 'loss'], sorted(got)
+    assert got['U'].shape == (69878, 128) and got['V'].shape == (10380, 128) and got['b'].shape == (10380,) and got['loss'].shape == (20,)
+    assert d['dump_outputs'] == {n: list(a.shape) for n, a in got.items()}
+    assert all(a.dtype == np.float32 and np.isfinite(a).all() for a in got.values())
+    assert sum(os.path.getsize(str(tmp_path / f)) for f in os.listdir(str(tmp_path))) <= 64 * 10 ** 6
+    assert (got['loss'] > 0).all()                                      # -log sigmoid(x_uij) + the L2 terms of each batch
 
 
 @pytest.mark.parametrize('own', ['1', '0'])
