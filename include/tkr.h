@@ -40,8 +40,9 @@ extern "C" {
 #define TKR_E_NOMEM (-5)       /* host text I/O: allocation failed */
 
 int tkr_version(void);
-/* 1: built with `make LAB=1` -- the library also holds the kernel forms that were measured slower and are nobody's default (K2o scalar
- * exchange / scout / 16 waves / loader ring, K4 bf16x3, the VBPR pair-sum placements 1 and 2); 0: asking for one returns TKR_E_UNSUPPORTED */
+/* 0.  The `make LAB=1` build that returned 1 is removed, with the kernel forms it held that were measured slower (K2o scalar exchange /
+ * scout / 8 and 16 waves / loader ring, K4 bf16x3, the VBPR pair-sum placements 1 and 2; last source: git show 7a0cd86:top-k-rec_amd/csrc/<file>).
+ * Asking for one of them returns TKR_E_UNSUPPORTED. */
 int tkr_lab_build(void);
 
 /* ---- K1: (u,i,j) draw + batch plan ---------------------------------------------------------
@@ -183,9 +184,7 @@ int tkr_bpr_flow_run(const tkr_flow_state* st, const int32_t* prec, const int32_
  * in the same state as K2f does: the two kernels, the exchange and get / set may be mixed freely between launches.  Item row r is
  * served by workgroup r % n_owner, which keeps the row, its slot, bias and acknowledge totals in LDS from the row's first update
  * in a launch on: the task of batch t+1 finds the row of batch t there instead of polling memory for it (what bounded K2f at
- * batch 256).  Partner rows are read from the tables as in K2f; `owner_waves` bit 15 selects the form in which the two item tasks
- * of a triplet exchange the scalars <u, v> + b through an 8-byte slot of `xch` instead of reading each other's rows (measured
- * slower: csrc/bpr_own.hip has both protocols and the numbers).  User tasks are handed out by tickets as in K2f.
+ * batch 256).  Partner rows are read from the tables as in K2f.  User tasks are handed out by tickets as in K2f.
  *   tkr_bpr_own_owners(n_items, k)   n_owner for the current device (its CU count), or 0 when ceil(n_items / CUs) rows of
  *                                    8*kp + 16 bytes do not fit one CU's 160 KB of LDS (use K2f then)
  *   tkr_sample_plan_owned            tkr_sample_plan's dataflow form (prec, pocc; batch_size <= 8192) with the records of every
@@ -196,9 +195,10 @@ int tkr_bpr_flow_run(const tkr_flow_state* st, const int32_t* prec, const int32_
  *                                    workgroups (all resident: n_owner <= CUs).  prec / pocc / occt / ohdr / loss_out point at
  *                                    batch 0 of the plan call; owner_waves: waves per workgroup that serve the owner queue, 0 =
  *                                    default (workgroups of 12 waves at k <= 128: 10 on the owner queue, 2 on user tickets; 8
- *                                    waves above: 7 + 1; bits 13 / 14: 8 / 16 waves at k <= 128); ctl as for tkr_bpr_flow_run.
- *                                    xch: 16 * batch_size bytes per batch of the plan (the scalar slots {value, epoch} of every
- *                                    (triplet, role); only the scalar form writes them), caller-owned, zeroed once; epoch: a
+ *                                    waves above: 7 + 1); ctl as for tkr_bpr_flow_run.  owner_waves bits 8, 15 (and 13, 14 at
+ *                                    k <= 128) asked for removed forms: TKR_E_UNSUPPORTED.
+ *                                    xch: 16 * batch_size bytes per batch of the plan (the user tasks' loss sums {value, epoch},
+ *                                    one slot per task), caller-owned, zeroed once; epoch: a
  *                                    number > 0 that no earlier launch on this xch used (a counter per plan buffer does).
  * k <= 256, n_batches <= 512. */
 int32_t tkr_bpr_own_owners(int32_t n_items, int32_t k);
@@ -223,8 +223,7 @@ int tkr_bpr_own_run(const tkr_flow_state* st, const int32_t* prec, const int32_t
  * 0 .. n_batches-1 plan a batch each in front of the step, csrc/bpr_own.hip PLAN; the last workgroup out adds the losses up): when
  * first_batch == 0, n_batches == plan->n_batches <= min(64, n_owner), batch_size <= 256, k <= 128, the default step form, n_users and
  * n_items below 2^25; otherwise tkr_sample_plan_owned's launches + the step's, as before.  Same words in every plan array and the same
- * tables either way.  owner_waves bit 12: never the one-launch form; bit 9: the losses always by their own launch; bit 8: the loader /
- * consumer form of the step (long launches only; measured slower). */
+ * tables either way.  owner_waves bit 12: never the one-launch form; bit 9: the losses always by their own launch. */
 typedef struct tkr_plan_call {
     const int32_t *tr_users, *row_ptr, *pos_cols, *cols_sorted;
     int32_t *ucnt, *icnt;
@@ -284,9 +283,8 @@ typedef struct {
 /* floats of scratch tkr_vbpr_run needs (split-K partials, s_t, P_t, W_t) */
 int64_t tkr_vbpr_workspace_floats(int32_t batch_size, int32_t kh, int32_t d);
 /* tkr_vbpr_run_cols: where the [B, B] pair sums S_t, T_t of a batch (vbpr.py:61) are formed -- 0: a launch of their own between the
- * projection and the update (three launches per batch); 1: every task of the update works out the sums it needs (batch <= 256);
- * 2: the first blocks of the update launch form them for everybody (two launches per batch).  Same sums, same order of summation,
- * bit for bit (1: within fp32 rounding of the others).  Initial value from TKR_VBPR_PAIRS. */
+ * projection and the update (three launches per batch), the only placement.  1 (every task of the update works out the sums it
+ * needs) and 2 (the first blocks of the update launch form them) were measured slower and removed: TKR_E_UNSUPPORTED. */
 int tkr_vbpr_set_pairs(int32_t mode);
 /* n_batches consecutive batches planned by tkr_sample_plan (tri_i / tri_j = its out_i / out_j);
  * kh <= 128 (any kh: tkr_vbpr_run_cols), batch_size <= 65536 (batches above 8192 are planned grid-wide, see tkr_sample_plan); loss_out as in tkr_bpr_run */
@@ -337,22 +335,19 @@ int tkr_vbpr_run_cols(const tkr_vbpr_state* st, const int32_t* tri_i, const int3
  *   workspace (nullable, device, workspace_bytes): scratch for per-item-range partial lists; with
  *     tkr_topk_workspace_bytes(n_rows, K) bytes the launch splits the catalogue so that the grid fills
  *     the 256 CUs in whole rounds (results are identical with or without it)
- * Arithmetic of the scores (tkr_topk_set_math, initial value from TKR_TOPK_MATH=refine|bf16x3|fp32):
+ * Arithmetic of the scores (tkr_topk_set_math, initial value from TKR_TOPK_MATH=refine|fp32):
  *   2 "refine" (default; k <= 128, needs the workspace, n_cols < 2^27): bound-and-refine.  ONE fp16 product per element
  *     (factors scaled by powers of two, v_mfma_f32_32x32x16_f16) scores the catalogue within a rigorous margin
  *     (2^-10 * 1.05 * |u| * max|v_i| + roundings, see csrc/topk.hip); the candidate lists keep everything within twice the
  *     margin of the K-th best approximate score, and the survivors are rescored with the arithmetic of mode 1, which
  *     decides the order: ids and score bits are those of mode 1, at 2.1x its speed.  A list that cannot hold its margin
  *     (massive near-ties) sends its user block through the mode-1 kernel.  Without a workspace the call runs as mode 1.
- *   0 "bf16x3" (k <= 128; lab library only, `make LAB=1`: TKR_E_UNSUPPORTED otherwise): each fp32 factor is split exactly into three bf16 parts and a product is the six
- *     leading partial products (each exact in fp32, the dropped ones < 2^-23 |ab|) accumulated in fp32 by
- *     v_mfma_f32_32x32x16_bf16 -- an fp32 dot product with yet another summation order: same error against fp64 as
- *     np.dot / the fp32 kernel, identical results whenever the partial sums are representable; finite inputs only;
+ *   0 "bf16x3" (six exact bf16 partial products) is removed: tkr_topk_set_math(0) returns TKR_E_UNSUPPORTED, and
+ *     TKR_TOPK_MATH=bf16x3 runs as mode 1;
  *   1 "fp32": v_mfma_f32_32x32x2_f32, used for every k and always for k > 128: per score the fma chain
  *     acc <- fma(v[j], u[j], acc); acc <- fma(v[KH+j], u[KH+j], acc), j = 0 .. KH-1, KH = ceil(k/2), then fl(acc + bias)
  *     (oracle/ref_np.py mfma_chain_scores restates it; bit-exact on generic inputs).
- *   On gfx950 the fp32 MFMA runs at the vector-ALU rate and overlaps nothing; mode 0 is 1.4-1.6x faster than mode 1,
- *   mode 2 1.5-2.1x.
+ *   On gfx950 the fp32 MFMA runs at the vector-ALU rate and overlaps nothing; mode 2 is 1.5-2.1x faster than mode 1.
  * K <= 32 per launch (larger K: rank 32, add the found columns to the mask with tkr_build_rated_mask, rank
  * again -- top-k-rec_amd/tkr_hip.py score_topk does this); any k (above 768: score_topk_wide_kernel, one wave per row, a lane per item,
  * the same fma chain; 256 < k <= 768: mode 1 with the k dimension in slabs of 256 --

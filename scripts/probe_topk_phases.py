@@ -1,5 +1,6 @@
-"""Cycle budget of the K4 tile loop by phase, from a TKR_ABL=256 build (scripts/ablate_topk.sh 256):
-TKR_HIP_LIB=$PWD/_ab_libs/libtkr_abl256.so python scripts/probe_topk_phases.py [netflix|ml10m] [mode]"""
+"""Cycle budget of the tile loop of K4's second bound-and-refine form (csrc/topk_refine.hip) by phase, from a -DTKR_R2_PROF build:
+make -C top-k-rec_amd/csrc EXTRA=-DTKR_R2_PROF (into a copy of the tree), then
+TKR_HIP_LIB=<that copy>/top-k-rec_amd/libtkr_hip.so python scripts/probe_topk_phases.py [netflix|ml10m] [mode]"""
 import ctypes as C, os, sys
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path[:0] = [ROOT, os.path.join(ROOT, 'top-k-rec_amd')]
@@ -25,7 +26,7 @@ e0.record(); tkr_hip.score_topk(U, V, K, mask=mask, mask_pitch=pitch); e1.record
 tkr_hip.lib().tkr_k4_prof_read(out)
 p = np.array(list(out), dtype=np.float64)
 tiles = max(p[7], 1)
-names = ['mfma+bias', 'staging', 'barrier', 'sched trims', 'filter', 'prologue', 'final stage']
+names = ['mfma+bias', 'next tile', 'barrier', 'sched trims', 'filter', 'prologue', 'final trim+dump']
 print('%s %s: %.2f ms; %d wave-tiles; 100 MHz ticks per wave-tile (x24 = 2.4 GHz cycles):' % (name, mode, e0.elapsed_time(e1), tiles))
 tot = p[:7].sum()
 for i, n in enumerate(names):

@@ -46,13 +46,13 @@ for case in range(n_cases):
     rated = [sorted(set(tr.get(x, []))) for x in range(n_users)]
     ptr = np.zeros(n_users + 1, np.int64); np.cumsum([len(x) for x in rated], out=ptr[1:])
     mask, pitch = tkr_hip.build_rated_mask(torch.from_numpy(ptr).to(dev), torch.tensor([c for x in rated for c in x] or [0], dtype=torch.int32, device=dev)[: max(1, int(ptr[-1]))], n_users, n_items)
-    for math in ('bf16x3', 'fp32'):
+    for math in ('refine', 'fp32'):
         tkr_hip.set_topk_math(math)
         ids = tkr_hip.score_topk(torch.from_numpy(qU).to(dev), torch.from_numpy(qV).to(dev), K, mask=mask, mask_pitch=pitch).cpu().numpy()
         s = np.dot(qU, qV.T)
         for x in range(0, n_users, max(1, n_users // 50)):
             want = R.filtered_topk(s[x], set(rated[x]), K, canonical=True)
             assert [c for c in ids[x].tolist() if c >= 0] == want, (case, math, x)
-    tkr_hip.set_topk_math('bf16x3')
+    tkr_hip.set_topk_math(tkr_hip.TOPK_MATH_DEFAULT)
     print('case %2d ok: users %4d items %4d k %3d B %4d nb %2d %s %s K %2d' % (case, n_users, n_items, k, B, nb, mode, opt, K), flush=True)
 print('all %d cases match' % n_cases)

@@ -16,8 +16,8 @@ def short(n):
         if k in n:
             if k == 'bpr_step_kernel' and re.search(r'bpr_step_kernel<\d+, (?:true|false), \d+, true>', n):
                 return 'tkr::bpr_step_kernel<SGD>'
-            if k == 'score_topk_bf16_kernel':           # <KS, IdT, REFINE>: the bound-and-refine arithmetic is its own line
-                return 'tkr::score_topk_bf16_kernel<refine>' if re.search(r'score_topk_bf16_kernel<\d+, [a-z ]+, true', n) else 'tkr::score_topk_bf16_kernel<bf16x3>'
+            if k == 'score_topk_bf16_kernel':           # <KS, IdT, IMG>; traces of older trees: <KS, IdT, REFINE, IMG>, REFINE = false was bf16x3
+                return 'tkr::score_topk_bf16_kernel<bf16x3>' if re.search(r'score_topk_bf16_kernel<\d+, [a-z ]+, false, ', n) else 'tkr::score_topk_bf16_kernel<refine>'
             if k == 'score_topk_kernel':
                 return 'tkr::score_topk_kernel (fp32 MFMA; ~5-8 us calls: the no-op fallback pass behind a refine launch)'
             return 'tkr::' + k

@@ -20,15 +20,12 @@ pytestmark = pytest.mark.gpu
 from oracle import ref_np as R
 
 
-@pytest.fixture(scope='module', params=['bf16x3', 'fp32', 'refine'])
+@pytest.fixture(scope='module', params=['fp32', 'refine'])
 def hip(request):
-    """every test runs under all score arithmetics of K4 (include/tkr.h, tkr_topk_set_math); 'bf16x3' was measured and dropped: it
-    lives in the lab library (make -C top-k-rec_amd/csrc LAB=1, TKR_HIP_LIB=.../libtkr_hip_lab.so) and is skipped otherwise"""
+    """every test runs under both score arithmetics of K4 (include/tkr.h, tkr_topk_set_math)"""
     import tkr_hip
     assert torch.cuda.is_available()
     tkr_hip.lib()
-    if request.param == 'bf16x3' and not tkr_hip.lab():
-        pytest.skip('bf16x3 is a lab form (make LAB=1)')
     tkr_hip.set_topk_math(request.param)
     yield tkr_hip
     tkr_hip.set_topk_math(tkr_hip.TOPK_MATH_DEFAULT)

@@ -147,6 +147,19 @@ def test_library_exports_every_declared_symbol():
     assert lib.tkr_score_topk(None, None, 0, None, None, 0, 0, None, 0, 0, None, None, None, 0, None) == -1
 
 
+def test_library_refuses_removed_forms():
+    """the measured-and-dropped kernel forms are gone from the library; asking for one is refused (include/tkr.h), host-only calls"""
+    import tkr_hip
+    lib = ctypes.CDLL(tkr_hip.LIB_PATH)
+    E_INVAL, E_UNSUPPORTED = -1, -2
+    assert lib.tkr_lab_build() == 0
+    assert lib.tkr_topk_set_math(ctypes.c_int32(0)) == E_UNSUPPORTED          # bf16x3
+    for mode in (1, 2):                                                        # the pair-sum placements other than their own launch
+        assert lib.tkr_vbpr_set_pairs(ctypes.c_int32(mode)) == E_UNSUPPORTED
+    assert lib.tkr_vbpr_set_pairs(ctypes.c_int32(3)) == E_INVAL
+    assert lib.tkr_vbpr_set_pairs(ctypes.c_int32(0)) == 0
+
+
 def test_missing_library_fails_loudly(tmp_path, monkeypatch):
     import tkr_hip
     monkeypatch.setattr(tkr_hip, '_lib', None)

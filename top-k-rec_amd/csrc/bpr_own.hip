@@ -10,40 +10,26 @@
 // stay in the owner's LDS from the row's first update of a launch on: the task of batch t+1 finds what the task of batch t left
 // there -- before that task's acknowledge wait and write-through stores, which now only serve the row's PARTNERS.
 //
-// Two forms of an item task (template parameter SCALAR; `owner_waves` bit 15 of tkr_bpr_own_run):
-//   * row-read (the default): the partner rows of an occurrence -- the user row and the OTHER item's row -- are read from the granule
-//     tables at their exact versions, as in K2f (flow_task.h run_task).  Measured 2.18 us per batch at the ML-10M shape against
-//     2.75 for K2f on the same box.  What bounds it: throughput -- two to three memory round trips per task in series at 2-3 us
-//     apiece, ~700 tasks per batch over 3,072 waves; the dependency structure alone forces only 0.38 hand-offs per batch against
-//     K2f's 1.14 (scripts/chain_model.py).
-//   * scalar exchange: x_uij = (<u, v_i> + b_i) - (<u, v_j> + b_j) (single/bpr.py:87-89), so the task of item i needs the other item of
-//     a triplet only through the scalar <u, v_j> + b_j, which the task of item j computes anyway.  Each publishes d = <u, v_own> +
-//     b_own as ONE 8-byte granule {d, epoch} in the slot of (batch, triplet, role) and reads the partner's slot (asked for together
-//     with the user rows: the partner has usually published before this task has its own row); the two never read each other's rows
-//     (half the partner traffic; one acknowledged reader per occurrence of an item row: the user task).  One wave of every workgroup,
-//     the "scout", runs ahead of the queue's head and publishes the scalars of every task whose rows are final, without waiting for
-//     anything: that is also what keeps the same-batch rendezvous free of deadlock (below).  Measured 2.74 us per batch: one more
-//     serial round trip per item task (publish, then the partner's slot where the early load missed it) and one wave of twelve
-//     spent on the scout.  Kept selectable; every test of tests/test_gpu_flow.py runs both forms.
+// An item task reads the partner rows of an occurrence -- the user row and the OTHER item's row -- from the granule tables at their
+// exact versions, as in K2f (flow_task.h run_task).  Measured 2.18 us per batch at the ML-10M shape against 2.75 for K2f on the same
+// box.  What bounds it: throughput -- two to three memory round trips per task in series at 2-3 us apiece, ~700 tasks per batch over
+// 3,072 waves; the dependency structure alone forces only 0.38 hand-offs per batch against K2f's 1.14 (scripts/chain_model.py,
+// DESIGN.md K2o).  The scalar-exchange form with its scout wave measured 2.74 and was removed (DESIGN.md section 4, K2o table;
+// source: git show 7a0cd86:top-k-rec_amd/csrc/bpr_own.hip).
 //
 // User tasks are handed out by tickets as in K2f, to the remaining waves of every workgroup.  The granule tables are written
 // through at every update exactly as by K2f, so a launch leaves them complete (get / set, the exchange of csrc/sync.hip, a K2f
 // launch all work on the same state), and a chunk may be cut into launches anywhere: a task whose row was not yet updated in THIS
 // launch (prec[5] < first batch of the launch) loads it from the tables like K2f does.
 //
-// Progress.  Producers of a task sit in earlier batches -- in the scalar form except the partner scalars of the SAME batch.  Owner
-// queues are taken in plan order by their own waves, tickets in plan order by the ticket waves, one task per wave at a time (no
-// claim-ahead: a claimed task that nobody works on blocked the waves behind it); the scout never waits.  Scalar form: take the oldest
-// batch with an unfinished task: all rows its tasks read are final (their writers sit in earlier batches, which are done), so the
-// scouts -- which scan from their queue's head on and skip only what is not final yet -- publish every scalar of that batch that a
-// taken task has not published itself (a task of several rounds announces ALL its scalars before it waits for any); the tasks of
-// that batch that hold a wave then finish, the heads move.  Needs every workgroup resident (grid = n_owner <= CUs); every spin is
-// bounded (status word), and the engine steps down to K2f when one runs out.
+// Progress.  Producers of a task sit in earlier batches.  Owner queues are taken in plan order by their own waves, tickets in plan
+// order by the ticket waves, one task per wave at a time (no claim-ahead: a claimed task that nobody works on blocked the waves
+// behind it).  Needs every workgroup resident (grid = n_owner <= CUs); every spin is bounded (status word), and the engine steps
+// down to K2f when one runs out.
 //
-// Results are bitwise reproducible run to run (scout and task run the same code on the same versions; the row-read form sums like
-// K2f); the scalar form differs from K2f in the last bits (x is the difference of two rounded dots): same tolerance to the oracle.
+// Results are bitwise reproducible run to run (the item and user tasks sum like K2f).
 #include "flow_task.h"
-// s_sleep between two polls of an LDS word (a row's tag, a ring slot's mark).  The polls are ds_read now (flow_task.h lds_peek; as
+// s_sleep between two polls of an LDS word (a row's tag).  The polls are ds_read now (flow_task.h lds_peek; as
 // flat loads each took a trip down the vector-memory path, which throttled them by accident): a wave that spins on LDS at full rate
 // takes issue cycles from the two working waves of its SIMD.  Measured per batch in steady state / per 20-batch call, ML-10M shape:
 // nap 0: 2.03 us / 112 us, 1: 2.00 / 105, 2: 1.98 / 101, 4: 1.95 / 99, 8: 1.98 / 98, 16: 2.01 / 99, 32: 2.12 / 102 (flat polls: 2.2 / 110).
@@ -122,14 +108,13 @@ __device__ __forceinline__ int4 plan_ld(const int4* __restrict__ prec, const __a
         return prec[idx16];
     }
 }
-constexpr int kDotWin = 1024;            // ring of "scalars of queue position p are out" marks (power of two)
-constexpr int kScoutAhead = 48;          // queue positions beyond the head the scout looks at
+constexpr int kDotWin = 1024;            // ring of "queue position p has run" marks (power of two; see the item tasks' loop)
 
 struct OwnQueue {                        // head of the workgroup's LDS block
     uint32_t head;                       // next position of the owner queue
     uint32_t total;                      // item tasks of this owner in the launch
     uint32_t arrival;
-    uint32_t head_batch;                 // a batch <= the batch of position `head` (where a scan may start)
+    uint32_t head_batch;                 // a batch <= the batch of position `head`
 };
 
 // the owner queue: position -> (batch, slot) through the prefix sums of the per-batch run lengths
@@ -204,8 +189,10 @@ struct ItemRow {                         // where the own row of an item task is
     const volatile uint32_t* tag;        // the row's version word in LDS
     const float* row;                    // the row's slot in LDS
     int halves;                          // 16-byte halves of a tail in the tables
-    bool rd_staged;                      // LOADER: the acknowledge word was copied beside the partner rows ...
-    uint32_t rd_val;                     // ... this is it (a lower bound of the word now: acknowledgements only grow)
+    // A copy of the row's acknowledge word taken beside the row, and whether there is one.  Always false since the loader that took
+    // it was removed; the test in item_own_wait stays because dropping it changes how the kernel's registers are allocated.
+    bool rd_staged;
+    uint32_t rd_val;
 };
 
 // the task's way: wait for the row (LDS: the task before it in the chain; tables: only at a launch's first touch), then the acknowledge word
@@ -229,7 +216,7 @@ __device__ __forceinline__ bool item_own_wait(const FlowTables& T, int lane, con
         asm volatile("" ::: "memory");                  // the row is read AFTER its tag
         lds_row_read<NP>(r.row, lane, sgd, own, ms, o);
         o.ok = true;
-        if (r.rd_staged) {                              // no trip to memory for the acknowledge word either: own_publish polls it if this copy falls short
+        if (r.rd_staged) {
             o.rd = r.rd_val;
             return true;
         }
@@ -237,27 +224,8 @@ __device__ __forceinline__ bool item_own_wait(const FlowTables& T, int lane, con
     return flow_own<NP>(T, lane, r.own_p, r.own_ms, r.own_tail, r.own_rd, r.ver, own, ms, o, sgd, ctl, spins, r.halves);   // o.ok: only rd is loaded
 }
 
-// the scout's way: the row if it is final NOW (values and bias only), else false
-template <int NP>
-__device__ __forceinline__ bool item_own_peek(int lane, const ItemRow& r, float (&own)[2 * NP], Own& o) {
-    if (r.from_lds) {
-        if (lds_peek(r.tag) != r.ver) return false;
-        asm volatile("" ::: "memory");
-        float ms[2 * NP];
-        lds_row_read<NP>(r.row, lane, true, own, ms, o);
-        return true;
-    }
-    v4u xo[NP];
-    issue_row<NP>(r.own_p, lane, xo);
-    const v2u xb = issue_bias(r.own_tail);
-    if (!__all(row_tagged<NP>(xo, r.ver) && xb.y == r.ver)) return false;
-    row_values<NP>(xo, own);
-    o.b = bcast_f(__uint_as_float(xb.x), 0);
-    return true;
-}
-
-// the row-read form of an item task (SCALAR = false: csrc/flow_task.h run_task, both partner rows of an occurrence read from the
-// tables like K2f does) takes its own row the same way and never prefetches a record
+// an item task (csrc/flow_task.h run_task: both partner rows of an occurrence read from the tables like K2f does) takes its own row
+// the way above and never prefetches a record
 template <int NP>
 struct LdsOwnStep {
     const FlowTables& T;
@@ -280,182 +248,6 @@ struct LdsOwnStep {
 struct NoFeed {
     __device__ __forceinline__ void prefetch(NextTask& nx, int) { nx.have = true; }
 };
-
-// ---- a round of up to G occurrences of an item task -----------------------------------------------------------------------------
-// Lane q < n of `d` holds occurrence q = (user, version of the user row, other | role<<31, version of the other item [unused]);
-// `tq` its triplet's index in the batch.  MODE kFull: the task's round.  kScout: one pass, nothing acknowledged, nothing waited
-// for, scalars only; false = not final yet.  kAnnounce: the user rows are waited for, the scalars published, nothing else (a task
-// of several rounds announces ALL its scalars before it waits for any partner's: two such tasks would otherwise wait for each
-// other's later rounds).
-constexpr int kFull = 0, kScout = 1, kAnnounce = 2;
-template <int G>
-constexpr int own_shift() { return G <= 4 ? 4 : 3; }      // lane L speaks for occurrence L >> shift
-
-template <int NP, int G, int MODE>
-__device__ __forceinline__ bool item_round(const tkr_flow_state& st, const FlowTables& T, int lane, int n, const int4 d, int tq, bool first_round,
-                                           const ItemRow& r, bool sgd, u64* xch_batch, int xch_bytes, uint32_t epoch, float (&own)[2 * NP],
-                                           float (&ms)[2 * NP], Own& o, float (&g)[2 * NP], float& gb, float& lam_sum, uint32_t* ctl,
-                                           uint32_t& spins, uint32_t tune) {
-    constexpr int SH = own_shift<G>();
-    static_assert(G == 4 || G == 8, "occurrences per round");
-    v4u xa[G][NP];
-    uint32_t waited = 0;
-    // the scalars of this round: the first lane of every group speaks for one occurrence
-    const int myq = lane >> SH;
-    const bool live = (lane & ((1 << SH) - 1)) == 0 && myq < n;
-    const bool role = __shfl(d.z, myq) < 0;                        // this row is the NEGATIVE item of the triplet
-    const int slot = (2 * __shfl(tq, myq) + (role ? 1 : 0)) * 8;   // bytes: granule (triplet, role)
-    const __amdgpu_buffer_rsrc_t xr = row_rsrc(xch_batch, xch_bytes);
-    v2u pvo;                                      // the PARTNER's scalar, asked for together with the user rows: a scout (or the partner
-    pvo.x = 0u; pvo.y = epoch;                    // itself) has usually published it long before this task has its own row, and the round
-    for (;;) {                                    // trip of the poll below would sit on the chain through a popular item.
-        // one pass ISSUES every user row of the round and only then looks at tags
-#pragma unroll
-        for (int q = 0; q < G; ++q) {
-            const int src = (q < n) ? q : 0;      // straight-line loads: idle slots repeat occurrence 0 (flow_fetch has the reason)
-            const int a = bcast_i(d.x, src);
-            const uint32_t va = (uint32_t)bcast_i(d.y, src);
-            issue_row<NP>(T.U + (va & 1u) * T.ustride + (size_t)a * T.kp, lane, xa[q]);
-        }
-        if constexpr (MODE == kFull) {
-            if (live) pvo = __builtin_amdgcn_raw_buffer_load_b64(xr, slot ^ 8, 0, kAuxLoad);
-        }
-        bool lane_ok = true, far = false;
-#pragma unroll
-        for (int q = 0; q < G; ++q) {
-            const int src = (q < n) ? q : 0;
-            const uint32_t va = (uint32_t)bcast_i(d.y, src);
-            lane_ok = lane_ok && row_tagged<NP>(xa[q], va);
-            far = far || (int)(va - (uint32_t)bcast_i((int)xa[q][0].y, 0)) >= 4;
-        }
-        if (__all(lane_ok)) break;
-        if constexpr (MODE == kScout) return false;
-        if (far) __builtin_amdgcn_s_sleep(127);
-        if (spin_fail(waited, ctl, 4)) {
-            if (waited >= kSpinLimit && lane == 0 && atomicCAS(ctl + kCtlDebug, 0u, 5u) == 0u) {
-                ctl[kCtlDebug + 1] = (uint32_t)d.x; ctl[kCtlDebug + 2] = (uint32_t)d.y; ctl[kCtlDebug + 3] = xa[0][0].y; ctl[kCtlDebug + 4] = (uint32_t)n;
-            }
-            return false;
-        }
-    }
-    spins += waited;
-    if constexpr (MODE == kScout) {
-        if (first_round && !item_own_peek<NP>(lane, r, own, o)) return false;
-    } else if constexpr (MODE == kFull) {
-        if (lane < n) __hip_atomic_fetch_add(T.rdU + 2 * (size_t)d.x + (d.y & 1), 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        if (first_round && !item_own_wait<NP>(T, lane, r, sgd, own, ms, o, ctl, spins)) return false;
-    }
-
-    // d_q = <u_q, v_own> + b_own, all reduced together; lane L holds occurrence L >> SH
-    float part[G];
-#pragma unroll
-    for (int q = 0; q < G; ++q) {
-        float acc = 0.f;
-#pragma unroll
-        for (int c = 0; c < NP; ++c) {
-            acc = fmaf(__uint_as_float(xa[q][c].x), own[2 * c], acc);
-            acc = fmaf(__uint_as_float(xa[q][c].z), own[2 * c + 1], acc);
-        }
-        part[q] = q < n ? acc : 0.f;
-    }
-    const float dme = reduce_multi<G>(part, lane) + o.b;
-    // publish mine; poll the partner's only where the early load did not find it
-    if (live) {
-        v2u pv;
-        pv.x = __float_as_uint(dme); pv.y = epoch;
-        __builtin_amdgcn_raw_buffer_store_b64(pv, xr, slot, 0, kAuxStore);
-    }
-    if constexpr (MODE != kFull) return true;
-    float dother = __uint_as_float(pvo.x);
-    waited = 0;
-    const bool early = __all(pvo.y == epoch);
-    while (!early) {
-        v2u pv = pvo;
-        if (live && pvo.y != epoch) pv = __builtin_amdgcn_raw_buffer_load_b64(xr, slot ^ 8, 0, kAuxLoad);
-#ifdef TKR_OWN_PROF
-        if (tune & 4u) pv.y = epoch;              // timing experiment only (wrong results): the partner's scalar is never waited for
-#endif
-        dother = __uint_as_float(pv.x);
-        if (__all(pv.y == epoch)) break;
-        if (spin_fail(waited, ctl, 1)) {
-            if (waited >= kSpinLimit && lane == 0 && atomicCAS(ctl + kCtlDebug, 0u, 6u) == 0u) {
-                ctl[kCtlDebug + 1] = (uint32_t)d.x; ctl[kCtlDebug + 2] = (uint32_t)d.z; ctl[kCtlDebug + 3] = (uint32_t)tq; ctl[kCtlDebug + 4] = epoch;
-            }
-            return false;
-        }
-    }
-    spins += waited;
-    const float x = role ? dother - dme : dme - dother;            // x_uij = x_ui - x_uj
-    const float sme = fast_sigmoid_neg(x);
-    const u64 roles = __ballot(lane < n && d.z < 0);
-#pragma unroll
-    for (int q = 0; q < G; ++q) {
-        if (q < n) {
-            const float sq = bcast_f(sme, q << SH);
-            const bool rj = (roles >> q) & 1ull;
-            const float sg = rj ? sq : -sq;
-            gb += sg;
-            lam_sum += rj ? st.lj : st.li;
-#pragma unroll
-            for (int c = 0; c < NP; ++c) {
-                g[2 * c] = fmaf(sg, __uint_as_float(xa[q][c].x), g[2 * c]);
-                g[2 * c + 1] = fmaf(sg, __uint_as_float(xa[q][c].z), g[2 * c + 1]);
-            }
-        }
-    }
-    return true;
-}
-
-// all the occurrences of an item task: up to four sit in the record (their triplet indices in its words 24..27), more come from
-// pocc / occt in rounds of eight.  SCOUT: scalars only; false = some row is not final yet (nothing is lost: the task publishes them too)
-template <int NP, bool SCOUT>
-__device__ __forceinline__ bool item_task(const tkr_flow_state& st, const FlowTables& T, int lane, int n_occ, int first, const int4 w,
-                                          const int4* __restrict__ pocc, const int32_t* __restrict__ occt, const ItemRow& r, bool sgd,
-                                          u64* xch_batch, int xch_bytes, uint32_t epoch, float (&own)[2 * NP], float (&ms)[2 * NP], Own& o,
-                                          float (&g)[2 * NP], float& gb, uint32_t* ctl, uint32_t& spins, uint32_t tune) {
-    constexpr int NE = 2 * NP;
-    constexpr int M = SCOUT ? kScout : kFull;
-    float lam_sum = 0.f;
-    if (n_occ <= 4) {                             // the common case: its occurrences sit in the record (lanes 2..5), their triplets in lane 6
-        const int src = (lane + 2) & 7;
-        const int4 d = make_int4(__shfl(w.x, src), __shfl(w.y, src), __shfl(w.z, src), __shfl(w.w, src));
-        const int t0 = bcast_i(w.x, 6), t1 = bcast_i(w.y, 6), t2 = bcast_i(w.z, 6), t3 = bcast_i(w.w, 6);
-        const int tq = lane == 0 ? t0 : lane == 1 ? t1 : lane == 2 ? t2 : t3;
-        if (!item_round<NP, 4, M>(st, T, lane, n_occ, d, tq, true, r, sgd, xch_batch, xch_bytes, epoch, own, ms, o, g, gb, lam_sum, ctl, spins, tune))
-            return false;
-    } else {
-        if constexpr (!SCOUT) {
-            if (n_occ > 8) {                      // several rounds: the own row first, then every round's scalars, and only then the waiting
-                if (!item_own_wait<NP>(T, lane, r, sgd, own, ms, o, ctl, spins)) return false;
-                for (int done = 0; done < n_occ; done += 8) {
-                    const int n = min(8, n_occ - done);
-                    int4 d = make_int4(0, 0, 0, 0);
-                    int tq = 0;
-                    if (lane < n) { d = pocc[first + done + lane]; tq = occt[first + done + lane]; }
-                    if (!item_round<NP, 8, kAnnounce>(st, T, lane, n, d, tq, false, r, sgd, xch_batch, xch_bytes, epoch, own, ms, o, g, gb, lam_sum, ctl,
-                                                      spins, tune))
-                        return false;
-                }
-            }
-        }
-        for (int done = 0; done < n_occ; done += 8) {
-            const int n = min(8, n_occ - done);
-            int4 d = make_int4(0, 0, 0, 0);
-            int tq = 0;
-            if (lane < n) { d = pocc[first + done + lane]; tq = occt[first + done + lane]; }
-            if (!item_round<NP, 8, M>(st, T, lane, n, d, tq, done == 0 && (SCOUT || n_occ <= 8), r, sgd, xch_batch, xch_bytes, epoch, own, ms, o, g, gb,
-                                      lam_sum, ctl, spins, tune))
-                return false;
-        }
-    }
-    if constexpr (!SCOUT) {
-        const bool l2 = (st.mode == 0);
-#pragma unroll
-        for (int e = 0; e < NE; ++e) g[e] = fmaf(lam_sum, l2 ? own[e] : sgn(own[e]), g[e]);
-        gb = fmaf((float)n_occ * st.lb, l2 ? o.b : sgn(o.b), gb);
-    }
-    return true;
-}
 
 // the new row from the old one and the gradient (TF SparseApplyRMSProp, momentum 0: single/bpr.py:100; or old/methods/bpr.py:57-61)
 template <int NP>
@@ -508,55 +300,16 @@ __device__ __forceinline__ bool own_publish(int lane, bool is_item, uint32_t bma
     return true;
 }
 
-// ---- the loader / consumer form (LOADER = true, round 5) -----------------------------------------------------------------------------
-// One wave of the workgroup -- the loader -- walks the owner queue ahead of the waves that run its tasks and copies every task's
-// record and PARTNER rows (an occurrence's user row, the other item's row and bias granule) into a ring of LDS slots by direct-to-LDS
-// loads (global_load_lds: no registers, a dozen in flight); the task's wave validates the tags it finds there (flow_task.h LdsStage)
-// and only goes to memory itself for what was not final yet when the loader asked.  The loader stays at most kLoadAhead batches in
-// front of the queue's head: further ahead, more of what it stages is stale by the time it is read.
-constexpr int kLoadSlotRows = 8;                                  // 4 occurrences x (user row, other item's row)
-constexpr int kLoadAhead = 2;
-constexpr int kLoaders = 3;                                       // loader waves per workgroup
-template <int NP>
-constexpr int load_slot_bytes() { return 128 + 64 + kLoadSlotRows * NP * 1024; }        // record | bias granules | rows (KB-aligned behind the first 192 bytes + pad)
-template <int NP>
-constexpr int load_slot_stride() { return (load_slot_bytes<NP>() + 1023) & ~1023; }
+// threads per workgroup: 12 waves at k <= 128 (<= 168 registers), 8 at k <= 256; launch bounds ask for one workgroup per CU
+constexpr int own_threads(int np) { return np == 1 ? 768 : 512; }
 
-__device__ __forceinline__ void wait_vmcnt_at_most(int n) {       // s_waitcnt takes an immediate: the loads of a slot are counted at run time
-    switch (n) {
-        case 0: asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); break;
-        case 1: asm volatile("s_waitcnt vmcnt(1)" ::: "memory"); break;
-        case 2: asm volatile("s_waitcnt vmcnt(2)" ::: "memory"); break;
-        case 3: asm volatile("s_waitcnt vmcnt(3)" ::: "memory"); break;
-        case 4: asm volatile("s_waitcnt vmcnt(4)" ::: "memory"); break;
-        case 5: asm volatile("s_waitcnt vmcnt(5)" ::: "memory"); break;
-        case 6: asm volatile("s_waitcnt vmcnt(6)" ::: "memory"); break;
-        case 7: asm volatile("s_waitcnt vmcnt(7)" ::: "memory"); break;
-        case 8: asm volatile("s_waitcnt vmcnt(8)" ::: "memory"); break;
-        case 9: asm volatile("s_waitcnt vmcnt(9)" ::: "memory"); break;
-        case 10: asm volatile("s_waitcnt vmcnt(10)" ::: "memory"); break;
-        case 11: asm volatile("s_waitcnt vmcnt(11)" ::: "memory"); break;
-        case 12: asm volatile("s_waitcnt vmcnt(12)" ::: "memory"); break;
-        case 13: asm volatile("s_waitcnt vmcnt(13)" ::: "memory"); break;
-        default: asm volatile("s_waitcnt vmcnt(14)" ::: "memory"); break;       // (a slot is at most 2 + 3 * 4 = 14 loads at k <= 128)
-    }
-}
-// 16 bytes per lane of the first `lanes` lanes, global -> LDS at dst + 16 * lane, past the L1 (sc1: the tags must be memory's)
-__device__ __forceinline__ void dma16(const void* src_lane, unsigned char* dst_wave, int lane, int lanes) {
-    if (lane < lanes)
-        __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)src_lane, (__attribute__((address_space(3))) void*)dst_wave, 16, 0, 16);
-}
-
-constexpr int own_min_waves(int np, int tpb) { return tpb / 256; }      // per SIMD: 16 waves per CU at <= 128 registers (k <= 128), 8 at <= 256
-
-// SCALAR: the item tasks of a triplet exchange scalars (one reader per occurrence of an item row: the user task; wave 0 of a
-// workgroup is the scout); else they read each other's rows like K2f (two readers; wave 0 is one more owner wave)
-template <int NP, int TPB, bool SCALAR, bool PLAN = false, bool LOADER = false>
-__global__ __launch_bounds__(TPB, own_min_waves(NP, TPB)) void bpr_own_kernel(
+template <int NP, bool PLAN = false>
+__global__ __launch_bounds__(own_threads(NP), own_threads(NP) / 256) void bpr_own_kernel(
     tkr_flow_state st, const int4* __restrict__ prec /*record 0 of the first batch to run*/, const int4* __restrict__ pocc,
     const int32_t* __restrict__ occt, const int32_t* __restrict__ ohdr /*[n_owner][ohdr_stride], at the first batch to run*/, int ohdr_stride,
     int first_batch, int nb, int B, int n_owner, int owner_waves, uint32_t tune, uint32_t* __restrict__ ctl, float* __restrict__ loss_out,
-    u64* __restrict__ xch /*scalar slots [batches of the plan][B][2], at batch 0 of the plan*/, uint32_t epoch, PlanArgs pa) {
+    u64* __restrict__ xch /*per-task loss slots [batches of the plan][B][2], at batch 0 of the plan*/, uint32_t epoch, PlanArgs pa) {
+    constexpr int TPB = own_threads(NP);
     constexpr int NE = 2 * NP;
     constexpr int KP = NP * 128;
     constexpr int ROWF = 2 * KP + 8;                                  // floats per resident row
@@ -574,22 +327,15 @@ __global__ __launch_bounds__(TPB, own_min_waves(NP, TPB)) void bpr_own_kernel(
     const bool sgd = st.opt == 1;
     const bool want_loss = loss_out != nullptr;
 
-    // ---- the workgroup's LDS: queue head | prefix sums | run starts | row tags | scout marks | rows
+    // ---- the workgroup's LDS: queue head | prefix sums | run starts | row tags | position marks | rows
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     OwnQueue* q = reinterpret_cast<OwnQueue*>(smem);
     uint32_t* pre = reinterpret_cast<uint32_t*>(smem + sizeof(OwnQueue));           // [nb + 1 + 64]
     uint32_t* start = pre + nb + 1 + TKR_WAVE;                                         // [nb]
     const int rows_here = (st.n_items + n_owner - 1) / n_owner;
     uint32_t* tags = start + nb;                                                       // [rows_here]
-    uint32_t* dotmark = tags + rows_here;                                              // [kDotWin]: position + 1 of the task whose scalars are out
+    uint32_t* dotmark = tags + rows_here;                                              // [kDotWin]: position + 1 of the task that has run
     float* rows = reinterpret_cast<float*>(smem + ((sizeof(OwnQueue) + (size_t)4 * (2 * nb + 1 + TKR_WAVE + rows_here + kDotWin) + 15) & ~(size_t)15));
-    // LOADER: ring_slots slots of partner rows behind the resident rows (KB-aligned), their ready / freed words behind the ring
-    unsigned char* ring = reinterpret_cast<unsigned char*>((reinterpret_cast<uintptr_t>(rows + (size_t)rows_here * ROWF) + 1023) & ~(uintptr_t)1023);
-    const int ring_slots = LOADER ? (int)((tune >> 8) & 0xffu) : 0;                     // (the host sizes the LDS: own_lds_bytes_loader)
-    const uint32_t load_ahead = LOADER ? (tune >> 16) : 0u;                             // batches the loaders may run in front of the queue's head
-    const int n_loaders = LOADER ? min(kLoaders, owner_waves) : 0;                      // of the owner_waves + 1 waves on the owner queue: at least one runs tasks
-    volatile uint32_t* ring_ready = reinterpret_cast<volatile uint32_t*>(ring + (size_t)ring_slots * load_slot_stride<NP>());   // position + 1 staged in the slot
-    volatile uint32_t* ring_freed = ring_ready + ring_slots;                            // position + 1 whose task has taken the slot's contents
 
     // owner number = workgroup number (every workgroup is resident: which CU it sits on means nothing).  The first ticket of a user-task
     // wave goes out NOW, beside the loads of the queue header: a launch used to start with three trips in series -- an arrival
@@ -607,9 +353,6 @@ __global__ __launch_bounds__(TPB, own_min_waves(NP, TPB)) void bpr_own_kernel(
     for (int b = threadIdx.x; b < TKR_WAVE; b += TPB) pre[nb + 1 + b] = 0xffffffffu;
     for (int s = threadIdx.x; s < rows_here; s += TPB) tags[s] = kOwnInvalid;
     for (int s = threadIdx.x; s < kDotWin; s += TPB) dotmark[s] = 0u;
-    if constexpr (LOADER) {
-        for (int s = threadIdx.x; s < 2 * ring_slots; s += TPB) lds_poke(ring_ready + s, 0u);
-    }
     if constexpr (PLAN) {
         static_assert(TPB == kWideThreads, "phase B of the planner is one thread per task slot");
         unsigned char* scratch = reinterpret_cast<unsigned char*>(rows);                 // the rows' region: no row is resident yet
@@ -702,14 +445,12 @@ __global__ __launch_bounds__(TPB, own_min_waves(NP, TPB)) void bpr_own_kernel(
 
     PLAN_STAMP(10);
     uint32_t spins = 0;
-    uint32_t ld_ready_spins = 0, ld_tasks = 0, ld_block_spins = 0, ld_fallback = 0;      // LOADER: diagnostics (scripts/probe_own.py)
 #ifdef TKR_OWN_PROF
     u64 prof[16] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
     u64 tprev = __builtin_amdgcn_s_memtime();
 #endif
     const QueueMap qm{pre, start, 3u * (uint32_t)B};
     const __amdgpu_buffer_rsrc_t prec_r = row_rsrc(prec, PLAN ? nb * 3 * B * 128 : 16);
-    const int xch_bytes = B * 16;
     const uint32_t q_total = q->total;
 
     // the own row of the item task whose record is w
@@ -732,125 +473,8 @@ __global__ __launch_bounds__(TPB, own_min_waves(NP, TPB)) void bpr_own_kernel(
         r.rd_val = 0u;
     };
 
-    constexpr uint32_t kItemReaders = SCALAR ? 1u : 2u;
-    if (SCALAR && wave == 0) {
-        // ================= the scout: scalars of the tasks ahead of the queue's head, as soon as their rows are final =================
-        uint32_t hpos = 0, hcur = 0;
-        int idle = 0;
-        const uint32_t ahead = (uint32_t)kScoutAhead;
-        for (;;) {
-            const uint32_t head = lds_peek(&q->head);
-            if (head >= q_total) break;
-            if ((idle & 63) == 63 && ld_u32(ctl + kCtlStatus) != 0u) break;          // somebody gave up
-            if (hpos < head || hpos >= q_total || hpos >= head + ahead) {              // (re)start at the head: what was skipped may be final now
-                if (hpos >= head && idle) __builtin_amdgcn_s_sleep(16);               // a whole window without work
-                hpos = head;
-                hcur = lds_peek(&q->head_batch);
-                idle = idle < (1 << 20) ? idle + 1 : idle;
-                if (hpos >= q_total) continue;
-            }
-            const uint32_t pos = hpos++;
-            if (lds_peek(&dotmark[pos & (kDotWin - 1)]) == pos + 1u) continue;
-            const uint32_t idx = qm.locate(pos, hcur, lane);
-            int4 w = make_int4(0, 0, 0, 0);
-            if (lane < 8) w = prec[(size_t)idx * 8 + lane];
-            ItemRow r;
-            int row, slot;
-            item_row(w, r, row, slot);
-            const int n_occ = bcast_i(w.z, 0), first = bcast_i(w.w, 0), batch = bcast_i(w.x, 1);
-            float own[NE], ms[NE], g[NE];
-            Own o = {};
-            float gb = 0.f;
-            if (item_task<NP, true>(st, T, lane, n_occ, first, w, pocc, occt, r, sgd, xch + (size_t)batch * B * 2, xch_bytes, epoch, own, ms, o, g, gb,
-                                    ctl, spins, tune)) {
-                if (lane == 0) dotmark[pos & (kDotWin - 1)] = pos + 1u;
-                idle = 0;
-            }
-        }
-    } else if (LOADER && wave > owner_waves - n_loaders && wave <= owner_waves) {
-        // ================= the loaders: partner rows of the queue's next tasks -> LDS =================
-        // (kLoaders waves, positions dealt round robin: one wave's turn is a record through the scalar cache -- a trip of its own --
-        // before it can address the rows; a single loader staged 0.4 tasks per us where the queue wants 0.8)
-        constexpr int SLOTB = load_slot_stride<NP>();
-        uint32_t lcur = 0;
-        int prev_slot = -1;
-        uint32_t prev_pos = 0;
-        uint32_t waited = 0;
-        for (uint32_t pos = (uint32_t)(owner_waves - wave); pos < q_total; pos += (uint32_t)n_loaders) {
-            const int slot = (int)(pos % (uint32_t)ring_slots);
-            const uint32_t idx = qm.locate(pos, lcur, lane);
-            // the slot is free (the task ring_slots positions back took its contents), and the head is not more than kLoadAhead batches behind
-            bool gave_up = false;
-            // (... unless a wave already waits for this very position: an owner whose tasks are batches apart must not wait for a head
-            // that waits for it)
-            auto blocked = [&]() {
-                return (pos >= (uint32_t)ring_slots && lds_peek(ring_freed + slot) != pos - (uint32_t)ring_slots + 1u) ||
-                       (lcur > lds_peek(&q->head_batch) + load_ahead &&
-                        pos >= lds_peek(&q->head));
-            };
-            if (blocked()) {
-                // before this wave waits for the queue, the slot it filled last goes out: the task that waits for THAT slot may be the
-                // one the queue is waiting for (first version: published only behind the next slot's loads -- with three task waves the
-                // workgroup locked up, with seven it merely stalled)
-                if (prev_slot >= 0) {
-                    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-                    if (lane == 0) lds_poke(ring_ready + prev_slot, prev_pos + 1u);
-                    prev_slot = -1;
-                }
-                while (blocked()) {
-                    __builtin_amdgcn_s_sleep(2);
-                    if (spin_fail(waited, ctl, 0)) { gave_up = true; break; }
-                }
-            }
-            if (gave_up) break;
-            unsigned char* sl = ring + (size_t)slot * SLOTB;
-            // the record: to the slot for the task's wave, and through the scalar cache for this wave's own addressing
-            const int4* rp = prec + (size_t)__builtin_amdgcn_readfirstlane((int)idx) * 8;
-            const int4 h0 = rp[0];
-            int loads = 1;
-            dma16(reinterpret_cast<const unsigned char*>(rp) + lane * 16, sl, lane, 8);
-            const int n_occ = h0.z;
-            {   // the acknowledge word of the task's own row (the buffer version ver + 1 will take): 4 bytes, lane 0
-                const int row_o = h0.x & 0x7fffffff;
-                const uint32_t ver_o = (uint32_t)h0.y;
-                const uint32_t* rdw = T.rdV + (T.imask + 1u) * (size_t)row_o + ((ver_o + 1u) & T.imask);
-                if (lane == 0)
-                    __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)rdw, (__attribute__((address_space(3))) void*)(sl + 192), 4, 0, 16);
-                loads += 1;
-            }
-            if (n_occ >= 1 && n_occ <= 4) {
-                const int4 oc[4] = {rp[2], rp[3], rp[4], rp[5]};
-#pragma unroll
-                for (int qo = 0; qo < 4; ++qo) {
-                    if (qo < n_occ) {                              // (a, version of a, b | role << 31, version of b): a = user, b = the other item
-                        const int a = oc[qo].x, b = oc[qo].z & 0x3fffffff;
-                        const uint32_t va = (uint32_t)oc[qo].y, vb = (uint32_t)oc[qo].w;
-                        const u64* ua = T.U + (va & 1u) * T.ustride + (size_t)a * T.kp;
-                        const u64* vbp = T.V + (vb & T.imask) * T.istride + (size_t)b * T.kp;
-                        const u64* tb = T.tailV + ((size_t)(vb & T.imask) * st.n_items + b) * (2 * (size_t)tail_halves(T.imask));
-#pragma unroll
-                        for (int c = 0; c < NP; ++c) {
-                            dma16(reinterpret_cast<const unsigned char*>(ua) + c * 1024 + lane * 16, sl + 1024 + ((2 * qo) * NP + c) * 1024, lane, 64);
-                            dma16(reinterpret_cast<const unsigned char*>(vbp) + c * 1024 + lane * 16, sl + 1024 + ((2 * qo + 1) * NP + c) * 1024, lane, 64);
-                        }
-                        dma16(reinterpret_cast<const unsigned char*>(tb), sl + 128 + 16 * qo, lane, 1);     // {bias, tag, its slot, tag}: the first granule is what a task reads
-                        loads += 2 * NP + 1;
-                    }
-                }
-            }
-            // the slot BEFORE this one is complete once at most this slot's loads are outstanding (loads return in order)
-            if (prev_slot >= 0) {
-                wait_vmcnt_at_most(loads);
-                if (lane == 0) lds_poke(ring_ready + prev_slot, prev_pos + 1u);
-            }
-            prev_slot = slot;
-            prev_pos = pos;
-        }
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-        if (prev_slot >= 0 && lane == 0) lds_poke(ring_ready + prev_slot, prev_pos + 1u);
-        spins += waited;
-        ld_block_spins += waited;
-    } else if (wave <= owner_waves) {                                                  // (SCALAR: waves 1 .. owner_waves; else 0 .. owner_waves; LOADER: 0 .. owner_waves - kLoaders)
+    constexpr uint32_t kItemReaders = 2u;                         // an occurrence's user task and its other item's task read an item row
+    if (wave <= owner_waves) {
         // ================= item tasks of the rows this workgroup owns =================
         uint32_t cur = 0;
         while (alive) {
@@ -861,36 +485,7 @@ __global__ __launch_bounds__(TPB, own_min_waves(NP, TPB)) void bpr_own_kernel(
             const uint32_t idx = qm.locate(pos, cur, lane);
             if (lane == 0) atomicMax(&q->head_batch, cur);
             int4 w = make_int4(0, 0, 0, 0);
-            LdsStage stg = {nullptr, nullptr, nullptr, 0u};
-            uint32_t staged_rd = 0u;
-            if constexpr (LOADER) {
-                // the loader has (or will have) this position's record and partner rows in slot pos % ring_slots
-                const int rslot = (int)(pos % (uint32_t)ring_slots);
-                unsigned char* sl = ring + (size_t)rslot * load_slot_stride<NP>();
-                uint32_t waited = 0;
-                while (lds_peek(ring_ready + rslot) != pos + 1u) {
-#if TKR_TAG_NAP > 0
-                    __builtin_amdgcn_s_sleep(TKR_TAG_NAP);
-#endif
-                    if (spin_fail(waited, ctl, 0)) { alive = false; break; }
-                }
-                if (!alive) break;
-                spins += waited;
-                ld_ready_spins += waited;
-                ld_tasks += 1u;
-                asm volatile("" ::: "memory");
-                if (lane < 8) { const v4u rw = *(const lds_v4u_t*)(sl + lane * 16); w = make_int4((int)rw.x, (int)rw.y, (int)rw.z, (int)rw.w); }
-                staged_rd = lds_peek(reinterpret_cast<const volatile uint32_t*>(sl + 192));
-                const int n_st = bcast_i(w.z, 0);
-                if (n_st >= 1 && n_st <= 4) {
-                    stg = LdsStage{sl + 1024, sl + 128, ring_freed + rslot, pos + 1u};
-                } else {
-                    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-                    if (lane == 0) lds_poke(ring_freed + rslot, pos + 1u);   // nothing staged beyond the record
-                }
-            } else {
-                if (lane < 8) w = plan_ld<PLAN>(prec, prec_r, (size_t)idx * 8 + lane);
-            }
+            if (lane < 8) w = plan_ld<PLAN>(prec, prec_r, (size_t)idx * 8 + lane);
 #ifdef TKR_OWN_PROF
             asm volatile("" : "+v"(w.x) :: "memory");
             const u64 t0 = __builtin_amdgcn_s_memtime();
@@ -899,10 +494,9 @@ __global__ __launch_bounds__(TPB, own_min_waves(NP, TPB)) void bpr_own_kernel(
             ItemRow r;
             int row, slot;
             item_row(w, r, row, slot);
-            if constexpr (LOADER) { r.rd_staged = true; r.rd_val = staged_rd; }
             const int rowk = bcast_i(w.x, 0);
             const uint32_t ver = r.ver;
-            const int n_occ = bcast_i(w.z, 0), first = bcast_i(w.w, 0), batch = bcast_i(w.x, 1);
+            const int n_occ = bcast_i(w.z, 0), first = bcast_i(w.w, 0);
             const size_t woff = (size_t)((ver + 1u) & T.imask) * T.istride + (size_t)row * T.kp;
             float* lrow = rows + (size_t)slot * ROWF;
 
@@ -911,26 +505,17 @@ __global__ __launch_bounds__(TPB, own_min_waves(NP, TPB)) void bpr_own_kernel(
             for (int e = 0; e < NE; ++e) { g[e] = 0.f; ms[e] = 0.f; }
             Own o = {};
             float gb = 0.f;
-            const uint32_t spins_before = spins;
-            if constexpr (SCALAR) {
-                alive = item_task<NP, false>(st, T, lane, n_occ, first, w, pocc, occt, r, sgd, xch + (size_t)batch * B * 2, xch_bytes, epoch, own, ms, o,
-                                             g, gb, ctl, spins, tune);
-            } else {
-                o.ok = r.from_lds;                                       // flow_fetch then leaves the own row alone
-                NextTask nx;
-                nx.idx = 0u; nx.w = make_int4(0, 0, 0, 0); nx.have = true;
-                NoFeed feed;
-                LdsOwnStep<NP> own_step{T, lane, r, sgd, ctl, spins};
-                float loss_lane = 0.f;
-                if constexpr (LOADER)
-                    alive = run_task<NP, true, NoFeed, LdsOwnStep<NP>, 4, LdsStage>(st, T, lane, n_occ, first, w, pocc, r.own_p, r.own_ms, r.own_tail, ver,
-                                                                                    own, ms, o, g, gb, loss_lane, false, sgd, ctl, spins, nx, feed, own_step, stg);
-                else
-                    alive = run_task<NP, true, NoFeed, LdsOwnStep<NP>, 4>(st, T, lane, n_occ, first, w, pocc, r.own_p, r.own_ms, r.own_tail, ver, own, ms, o,
-                                                                          g, gb, loss_lane, false, sgd, ctl, spins, nx, feed, own_step);
-            }
+            o.ok = r.from_lds;                                           // flow_fetch then leaves the own row alone
+            NextTask nx;
+            nx.idx = 0u; nx.w = make_int4(0, 0, 0, 0); nx.have = true;
+            NoFeed feed;
+            LdsOwnStep<NP> own_step{T, lane, r, sgd, ctl, spins};
+            float loss_lane = 0.f;
+            alive = run_task<NP, true, NoFeed, LdsOwnStep<NP>, 4>(st, T, lane, n_occ, first, w, pocc, r.own_p, r.own_ms, r.own_tail, ver, own, ms, o, g,
+                                                                  gb, loss_lane, false, sgd, ctl, spins, nx, feed, own_step);
             if (!alive) break;
-            if constexpr (LOADER && !SCALAR) { if (spins != spins_before) ld_fallback += 1u; }
+            // (the position marks and head_batch were read by the scout of the scalar-exchange form; the marks' words stay in the LDS
+            // budget, which sets the item counts K2o takes)
             if (lane == 0) dotmark[pos & (kDotWin - 1)] = pos + 1u;
 #ifdef TKR_OWN_PROF
             const u64 t1 = __builtin_amdgcn_s_memtime();
@@ -958,8 +543,7 @@ __global__ __launch_bounds__(TPB, own_min_waves(NP, TPB)) void bpr_own_kernel(
                                     mn, bn, mbn, ctl, spins, kItemReaders);
 #ifdef TKR_OWN_PROF
             tprev = __builtin_amdgcn_s_memtime();
-            if constexpr (SCALAR) prof[0] += t1 - t0;
-            else { prof[0] += o.t_own0 - t0; prof[1] += o.t_own1 - o.t_own0; prof[2] += t1 - o.t_own1; }
+            prof[0] += o.t_own0 - t0; prof[1] += o.t_own1 - o.t_own0; prof[2] += t1 - o.t_own1;
             prof[3] += o.t_ack - t1; prof[4] += tprev - o.t_ack; prof[6] += 1; prof[7] += r.from_lds ? 1 : 0;
 #endif
         }
@@ -1017,13 +601,11 @@ __global__ __launch_bounds__(TPB, own_min_waves(NP, TPB)) void bpr_own_kernel(
             if (want_loss) {
                 // A batch's loss is the sum over its ~250 user tasks.  As atomics on loss_out[batch] -- one word, one memory channel --
                 // they cost 0.9 us of a 2.2 us batch (hardware fp32 atomics or a compare-and-swap loop alike: each is a memory
-                // operation that the next task's first load waits behind).  The row-read form leaves `xch` alone: the task's sum goes
-                // there as ONE plain 8-byte store {sum, epoch} in the slot of its record, and own_loss_kernel adds the slots of a batch
-                // up after the launch (fixed order: the losses are bitwise reproducible).
+                // operation that the next task's first load waits behind).  Instead the task's sum goes to `xch` as ONE plain 8-byte
+                // store {sum, epoch} in the slot of its record, and own_loss_kernel adds the slots of a batch up after the launch (fixed
+                // order: the losses are bitwise reproducible).
                 const float tot = wave_sum(loss_lane);
-                if constexpr (SCALAR) {
-                    if (lane == 0) loss_add(loss_out + batch, tot);
-                } else if (lane == 0) {
+                if (lane == 0) {
                     const uint32_t slot = idx - (uint32_t)(batch - first_batch) * 3u * (uint32_t)B;     // user tasks: the first slots of a batch's 3B
                     // (write-through: the workgroup that adds the slots up -- own_loss_kernel, or the LAST one of this launch -- may sit on another XCD)
                     __hip_atomic_store(xch + ((size_t)batch * B + slot) * 2, ((u64)epoch << 32) | (u64)__float_as_uint(tot), __ATOMIC_RELAXED,
@@ -1043,12 +625,6 @@ __global__ __launch_bounds__(TPB, own_min_waves(NP, TPB)) void bpr_own_kernel(
     }
 
     if (lane == 0 && spins) atomicAdd(ctl + kCtlSpins, spins);
-    if constexpr (LOADER) {
-        if (lane == 0) {
-            atomicAdd(ctl + kCtlProf + 64, ld_tasks); atomicAdd(ctl + kCtlProf + 65, ld_ready_spins);
-            atomicAdd(ctl + kCtlProf + 66, ld_block_spins); atomicAdd(ctl + kCtlProf + 67, ld_fallback);
-        }
-    }
 #ifdef TKR_OWN_PROF
     if (lane == 0)
         for (int qq = 0; qq < 16; ++qq) atomicAdd(reinterpret_cast<u64*>(ctl + kCtlProf) + qq, prof[qq]);
@@ -1060,7 +636,7 @@ __global__ __launch_bounds__(TPB, own_min_waves(NP, TPB)) void bpr_own_kernel(
     if constexpr (PLAN) {
         if (commit_key != -1) plan_commit_first_touch(make_int4(commit_key, 0, 0, 0), -1, commit_total, pa.ucnt, pa.icnt, pa.touch_u, pa.touch_i);
     }
-    const bool fold_loss = !SCALAR && want_loss && (tune & 8u) != 0u;       // tune bit 3 (set by the host for short launches): the last workgroup out adds the losses up
+    const bool fold_loss = want_loss && (tune & 8u) != 0u;       // tune bit 3 (set by the host for short launches): the last workgroup out adds the losses up
     if (threadIdx.x == 0) {
         const bool last = __hip_atomic_fetch_add(ctl + kCtlLeave, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) == gridDim.x - 1u;
         if (last) {
@@ -1116,18 +692,6 @@ static size_t own_lds_bytes(int np, int nb, int n_items, int n_owner) {
     return head + (size_t)rows_here * (2 * np * 128 + 8) * 4;
 }
 
-// ... with the loader's ring of `slots` slots behind the rows (KB-aligned) and the slots' ready / freed words
-static size_t own_lds_bytes_loader(int np, int nb, int n_items, int n_owner, int slots) {
-    const size_t base = (own_lds_bytes(np, nb, n_items, n_owner) + 1023) & ~(size_t)1023;
-    const size_t stride = np == 1 ? load_slot_stride<1>() : load_slot_stride<2>();
-    return base + (size_t)slots * stride + (size_t)slots * 8 + 16;
-}
-static int own_loader_slots(int np, int nb, int n_items, int n_owner) {            // as many as fit, at most 16; fewer than 4: no loader form
-    int slots = 16;
-    while (slots >= 4 && own_lds_bytes_loader(np, nb, n_items, n_owner, slots) > 160 * 1024) --slots;
-    return slots >= 4 ? slots : 0;
-}
-
 // ... with the planner prologue: its scratch (phase A: sort keys + scan; phase B: the batch's occurrences, owner bitmaps) lies over the
 // rows' region, which may be smaller (test shapes)
 static size_t own_lds_bytes_planned(int np, int nb, int n_items, int n_owner, int B, int npad_items, int own_words) {
@@ -1175,7 +739,7 @@ static int own_launch(const tkr_flow_state* st, const int32_t* prec, const int32
     int dev = 0;
     TKR_CHECK(hipGetDevice(&dev));
     static int cached_cus[64];
-    static bool attr_set[64][6][2];
+    static bool attr_set[64][3];
     int cus;
     if (dev >= 0 && dev < 64 && cached_cus[dev] > 0) cus = cached_cus[dev];
     else {
@@ -1188,78 +752,49 @@ static int own_launch(const tkr_flow_state* st, const int32_t* prec, const int32
     if (lds > 160 * 1024) return TKR_EUNSUPPORTED;
     const uint32_t tune = ((uint32_t)owner_waves >> 8) & 0xffu;     // experiment switches ride in bits 8..15
     owner_waves &= 0xff;
-    const bool wide = np == 1 && (tune & 64u) != 0u;                 // tune bit 6: 16 waves per workgroup (k <= 128: <= 128 registers) instead of 8
-    const bool mid = np == 1 && !wide && (tune & 32u) == 0u;          // k <= 128: 12 waves (<= 168 registers) unless tune bit 5 asks for 8
-    const int tpb = wide ? 1024 : mid ? 768 : 512;
+    // owner_waves bits 8 and 15 asked for the loader / consumer ring and the scalar exchange, bits 13 and 14 for 8 and 16 waves at
+    // k <= 128: forms that were measured and lost, no longer built
+    if ((tune & (1u | 128u)) || (np == 1 && (tune & (32u | 64u)))) return TKR_EUNSUPPORTED;
+    if (pa && np != 1) return TKR_EINVAL;
+    const int tpb = tkr::own_threads(np);
     const int waves = tpb / TKR_WAVE;
-    // one scout, `ow` waves on the owner queue, the rest on user tickets
-    int ow = owner_waves > 0 ? owner_waves : (waves == 16 ? 9 : waves == 12 ? 9 : 6);
+    // `ow` waves on the owner queue (waves 0 .. ow), the rest on user tickets
+    int ow = owner_waves > 0 ? owner_waves : (waves == 12 ? 9 : 6);
     if (ow < 1) ow = 1;
     if (ow > waves - 2) ow = waves - 2;
-    const bool scalar = (tune & 128u) != 0u;                         // tune bit 7: the scalar-exchange form of the item tasks (default: they read rows)
-    if (pa && !(mid && !scalar)) return TKR_EINVAL;
     // a short launch adds its losses up itself (its last workgroup out); tune bit 1 (owner_waves bit 9): always own_loss_kernel
-    const bool fold = loss_out && !scalar && n_batches <= 64 && !(tune & 2u);
-    // tune bit 0 (owner_waves bit 8): the loader / consumer form (k <= 128, 12 waves, row-read item tasks, no planner prologue) where
-    // at least four slots of partner rows fit behind the owner's rows
-    const int ring_slots = ((tune & 1u) && mid && !scalar && !pa) ? tkr::own_loader_slots(np, n_batches, st->n_items, n_owner) : 0;
-    if (ring_slots) lds = tkr::own_lds_bytes_loader(np, n_batches, st->n_items, n_owner, ring_slots);
-    static const int ahead_env = getenv("TKR_OWN_AHEAD") ? atoi(getenv("TKR_OWN_AHEAD")) : 0;       // tuning aid
-    const uint32_t ktune = (tune & ~8u & 0xffu) | (fold ? 8u : 0u) | ((uint32_t)ring_slots << 8) | ((uint32_t)(ahead_env > 0 ? ahead_env : tkr::kLoadAhead) << 16);
-#ifdef TKR_LAB
-    const void* fn = pa ? (const void*)tkr::bpr_own_kernel<1, 768, false, true>
-                   : ring_slots ? (const void*)tkr::bpr_own_kernel<1, 768, false, false, true>
-                   : np == 1 ? (wide ? (scalar ? (const void*)tkr::bpr_own_kernel<1, 1024, true> : (const void*)tkr::bpr_own_kernel<1, 1024, false>)
-                                : mid ? (scalar ? (const void*)tkr::bpr_own_kernel<1, 768, true> : (const void*)tkr::bpr_own_kernel<1, 768, false>)
-                                     : (scalar ? (const void*)tkr::bpr_own_kernel<1, 512, true> : (const void*)tkr::bpr_own_kernel<1, 512, false>))
-                             : (scalar ? (const void*)tkr::bpr_own_kernel<2, 512, true> : (const void*)tkr::bpr_own_kernel<2, 512, false>);
-#else
-    // the default library holds the forms that run by default -- 12 waves and row-read item tasks at k <= 128 (with and without the planner
-    // prologue), 8 waves at k <= 256; the forms that were measured and lost (scalar exchange + scout, 16 and 8 waves at k <= 128, the
-    // loader / consumer ring: DESIGN.md section 4, K2o table) are built by `make LAB=1` only
-    if (scalar || wide || (np == 1 && !mid) || (tune & 1u)) return TKR_EUNSUPPORTED;
-    const void* fn = pa ? (const void*)tkr::bpr_own_kernel<1, 768, false, true>
-                   : np == 1 ? (const void*)tkr::bpr_own_kernel<1, 768, false> : (const void*)tkr::bpr_own_kernel<2, 512, false>;
-#endif
-    const int variant = pa ? 4 : ring_slots ? 5 : np == 2 ? 3 : wide ? 2 : mid ? 1 : 0;
-    if (lds > 64 * 1024 && !(dev >= 0 && dev < 64 && attr_set[dev][variant][scalar])) {
+    const bool fold = loss_out && n_batches <= 64 && !(tune & 2u);
+    const uint32_t ktune = (tune & ~8u) | (fold ? 8u : 0u);
+    const void* fn = pa ? (const void*)tkr::bpr_own_kernel<1, true>
+                   : np == 1 ? (const void*)tkr::bpr_own_kernel<1, false> : (const void*)tkr::bpr_own_kernel<2, false>;
+    const int form = pa ? 2 : np - 1;
+    if (lds > 64 * 1024 && !(dev >= 0 && dev < 64 && attr_set[dev][form])) {
         TKR_CHECK(hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-        if (dev >= 0 && dev < 64) attr_set[dev][variant][scalar] = true;
+        if (dev >= 0 && dev < 64) attr_set[dev][form] = true;
     }
     // every owner must be RESIDENT (the dataflow inside a launch waits for workgroups that have to be running): asked of the runtime
     // once per kernel form and device, at the largest LDS size a launch may ask for (K2f had the query, K2o did not)
-    static signed char fits[64][6][2];
-    if (dev >= 0 && dev < 64 && fits[dev][variant][scalar] == 0) {
+    static signed char fits[64][3];
+    if (dev >= 0 && dev < 64 && fits[dev][form] == 0) {
         int per_cu = 0;
         TKR_CHECK(hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, fn, tpb, 160 * 1024));
-        fits[dev][variant][scalar] = per_cu >= 1 ? 1 : -1;
+        fits[dev][form] = per_cu >= 1 ? 1 : -1;
     }
-    if (dev >= 0 && dev < 64 && fits[dev][variant][scalar] < 0) return TKR_EUNSUPPORTED;
+    if (dev >= 0 && dev < 64 && fits[dev][form] < 0) return TKR_EUNSUPPORTED;
     hipStream_t s = (hipStream_t)stream;
     const int4* r4 = reinterpret_cast<const int4*>(prec) + (size_t)first_batch * 3 * batch_size * 8;      // record 0 of the first batch to run
     const int4* o4 = reinterpret_cast<const int4*>(pocc);
     ohdr += first_batch;
     const tkr::PlanArgs no_plan = {};
-#define TKR_OWN_LAUNCH(NPV, TPBV, SC, PL)                                                                                                 \
-    hipLaunchKernelGGL((tkr::bpr_own_kernel<NPV, TPBV, SC, PL>), dim3(n_owner), dim3(TPBV), lds, s, *st, r4, o4, occt, ohdr, ohdr_stride, first_batch, \
-                       n_batches, batch_size, n_owner, ow, ktune, ctl, loss_out, static_cast<tkr::u64*>(xch), epoch, PL ? *pa : no_plan)
-#ifdef TKR_LAB
-    if (pa) TKR_OWN_LAUNCH(1, 768, false, true);
-    else if (ring_slots)
-        hipLaunchKernelGGL((tkr::bpr_own_kernel<1, 768, false, false, true>), dim3(n_owner), dim3(768), lds, s, *st, r4, o4, occt, ohdr, ohdr_stride,
-                           first_batch, n_batches, batch_size, n_owner, ow, ktune, ctl, loss_out, static_cast<tkr::u64*>(xch), epoch, no_plan);
-    else if (np == 1 && wide) { if (scalar) TKR_OWN_LAUNCH(1, 1024, true, false); else TKR_OWN_LAUNCH(1, 1024, false, false); }
-    else if (np == 1 && mid) { if (scalar) TKR_OWN_LAUNCH(1, 768, true, false); else TKR_OWN_LAUNCH(1, 768, false, false); }
-    else if (np == 1) { if (scalar) TKR_OWN_LAUNCH(1, 512, true, false); else TKR_OWN_LAUNCH(1, 512, false, false); }
-    else { if (scalar) TKR_OWN_LAUNCH(2, 512, true, false); else TKR_OWN_LAUNCH(2, 512, false, false); }
-#else
-    if (pa) TKR_OWN_LAUNCH(1, 768, false, true);
-    else if (np == 1) TKR_OWN_LAUNCH(1, 768, false, false);
-    else TKR_OWN_LAUNCH(2, 512, false, false);
-#endif
+#define TKR_OWN_LAUNCH(NPV, PL)                                                                                                           \
+    hipLaunchKernelGGL((tkr::bpr_own_kernel<NPV, PL>), dim3(n_owner), dim3(tkr::own_threads(NPV)), lds, s, *st, r4, o4, occt, ohdr, ohdr_stride,   \
+                       first_batch, n_batches, batch_size, n_owner, ow, ktune, ctl, loss_out, static_cast<tkr::u64*>(xch), epoch, PL ? *pa : no_plan)
+    if (pa) TKR_OWN_LAUNCH(1, true);
+    else if (np == 1) TKR_OWN_LAUNCH(1, false);
+    else TKR_OWN_LAUNCH(2, false);
 #undef TKR_OWN_LAUNCH
     TKR_LAUNCH_CHECK();
-    if (loss_out && !scalar && !fold) {
+    if (loss_out && !fold) {
         hipLaunchKernelGGL(tkr::own_loss_kernel, dim3(n_batches), dim3(256), 0, s, static_cast<const tkr::u64*>(xch), first_batch, batch_size, epoch,
                            loss_out);
         TKR_LAUNCH_CHECK();

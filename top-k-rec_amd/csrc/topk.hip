@@ -32,24 +32,6 @@
 #include "topk_refine.h"
 #include "../../include/tkr.h"
 
-#ifndef TKR_ABL
-#define TKR_ABL 0      // timing experiments only (scripts/ablate_topk.sh): 1 no filter, 2 no staging, 4 no per-tile barrier, 8 no on-demand trims, 16 no scheduled trims, 32 no appends, 64 no final stage of the refine kernel, 256 per-phase cycle counters (tkr_k4_prof_read)
-#endif
-
-#if TKR_ABL & 256
-// cycle sums per phase of the bf16 / refine tile loop, all waves: [0] MFMA chain + bias, [1] staging, [2] barrier, [3] scheduled
-// trims, [4] filter, [5] prologue (operands, first tile), [6] final stage, [7] wave-tiles.  scripts/probe_topk_phases.py reads them.
-__device__ unsigned long long g_k4_prof[8];
-#define K4_MARK(i)                                                           \
-    {                                                                        \
-        const unsigned long long n_ = __builtin_amdgcn_s_memtime();          \
-        k4p[i] += n_ - k4t;                                                  \
-        k4t = n_;                                                            \
-    }
-#else
-#define K4_MARK(i)
-#endif
-
 namespace tkr {
 
 template <typename IdT>
@@ -275,9 +257,6 @@ __device__ __forceinline__ void filter_tile(const TopkSmem<IdT>& sm, const f32x1
 #pragma unroll
     for (int r = 0; r < 16; ++r) { hr[r] = __ballot(sc[r] >= thr); any |= hr[r]; }
     if (!any) return;
-#if TKR_ABL & 32
-    if (any != 12345u) return;
-#endif
     uint32_t hits = 0;                                           // bit r: register r of this lane is a candidate
 #pragma unroll
     for (int r = 0; r < 16; ++r) hits |= (sc[r] >= thr) ? (1u << r) : 0u;
@@ -288,7 +267,6 @@ __device__ __forceinline__ void filter_tile(const TopkSmem<IdT>& sm, const f32x1
     int pos = 0;
     const int n_mine = __popc(hits);
     if (hits) pos = atomicAdd(&sm.cnt[uw], n_mine);              // one LDS atomic per lane reserves all its slots
-#if !(TKR_ABL & 512)
     if (__ballot(pos + n_mine > kCap) == 0) {
         // Every reservation of the wave fits (the rule; an overflow takes the general loop below).  The filter is bound by
         // instruction issue, and the general visit is ~25 issued instructions for the one or two lanes that hold a candidate in a
@@ -302,7 +280,6 @@ __device__ __forceinline__ void filter_tile(const TopkSmem<IdT>& sm, const f32x1
         else FastVisit<IdT, REFINE, true, 0>::run(hr, hits, sc, as, ai, ss, si, col0);
         return;
     }
-#endif
 #pragma unroll
     for (int r = 0; r < 16; ++r)
         if (hr[r]) {                                             // scalar branch: most registers hold no candidate
@@ -320,9 +297,6 @@ __device__ __forceinline__ void filter_tile(const TopkSmem<IdT>& sm, const f32x1
     // rare: some user's list overflowed.  Exact trim of that user (keeps K, raises the threshold), then its
     // lanes append what still qualifies: at most 32 per user and tile, K + 32 <= kCap.
     uint64_t ov = __ballot(unplaced != 0);
-#if TKR_ABL & 8
-    ov = 0;
-#endif
     while (ov) {
         const int u = (__ffsll((long long)ov) - 1) & 31;
         float nt;
@@ -826,32 +800,19 @@ __global__ __launch_bounds__(256) void score_topk_slab_kernel(
     write_rows<IdT>(sm, ws, n_rows, K, thr, out_ids, out_scores, part);
 }
 
-// ---- K4 on the dense matrix pipe: 6-product bf16 split of the fp32 factors ------------------------------------
-// Every fp32 factor is split EXACTLY into three bf16 parts a = a1 + a2 + a3 (8 significant bits each, round to
-// nearest at each step; bf16 has fp32's exponent range).  The product a*b is taken as the six partial products
-// a1b1 + a1b2 + a2b1 + a1b3 + a2b2 + a3b1 (the dropped a2b3, a3b2, a3b3 are below 2^-23 |ab|), each EXACT in fp32
-// (8 x 8 significant bits), accumulated in fp32 by v_mfma_f32_32x32x16_bf16 -- the rounding behaviour of an fp32
-// dot product with a different summation order (measured error against fp64: same order as the fp32-MFMA path and as
-// numpy's sgemm, tests/test_gpu_topk.py).  Inputs whose products and partial sums are representable (the golden
-// fixtures) give exactly the same scores as the fp32 path.  Why: 48 bf16 MFMAs of 8 passes replace 64 fp32 MFMAs of
-// 16 passes per 32x32xk=128 block (1.8 us against 3.4 us per 256-user tile, scripts/ubench/bf16x3_ubench.hip), and on
-// gfx950 the fp32 MFMA does not overlap other work of the SIMD at all.  Finite inputs only (inf - inf in the split).
-__device__ __forceinline__ void split3(float a, __bf16& p1, __bf16& p2, __bf16& p3) {
-    p1 = (__bf16)a;
-    const float r1 = a - (float)p1;
-    p2 = (__bf16)r1;
-    p3 = (__bf16)(r1 - (float)p2);
-}
+// ---- K4 on the dense matrix pipe: bound-and-refine ------------------------------------------------------------------------------
+// The first form of bound-and-refine; csrc/topk_refine.hip holds the second, which runs where it applies.  The bf16x3 form (every
+// fp32 factor split exactly into three bf16 parts, six partial products) measured slower and was removed (DESIGN.md section 4, K4;
+// source: git show 7a0cd86:top-k-rec_amd/csrc/topk.hip).
+//
+// Waves per workgroup: 4 -- TWO workgroups per CU (LDS: 17 KB of tiles + 48 KB of lists each; 256 VGPRs per wave either way).  The
+// one barrier of a tile makes every wave wait for the slowest filter of its workgroup; with four waves per barrier instead of eight,
+// and a second workgroup to run while one waits, the Netflix shape went 10.18 -> 9.59 ms (ML-10M 1.44 -> 1.35).  16-bit column
+// ids; 6 with 32-bit ones.
+template <int KS, typename IdT>
+constexpr int topk_waves_bf16() { return sizeof(IdT) == 2 ? 4 : 6; }
 
-// waves per workgroup.  bf16x3: 8 (one workgroup per CU).  Bound-and-refine: 4 -- TWO workgroups per CU (LDS: 17 KB of tiles +
-// 48 KB of lists each; 256 VGPRs per wave either way).  The one barrier of a tile makes every wave wait for the slowest filter of
-// its workgroup; with four waves per barrier instead of eight, and a second workgroup to run while one waits, the Netflix
-// shape went 10.18 -> 9.59 ms (ML-10M 1.44 -> 1.35).  The three-part tiles of bf16x3 do not fit twice (measured: 14.4 -> 30.8 ms).
-template <int KS, typename IdT, bool REFINE = false>
-constexpr int topk_waves_bf16() { return sizeof(IdT) == 2 ? (REFINE ? 4 : kTopkMaxWaves) : 6; }
-
-// REFINE = bound-and-refine arithmetic (tkr_topk_set_math(2)): ONE fp16 product per element instead of six bf16 ones
-// (v_mfma_f32_32x32x16_f16, the same rate).  fp16 has 11 significant bits but a narrow exponent range, so both sides are
+// Bound-and-refine arithmetic (tkr_topk_set_math(2)): ONE fp16 product per element (v_mfma_f32_32x32x16_f16).  fp16 has 11 significant bits but a narrow exponent range, so both sides are
 // scaled by powers of two first: the item factors by sv (max |V| lands in [2^13, 2^14)), each user's row by its own su;
 // the filter, the lists and the thresholds of a user live in these scaled units (scale = su * sv; the bias enters as
 // fma(bias, scale, acc)).  In them the approximate score is within
@@ -862,10 +823,10 @@ constexpr int topk_waves_bf16() { return sizeof(IdT) == 2 ? (REFINE ? 4 : kTopkM
 // everything within 2 * margin of the K-th best approximate score therefore holds the exact best K; they are rescored exactly
 // at the end.  `extra`: bits of [0] max |v_i|, [1] max |bias|, [2] max |V element| (topk_bounds_kernel); [4 + block] = 1
 // when a list of the block overflowed.
-// IMG (bound-and-refine only): the scaled fp16 item factors come PRE-CONVERTED, as the LDS image of every 32-item tile
+// IMG: the scaled fp16 item factors come PRE-CONVERTED, as the LDS image of every 32-item tile
 // (topk_image_kernel below; `vimg`), and a tile is staged by ONE direct-to-LDS load per thread (global_load_lds_dwordx4): no
 // staging registers, no conversion, no ds_write.  Without it every workgroup converts the same V again -- 1,876 times at the
-// Netflix shape, 2.0 of 10.85 ms (scripts/ablate_topk.sh).  The direct load writes LDS linearly (wave base + 16 * lane), so the
+// Netflix shape, 2.0 of 10.85 ms.  The direct load writes LDS linearly (wave base + 16 * lane), so the
 // image carries no row padding; bank conflicts of the fragment reads are avoided by an XOR swizzle of the 16-byte chunks of a
 // row instead (chunk j of item row r sits at j ^ swz(r), identical in the image and in the read: the b128 lane groups of
 // MI355X_MICROARCH.md hold 16 distinct values of r & 15).
@@ -889,21 +850,16 @@ __global__ __launch_bounds__(256) void topk_image_kernel(const float* __restrict
     }
 }
 
-template <int KS, typename IdT, bool REFINE = false, bool IMG = false>
-__global__ __launch_bounds__((topk_waves_bf16<KS, IdT, REFINE>() * TKR_WAVE), 2) void score_topk_bf16_kernel(
+template <int KS, typename IdT, bool IMG = false>
+__global__ __launch_bounds__((topk_waves_bf16<KS, IdT>() * TKR_WAVE), 2) void score_topk_bf16_kernel(
     const float* __restrict__ U, const int32_t* __restrict__ uidx, int n_rows, const float* __restrict__ Vt,
     const float* __restrict__ bias, int n_cols, int k, const uint32_t* __restrict__ mask, int mask_pitch, int K,
     int32_t* __restrict__ out_ids, float* __restrict__ out_scores, int tiles_per_split, uint64_t* __restrict__ part,
     uint32_t* __restrict__ thr_shared, const int4* __restrict__ items /*(block, t_begin, t_end, slot | stride << 16) or null*/,
     uint32_t* __restrict__ extra, const unsigned char* __restrict__ vimg) {
-    static_assert(!IMG || REFINE, "the tile image is the scaled fp16 operand of the bound-and-refine arithmetic");
     extern __shared__ __attribute__((aligned(16))) unsigned char smem_raw[];
-#if TKR_ABL & 256
-    const unsigned long long k4_start = __builtin_amdgcn_s_memtime();
-#endif
-    constexpr int NPART = REFINE ? 1 : 3;
-    constexpr int PARTB = KS * 32;                               // bytes of one bf16 part of an item row (KS*16 elements)
-    constexpr int ROWB = IMG ? PARTB : NPART * PARTB + 16;       // padded row: conflict-free ds_read_b128 (ROWB/4 = 4 mod 8); IMG: swizzled instead
+    constexpr int PARTB = KS * 32;                               // bytes of an fp16 item row (KS*16 elements)
+    constexpr int ROWB = IMG ? PARTB : PARTB + 16;               // padded row: conflict-free ds_read_b128 (ROWB/4 = 4 mod 8); IMG: swizzled instead
     constexpr int KPAD = KS * 16;
     const int W = blockDim.x >> 6;
     const int users = W * 32;
@@ -926,9 +882,8 @@ __global__ __launch_bounds__((topk_waves_bf16<KS, IdT, REFINE>() * TKR_WAVE), 2)
     const int row = ws.block * users + uw;
     const bool user_ok = row < n_rows;
 
-    // ---- B operand: lane (user ul, k-group h) holds elements 16s + 8h .. +7 of its user's row, three parts each
-    bf16x8 breg[REFINE ? 1 : KS][NPART];
-    f16x8 hreg[REFINE ? KS : 1];
+    // ---- B operand: lane (user ul, k-group h) holds elements 16s + 8h .. +7 of its user's row, scaled to fp16
+    f16x8 hreg[KS];
     float margin = 0.f, bscale = 1.f, inv_bscale = 1.f, sv = 1.f;
     {
         const int urow = user_ok ? (uidx ? uidx[row] : row) : 0;
@@ -954,50 +909,39 @@ __global__ __launch_bounds__((topk_waves_bf16<KS, IdT, REFINE>() * TKR_WAVE), 2)
                     uv[s][i] = (user_ok && e < k) ? v : 0.f;
                 }
         }
-        if constexpr (REFINE) {
-            float nu = 0.f, amax = 0.f;
+        float nu = 0.f, amax = 0.f;
 #pragma unroll
-            for (int s = 0; s < KS; ++s)
+        for (int s = 0; s < KS; ++s)
 #pragma unroll
-                for (int i = 0; i < 8; ++i) {
-                    nu = fmaf(uv[s][i], uv[s][i], nu);
-                    amax = fmaxf(amax, fabsf(uv[s][i]));
-                }
-            nu += __shfl_xor(nu, 32, 64);                          // the other k-group of the same user
-            amax = fmaxf(amax, __shfl_xor(amax, 32, 64));
-            const float su = pow2_scale(amax);
-            sv = pow2_scale(__uint_as_float(extra[2]));
-            bscale = su * sv;
-            inv_bscale = __uint_as_float((254u - ((__float_as_uint(bscale) >> 23) & 0xffu)) << 23);
+            for (int i = 0; i < 8; ++i) {
+                nu = fmaf(uv[s][i], uv[s][i], nu);
+                amax = fmaxf(amax, fabsf(uv[s][i]));
+            }
+        nu += __shfl_xor(nu, 32, 64);                          // the other k-group of the same user
+        amax = fmaxf(amax, __shfl_xor(amax, 32, 64));
+        const float su = pow2_scale(amax);
+        sv = pow2_scale(__uint_as_float(extra[2]));
+        bscale = su * sv;
+        inv_bscale = __uint_as_float((254u - ((__float_as_uint(bscale) >> 23) & 0xffu)) << 23);
 #pragma unroll
-            for (int s = 0; s < KS; ++s)
+        for (int s = 0; s < KS; ++s)
 #pragma unroll
-                for (int i = 0; i < 8; ++i) hreg[s][i] = (_Float16)(uv[s][i] * su);
-            const float reach = sqrtf(nu) * 1.001f * __uint_as_float(extra[0]);      // >= |u| * max |v_i|
-            margin = (fmaf(1.05f * 0.0009765625f, reach, 3.8146973e-6f * (reach + __uint_as_float(extra[1]))) + 7.7e-34f) * bscale +
-                     2.01f * (float)KPAD;
-        } else {
-#pragma unroll
-            for (int s = 0; s < KS; ++s)
-#pragma unroll
-                for (int i = 0; i < 8; ++i) {
-                    __bf16 p1, p2, p3;
-                    split3(uv[s][i], p1, p2, p3);
-                    breg[s][0][i] = p1; breg[s][NPART > 1 ? 1 : 0][i] = p2; breg[s][NPART > 2 ? 2 : 0][i] = p3;
-                }
-        }
+            for (int i = 0; i < 8; ++i) hreg[s][i] = (_Float16)(uv[s][i] * su);
+        const float reach = sqrtf(nu) * 1.001f * __uint_as_float(extra[0]);      // >= |u| * max |v_i|
+        margin = (fmaf(1.05f * 0.0009765625f, reach, 3.8146973e-6f * (reach + __uint_as_float(extra[1]))) + 7.7e-34f) * bscale +
+                 2.01f * (float)KPAD;
     }
     const float m2 = 2.f * margin;
     bool lost = false;
     for (int s = tid; s < users; s += blockDim.x) sm.cnt[s] = 0;
     float thr = (thr_shared && user_ok) ? unordered_bits(thr_shared[row]) : -INFINITY;   // what other item ranges found so far
-    if constexpr (REFINE) thr = thr * bscale - margin;
+    thr = thr * bscale - margin;
     const int n_tiles_all = (n_cols + 31) >> 5;
     const int t_begin = it.y;
     const int n_tiles = items ? it.z : min(n_tiles_all, t_begin + tiles_per_split);
 
-    // ---- tile staging: float4 of Vt -> registers (early) -> three 4 x bf16 parts -> LDS (after the MFMA chain)
-    constexpr int NT_ = topk_waves_bf16<KS, IdT, REFINE>() * 64;
+    // ---- tile staging: float4 of Vt -> registers (early) -> 4 x fp16 -> LDS (after the MFMA chain)
+    constexpr int NT_ = topk_waves_bf16<KS, IdT>() * 64;
     constexpr int TILEB = 32 * ROWB;                             // bytes of one staged tile
     constexpr int NG = IMG ? (TILEB / 16 + NT_ - 1) / NT_ : 1;   // IMG: 16-byte direct-to-LDS loads per thread and tile
     auto stage_direct = [&](int t, int buf) {                     // IMG: tile t of the image -> LDS buffer buf, asynchronously (vmcnt)
@@ -1055,23 +999,10 @@ __global__ __launch_bounds__((topk_waves_bf16<KS, IdT, REFINE>() * TKR_WAVE), 2)
             for (int q = 0; q < NC; ++q)
                 if (src_off[q] >= 0) {
                     const float a[4] = {stg[q].x, stg[q].y, stg[q].z, stg[q].w};
-                    if constexpr (REFINE) {
-                        f16x4 p1;
+                    f16x4 p1;
 #pragma unroll
-                        for (int i = 0; i < 4; ++i) p1[i] = (_Float16)(a[i] * sv);
-                        *reinterpret_cast<f16x4*>(dst + dst_off[q]) = p1;
-                    } else {
-                        bf16x4 p1, p2, p3;
-#pragma unroll
-                        for (int i = 0; i < 4; ++i) {
-                            __bf16 x1, x2, x3;
-                            split3(a[i], x1, x2, x3);
-                            p1[i] = x1; p2[i] = x2; p3[i] = x3;
-                        }
-                        *reinterpret_cast<bf16x4*>(dst + dst_off[q]) = p1;
-                        *reinterpret_cast<bf16x4*>(dst + dst_off[q] + (NPART - 1) / 2 * PARTB) = p2;
-                        *reinterpret_cast<bf16x4*>(dst + dst_off[q] + (NPART - 1) * PARTB) = p3;
-                    }
+                    for (int i = 0; i < 4; ++i) p1[i] = (_Float16)(a[i] * sv);
+                    *reinterpret_cast<f16x4*>(dst + dst_off[q]) = p1;
                 }
         } else {
             for (int c = tid; c < 32 * KPAD; c += nthreads) {
@@ -1079,13 +1010,7 @@ __global__ __launch_bounds__((topk_waves_bf16<KS, IdT, REFINE>() * TKR_WAVE), 2)
                 float v = 0.f;
                 if (e < k && col < n_cols) v = Vt[(size_t)col * k + e];
                 __bf16* rowp = reinterpret_cast<__bf16*>(dst + item * ROWB);
-                if constexpr (REFINE) {
-                    reinterpret_cast<_Float16*>(rowp)[e] = (_Float16)(v * sv);
-                } else {
-                    __bf16 x1, x2, x3;
-                    split3(v, x1, x2, x3);
-                    rowp[e] = x1; rowp[(NPART - 1) / 2 * KPAD + e] = x2; rowp[(NPART - 1) * KPAD + e] = x3;
-                }
+                reinterpret_cast<_Float16*>(rowp)[e] = (_Float16)(v * sv);
             }
         }
         if (tid < 32) sm.tbias[buf * 32 + tid] = stg_bias;
@@ -1108,131 +1033,66 @@ __global__ __launch_bounds__((topk_waves_bf16<KS, IdT, REFINE>() * TKR_WAVE), 2)
 
     const uint32_t tail_mask = (n_cols & 31) ? (0xffffffffu << (n_cols & 31)) : 0u;
     int next_sched = t_begin + 2;
-#if TKR_ABL & 256
-    unsigned long long k4p[8] = {0, 0, 0, 0, 0, 0, 0, 0}, k4t = k4_start;
-    K4_MARK(5)
-#endif
     // the rated-item word of (tile, user) comes from HBM (every workgroup reads its own 512 bytes per tile: never a cache hit): it
     // is asked for one tile ahead, right behind the barrier, and has the filter of this tile and the chain of the next to arrive
     uint32_t mask_next = (mask && user_ok && t_begin < n_tiles) ? mask[(size_t)t_begin * mask_pitch + row] : 0u;
     for (int t = t_begin; t < n_tiles; ++t) {
         const int buf = t & 1;
         uint32_t maskw = mask_next;
-        // ---- 32 items x 32 users x k: six bf16 partial products per 16-wide k step, fp32 accumulation.
-        // A operand: lane (item ul, k-group h) reads elements 16s + 8h .. +7 of each part; small terms first.
+        // ---- 32 items x 32 users x k: one fp16 product per 16-wide k step, fp32 accumulation.
+        // A operand: lane (item ul, k-group h) reads elements 16s + 8h .. +7.
         f32x16 acc = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
         const unsigned char* arow = tile + buf * 32 * ROWB + ul * ROWB + h * 16;
         // IMG: tile t+1 streams into the other buffer while this one is multiplied (nobody reads that buffer after the barrier
         // of tile t-1; the bias of a tile is folded into the accumulator before its barrier, so tbias is free as well)
         if constexpr (IMG) { if (t + 1 < n_tiles) stage_direct(t + 1, buf ^ 1); }
-        if constexpr (REFINE) {                                   // one MFMA per fragment: all the LDS reads go out first
-            f16x8 afrag[KS];
-#pragma unroll
-            for (int s = 0; s < KS; ++s) {
-                if constexpr (IMG) afrag[s] = *reinterpret_cast<const f16x8*>(tile + buf * TILEB + ul * ROWB + ((2 * s + h) ^ tile_swizzle<KS>(ul)) * 16);
-                else afrag[s] = *reinterpret_cast<const f16x8*>(arow + s * 32);
-            }
-#pragma unroll
-            for (int s = 0; s < KS; ++s) acc = __builtin_amdgcn_mfma_f32_32x32x16_f16(afrag[s], hreg[s], acc, 0, 0, 0);
-            __builtin_amdgcn_sched_group_barrier(0x100, KS, 0);   // the scheduler otherwise reloads one fragment register before every MFMA
-            __builtin_amdgcn_sched_group_barrier(0x008, KS, 0);
-        }
+        f16x8 afrag[KS];                                          // one MFMA per fragment: all the LDS reads go out first
 #pragma unroll
         for (int s = 0; s < KS; ++s) {
-            if constexpr (!REFINE) {
-                const bf16x8 a1 = *reinterpret_cast<const bf16x8*>(arow + s * 32);
-                const bf16x8 a2 = *reinterpret_cast<const bf16x8*>(arow + (NPART - 1) / 2 * PARTB + s * 32);
-                const bf16x8 a3 = *reinterpret_cast<const bf16x8*>(arow + (NPART - 1) * PARTB + s * 32);
-                acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a3, breg[s][0], acc, 0, 0, 0);
-                acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a2, breg[s][NPART > 1 ? 1 : 0], acc, 0, 0, 0);
-                acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a1, breg[s][NPART > 2 ? 2 : 0], acc, 0, 0, 0);
-                acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a2, breg[s][0], acc, 0, 0, 0);
-                acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a1, breg[s][NPART > 1 ? 1 : 0], acc, 0, 0, 0);
-                acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a1, breg[s][0], acc, 0, 0, 0);
-            }
+            if constexpr (IMG) afrag[s] = *reinterpret_cast<const f16x8*>(tile + buf * TILEB + ul * ROWB + ((2 * s + h) ^ tile_swizzle<KS>(ul)) * 16);
+            else afrag[s] = *reinterpret_cast<const f16x8*>(arow + s * 32);
         }
+#pragma unroll
+        for (int s = 0; s < KS; ++s) acc = __builtin_amdgcn_mfma_f32_32x32x16_f16(afrag[s], hreg[s], acc, 0, 0, 0);
+        __builtin_amdgcn_sched_group_barrier(0x100, KS, 0);   // the scheduler otherwise reloads one fragment register before every MFMA
+        __builtin_amdgcn_sched_group_barrier(0x008, KS, 0);
+#pragma unroll
+        for (int s = 0; s < KS; ++s) {                            // (empty since the bf16x3 products left it; without it the tile-image
+        }                                                         // kernels allocate their registers differently)
         mfma_result_guard_8pass(acc);
-        // Where the one barrier of the tile sits.  k <= 64: EARLY, right after the staging -- tile t+1 is in LDS, every wave
-        // is done reading tile t, and the filter touches only the wave's own lists, so a wave whose filter is short starts
-        // the next MFMA chain while its neighbours still append or trim (Netflix shape, k = 64: 11.2 -> 10.2 ms).  The bias
-        // is folded into the accumulator first: tile t+2's bias may land in this slot before a slow wave filters.
-        // k = 128: measured slower that way (14.4 -> 17.7 ms) -- the MFMA chains dominate there and the two waves of a SIMD
-        // interleave them best when they start together (a lone dependent chain issues at ~44 instead of 32 cycles per
-        // MFMA); there the barrier stays behind the filter.
-        constexpr bool kEarlyBarrier = REFINE || KS <= 4;    // refine: the chain is 8 MFMAs at every width, the filter dominates
-        if constexpr (kEarlyBarrier) {
-            if constexpr (REFINE) {
-                if (bias) add_scaled_bias_inplace(acc, sm.tbias + buf * 32, h, bscale);     // VBPR models have no item bias: 16 fma per tile less
-            }
-            else add_bias_inplace(acc, sm.tbias + buf * 32, h);
-        }
-#if TKR_ABL & 256
-        asm volatile("" : "+v"(acc));
-        K4_MARK(0)
-#endif
-#if !(TKR_ABL & 2)
+        // The one barrier of the tile sits EARLY, right after the staging -- tile t+1 is in LDS, every wave is done reading
+        // tile t, and the filter touches only the wave's own lists, so a wave whose filter is short starts the next MFMA chain
+        // while its neighbours still append or trim (the chain is 8 MFMAs at every width, the filter dominates).  The bias is
+        // folded into the accumulator first: tile t+2's bias may land in this slot before a slow wave filters.
+        if (bias) add_scaled_bias_inplace(acc, sm.tbias + buf * 32, h, bscale);     // VBPR models have no item bias: 16 fma per tile less
         if constexpr (!IMG) {
             if (t + 1 < n_tiles) stage_store(t + 1, buf ^ 1);
             if (t + 2 < n_tiles) stage_load(t + 2);
         }
-#endif
         if constexpr (IMG) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");      // tile t+1 has landed (issued a whole MFMA chain ago)
-        K4_MARK(1)
-        if constexpr (kEarlyBarrier) __syncthreads();
-        K4_MARK(2)
+        __syncthreads();
         if (mask && user_ok && t + 1 < n_tiles) mask_next = mask[(size_t)(t + 1) * mask_pitch + row];
         if (!user_ok) maskw = 0xffffffffu;
         if (t == n_tiles_all - 1) maskw |= tail_mask;
-        if (t == next_sched && !(TKR_ABL & 16)) {
+        if (t == next_sched) {
             if (__ballot(sm.cnt[uw] > kCap / 2) != 0) {            // lists still short (thresholds shared by earlier ranges): nothing to gain
-                if constexpr (REFINE) {
-                    thr = trim_all_users<IdT, true>(sm, uw, h, K, thr, m2);
-                    // 1 / scale (a power of two) is rebuilt here from an opaque copy: hoisted out of the tile loop it is one more
-                    // register alive across it, and the allocator, at its 256-register cap, spilled exactly that one
-                    float bs = bscale;
-                    int row_here = row;                          // likewise the address of the row's shared bound
-                    asm volatile("" : "+v"(bs), "+v"(row_here));
-                    thr = share_bound(thr_shared, row_here, user_ok && h == 0, thr, margin, bscale,
-                                      __uint_as_float((254u - ((__float_as_uint(bs) >> 23) & 0xffu)) << 23));
-                } else {
-                    thr = trim_all_users<IdT>(sm, uw, h, K, thr);
-                    int row_here = row;
-                    asm volatile("" : "+v"(row_here));
-                    thr = share_threshold(thr_shared, row_here, user_ok && h == 0, thr);
-                }
+                thr = trim_all_users<IdT, true>(sm, uw, h, K, thr, m2);
+                // 1 / scale (a power of two) is rebuilt here from an opaque copy: hoisted out of the tile loop it is one more
+                // register alive across it, and the allocator, at its 256-register cap, spilled exactly that one
+                float bs = bscale;
+                int row_here = row;                              // likewise the address of the row's shared bound
+                asm volatile("" : "+v"(bs), "+v"(row_here));
+                thr = share_bound(thr_shared, row_here, user_ok && h == 0, thr, margin, bscale,
+                                  __uint_as_float((254u - ((__float_as_uint(bs) >> 23) & 0xffu)) << 23));
             }
             next_sched = t + ((t - t_begin + 1) >> 1);
         }
-        K4_MARK(3)
-#if !(TKR_ABL & 1)
-        filter_tile<IdT, kEarlyBarrier, REFINE>(sm, acc, sm.tbias + buf * 32, maskw, t, K, thr, m2, &lost, bscale);
-#else
-        if (acc[0] + acc[5] + acc[10] + acc[15] == 12345.678f) sm.cnt[uw] = 1;     // keeps the chain alive
-#endif
-#if !(TKR_ABL & 4)
-        if constexpr (!kEarlyBarrier) __syncthreads();
-#endif
-#if TKR_ABL & 256
-        asm volatile("" : "+v"(thr));
-        K4_MARK(4)
-        k4p[7] += 1;
-#endif
+        filter_tile<IdT, true, true>(sm, acc, sm.tbias + buf * 32, maskw, t, K, thr, m2, &lost, bscale);
     }
-    if constexpr (REFINE) {
-        if (__ballot(lost) != 0 && lane == 0) extra[4 + ws.block] = 1u;       // the exact kernel redoes this block
-#if !(TKR_ABL & 64)
-        // (the kernel that stages its tiles through registers has fewer to spare: 4 instead of 8 loads per half in flight, no scratch)
-        write_rows_refine<IdT, KS, IMG ? kRescoreInFlight : 4>(sm, ws, n_rows, K, thr, m2, U, uidx, Vt, bias, k, out_ids, out_scores, part,
-                                                               tile, 2 * TILEB);                                // the tile buffers are free now
-#endif
-    } else {
-        write_rows<IdT>(sm, ws, n_rows, K, thr, out_ids, out_scores, part);
-    }
-#if TKR_ABL & 256
-    K4_MARK(6)
-    if (lane == 0)
-        for (int q = 0; q < 8; ++q) atomicAdd(&g_k4_prof[q], k4p[q]);
-#endif
+    if (__ballot(lost) != 0 && lane == 0) extra[4 + ws.block] = 1u;       // the exact kernel redoes this block
+    // (the kernel that stages its tiles through registers has fewer to spare: 4 instead of 8 loads per half in flight, no scratch)
+    write_rows_refine<IdT, KS, IMG ? kRescoreInFlight : 4>(sm, ws, n_rows, K, thr, m2, U, uidx, Vt, bias, k, out_ids, out_scores, part,
+                                                           tile, 2 * TILEB);                                    // the tile buffers are free now
 }
 
 // max_i |v_i| (2-norm, rounded up) and max_i |bias_i| for the margin of the bound-and-refine kernel; bounds[] zeroed before
@@ -1597,31 +1457,28 @@ static size_t topk_image_bytes(int n_cols, int k) {               // the fp16 ti
 }
 
 
-template <int KS, typename IdT, bool REFINE>
+template <int KS, typename IdT>
 static int launch_topk_bf16(const float* U, const int32_t* uidx, int n_rows, const float* Vt, const float* bias, int n_cols,
                             int k, const uint32_t* mask, int pitch, int K, int32_t* out_ids, float* out_scores,
                             void* workspace, size_t workspace_bytes, hipStream_t stream) {
-    // REFINE: the tile image lives at the END of the workspace when the caller sized it with tkr_topk_workspace_bytes_for
+    // the tile image lives at the END of the workspace when the caller sized it with tkr_topk_workspace_bytes_for
     unsigned char* vimg = nullptr;
-    if constexpr (REFINE) {
-        static const bool no_img = getenv("TKR_TOPK_IMAGE") && getenv("TKR_TOPK_IMAGE")[0] == '0';
-        const size_t img = (topk_image_bytes(n_cols, k) + 255) & ~(size_t)255;
-        const size_t base = (size_t)tkr_topk_workspace_bytes(n_rows, K);
-        if (!no_img && workspace && workspace_bytes >= base + img + 256) {
-            const size_t off = (workspace_bytes - img) & ~(size_t)255;
-            vimg = static_cast<unsigned char*>(workspace) + off;
-            workspace_bytes = off;
-        }
+    static const bool no_img = getenv("TKR_TOPK_IMAGE") && getenv("TKR_TOPK_IMAGE")[0] == '0';
+    const size_t img = (topk_image_bytes(n_cols, k) + 255) & ~(size_t)255;
+    const size_t base = (size_t)tkr_topk_workspace_bytes(n_rows, K);
+    if (!no_img && workspace && workspace_bytes >= base + img + 256) {
+        const size_t off = (workspace_bytes - img) & ~(size_t)255;
+        vimg = static_cast<unsigned char*>(workspace) + off;
+        workspace_bytes = off;
     }
     const bool use_img = vimg != nullptr;
-    const int ROWB = use_img ? KS * 32 : (REFINE ? 1 : 3) * KS * 32 + 16;
-    const int W = topk_waves_bf16<KS, IdT, REFINE>();
+    const int ROWB = use_img ? KS * 32 : KS * 32 + 16;
+    const int W = topk_waves_bf16<KS, IdT>();
     const int users = W * 32;
-    size_t lds = (size_t)2 * 32 * ROWB + 64 * 4 + (size_t)users * 8 + (size_t)users * kCap * (4 + sizeof(IdT));
-    if (const char* e = getenv("TKR_TOPK_LDS_PAD")) lds += (size_t)atoi(e);      // occupancy experiments (scripts/)
+    const size_t lds = (size_t)2 * 32 * ROWB + 64 * 4 + (size_t)users * 8 + (size_t)users * kCap * (4 + sizeof(IdT));
     if (lds > 160 * 1024) return TKR_EUNSUPPORTED;
-    auto kern = score_topk_bf16_kernel<KS, IdT, REFINE, false>;
-    auto kern_img = score_topk_bf16_kernel<KS, IdT, REFINE, REFINE>;
+    auto kern = score_topk_bf16_kernel<KS, IdT, false>;
+    auto kern_img = score_topk_bf16_kernel<KS, IdT, true>;
     hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(use_img ? kern_img : kern), hipFuncAttributeMaxDynamicSharedMemorySize,
                                        160 * 1024);
     if (e != hipSuccess) return (int)e;
@@ -1629,12 +1486,12 @@ static int launch_topk_bf16(const float* U, const int32_t* uidx, int n_rows, con
     // the second form of bound-and-refine (csrc/topk_refine.hip: packed lists, three workgroups per CU, every row ranked once by
     // topk_finish2_kernel): 16-bit column ids, the tile image, room for the pieces' dumps.  TKR_TOPK_V2=0: the first form.
     static const bool v2_off = getenv("TKR_TOPK_V2") && getenv("TKR_TOPK_V2")[0] == '0';
-    const bool want_v2 = REFINE && sizeof(IdT) == 2 && use_img && !v2_off && refine2_supports(n_cols, k) && users == kR2Users;
+    const bool want_v2 = sizeof(IdT) == 2 && use_img && !v2_off && refine2_supports(n_cols, k) && users == kR2Users;
     TopkPlan p;
-    int rc = plan_topk(users, n_rows, n_cols, K, workspace, workspace_bytes, REFINE ? (size_t)(4 + n_blocks) : 0, stream, p,
+    int rc = plan_topk(users, n_rows, n_cols, K, workspace, workspace_bytes, (size_t)(4 + n_blocks), stream, p,
                        want_v2 ? kR2SpansPerCU : 0);
     if (rc != TKR_OK) return rc;
-    if constexpr (REFINE && sizeof(IdT) == 2) {
+    if constexpr (sizeof(IdT) == 2) {
         const size_t used = (p.used_bytes + 255) & ~(size_t)255;
         if (want_v2 && p.extra && used + refine2_dump_bytes((size_t)p.n_pieces) <= workspace_bytes) {
             hipLaunchKernelGGL(topk_bounds_kernel, dim3(std::min(256, (n_cols + 3) / 4)), dim3(256), 0, stream, Vt, bias, n_cols, k, p.extra);
@@ -1652,29 +1509,25 @@ static int launch_topk_bf16(const float* U, const int32_t* uidx, int n_rows, con
             rc = launch_refine2(a, stream);
             if (rc != TKR_OK) return rc;
             // blocks with an overflowed list: the fp32 kernel on the same work items, merged where a block was cut
-            rc = launch_fp32_planned<IdT, topk_waves_bf16<KS, IdT, true>()>(p, U, uidx, n_rows, Vt, bias, n_cols, k, mask, pitch, K, out_ids, out_scores,
-                                                                            p.extra + 4, stream);
+            rc = launch_fp32_planned<IdT, topk_waves_bf16<KS, IdT>()>(p, U, uidx, n_rows, Vt, bias, n_cols, k, mask, pitch, K, out_ids, out_scores,
+                                                                      p.extra + 4, stream);
             if (rc != TKR_OK) return rc;
             return merge_planned(p, users, n_rows, K, out_ids, out_scores, stream, p.extra + 4);
         }
     }
-    if constexpr (REFINE) {
-        if (!p.extra) return TKR_EAGAIN_EXACT;                    // no room for the block flags: the caller runs the fp32 kernel
-        hipLaunchKernelGGL(topk_bounds_kernel, dim3(std::min(256, (n_cols + 3) / 4)), dim3(256), 0, stream, Vt, bias, n_cols, k, p.extra);
-        if (use_img)
-            hipLaunchKernelGGL(topk_image_kernel<KS>, dim3(std::min(2048, ((n_cols + 31) / 32 * 32 * 2 * KS + 255) / 256)), dim3(256), 0, stream, Vt,
-                               n_cols, k, p.extra, vimg);
-    }
+    if (!p.extra) return TKR_EAGAIN_EXACT;                        // no room for the block flags: the caller runs the fp32 kernel
+    hipLaunchKernelGGL(topk_bounds_kernel, dim3(std::min(256, (n_cols + 3) / 4)), dim3(256), 0, stream, Vt, bias, n_cols, k, p.extra);
+    if (use_img)
+        hipLaunchKernelGGL(topk_image_kernel<KS>, dim3(std::min(2048, ((n_cols + 31) / 32 * 32 * 2 * KS + 255) / 256)), dim3(256), 0, stream, Vt,
+                           n_cols, k, p.extra, vimg);
     hipLaunchKernelGGL(use_img ? kern_img : kern, p.grid, dim3(W * 64), lds, stream, U, uidx, n_rows, Vt, bias, n_cols, k, mask, pitch, K,
                        out_ids, out_scores, p.tps, p.part, p.thr_shared, p.items, p.extra, (const unsigned char*)vimg);
     rc = (int)hipGetLastError();
     if (rc != TKR_OK) return rc;
-    if constexpr (REFINE) {
-        // blocks with an overflowed list: the fp32 kernel, same work items
-        rc = launch_fp32_planned<IdT, topk_waves_bf16<KS, IdT, true>()>(p, U, uidx, n_rows, Vt, bias, n_cols, k, mask, pitch, K, out_ids, out_scores,
-                                                                        p.extra + 4, stream);
-        if (rc != TKR_OK) return rc;
-    }
+    // blocks with an overflowed list: the fp32 kernel, same work items
+    rc = launch_fp32_planned<IdT, topk_waves_bf16<KS, IdT>()>(p, U, uidx, n_rows, Vt, bias, n_cols, k, mask, pitch, K, out_ids, out_scores, p.extra + 4,
+                                                              stream);
+    if (rc != TKR_OK) return rc;
     return merge_planned(p, users, n_rows, K, out_ids, out_scores, stream);
 }
 
@@ -1742,9 +1595,9 @@ __global__ __launch_bounds__(256) void score_topk_wide_kernel(const float* __res
     }
 }
 
-// arithmetic of the score block: 2 = bound-and-refine (default; k <= 128 and a workspace, else it runs as 1), 0 = bf16-split
-// products on the dense matrix pipe (k <= 128), 1 = fp32 MFMA for every k.
-// Initial value from TKR_TOPK_MATH=refine|bf16x3|fp32; tkr_topk_set_math changes it for the process.
+// arithmetic of the score block: 2 = bound-and-refine (default; k <= 128 and a workspace, else it runs as 1), 1 = fp32 MFMA for
+// every k.  0 was the bf16-split products (removed): TKR_TOPK_MATH=bf16x3 still selects it and runs as 1, tkr_topk_set_math(0)
+// refuses it.  Initial value from TKR_TOPK_MATH=refine|bf16x3|fp32; tkr_topk_set_math changes it for the process.
 static int g_topk_math = -1;
 static int topk_math() {
     if (g_topk_math < 0) {
@@ -1762,8 +1615,8 @@ static int dispatch_topk(const float* U, const int32_t* uidx, int n_rows, const 
         int rc = TKR_EAGAIN_EXACT;
 #define TKR_TOPK_REFINE_CASE(KS)                                                                                        \
     if (rc == TKR_EAGAIN_EXACT && k <= 16 * KS) {                                                                       \
-        rc = launch_topk_bf16<KS, IdT, true>(U, uidx, n_rows, Vt, bias, n_cols, k, mask, pitch, K, out_ids, out_scores, \
-                                             workspace, workspace_bytes, stream);                                      \
+        rc = launch_topk_bf16<KS, IdT>(U, uidx, n_rows, Vt, bias, n_cols, k, mask, pitch, K, out_ids, out_scores,       \
+                                       workspace, workspace_bytes, stream);                                            \
         if (rc != TKR_EAGAIN_EXACT) return rc;                                                                          \
         rc = TKR_OK;                                                                                                    \
     }
@@ -1773,19 +1626,6 @@ static int dispatch_topk(const float* U, const int32_t* uidx, int n_rows, const 
         TKR_TOPK_REFINE_CASE(8)
 #undef TKR_TOPK_REFINE_CASE
     }
-#ifdef TKR_LAB                                                   // bf16x3 (six exact partial products): measured slower than bound-and-refine; `make LAB=1`
-    if (k <= 128 && topk_math() == 0) {
-#define TKR_TOPK_BF16_CASE(KS)                                                                                          \
-    if (k <= 16 * KS)                                                                                                   \
-        return launch_topk_bf16<KS, IdT, false>(U, uidx, n_rows, Vt, bias, n_cols, k, mask, pitch, K, out_ids, out_scores, \
-                                                workspace, workspace_bytes, stream);
-        TKR_TOPK_BF16_CASE(1)
-        TKR_TOPK_BF16_CASE(2)
-        TKR_TOPK_BF16_CASE(4)
-        TKR_TOPK_BF16_CASE(8)
-#undef TKR_TOPK_BF16_CASE
-    }
-#endif
     const int kh = (k + 1) / 2;
 #define TKR_TOPK_CASE(KHP)                                                                                   \
     if (kh <= KHP)                                                                                           \
@@ -1819,20 +1659,9 @@ extern "C" int tkr_build_rated_mask(const int64_t* rated_ptr, const int32_t* rat
     return TKR_OK;
 }
 
-#if TKR_ABL & 256
-extern "C" int tkr_k4_prof_read(unsigned long long* out8) {      // timing builds only: read and reset the phase counters
-    unsigned long long zero[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-    hipError_t e = hipMemcpyFromSymbol(out8, HIP_SYMBOL(g_k4_prof), sizeof(zero));
-    if (e == hipSuccess) e = hipMemcpyToSymbol(HIP_SYMBOL(g_k4_prof), zero, sizeof(zero));
-    return (int)e;
-}
-#endif
-
 extern "C" int tkr_topk_set_math(int32_t mode) {
     if (mode < 0 || mode > 2) return TKR_EINVAL;
-#ifndef TKR_LAB
-    if (mode == 0) return TKR_EUNSUPPORTED;                      // bf16x3 lives in the lab library (make LAB=1)
-#endif
+    if (mode == 0) return TKR_EUNSUPPORTED;                      // bf16x3: removed (topk_math)
     tkr::g_topk_math = mode;
     return TKR_OK;
 }

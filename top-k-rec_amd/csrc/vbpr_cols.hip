@@ -309,8 +309,6 @@ __global__ __launch_bounds__(W * 64) void vbpr_tproject_kernel(tkr_vbpr_state st
 
 // L2: the [B, B] pair sums (csrc/vbpr_step.hip, head).  One wave per triplet t, every alpha / beta the wave needs loaded up front
 // (B <= 1024: 16 per lane and array):  S_t = sum_b sigma(-(alpha_t + beta_b)),  T_t = sum_a sigma(-(alpha_a + beta_t)).
-// FRESH: the sums are read by other blocks of the SAME launch (the pair blocks of vbpr_update_kernel): stored write-through
-template <bool FRESH>
 __device__ __forceinline__ void pairsum_wave(const float* __restrict__ ab /*[4][B]*/, int B, float* sS, float* sT, float* __restrict__ loss_out,
                                              int t, int lane) {
     if (t >= B) return;
@@ -340,14 +338,7 @@ __device__ __forceinline__ void pairsum_wave(const float* __restrict__ ab /*[4][
     }
     s_row = wave_sum(s_row);
     s_col = wave_sum(s_col);
-    if (lane == 0) {
-        if constexpr (FRESH) {
-            __hip_atomic_store(sS + t, s_row, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-            __hip_atomic_store(sT + t, s_col, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        } else {
-            sS[t] = s_row; sT[t] = s_col;
-        }
-    }
+    if (lane == 0) { sS[t] = s_row; sT[t] = s_col; }
     if (loss_out) {
         loss = wave_sum(loss);
         if (lane == 0) loss_out[B + t] = loss;
@@ -355,7 +346,7 @@ __device__ __forceinline__ void pairsum_wave(const float* __restrict__ ab /*[4][
 }
 __global__ __launch_bounds__(256) void vbpr_pairsum_kernel(const float* __restrict__ ab /*[4][B]*/, int B, float* __restrict__ sS,
                                                           float* __restrict__ sT, float* __restrict__ loss_out) {
-    pairsum_wave<false>(ab, B, sS, sT, loss_out, blockIdx.x * 4 + (threadIdx.x >> 6), threadIdx.x & 63);
+    pairsum_wave(ab, B, sS, sT, loss_out, blockIdx.x * 4 + (threadIdx.x >> 6), threadIdx.x & 63);
 }
 
 // L3.  Blocks [0, n_row_blocks) run the row tasks of the batch (vbpr_rows_body: the launch records of K1), the others the
@@ -437,8 +428,6 @@ __device__ __forceinline__ void col_block(const tkr_vbpr_state& st, const PS& ps
             wr[q] = live ? *reinterpret_cast<const float4*>(Wraw + (size_t)t * kh + 4 * gl) : make_float4(0.f, 0.f, 0.f, 0.f);
         }
     }
-    // (pair sums formed by the first blocks of THIS launch: every wave of the block comes by here, with the loads above in flight)
-    pair_sums_wait(ps);
     if (light) {
         float tt[3], ss[3];
         ps.get(et, n, ss, tt);
@@ -527,122 +516,45 @@ __device__ __forceinline__ void col_block(const tkr_vbpr_state& st, const PS& ps
     }
 }
 
-// INLINE: no pair-sum launch in front of this one -- rows and columns work S_t / T_t out where they need them (PairSumInline; s_in
-// then points at the batch's [alpha | beta | e^alpha | e^beta]), and B / 4 more blocks at the end of the grid add up the pair terms
-// of the loss, one wave per triplet (what vbpr_pairsum_kernel did beside its sums).
-// FUSED (round 5): no pair-sum launch either, and nobody recomputes anything -- the first (B + 3) / 4 blocks of the grid ARE the pair-sum
-// kernel (same code, same order of summation: S_t, T_t and the loss words are bit for bit those of the three-launch form), store
-// their sums write-through, drain, and bump `pair_done`; every other block runs its chain (header -> entries -> uce rows; the rows'
-// records and occurrences) and only looks at the counter where it first needs a sum (PairSumFresh) -- by then, ~2.5 us into the
-// launch, the pair blocks (~3 us) are done or nearly so.  s_in = S, t_in = T as in the three-launch form, ab = the batch's
-// [alpha | beta | e^alpha | e^beta].  Two launches per batch.
-// MEASURED (MI355X, ML-10M shape, batch 256, per batch without the loss): sparse d = 20,000: 25.4 us against 22.7 with the pair-sum
-// launch; dense d_c = 128: 23.6 against 18.0 (first version, every wave polling the counter and reading the sums past the L1: 28.6 /
-// 21.8).  The pair blocks are not done at ~3 us but at ~5 (two trips for their inputs, the write-through stores' drain, the
-// counter's atomic), the waiters see it a poll later, and the update's own chain behind the sums (sums -> entries 4..7 -> stores) is
-// still ahead of them: what overlaps is the 2.5 us of header + first gathers, what is added is the hand-off.  The third way of
-// removing the pair launch that lost (after round 4's last-block sums and round 5's inline sums): selectable (tkr_vbpr_set_pairs(2)),
-// bit-identical, not the default.
-template <int NE, int LPC, bool INLINE, int UNL = 4, bool FUSED = false>
+// The pair sums S_t, T_t come from their own launch in front of this one (vbpr_pairsum_kernel: three launches per batch).  Two other
+// placements measured slower and were removed (source: git show 7a0cd86:top-k-rec_amd/csrc/vbpr_cols.hip):
+// every task working out the sums it needs (31.6 us per batch against 23.1, B = 256, d = 20,000), and the first blocks of this launch
+// forming them while the others wait (sparse d = 20,000: 25.4 us against 22.7; dense d_c = 128: 23.6 against 18.0).
+template <int NE, int LPC, int UNL = 4>
 __global__ __launch_bounds__(256) void vbpr_update_kernel(
     tkr_vbpr_state st, const int32_t* __restrict__ rec_all, const int2* __restrict__ occ, const int32_t* __restrict__ occt,
     const int4* __restrict__ hdr, const float* __restrict__ s_in, const float* __restrict__ t_in, const float* __restrict__ P,
     const float* __restrict__ Wraw /*[B][kh]: uce_u(t)*/, const int4* __restrict__ colh, const int2* __restrict__ cent,
     int n_row_blocks, int n_col_blocks, int cpb, float* __restrict__ loss_out /*the batch's loss words: [B] projection | [B] pair sums | [column blocks]*/,
-    int ps_B /*batch size*/, int tune, const float* __restrict__ ab = nullptr, uint32_t* pair_done = nullptr, uint32_t pair_target = 0u) {
+    int ps_B /*batch size*/, int tune) {
     constexpr int G = 256 / LPC;
     constexpr int ROWS_LDS = 2 * 4 * (NE * TKR_WAVE + 1);
     constexpr int COLS_LDS = G * (4 * LPC + 1) + 2 * G;
     __shared__ float shm[ROWS_LDS > COLS_LDS ? ROWS_LDS : COLS_LDS];
     typedef float (*red_t)[NE * TKR_WAVE + 1];
-    if constexpr (FUSED) {
-        static_assert(!INLINE, "one way of getting the pair sums");
-        const int n_pair = (ps_B + 3) / 4;
-        if ((int)blockIdx.x < n_pair) {
-            pairsum_wave<true>(ab, ps_B, const_cast<float*>(s_in), const_cast<float*>(t_in), loss_out, blockIdx.x * 4 + (threadIdx.x >> 6), threadIdx.x & 63);
-            asm volatile("s_waitcnt vmcnt(0)" ::: "memory");          // the write-through stores are in memory
-            __syncthreads();
-            if (threadIdx.x == 0) __hip_atomic_fetch_add(pair_done, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-            return;
-        }
-        const int bid = (int)blockIdx.x - n_pair;
-        const bool past_l1 = (ps_B & 31) != 0;
-        if (bid < n_row_blocks) {
-            if (tune & 8) return;
-            const PairSumFresh ps{s_in, t_in, pair_done, pair_target, nullptr, past_l1};
-            vbpr_rows_body<NE, 4>(st, rec_all, occ, occt, hdr, ps, P, nullptr, nullptr, nullptr, reinterpret_cast<red_t>(shm),
-                                  reinterpret_cast<red_t>(shm + 4 * (NE * TKR_WAVE + 1)), bid, n_row_blocks);
-            return;
-        }
-        __shared__ uint32_t pairs_here;                                // wave 0 of the block tells the others (PairSumFresh)
-        if (threadIdx.x == 0) pairs_here = 0u;
-        __syncthreads();
-        const PairSumFresh ps{s_in, t_in, pair_done, pair_target, &pairs_here, past_l1};
-        col_block<LPC, PairSumFresh, UNL>(st, ps, Wraw, colh, cent, bid - n_row_blocks, cpb, loss_out ? loss_out + 2 * ps_B : nullptr, tune, shm);
-    } else if constexpr (INLINE) {
-        const float* ab = s_in;
-        if ((int)blockIdx.x >= n_row_blocks + n_col_blocks) {        // the pair terms of the loss: wave per triplet
-            const int lane = threadIdx.x & 63, t = ((int)blockIdx.x - n_row_blocks - n_col_blocks) * 4 + (threadIdx.x >> 6);
-            if (t >= ps_B || !loss_out) return;
-            const float a_t = ab[t], ea_t = ab[2 * ps_B + t];
-            float loss = 0.f;
-            for (int b = lane; b < ps_B; b += 64) loss += pair_softplus_neg(ea_t, ab[3 * ps_B + b], a_t + ab[ps_B + b]);
-            loss = wave_sum(loss);
-            if (lane == 0) loss_out[ps_B + t] = loss;
-            return;
-        }
-        if ((int)blockIdx.x < n_row_blocks) {
-            if (tune & 8) return;
-            PairSumInline<64> ps;
-            ps.load(ab + 2 * ps_B, ab + 3 * ps_B, ps_B);
-            vbpr_rows_body<NE, 4>(st, rec_all, occ, occt, hdr, ps, P, nullptr, nullptr, nullptr, reinterpret_cast<red_t>(shm),
-                                  reinterpret_cast<red_t>(shm + 4 * (NE * TKR_WAVE + 1)), blockIdx.x, n_row_blocks);
-            return;
-        }
-        PairSumInline<LPC> ps;
-        ps.load(ab + 2 * ps_B, ab + 3 * ps_B, ps_B);
-        col_block<LPC>(st, ps, Wraw, colh, cent, (int)blockIdx.x - n_row_blocks, cpb, loss_out ? loss_out + 2 * ps_B : nullptr, tune, shm);
-    } else {
-        const PairSumArrays ps{s_in, t_in};
-        if ((int)blockIdx.x < n_row_blocks) {
-            if (tune & 8) return;
-            vbpr_rows_body<NE, 4>(st, rec_all, occ, occt, hdr, ps, P, nullptr, nullptr, nullptr, reinterpret_cast<red_t>(shm),
-                                  reinterpret_cast<red_t>(shm + 4 * (NE * TKR_WAVE + 1)), blockIdx.x, n_row_blocks);
-            return;
-        }
-        col_block<LPC, PairSumArrays, UNL>(st, ps, Wraw, colh, cent, (int)blockIdx.x - n_row_blocks, cpb, loss_out ? loss_out + 2 * ps_B : nullptr, tune, shm);
+    const PairSumArrays ps{s_in, t_in};
+    if ((int)blockIdx.x < n_row_blocks) {
+        if (tune & 8) return;
+        vbpr_rows_body<NE, 4>(st, rec_all, occ, occt, hdr, ps, P, nullptr, nullptr, nullptr, reinterpret_cast<red_t>(shm),
+                              reinterpret_cast<red_t>(shm + 4 * (NE * TKR_WAVE + 1)), blockIdx.x, n_row_blocks);
+        return;
     }
+    col_block<LPC, PairSumArrays, UNL>(st, ps, Wraw, colh, cent, (int)blockIdx.x - n_row_blocks, cpb, loss_out ? loss_out + 2 * ps_B : nullptr, tune, shm);
 }
 
 template <int NE, int LPC>
 static void launch_update(const tkr_vbpr_state& st, const int32_t* rec, const int2* occ2, const int32_t* occt, const int4* hdr4,
                           const float* s_buf, const float* t_buf, const float* P, const float* Wm, const int4* colh, const int2* cent,
-                          int B, int cpb, float* loss, hipStream_t stream, int tune, const float* ab_inline /*or null: S / T from s_buf / t_buf*/,
-                          bool long_runs, const float* ab_fused = nullptr /*the pair sums by the first blocks of this launch*/,
-                          uint32_t* pair_done = nullptr, uint32_t pair_target = 0u) {
+                          int B, int cpb, float* loss, hipStream_t stream, int tune, bool long_runs) {
     constexpr int G = 256 / LPC;
     if (cpb <= 0 || cpb > G) cpb = G;
     const int n_row_blocks = vbpr_grid(B, 4);
     const int n_col_blocks = (st.d + cpb - 1) / cpb;
-#ifdef TKR_LAB                                                   // the two placements of the pair sums that lost to a launch of their own: make LAB=1
-    if (ab_fused) {
-        const dim3 grid((B + 3) / 4 + n_row_blocks + n_col_blocks);
-        if (long_runs)
-            hipLaunchKernelGGL((vbpr_update_kernel<NE, LPC, false, 16, true>), grid, dim3(256), 0, stream, st, rec, occ2, occt, hdr4, s_buf, t_buf, P, Wm, colh,
-                               cent, n_row_blocks, n_col_blocks, cpb, loss, B, tune, ab_fused, pair_done, pair_target);
-        else
-            hipLaunchKernelGGL((vbpr_update_kernel<NE, LPC, false, 4, true>), grid, dim3(256), 0, stream, st, rec, occ2, occt, hdr4, s_buf, t_buf, P, Wm, colh,
-                               cent, n_row_blocks, n_col_blocks, cpb, loss, B, tune, ab_fused, pair_done, pair_target);
-    } else if (ab_inline)
-        hipLaunchKernelGGL((vbpr_update_kernel<NE, LPC, true>), dim3(n_row_blocks + n_col_blocks + (loss ? (B + 3) / 4 : 0)), dim3(256), 0, stream, st, rec,
-                           occ2, occt, hdr4, ab_inline, nullptr, P, Wm, colh, cent, n_row_blocks, n_col_blocks, cpb, loss, B, tune);
-    else
-#endif
     if (long_runs)           // a narrow dense feat: every column's run is split over the block's groups, 16 entries in flight (168 registers; 32: slower, 21.5 vs 19.7 us)
-        hipLaunchKernelGGL((vbpr_update_kernel<NE, LPC, false, 16>), dim3(n_row_blocks + n_col_blocks), dim3(256), 0, stream, st, rec, occ2, occt, hdr4,
+        hipLaunchKernelGGL((vbpr_update_kernel<NE, LPC, 16>), dim3(n_row_blocks + n_col_blocks), dim3(256), 0, stream, st, rec, occ2, occt, hdr4,
                            s_buf, t_buf, P, Wm, colh, cent, n_row_blocks, n_col_blocks, cpb, loss, B, tune);
     else
-        hipLaunchKernelGGL((vbpr_update_kernel<NE, LPC, false>), dim3(n_row_blocks + n_col_blocks), dim3(256), 0, stream, st, rec, occ2, occt, hdr4,
+        hipLaunchKernelGGL((vbpr_update_kernel<NE, LPC>), dim3(n_row_blocks + n_col_blocks), dim3(256), 0, stream, st, rec, occ2, occt, hdr4,
                            s_buf, t_buf, P, Wm, colh, cent, n_row_blocks, n_col_blocks, cpb, loss, B, tune);
 }
 
@@ -666,33 +578,11 @@ __global__ __launch_bounds__(256) void vbpr_loss_sum_kernel(const float* __restr
 }
 }  // namespace tkr
 
-// where the pair sums S_t, T_t of a batch come from: 0 = their own launch between the projection and the update (three launches
-// per batch), 1 = every task works out the ones it needs (PairSumInline, batch <= 256), 2 = the first blocks of the update launch
-// (vbpr_update_kernel FUSED).  Initial value: TKR_VBPR_PAIRS, else kVbprPairsDefault.
-namespace tkr {
-constexpr int kVbprPairsDefault = 0;
-static int g_vbpr_pairs = -1;
-static int vbpr_pairs_mode() {
-    if (g_vbpr_pairs < 0) {
-        const char* e = getenv("TKR_VBPR_PAIRS");
-        const int v = e ? atoi(e) : kVbprPairsDefault;
-#ifdef TKR_LAB
-        g_vbpr_pairs = (v >= 0 && v <= 2) ? v : kVbprPairsDefault;
-#else
-        (void)v;
-        g_vbpr_pairs = kVbprPairsDefault;
-#endif
-    }
-    return g_vbpr_pairs;
-}
-}  // namespace tkr
+// where the pair sums S_t, T_t of a batch come from: 0 = their own launch between the projection and the update, the one placement
+// there is; 1 (every task works them out) and 2 (the first blocks of the update launch) were removed (vbpr_update_kernel)
 extern "C" int tkr_vbpr_set_pairs(int32_t mode) {
     if (mode < 0 || mode > 2) return TKR_EINVAL;
-#ifndef TKR_LAB
-    if (mode != 0) return TKR_EUNSUPPORTED;                      // placements 1 and 2 live in the lab library (make LAB=1)
-#endif
-    tkr::g_vbpr_pairs = mode;
-    return TKR_OK;
+    return mode == 0 ? TKR_OK : TKR_EUNSUPPORTED;
 }
 
 extern "C" int64_t tkr_vbpr_colplan_lds_bytes(int32_t batch_size, int32_t d) {
@@ -770,17 +660,6 @@ extern "C" int tkr_vbpr_run_cols(const tkr_vbpr_state* st, const int32_t* tri_i,
     float* slots = loss_out ? workspace + tkr_vbpr_workspace_core_floats(B, kh, st->d) : nullptr;
     if (slots && (n_batches > 512 || (int64_t)n_batches * (int64_t)loss_stride > tkr_vbpr_workspace_floats(B, kh, st->d) - tkr_vbpr_workspace_core_floats(B, kh, st->d)))
         return TKR_EUNSUPPORTED;
-    // The pair sums INSIDE the update launch (two launches per batch: TKR_VBPR_PAIRS=1): rows and column groups work S_t / T_t out for
-    // their own entries from e^alpha / e^beta (PairSumInline).  Measured (round 5, B = 256, d = 20,000): 31.6 us per batch against
-    // 23.1 with the pair-sum launch -- the 4.5 us launch and its boundary go, but every one of the update's ~1,400 blocks now does
-    // 100-250 reciprocals per lane in front of its stores.  Parity-green, not the default.
-    // TKR_VBPR_PAIRS=2: the pair sums by the first blocks of the update launch (vbpr_update_kernel FUSED) -- two launches per batch
-    // and nothing recomputed; 0: the three-launch form.
-    const int pairs_mode = wide ? 0 : tkr::vbpr_pairs_mode();
-    const bool inline_pairs = pairs_mode == 1 && B <= 256;
-    const bool fused_pairs = pairs_mode == 2;
-    uint32_t* pair_done = reinterpret_cast<uint32_t*>(workspace + tkr_vbpr_workspace_floats(B, kh, st->d) - 64);     // the call's counter: last 64 words
-    if (fused_pairs) TKR_CHECK(hipMemsetAsync(pair_done, 0, sizeof(uint32_t), (hipStream_t)stream));
     const bool long_runs = 2.0 * B * (double)row_cap / st->d > (double)tkr::kLightRun;      // (row_cap: the longest row of feat)
     for (int b = 0; b < n_batches; ++b) {
         const int32_t* ti = tri_i + (size_t)b * B;
@@ -809,11 +688,10 @@ extern "C" int tkr_vbpr_run_cols(const tkr_vbpr_state* st, const int32_t* tri_i,
         else if (NH == 1) hipLaunchKernelGGL((tkr::vbpr_tproject_kernel<1, 16>), dim3(B), dim3(1024), 0, s, *st, ti, tj, tu, tp, tc, te, tcap, B, P, ab2, Wm, l, tune);
         else if (pw == 4) hipLaunchKernelGGL((tkr::vbpr_tproject_kernel<2, 4>), dim3(B), dim3(256), 0, s, *st, ti, tj, tu, tp, tc, te, tcap, B, P, ab2, Wm, l, tune);
         else hipLaunchKernelGGL((tkr::vbpr_tproject_kernel<2, 8>), dim3(B), dim3(512), 0, s, *st, ti, tj, tu, tp, tc, te, tcap, B, P, ab2, Wm, l, tune);
-        if (!(tune & 32) && !inline_pairs && !fused_pairs) hipLaunchKernelGGL(tkr::vbpr_pairsum_kernel, dim3((B + 3) / 4), dim3(256), 0, s, ab2, B, s_buf, t_buf, l);
+        if (!(tune & 32)) hipLaunchKernelGGL(tkr::vbpr_pairsum_kernel, dim3((B + 3) / 4), dim3(256), 0, s, ab2, B, s_buf, t_buf, l);
         if (tune & 128) continue;
         const int lpc = kh <= 16 ? 4 : (kh <= 32 ? 8 : (kh <= 64 ? 16 : 32));
-#define TKR_UPD(NE_, LPC_) tkr::launch_update<NE_, LPC_>(*st, r, o2, ot, h4, s_buf, t_buf, P, Wm, ch, ce, B, cols_per_block, l, s, tune, inline_pairs ? ab2 : nullptr, long_runs, \
-                                                         fused_pairs ? ab2 : nullptr, pair_done, (uint32_t)(b + 1) * (uint32_t)((B + 3) / 4))
+#define TKR_UPD(NE_, LPC_) tkr::launch_update<NE_, LPC_>(*st, r, o2, ot, h4, s_buf, t_buf, P, Wm, ch, ce, B, cols_per_block, l, s, tune, long_runs)
         switch (lpc) {
             case 4: TKR_UPD(1, 4); break;
             case 8: TKR_UPD(1, 8); break;

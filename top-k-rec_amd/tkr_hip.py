@@ -370,12 +370,12 @@ def own_stepper(state, B, ctl, owner_waves=0):
     step.state = state
     step.takes_events = True
     step.plan_and_run = plan_and_run
-    step.assigns_loss = not ((owner_waves >> 8) & 0x80)      # the row-read form writes loss_out[b] (csrc/bpr_own.hip own_loss_kernel); the scalar form adds
+    step.assigns_loss = True          # loss_out[b] is written, not added to (csrc/bpr_own.hip own_loss_kernel)
     return step
 
 
 def set_vbpr_pairs(mode):
-    """where tkr_vbpr_run_cols forms a batch's pair sums: 0 own launch, 1 every task for itself, 2 the first blocks of the update launch (include/tkr.h)"""
+    """where tkr_vbpr_run_cols forms a batch's pair sums: 0 own launch, the only placement; 1 and 2 were removed (include/tkr.h)"""
     _check(lib().tkr_vbpr_set_pairs(C.c_int32(int(mode))), 'tkr_vbpr_set_pairs')
 
 
@@ -457,14 +457,14 @@ TOPK_MATH_DEFAULT = 'refine'
 
 def set_topk_math(mode):
     """'refine' (default: one scaled fp16 pass with a rigorous error bound picks the candidates, the arithmetic of 'fp32' ranks
-    them -- same lists and score bits as 'fp32'; k <= 128), 'bf16x3' (split products on the dense matrix pipe, k <= 128) or
-    'fp32' (fp32 MFMA) -- see include/tkr.h"""
+    them -- same lists and score bits as 'fp32'; k <= 128) or 'fp32' (fp32 MFMA) -- see include/tkr.h.  'bf16x3' was removed: the
+    library refuses it (TKR_E_UNSUPPORTED)"""
     _check(lib().tkr_topk_set_math(C.c_int32({'bf16x3': 0, 'fp32': 1, 'refine': 2}[mode])), 'tkr_topk_set_math')
 
 
 def lab():
-    """True when the loaded library was built with `make LAB=1` (csrc/Makefile): it then also holds the kernel forms that were measured
-    and dropped (K2o scalar exchange / scout / 16 waves / loader ring, K4 bf16x3, the VBPR pair-sum placements 1 and 2)"""
+    """False: the `make LAB=1` build with the kernel forms that were measured and dropped (K2o scalar exchange / scout / 8 and 16
+    waves / loader ring, K4 bf16x3, the VBPR pair-sum placements 1 and 2) is removed; tkr_lab_build() stays in the ABI and returns 0"""
     return bool(lib().tkr_lab_build())
 
 
