@@ -151,14 +151,15 @@ def test_sharded_accuracy_tracks_single_stream(tmp_path):
     assert single.mean(0)[-1] > 2 * base[-1] and sharded.mean(0)[-1] > 2 * base[-1]
 
 
-@pytest.mark.parametrize('S', [2, 3])
-def test_streams_mode_matches_oracle_simulation(tmp_path, S):
+@pytest.mark.parametrize('S', [2, 3, 4])
+def test_streams_mode_matches_oracle_simulation(tmp_path, monkeypatch, S):
     """train(streams=S): S user shards on S HIP streams of one GPU == oracle simulation of S shards
-    with the per-epoch sum-of-deltas exchange (the multi-GPU rule applied inside one GPU)."""
+    with the per-epoch sum-of-deltas exchange (the multi-GPU rule applied inside one GPU).  S = 4: every shard plans on a
+    planner stream of its own, and the first chunk of the epoch after the exchange is planned ahead of it."""
     sys.path[:0] = [ROOT, os.path.join(ROOT, 'top-k-rec_amd')]
     import synth
     import dist as tdist
-    from single import BPR
+    from single import BPR, _engine
     from oracle import plan_np as P, ref_np as R
     r = synth.make_ratings(150, 60, 0, seed=17, mu=2.6, sigma=0.4, min_r=4, max_r=25)
     data = str(tmp_path / 'data')
@@ -170,6 +171,13 @@ def test_streams_mode_matches_oracle_simulation(tmp_path, S):
     init = [(rng.standard_normal((m.n_users, k)) * 0.1).astype(np.float32), (rng.standard_normal((m.n_items, k)) * 0.1).astype(np.float32),
             np.zeros((m.n_items, 1), np.float32)]
     m.fue, m.fie, m.fib = (a.copy() for a in init)
+    planned = []                                         # (engine, first triplet, planned ahead of an exchange?) of every K1 chunk
+    plan_chunk = _engine.BprEngine._plan_chunk
+
+    def spy(self, *a, **kw):
+        planned.append((self, a[3], kw.get('shadow') is not None))
+        return plan_chunk(self, *a, **kw)
+    monkeypatch.setattr(_engine.BprEngine, '_plan_chunk', spy)
     m.train(epochs=epochs, batch_size=B, epoch_sample_limit=limit, seed=11, verbose=False, streams=S)
     # every shard ran a persistent step, not the per-batch one: with owned item rows (K2o) on half the CUs each at two shards, K2f from
     # three shards on (a third of the CUs as owners is slower than K2f beside the other shards)
@@ -181,6 +189,18 @@ def test_streams_mode_matches_oracle_simulation(tmp_path, S):
         assert m._eng._plan_owners(B) == 0 and m._eng._last_step_kind == 'flow'
     hp = dict(lu=m.lu, li=m.li, lj=m.lj, lb=m.lb, lr=lr, mode='l2')
     nb = (limit // B) // S
+    assert m._eng.plan_in_order is (S < 4)
+    if S == 4:
+        # private planner streams: every shard planned the first chunk of the epoch after each exchange ahead of it (against a shadow
+        # of the item counters), and ran that chunk -- it was never planned again
+        by_engine = {}
+        for e, first, ahead in planned:
+            by_engine.setdefault(id(e), []).append((first, ahead))
+        assert sorted(min(f for f, _ in v) for v in by_engine.values()) == [q * epochs * nb * B for q in range(S)]
+        for v in by_engine.values():
+            start = min(f for f, _ in v)
+            for ep in range(1, epochs):
+                assert [ahead for f, ahead in v if f == start + ep * nb * B] == [True]
     row_ptr, pos, srt = P.build_csr(m.tr_data, m.n_users)
     st = [dict(U=init[0].copy(), V=init[1].copy(), b=init[2].ravel().copy(), msU=np.ones_like(init[0]), msV=np.ones_like(init[1]),
                msb=np.ones(m.n_items, np.float32)) for _ in range(S)]
@@ -201,6 +221,32 @@ def test_streams_mode_matches_oracle_simulation(tmp_path, S):
     np.testing.assert_allclose(m.fie, st[0]['V'], rtol=2e-4, atol=1e-5)
     np.testing.assert_allclose(m.fib.ravel(), st[0]['b'], rtol=2e-4, atol=1e-5)
     np.testing.assert_allclose(m.fue, U, rtol=2e-4, atol=1e-5)
+
+
+def test_local_shards_report_no_give_up_without_a_status_word():
+    """dist.LocalShards.any_gave_up: the last word of the summed vector is a status only where every shard's pack put one there.  The
+    plain-tensor pack (engines without replicated_tables) ends in a slot mean -- here 1/2 + 1/2 of slots at one -- and nothing gave up"""
+    sys.path[:0] = [ROOT, os.path.join(ROOT, 'top-k-rec_amd')]
+    import dist as tdist
+
+    class Eng:                      # the engine surface ItemSync needs
+        def __init__(self):
+            ones = dict(device='cuda', dtype=torch.float32)
+            self.t = {'V': [torch.randn(9, 4, device='cuda'), torch.ones(9, 4, **ones)], 'b': [torch.zeros(9, **ones), torch.ones(9, **ones)]}
+
+        def get(self, n):
+            return self.t[n][0], self.t[n][1]
+
+        def set_replicated(self, new):
+            for n, (p, ms) in new.items():
+                self.t[n] = [p.clone(), ms.clone()]
+    shards = tdist.LocalShards([Eng(), Eng()], [torch.cuda.Stream(), torch.cuda.Stream()])
+    torch.cuda.synchronize()
+    shards.begin()
+    shards.end()
+    assert float(shards.acc[-1]) == 1.0
+    assert shards.any_gave_up() is False
+    assert shards.any_gave_up(True) is True
 
 
 def _run_cli_ranks(args, world, port, tmp_path):

@@ -111,7 +111,7 @@ def test_train_restarts_one_kernel_down_when_a_step_gives_up(tmp_path, monkeypat
     the first epoch) BPR.train puts back the state it started from and runs again on the next kernel down -- K2o -> K2f -> K2 --
     instead of raising with half-updated tables.  Same start, same counter-based stream: the result is bit for
     bit what a run that never had the upper kernels produces -- also when the launch gave up inside its planner prologue and left
-    K1's touch bitmaps dirty."""
+    K1's touch bitmaps dirty.  The same for the shards of train(streams=2) when one of them gives up."""
     import tkr_hip
     from single import BPR, _engine
     data = _dataset(tmp_path, seed=6)
@@ -153,6 +153,45 @@ def test_train_restarts_one_kernel_down_when_a_step_gives_up(tmp_path, monkeypat
             assert np.array_equal(a, b)
         # (K2f adds a batch's loss up with LDS atomics, K2 with a sliced sum: the tables are bitwise, the reported loss to its last bits)
         assert abs(m.last_epoch_loss - clean.last_epoch_loss) <= 1e-5 * abs(clean.last_epoch_loss)
+    # train(streams=2): the step of ONE shard (the second shard's launch of the first epoch) gives up.  Both shards go back to the lead's
+    # snapshot and on one kernel down together (K2o -> K2f): bit for bit a clean streams=2 run that never had K2o.  TKR_RESTART=0: it raises
+    B, nb, epochs = 64, 15, 2
+    for restart in ('0', '1'):
+        runs = []                                        # (engine, kernel) of every run_batches call
+
+        def flaky_shard(self, *a, **kw):
+            out = orig(self, *a, **kw)
+            if len(runs) == 1:
+                self.ctl[tkr_hip.FLOW_CTL_STATUS] = 1
+                self._cnt.touch_u[::3] = 0x5a5a
+                self._cnt.touch_i[::2] = 0x0f0f
+            runs.append((self, self._last_step_kind))
+            return out
+        monkeypatch.setattr(_engine.BprEngine, 'run_batches', flaky_shard)
+        monkeypatch.setenv('TKR_RESTART', restart)
+        m = model()
+        if restart == '0':
+            with pytest.raises(tkr_hip.StepGaveUp):
+                m.train(epochs=epochs, batch_size=B, epoch_sample_limit=B * 2 * nb, seed=9, verbose=False, streams=2)
+            assert len(runs) == 2
+            continue
+        with pytest.warns(UserWarning, match='restarts from its initial state'):
+            m.train(epochs=epochs, batch_size=B, epoch_sample_limit=B * 2 * nb, seed=9, verbose=False, streams=2)
+        shards = list({id(e): e for e, _ in runs}.values())
+        assert len(shards) == 2 and shards[0] is m._eng
+        assert [k for _, k in runs] == ['own'] * 2 + ['flow'] * 2 * epochs
+        for q, e in enumerate(shards):
+            assert e.layout == 'flow' and e._plan_owners(B) == 0
+            assert e.triplets_drawn == (q + 1) * epochs * nb * B
+    monkeypatch.delenv('TKR_RESTART')
+    monkeypatch.setattr(_engine.BprEngine, 'run_batches', orig)
+    monkeypatch.setenv('TKR_OWN', '0')
+    clean = model()
+    clean.train(epochs=epochs, batch_size=B, epoch_sample_limit=B * 2 * nb, seed=9, verbose=False, streams=2)
+    monkeypatch.delenv('TKR_OWN')
+    assert clean._eng._last_step_kind == 'flow'
+    for a, b in ((m.fue, clean.fue), (m.fie, clean.fie), (m.fib, clean.fib)):
+        assert np.array_equal(a, b)
 
 
 def test_call_ahead_plans_the_next_call_behind_this_one():

@@ -116,8 +116,8 @@ def test_vbpr_class_end_to_end(tmp_path):
 
 
 def test_vbpr_streams_mode_matches_oracle_simulation(tmp_path):
-    """VBPR.train(streams=2) on the column-plan step (plan_ahead built its buffers without the column plan and the step
-    raised AttributeError; only BPR had a streams test): two user shards on two HIP streams == the oracle simulation of two shards
+    """VBPR.train(streams=2) on the column-plan step (the streams mode's planner built its buffers without the column plan
+    and the step raised AttributeError; only BPR had a streams test): two user shards on two HIP streams == the oracle simulation of two shards
     with the per-epoch exchange of ire / irb / cem / icb (sum of deltas, slots averaged)"""
     import synth
     import dist as tdist

@@ -118,6 +118,7 @@ class ItemSync:
         self.tabs = None
         self._bound = None
         self._start_valid = None     # (binding, engine.item_mutations) for which start_flat already holds the epoch's start
+        self._flagged = False        # the last word of flat is this rank's gave-up flag (_flag_status), not a slot mean
         self.timing = None           # a list: end() appends (before pack, after pack, after collective, after unpack) timing events
         self._bind()
 
@@ -214,7 +215,7 @@ class ItemSync:
 
     def any_gave_up(self, mine=False):
         """after end(): True on EVERY rank if a persistent step gave up on ANY rank during the epoch just exchanged (host wait)"""
-        if getattr(self, '_flagged', False):
+        if self._flagged:
             self._flagged = False
             return bool(mine) or float(self.flat[-1]) > 0.0
         return bool(mine)
@@ -355,7 +356,12 @@ class LocalShards:
             self.timing.append(tuple(ev))
 
     def any_gave_up(self, mine=False):
-        return bool(mine) or (self.acc is not None and float(self.acc[-1]) > 0.0)
+        """after end(): True if a persistent step gave up on ANY shard during the epoch just exchanged (host wait).  The last word of
+        the sum is a status only where every shard's pack put one there (ItemSync._flag_status); the plain-tensor pack ends in a slot mean"""
+        flagged = all(s._flagged for s in self.syncs)
+        for s in self.syncs:
+            s._flagged = False
+        return bool(mine) or (flagged and self.acc is not None and float(self.acc[-1]) > 0.0)
 
 
 def gather_owned_rows(owned, rows: torch.Tensor, slots: torch.Tensor):

@@ -234,7 +234,7 @@ class PlanMixin:
     many batches to run, otherwise exactly what the call has left -- every run_batches call samples and plans its own
     batches, like the loop of single/bpr.py:138-147 does (rounds 1-2 always planned a full chunk, so a short call consumed
     batches that an earlier call had sampled: bench.py's 20 timed steps contained no K1 -- VERDICT r2).  A chunk that a
-    caller leaves unfinished all the same (an exception, plan_ahead's users) is continued by the next call, and whenever
+    caller leaves unfinished all the same (an exception) is continued by the next call, and whenever
     something needs the counters of the batches that really RAN (get / set of parameters, the per-epoch exchange, a
     different batch size or sample position) settle() takes the rest of the plan out again (tkr_plan_rollback): K1
     advances the update counters for every PLANNED batch.  The stream is counter-based, so re-planning from the same
@@ -264,7 +264,7 @@ class PlanMixin:
 
     def _plan_overlap(self, B):
         """plan the chunk after the running one on the side stream?"""
-        if getattr(self, 'plan_in_order', False):      # one of several shards on one GPU: no planner stream (see BPR._train_streams)
+        if getattr(self, 'plan_in_order', False):      # one of several shards on one GPU: no planner stream (see BPR._stream_shards)
             return False
         return B >= self.cfg.overlap_min_batch or self._plan_flow()
 
@@ -312,7 +312,7 @@ class PlanMixin:
     def settle(self, check=True, keep_epoch_ahead=False):
         """drop what is planned but has not run; afterwards the counters describe the tables.  Everything that takes results
         out of an engine (get / set, the exchange, the counters) comes through here, so this is also where a failed
-        persistent step is reported (only BPR._run_epoch looked at the status word).
+        persistent step is reported (only BPR.train's epoch loop looked at the status word).
         ``keep_epoch_ahead`` (the exchange itself): a chunk planned ahead of the exchange stays -- the item counters it was
         planned against are its own (shadow) or, once adopted, describe tables that are exactly as the plan assumes."""
         if check:
@@ -466,46 +466,6 @@ class PlanMixin:
             loss = plan.loss[lo:lo + m] if want_loss else None
             self.plan = plan
         return loss
-
-
-def plan_ahead(eng, csr, n_batches, B):
-    """K1 for n_batches batches into freshly held buffers (no stepping): -> [(PlanBuffers, nb), ...].
-    Used by the multi-stream mode, where planner launches would disturb the other streams' step chains."""
-    eng.settle()
-    cap = eng._cap(B)                 # an engine may plan fewer batches per call than the bitmap allows (VBPR: its column plans)
-    cols = eng._plan_cols(B)          # ... and want the column plan of its batches beside K1's (ADVICE r3: VBPR train(streams > 1) crashed without)
-    planned, left = [], n_batches
-    pool = getattr(eng, '_plan_pool', [])
-    idx = 0
-    while left:
-        nb = min(cap, left)
-        if idx >= len(pool) or pool[idx].B != B or pool[idx].cap < nb or pool[idx].cols != cols or pool[idx].flow:
-            buf = PlanBuffers(cap, B, eng.device, cols=cols)
-            if idx < len(pool):
-                pool[idx] = buf
-            else:
-                pool.append(buf)
-        buf = pool[idx]
-        tkr_hip.sample_plan(csr, eng.n_users, eng.n_items, eng.seed, eng._drawn, nb, B, eng._cnt, buf)
-        eng._plan_extra(buf, nb, B)
-        eng._drawn += nb * B
-        planned.append((buf, nb))
-        left -= nb
-        idx += 1
-    eng._plan_pool = pool
-    return planned
-
-
-def run_planned(eng, planned, B, want_loss, step_fn):
-    """step kernels of batches planned by plan_ahead, on the current stream"""
-    loss = None
-    for plan, nb in planned:
-        if want_loss:
-            plan.loss[:nb].zero_()
-        step_fn(plan, 0, nb, plan.loss if want_loss else None)
-        loss = plan.loss[:nb] if want_loss else None
-        eng.plan = plan
-    return loss
 
 
 class DoubleTable:
@@ -662,7 +622,7 @@ class BprEngine(PlanMixin):
                 cus = torch.cuda.get_device_properties(self.device).multi_processor_count if self.device.type == 'cuda' else 0
                 warnings.warn('K2o is off: %d ranks share this GPU and %d item rows of width %d do not fit %d owners\' LDS; the persistent '
                               'step without owned rows (K2f) runs instead' % (share, self.n_items, self.k, cus // share))
-        if cache[share] < getattr(self, 'own_min_owners', 0):          # shards of one process (BPR._train_streams): K2f below that many owners
+        if cache[share] < getattr(self, 'own_min_owners', 0):          # shards of one process (BPR._stream_shards): K2f below that many owners
             return 0
         return cache[share]
 

@@ -240,72 +240,59 @@ class BPR(REC):
             # by the hand-offs of its dependency chain and leaves most of the chip idle (bench.py shards_on_one_gpu).  Not
             # the reference's single-stream semantics: off by default.
             assert world == 1, 'streams > 1 and torch.distributed sharding are not combined'
-            self._train_streams(epochs, n_batches, batch_size, streams, verbose)
-            self._collect()
-            return
+            shards = self._stream_shards(streams, batch_size)
+        else:
+            # one engine; sharded: each rank owns the rows of its users (build_graph allocated only those and re-indexed the CSR), the
+            # item-side tables are replicas, reconciled once per epoch; the user rows are gathered once, after training (_collect)
+            shards = [(self._eng, self._csr, None)]
+        nb = tdist.batches_per_rank(n_batches, world * streams)
+        for i, (e, _, _) in enumerate(shards):
+            e.triplets_drawn = (rank + i) * epochs * nb * batch_size          # disjoint stream positions, one key
         if world > 1:
-            # each rank owns the rows of its users (build_graph allocated only those and re-indexed the CSR); the item-side
-            # tables are replicas, reconciled once per epoch; the user rows are gathered once, after training (_collect)
-            n_batches = tdist.batches_per_rank(n_batches, world)
-            self._eng.triplets_drawn = rank * epochs * n_batches * batch_size      # disjoint stream positions
             tdist.assert_replicated(self._eng)             # same seed, same warm start: the replicas must start equal
         # A persistent step (K2f / K2o) that cannot get its workgroups resident -- a GPU shared with something that never ends --
         # gives up after a bounded spin and leaves half-updated tables; the engine then steps down one kernel (K2o -> K2f -> K2).
         # The run starts again from the state kept here, on the same counter-based sample stream: it degrades instead of raising.
+        # (VBPR steps one launch at a time: nothing to give up; TKR_RESTART=0: no copy of the tables, a step that gives up raises)
+        # Shards of one GPU all start from the lead's model: its snapshot restores every one of them.
+        lead = self._eng
+        start = lead.snapshot() if (getattr(lead, 'layout', None) == 'flow' and lead.cfg.restart) else None
+        if len(shards) > 1:                                # where the user rows of the shards are merged from after training
+            users_start = start['U'] if start is not None else tuple(t.clone() for t in lead.get('U'))
         for attempt in range(3):
-            # (VBPR steps one launch at a time: nothing to give up; TKR_RESTART=0: no copy of the tables, a step that gives up raises)
-            start = self._eng.snapshot() if (getattr(self._eng, 'layout', None) == 'flow' and self._eng.cfg.restart) else None
-            if self._train_epochs(epochs, n_batches, batch_size, world, verbose):
+            if len(shards) > 1:
+                exchange = tdist.LocalShards([e for e, _, _ in shards], [st for _, _, st in shards])
+            else:
+                exchange = tdist.ItemSync(lead) if world > 1 else None
+            if self._train_epochs(shards, exchange, epochs, nb, batch_size, verbose):
                 break
+            # every engine's status word before anything is put back: one whose own step gave up goes through _failed() (which zeroes
+            # it and picks the next kernel down), unless it did so in the epoch loop already; the others step down in lockstep with it
+            for e, _, _ in shards:
+                try:
+                    e.check()
+                except tkr_hip.StepGaveUp as x:
+                    warnings.warn('BPR.train restarts from its initial state: %s' % x)
+                if not getattr(e, 'tables_invalid', False):
+                    e.step_down()
             if start is None or attempt == 2:
                 raise tkr_hip.StepGaveUp('BPR.train: the step gave up on every kernel form')
-            self._eng.restore(start)
-            self._eng.prepare(batch_size)                  # (the table layout of the kernel the engine stepped down to)
+            for i, (e, _, _) in enumerate(shards):
+                e.restore(start)
+                e.triplets_drawn = (rank + i) * epochs * nb * batch_size
+                e.prepare(batch_size)                      # (the table layout of the kernel the engine stepped down to)
+        if len(shards) > 1:                                # every user row was changed by at most one shard
+            (p0, ms0), parts = users_start, [e.get('U') for e, _, _ in shards]
+            lead.set_users(U=p0 + sum(p - p0 for p, _ in parts), msU=ms0 + sum(ms - ms0 for _, ms in parts))     # slots may come from a checkpoint, not 1
         self._collect()
 
-    def _train_epochs(self, epochs, n_batches, batch_size, world, verbose):
-        """the epoch loop of bpr.py:136-150; False = a persistent step gave up on some rank (every rank returns False then)"""
-        import dist as tdist
-        sync = tdist.ItemSync(self._eng) if world > 1 else None
-        for eid in range(epochs):
-            t0 = time.time()
-            if sync is not None:
-                sync.begin()
-            # sharded: the exchange follows this call, then an epoch of n_batches more -- its first chunk is planned behind this
-            # epoch's last steps (PlanMixin), and the host looks at the loss only after the exchange is queued
-            gave_up = mine = False
-            try:
-                loss = self._run_epoch(n_batches, batch_size, n_batches if (sync is not None and eid + 1 < epochs) else 0, defer=sync is not None)
-                if sync is not None:
-                    sync.end()
-                    loss = self._epoch_loss(loss)
-            except tkr_hip.StepGaveUp as e:
-                warnings.warn('BPR.train restarts from its initial state: %s' % e)
-                gave_up = mine = True
-            if sync is not None:
-                gave_up = sync.any_gave_up(gave_up)          # the flag rode in the exchange: every rank agrees, no extra collective
-            if gave_up:
-                if not mine and hasattr(self._eng, 'step_down'):
-                    self._eng.step_down()                    # in lockstep with the rank whose step gave up
-                return False
-            torch.cuda.synchronize(self._eng.device)
-            spent = time.time() - t0
-            self.last_epoch_loss = loss
-            if verbose:
-                sys.stderr.write('\rEpoch=%3d, batch=%6d, loss=%8.4f, time=%4.4fs' % (eid + 1, n_batches, loss, spent / n_batches))
-                sys.stderr.write(' ... total time collapse %8.4fs' % spent)
-                sys.stderr.flush()
-                print()
-        return True
-
-    def _train_streams(self, epochs, n_batches, batch_size, S, verbose):
-        """the multi-GPU layout inside ONE GPU: S user shards with replicated item tables, each a persistent step of its own on
-        CUs // S owners (K2o; K2f / K2 where the layout asks for them) on its own HIP stream, reconciled once per epoch by
-        dist.LocalShards -- pack, sum, unpack: the exchange of the sharded loop (bpr.py:136-147) without the collective."""
+    def _stream_shards(self, S, batch_size):
+        """the S shards of train(streams=S) as (engine, training CSR of its users, HIP stream): the multi-GPU layout inside ONE GPU,
+        each shard a persistent step of its own on CUs // S owners (K2o; K2f / K2 where the layout asks for them), every one starting
+        from the lead's (possibly warm-started) model"""
         import dist as tdist
         dev = self._eng.device
         engines = [self._eng] + [self._make_engine(dev, self._eng.seed) for _ in range(S - 1)]
-        lead = engines[0]
         for e in engines:
             e.ranks_on_device = S                          # the CUs are split between the shards' launches
             # ... through K2o down to half the CUs per shard; on fewer owners a shard's K2o is slower than K2f beside the other shards
@@ -317,50 +304,52 @@ class BPR(REC):
             # (S = 2: 105 -> 133 M triplets/s with K1 in order on the shard's stream; S = 4 / 8: 127 / 125 -> 123 / 123, kept as they were)
             e.plan_in_order = S + 1 <= 4 < 2 * S + 1
             e.prepare(batch_size)
-        for e in engines[1:]:                              # every shard starts from the same (possibly warm-started) model
-            e.copy_model_from(lead)
-        nb = tdist.batches_per_rank(n_batches, S)
-        csrs, hip_streams = [], []
-        for i, e in enumerate(engines):
-            csrs.append(self._make_csr(tdist.shard_users(self.tr_users, i, S), dev))
-            e.triplets_drawn = i * epochs * nb * batch_size                      # disjoint stream positions, one key
-            hip_streams.append(torch.cuda.Stream(device=dev))
-        users_start, users_ms_start = (t.clone() for t in lead.get('U'))
-        shards = tdist.LocalShards(engines, hip_streams)
-        self._shards = shards
-        torch.cuda.synchronize(dev)
+        for e in engines[1:]:
+            e.copy_model_from(engines[0])
+        return [(e, self._make_csr(tdist.shard_users(self.tr_users, i, S), dev), torch.cuda.Stream(device=dev)) for i, e in enumerate(engines)]
+
+    def _train_epochs(self, shards, exchange, epochs, nb, batch_size, verbose):
+        """the epoch loop of bpr.py:136-150 for every shard [(engine, training CSR, HIP stream or None)], nb batches each, the item tables
+        reconciled after every epoch by ``exchange``: dist.ItemSync between ranks, dist.LocalShards between the shards of one GPU (pack,
+        sum, unpack: the exchange of the ranks without the collective), None for one engine alone.  False = a persistent step gave up on
+        some shard or rank (every rank returns False then)."""
+        lead = shards[0][0]
+        torch.cuda.synchronize(lead.device)                # the shards' streams start behind the set-up (or restore) on this one
         for eid in range(epochs):
             t0 = time.time()
-            shards.begin()
-            losses = []
-            for e, csr, st in zip(engines, csrs, hip_streams):                  # S persistent launches side by side
-                with torch.cuda.stream(st):
-                    losses.append(e.run_batches(csr, nb, batch_size, want_loss=True, then_exchange=nb if eid + 1 < epochs else 0)[-1:].clone())
-            shards.end()
-            torch.cuda.synchronize(dev)
-            if shards.any_gave_up():
-                raise tkr_hip.StepGaveUp('BPR.train(streams=%d): a persistent step gave up on one of the shards' % S)
+            # with an exchange: it follows the steps, then an epoch of nb more -- its first chunk is planned behind this epoch's last steps
+            # (PlanMixin), and the host looks at the loss only after the exchange is queued
+            more = nb if (exchange is not None and eid + 1 < epochs) else 0
+            gave_up = False
+            try:
+                if exchange is not None:
+                    exchange.begin()
+                losses = []
+                for e, csr, st in shards:                  # S persistent launches side by side
+                    with torch.cuda.stream(st):
+                        last = e.run_batches(csr, nb, batch_size, want_loss=True, then_exchange=more)[-1:]
+                        losses.append(last if exchange is None else last.clone())
+                if exchange is not None:
+                    exchange.end()
+                loss = float(losses[0][0])                 # the lead's
+                lead.check()
+            except tkr_hip.StepGaveUp as x:
+                warnings.warn('BPR.train restarts from its initial state: %s' % x)
+                gave_up = True
+            if exchange is not None:
+                gave_up = exchange.any_gave_up(gave_up)    # the flag rode in the exchange: every rank and shard agrees, no extra collective
+            torch.cuda.synchronize(lead.device)            # (a restart puts the tables back on this stream: nothing may still run on the others)
+            if gave_up:
+                return False
             spent = time.time() - t0
-            self.last_epoch_loss = float(losses[0][0])
+            self.last_epoch_loss = loss
             if verbose:
-                sys.stderr.write('\rEpoch=%3d, batch=%6d, loss=%8.4f, time=%4.4fs' % (eid + 1, nb * S, self.last_epoch_loss, spent / (nb * S)))
+                total = nb * len(shards)
+                sys.stderr.write('\rEpoch=%3d, batch=%6d, loss=%8.4f, time=%4.4fs' % (eid + 1, total, loss, spent / total))
                 sys.stderr.write(' ... total time collapse %8.4fs' % spent)
                 sys.stderr.flush()
                 print()
-        parts = [e.get('U') for e in engines]               # every user row was changed by at most one shard
-        lead.set_users(U=users_start + sum(p - users_start for p, _ in parts),
-                       msU=users_ms_start + sum(ms - users_ms_start for _, ms in parts))     # slots may come from a checkpoint, not 1
-
-    def _run_epoch(self, n_batches, batch_size, then_exchange=0, defer=False):
-        losses = self._eng.run_batches(self._csr, n_batches, batch_size, want_loss=True, then_exchange=then_exchange)
-        if defer:
-            return losses[-1:].clone()         # read by _epoch_loss once the exchange is queued behind the steps
-        return self._epoch_loss(losses[-1:])
-
-    def _epoch_loss(self, last):
-        last = float(last[0])
-        self._eng.check()
-        return last
+        return True
 
     # ------------------------------------------------------------------ sampler (bpr.py:155-165)
     def _uniform_user_sampling(self, batch_size: int):

@@ -25,7 +25,7 @@ class TkrError(RuntimeError):
 
 class StepGaveUp(TkrError):
     """a bounded spin of a persistent step kernel ran out: the tables of the run are invalid, the engine has stepped down to the
-    next kernel (K2o -> K2f -> K2) and works again once valid tables are put back (BPR.train does: single/bpr.py _run_epoch)"""
+    next kernel (K2o -> K2f -> K2) and works again once valid tables are put back (BPR.train does)"""
 
 
 class BprState(C.Structure):
