@@ -280,14 +280,17 @@ typedef struct {
     int64_t* item_tag;
 } tkr_vbpr_state;
 
-/* floats of scratch tkr_vbpr_run needs (split-K partials, s_t, P_t, W_t) */
+/* floats of scratch tkr_vbpr_run needs (split-K partials, s_t, P_t, W_t; the sparse view's per-item sums A, a: the same carve at any kh) */
 int64_t tkr_vbpr_workspace_floats(int32_t batch_size, int32_t kh, int32_t d);
 /* tkr_vbpr_run_cols: where the [B, B] pair sums S_t, T_t of a batch (vbpr.py:61) are formed -- 0: a launch of their own between the
  * projection and the update (three launches per batch), the only placement.  1 (every task of the update works out the sums it
  * needs) and 2 (the first blocks of the update launch form them) were measured slower and removed: TKR_E_UNSUPPORTED. */
 int tkr_vbpr_set_pairs(int32_t mode);
 /* n_batches consecutive batches planned by tkr_sample_plan (tri_i / tri_j = its out_i / out_j);
- * kh <= 128 (any kh: tkr_vbpr_run_cols), batch_size <= 65536 (batches above 8192 are planned grid-wide, see tkr_sample_plan); loss_out as in tkr_bpr_run */
+ * any batch_size (batches above 8192 are planned grid-wide, see tkr_sample_plan; above 65,536 the first four triplet indices of a
+ * launch record are read from occt); kh <= 128 holds rows in registers, kh > 128 runs the generic form of the sparse view
+ * (csrc/vbpr_wide.hip: factors walked in passes) and needs the CSR view (st->f_ptr): the dense MFMA view at kh > 128 is
+ * TKR_E_UNSUPPORTED; loss_out as in tkr_bpr_run */
 int tkr_vbpr_run(const tkr_vbpr_state* st, const int32_t* tri_i, const int32_t* tri_j, const int32_t* rec,
                  const int32_t* occ, const int32_t* hdr, const int32_t* occt, const int32_t* tri_u /*nullable*/,
                  const int32_t* tpar /*nullable*/, int32_t batch_size,

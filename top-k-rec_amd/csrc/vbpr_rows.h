@@ -38,7 +38,11 @@ struct WaveRec {
     int oa[4], ob[4], ot[4];
 };
 
-__device__ __forceinline__ WaveRec read_rec(const int32_t* __restrict__ rec_all, int team, int blk, int wave, int lane) {
+// kBig (batches above 65,536): the record's 16-bit halves cannot hold a triplet index, so the first four are taken from occt, which
+// holds every occurrence's (the record layout stays as it is: K1 and BPR's step kernels share it)
+template <bool kBig = false>
+__device__ __forceinline__ WaveRec read_rec(const int32_t* __restrict__ rec_all, int team, int blk, int wave, int lane,
+                                            const int32_t* __restrict__ occt = nullptr) {
     const int word = (lane < 16) ? rec_all[((size_t)blk * team + wave) * 16 + lane] : 0;
     WaveRec r;
     r.rowk = bcast_i(word, 0);
@@ -49,8 +53,14 @@ __device__ __forceinline__ WaveRec read_rec(const int32_t* __restrict__ rec_all,
     r.first = bcast_i(word, 3);
 #pragma unroll
     for (int q = 0; q < 4; ++q) { r.oa[q] = bcast_i(word, 4 + 2 * q); r.ob[q] = bcast_i(word, 5 + 2 * q); }
-    const int t01 = bcast_i(word, 13), t23 = bcast_i(word, 14);
-    r.ot[0] = t01 & 0xffff; r.ot[1] = (t01 >> 16) & 0xffff; r.ot[2] = t23 & 0xffff; r.ot[3] = (t23 >> 16) & 0xffff;
+    if constexpr (kBig) {
+        const int t = (r.rowk != -1 && lane < min(4, r.n_occ)) ? occt[r.first + lane * r.team] : 0;
+#pragma unroll
+        for (int q = 0; q < 4; ++q) r.ot[q] = bcast_i(t, q);
+    } else {
+        const int t01 = bcast_i(word, 13), t23 = bcast_i(word, 14);
+        r.ot[0] = t01 & 0xffff; r.ot[1] = (t01 >> 16) & 0xffff; r.ot[2] = t23 & 0xffff; r.ot[3] = (t23 >> 16) & 0xffff;
+    }
     return r;
 }
 
@@ -86,7 +96,7 @@ struct PairSumArrays {
     }
 };
 
-template <int NE, int kVTeam, typename PairSums>
+template <int NE, int kVTeam, typename PairSums, bool kBig = false>
 __device__ __forceinline__ void vbpr_rows_body(
     const tkr_vbpr_state& st, const int32_t* __restrict__ rec_all, const int2* __restrict__ occ,
     const int32_t* __restrict__ occt, const int4* __restrict__ hdr, const PairSums& ps, const float* __restrict__ P, const float* __restrict__ Wm,
@@ -102,7 +112,7 @@ __device__ __forceinline__ void vbpr_rows_body(
     for (int it = first_blk; it < n_blocks; it += blk_stride) {
         const int blk = n_blocks - 1 - it;           // backwards: the heavy teams at the end of the record list start first (csrc/bpr_step.hip)
         const bool heavy = blk >= nlb;
-        const WaveRec r = read_rec(rec_all, kVTeam, blk, wave, lane);
+        const WaveRec r = read_rec<kBig>(rec_all, kVTeam, blk, wave, lane, occt);
         if (r.rowk == -1) continue;
         const bool is_item = r.rowk < 0;
         const int row = r.rowk & 0x7fffffff, par = r.par;

@@ -34,7 +34,8 @@
 // batch's membership bitmap; V3 is replaced by S3, one wave per feature column walking the column's (item, value) list
 // (CSC), adding value * A[slot] for the tagged items in ascending item order (deterministic) and applying the same
 // dense RMSProp.  Work drops from 4*d*kh flop per triplet to ~2*nnz_row*kh; what remains is the 16*d*kh B of
-// dense optimizer traffic per batch plus the 8 B per nonzero of the CSC walk.
+// dense optimizer traffic per batch plus the 8 B per nonzero of the CSC walk.  kh > 128: the same five launches in their generic form
+// (csrc/vbpr_wide.hip G1-G4, the factors walked in passes, nothing held per factor), on the same records and workspace carve.
 //
 // Roofline (dense features, d = 20,000, kh = 64, B = 256): 4*d*kh = 5.12 MFLOP per triplet on the
 // fp32 MFMA (V1 + V3) against 2*4d B = 160 KB of feature rows per triplet read twice from HBM/MALL
@@ -157,7 +158,7 @@ __global__ __launch_bounds__(1024) void vbpr_reduce_kernel(const float* __restri
 
 // ------------------------------------------------------------------------------------------------
 // V1b: user occurrences -> s_t, P_t, W_t, loss.   NH = ceil(kh / 64)
-template <int NH, int kVTeam>
+template <int NH, int kVTeam, bool kBig = false>
 __global__ __launch_bounds__((kVTeam * TKR_WAVE)) void vbpr_occur_kernel(
     tkr_vbpr_state st, const int32_t* __restrict__ rec_all, const int2* __restrict__ occ,
     const int32_t* __restrict__ occt, const int4* __restrict__ hdr, int B, const float* __restrict__ Q,
@@ -169,7 +170,7 @@ __global__ __launch_bounds__((kVTeam * TKR_WAVE)) void vbpr_occur_kernel(
     const size_t ustride = (size_t)st.n_users * k2, istride = (size_t)st.n_items * kh;
     const bool l2 = st.mode == 0;
     for (int blk = blockIdx.x; blk < n_blocks; blk += gridDim.x) {
-        const WaveRec r = read_rec(rec_all, kVTeam, blk, wave, lane);
+        const WaveRec r = read_rec<kBig>(rec_all, kVTeam, blk, wave, lane, occt);
         if (r.rowk < 0) continue;                       // item task or idle wave (-1): nothing to do here
         const int u = r.rowk;
         const float* urow = st.U + r.par * ustride + (size_t)u * k2;
@@ -280,7 +281,7 @@ __global__ __launch_bounds__(256) void vbpr_pair_kernel(const float* __restrict_
     }
 }
 
-template <int NE, int kVTeam>
+template <int NE, int kVTeam, bool kBig = false>
 __global__ __launch_bounds__((kVTeam * TKR_WAVE)) void vbpr_rows_kernel(
     tkr_vbpr_state st, const int32_t* __restrict__ rec_all, const int2* __restrict__ occ,
     const int32_t* __restrict__ occt, const int4* __restrict__ hdr, const float* __restrict__ s_in /*S_t*/,
@@ -288,7 +289,8 @@ __global__ __launch_bounds__((kVTeam * TKR_WAVE)) void vbpr_rows_kernel(
     float* __restrict__ Aw /*[slots][kh] or null*/, float* __restrict__ ab /*[slots]*/) {
     __shared__ float red[kVTeam][NE * TKR_WAVE + 1];
     __shared__ float red2[kVTeam][NE * TKR_WAVE + 1];
-    vbpr_rows_body<NE, kVTeam>(st, rec_all, occ, occt, hdr, PairSumArrays{s_in, t_in}, P, Wm, Aw, ab, red, red2, blockIdx.x, gridDim.x);
+    vbpr_rows_body<NE, kVTeam, PairSumArrays, kBig>(st, rec_all, occ, occt, hdr, PairSumArrays{s_in, t_in}, P, Wm, Aw, ab, red, red2, blockIdx.x,
+                                                    gridDim.x);
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -631,7 +633,7 @@ __global__ __launch_bounds__(256) void vbpr_sdense_kernel(tkr_vbpr_state st, con
 }
 
 
-template <int NT, int TEAM>
+template <int NT, int TEAM, bool kBig = false>
 static int launch_vbpr_t(const tkr_vbpr_state& st, const int32_t* ti, const int32_t* tj, const int32_t* rec,
                          const int32_t* occ, const int32_t* hdr, const int32_t* occt, int B, float* ws, float* loss,
                          hipStream_t stream, const int32_t* tu, const int32_t* tpar) {
@@ -661,15 +663,15 @@ static int launch_vbpr_t(const tkr_vbpr_state& st, const int32_t* ti, const int3
         hipLaunchKernelGGL(vbpr_reduce_kernel, dim3(B), dim3(1024), 0, stream, ppart, S, B, kh, P, Q);
     }
     if (!(sparse && tpar)) {
-        if (NH == 1) hipLaunchKernelGGL((vbpr_occur_kernel<1, TEAM>), rgrid, rblock, 0, stream, st, rec, occ2, occt, hdr4, B, Q, ab2, P, Wm, loss);
-        else hipLaunchKernelGGL((vbpr_occur_kernel<2, TEAM>), rgrid, rblock, 0, stream, st, rec, occ2, occt, hdr4, B, Q, ab2, P, Wm, loss);
+        if (NH == 1) hipLaunchKernelGGL((vbpr_occur_kernel<1, TEAM, kBig>), rgrid, rblock, 0, stream, st, rec, occ2, occt, hdr4, B, Q, ab2, P, Wm, loss);
+        else hipLaunchKernelGGL((vbpr_occur_kernel<2, TEAM, kBig>), rgrid, rblock, 0, stream, st, rec, occ2, occt, hdr4, B, Q, ab2, P, Wm, loss);
     }
     hipLaunchKernelGGL(vbpr_pair_kernel, dim3((B + 3) / 4), dim3(256), 0, stream, ab2, B, kh, s_buf, t_buf, Wm, loss);
     switch (NE) {
-        case 1: hipLaunchKernelGGL((vbpr_rows_kernel<1, TEAM>), rgrid, rblock, 0, stream, st, rec, occ2, occt, hdr4, s_buf, t_buf, P, Wm, Aw, ab); break;
-        case 2: hipLaunchKernelGGL((vbpr_rows_kernel<2, TEAM>), rgrid, rblock, 0, stream, st, rec, occ2, occt, hdr4, s_buf, t_buf, P, Wm, Aw, ab); break;
-        case 3: hipLaunchKernelGGL((vbpr_rows_kernel<3, TEAM>), rgrid, rblock, 0, stream, st, rec, occ2, occt, hdr4, s_buf, t_buf, P, Wm, Aw, ab); break;
-        default: hipLaunchKernelGGL((vbpr_rows_kernel<4, TEAM>), rgrid, rblock, 0, stream, st, rec, occ2, occt, hdr4, s_buf, t_buf, P, Wm, Aw, ab); break;
+        case 1: hipLaunchKernelGGL((vbpr_rows_kernel<1, TEAM, kBig>), rgrid, rblock, 0, stream, st, rec, occ2, occt, hdr4, s_buf, t_buf, P, Wm, Aw, ab); break;
+        case 2: hipLaunchKernelGGL((vbpr_rows_kernel<2, TEAM, kBig>), rgrid, rblock, 0, stream, st, rec, occ2, occt, hdr4, s_buf, t_buf, P, Wm, Aw, ab); break;
+        case 3: hipLaunchKernelGGL((vbpr_rows_kernel<3, TEAM, kBig>), rgrid, rblock, 0, stream, st, rec, occ2, occt, hdr4, s_buf, t_buf, P, Wm, Aw, ab); break;
+        default: hipLaunchKernelGGL((vbpr_rows_kernel<4, TEAM, kBig>), rgrid, rblock, 0, stream, st, rec, occ2, occt, hdr4, s_buf, t_buf, P, Wm, Aw, ab); break;
     }
     if (sparse) {
         if (NH == 1) hipLaunchKernelGGL(vbpr_sdense_kernel<1>, dim3((st.d + 3) / 4), dim3(256), 0, stream, st, Aw, ab, loss);
@@ -690,11 +692,45 @@ template <int NT>
 static int launch_vbpr(const tkr_vbpr_state& st, const int32_t* ti, const int32_t* tj, const int32_t* rec,
                        const int32_t* occ, const int32_t* hdr, const int32_t* occt, int B, float* ws, float* loss,
                        hipStream_t stream, const int32_t* tu, const int32_t* tpar) {
+    // above 65,536 the records' 16-bit triplet halves no longer hold an index: the first four come from occt (vbpr_rows.h read_rec)
+    const bool big = B > 65536;
+#define TKR_LV(T) (big ? launch_vbpr_t<NT, T, true>(st, ti, tj, rec, occ, hdr, occt, B, ws, loss, stream, tu, tpar) \
+                       : launch_vbpr_t<NT, T>(st, ti, tj, rec, occ, hdr, occt, B, ws, loss, stream, tu, tpar))
     switch (tkr_plan_team(B)) {                    // csrc/plan_parts.h team_for
-        case 4: return launch_vbpr_t<NT, 4>(st, ti, tj, rec, occ, hdr, occt, B, ws, loss, stream, tu, tpar);
-        case 8: return launch_vbpr_t<NT, 8>(st, ti, tj, rec, occ, hdr, occt, B, ws, loss, stream, tu, tpar);
-        default: return launch_vbpr_t<NT, 16>(st, ti, tj, rec, occ, hdr, occt, B, ws, loss, stream, tu, tpar);
+        case 4: return TKR_LV(4);
+        case 8: return TKR_LV(8);
+        default: return TKR_LV(16);
     }
+#undef TKR_LV
+}
+
+// kh > 128 (csrc/vbpr_wide.hip): the generic form of the sparse view on the same records and the same carve of the workspace
+__attribute__((visibility("hidden"))) void vbpr_gen_front(const tkr_vbpr_state& st, const int32_t* ti, const int32_t* tj, const int32_t* rec,
+                                                          const int2* occ2, const int32_t* occt, const int4* hdr4, int B, int team,
+                                                          const int32_t* tu, const int32_t* tpar, float* P, float* Q, float* ab2, float* Wm,
+                                                          float* loss, hipStream_t s);
+__attribute__((visibility("hidden"))) void vbpr_gen_back(const tkr_vbpr_state& st, const int32_t* rec, const int2* occ2, const int32_t* occt,
+                                                         const int4* hdr4, int B, int team, const float* s_buf, const float* t_buf, const float* P,
+                                                         const float* Wm, float* Aw, float* ab, float* loss, hipStream_t s);
+
+static int launch_vbpr_gen(const tkr_vbpr_state& st, const int32_t* ti, const int32_t* tj, const int32_t* rec, const int32_t* occ,
+                           const int32_t* hdr, const int32_t* occt, int B, float* ws, float* loss, hipStream_t stream, const int32_t* tu,
+                           const int32_t* tpar) {
+    const int kh = st.kh, S = vbpr_slices(st.d), team = tkr_plan_team(B);
+    float* s_buf = ws + (size_t)S * B * (kh + 1);                                   // the carve of launch_vbpr_t
+    float* P = s_buf + B;
+    float* Wm = P + (size_t)B * kh;
+    float* Q = Wm + (size_t)B * kh;
+    float* Aw = Q + B;
+    float* ab = Aw + (size_t)tkr_plan_max_blocks(B) * team * kh;
+    float* ab2 = ws + tkr_vbpr_workspace_core_floats(B, kh, st.d) - 5 * (size_t)B;
+    float* t_buf = ab2 + 4 * (size_t)B;
+    const int2* occ2 = reinterpret_cast<const int2*>(occ);
+    const int4* hdr4 = reinterpret_cast<const int4*>(hdr);
+    vbpr_gen_front(st, ti, tj, rec, occ2, occt, hdr4, B, team, tu, tpar, P, Q, ab2, Wm, loss, stream);
+    hipLaunchKernelGGL(vbpr_pair_kernel, dim3((B + 3) / 4), dim3(256), 0, stream, ab2, B, kh, s_buf, t_buf, Wm, loss);
+    vbpr_gen_back(st, rec, occ2, occt, hdr4, B, team, s_buf, t_buf, P, Wm, Aw, ab, loss, stream);
+    return (int)hipGetLastError();
 }
 
 }  // namespace tkr
@@ -751,7 +787,10 @@ extern "C" int tkr_vbpr_run(const tkr_vbpr_state* st, const int32_t* tri_i, cons
         return TKR_EINVAL;
     if (st->n_users <= 0 || st->n_items <= 0 || st->kh <= 0 || st->d <= 0) return TKR_EINVAL;
     if (!tri_i || !tri_j || !rec || !occ || !hdr || !occt || !workspace || batch_size <= 0 || n_batches < 0) return TKR_EINVAL;
-    if (st->kh > 128 || batch_size > 65536) return TKR_EUNSUPPORTED;     // the launch records carry a triplet's index in 16 bits
+    // kh > 128: the generic form of the sparse view (csrc/vbpr_wide.hip); the dense MFMA view (f_ptr == NULL) holds at most 128 factors
+    // in its tiles and stays unsupported there (single/_engine.py takes the CSR view whenever k // 2 > 128).  Any batch size: above
+    // 65,536 the first four triplet indices of a launch record come from occt instead of its 16-bit halves (vbpr_rows.h read_rec)
+    if (st->kh > 128 && !st->f_ptr) return TKR_EUNSUPPORTED;
     if (st->f_ptr && (!st->f_col || !st->f_val || !st->c_ptr || !st->c_item || !st->c_val || !st->item_tag)) return TKR_EINVAL;
     const size_t stride_r = (size_t)tkr_plan_max_blocks(batch_size) * tkr_plan_team(batch_size) * 16;
     const size_t stride_o = (size_t)3 * batch_size;
@@ -769,7 +808,8 @@ extern "C" int tkr_vbpr_run(const tkr_vbpr_state* st, const int32_t* tri_i, cons
         const int32_t* tp = (tri_u && tpar) ? tpar + (size_t)b * batch_size : nullptr;
         float* l = ls.of(b);
         int rc;
-        switch (NT) {
+        if (st->kh > 128) rc = tkr::launch_vbpr_gen(*st, ti, tj, r, o, h, ot, batch_size, workspace, l, (hipStream_t)stream, tu, tp);
+        else switch (NT) {
             case 1: rc = tkr::launch_vbpr<1>(*st, ti, tj, r, o, h, ot, batch_size, workspace, l, (hipStream_t)stream, tu, tp); break;
             case 2: rc = tkr::launch_vbpr<2>(*st, ti, tj, r, o, h, ot, batch_size, workspace, l, (hipStream_t)stream, tu, tp); break;
             case 3: rc = tkr::launch_vbpr<3>(*st, ti, tj, r, o, h, ot, batch_size, workspace, l, (hipStream_t)stream, tu, tp); break;

@@ -948,7 +948,7 @@ class VbprEngine(PlanMixin):
         nnz = int(torch.count_nonzero(self.feat))
         # the gather view: sparse features (tf-idf-like, ~0.5 % dense at d = 20,000), and narrow dense ones (BASELINE.json's literal
         # "d = 128"): the fp32-MFMA kernels tile d by 128 / 64 columns and run on 1-2 workgroups there
-        # (k // 2 > 128: only the column-plan step has a generic form, and it gathers: the CSR view whatever the density)
+        # (k // 2 > 128: the generic forms gather, both the column-plan step's and the sparse view's: the CSR view whatever the density)
         if sparse or (sparse is None and (nnz <= self.SPARSE_DENSITY * n_items * d or d <= self.NARROW_D or self.kh > 128)):
             self.sparse = self._sparse_view(self.feat)
             per_row = (self.sparse['f_ptr'][1:] - self.sparse['f_ptr'][:-1])
@@ -1061,14 +1061,20 @@ class VbprEngine(PlanMixin):
     copy_model_from = BprEngine.copy_model_from
 
     def run_batches(self, csr: TrainingCSR, n_batches: int, B: int, want_loss=True, then_exchange=0):
-        if B > 65536 or (self.kh > 128 and not self.wants_cols(B)):
-            raise ValueError('VBPR on the HIP path: batch_size <= 65536, and k // 2 > 128 only through the column-plan step (batch_size <= %d, '
-                             'feature rows of at most 1024 nonzeros; got k = %d, batch_size = %d)' % (self.COLS_MAX_BATCH, self.k, B))
+        if self.kh > 128 and self.sparse is None:
+            raise ValueError('VBPR: k // 2 = %d takes the CSR view of feat (sparse=True or None): the dense fp32-MFMA view holds at most '
+                             '128 factors' % self.kh)
+        if B > 65536 and not getattr(self, '_warned_big', False):
+            self._warned_big = True
+            import warnings
+            warnings.warn('VBPR: batch_size = %d: the objective sums over all B^2 = %.3g pairs of a batch (vbpr.py:61,64 broadcast to [B, B]), '
+                          'so the pair sums of every batch are O(B^2) work' % (B, float(B) * B))
         if self.kh > 128 and not getattr(self, '_warned_wide', False):
             self._warned_wide = True
             import warnings
             warnings.warn('VBPR: k // 2 = %d is wider than the step\'s kernels hold a row in registers (128): the generic form steps '
-                          '(csrc/vbpr_wide.hip: every kernel walks the factors in strides of its threads)' % self.kh)
+                          '(csrc/vbpr_wide.hip: every kernel walks the factors in passes of its threads; the column plan where it applies, '
+                          'the five-launch sparse view elsewhere)' % self.kh)
         if getattr(self, '_step_key', None) != B:           # the C struct and the closure are built once per batch size, not per call
             self._step_key, self._step = B, self.step_fn(B)
         return self._run(csr, n_batches, B, want_loss, self._step)
