@@ -31,7 +31,7 @@
 extern "C" {
 #endif
 
-#define TKR_VERSION 118 /* 0.1.18: K4 second form of bound-and-refine (csrc/topk_refine.hip; tkr_topk_workspace_bytes_for grows by the pieces' packed lists), any k (bpr_wide_kernel, score_topk_wide_kernel), tkr_lab_build; tkr_topk_set_finish is gone, tkr_topk_set_math(0) and tkr_vbpr_set_pairs(1 | 2) need the lab library. 0.1.17: tkr_vbpr_set_pairs (tkr_vbpr_workspace_floats + 64). 0.1.16: tkr_topk_set_finish (larger tkr_topk_workspace_bytes), tkr_bpr_own_plan_run plans inside the step's launch. 0.1.15: tkr_bpr_own_owners_shared; tkr_bpr_run takes `rec` non-const. 0.1.14: per-task loss sums instead of atomics on loss_out (larger tkr_vbpr_workspace_floats; K2 writes word 15 of its records). 0.1.13: tkr_bpr_own_plan_run, K4 to k = 768. 0.1.12: tkr_bpr_own_run_between. 0.1.11: K2o (tkr_sample_plan_owned, tkr_bpr_own_run: item rows owned by one workgroup each, resident in its LDS); prec[5] = last batch of the call that updated the row. 0.1.10: tkr_topk_workspace_bytes_for (K4 stages pre-converted fp16 tiles). 0.1.9: tkr_vbpr_colplan + tkr_vbpr_run_cols (VBPR in three launches per batch). 0.1.8: tkr_sync_flow_* (exchange of the granule tables). 0.1.7: K4 bound-and-refine arithmetic (tkr_topk_set_math(2), the default; larger tkr_topk_workspace_bytes); K2f leaves its ticket words zero. 0.1.6: K2f persistent dataflow step, tkr_plan_rollback, batches above 8192 */
+#define TKR_VERSION 119 /* 0.1.19: K8 tkr_like_ranks + tkr_like_ranks_workspace_bytes (filtered rank of every liked test column; csrc/like_ranks.hip). 0.1.18: K4 second form of bound-and-refine (csrc/topk_refine.hip; tkr_topk_workspace_bytes_for grows by the pieces' packed lists), any k (bpr_wide_kernel, score_topk_wide_kernel), tkr_lab_build; tkr_topk_set_finish is gone, tkr_topk_set_math(0) and tkr_vbpr_set_pairs(1 | 2) need the lab library. 0.1.17: tkr_vbpr_set_pairs (tkr_vbpr_workspace_floats + 64). 0.1.16: tkr_topk_set_finish (larger tkr_topk_workspace_bytes), tkr_bpr_own_plan_run plans inside the step's launch. 0.1.15: tkr_bpr_own_owners_shared; tkr_bpr_run takes `rec` non-const. 0.1.14: per-task loss sums instead of atomics on loss_out (larger tkr_vbpr_workspace_floats; K2 writes word 15 of its records). 0.1.13: tkr_bpr_own_plan_run, K4 to k = 768. 0.1.12: tkr_bpr_own_run_between. 0.1.11: K2o (tkr_sample_plan_owned, tkr_bpr_own_run: item rows owned by one workgroup each, resident in its LDS); prec[5] = last batch of the call that updated the row. 0.1.10: tkr_topk_workspace_bytes_for (K4 stages pre-converted fp16 tiles). 0.1.9: tkr_vbpr_colplan + tkr_vbpr_run_cols (VBPR in three launches per batch). 0.1.8: tkr_sync_flow_* (exchange of the granule tables). 0.1.7: K4 bound-and-refine arithmetic (tkr_topk_set_math(2), the default; larger tkr_topk_workspace_bytes); K2f leaves its ticket words zero. 0.1.6: K2f persistent dataflow step, tkr_plan_rollback, batches above 8192 */
 #define TKR_OK 0
 #define TKR_E_INVAL (-1)
 #define TKR_E_UNSUPPORTED (-2)
@@ -390,6 +390,26 @@ int tkr_raw_ranks(const float* U, const int32_t* user_idx, int32_t n_rows, const
 int tkr_count_hits_rr(const int32_t* ids, const int32_t* raw_rank, int32_t n_rows, int32_t K, const int64_t* like_ptr,
                       const int32_t* like_cols, int32_t step, int32_t interval, int32_t* hit_first, double* rr_first,
                       void* stream);
+
+/* ---- K8: filtered rank of every liked test column (the rank walk of evaluate.py:96-105, to any depth) -----------
+ * U, user_idx, n_rows, Vt, bias, n_cols, k, mask, mask_pitch: exactly those of tkr_score_topk (mask nullable);
+ * like_ptr [n_rows+1] (starts at 0), like_cols: the CSR of tkr_count_hits, ascending columns inside a row.  For entry e of row r
+ * with column l = like_cols[e]:
+ *   rank_out[e] = -1 when l is masked for the row (a rated like is never reached by the reference walk) or not in [0, n_cols)
+ *   rank_out[e] = #{c < n_cols unmasked, c != l : s(r,c) > s(r,l) or (s(r,c) == s(r,l) and c > l)} otherwise
+ * -- the number of kept columns in front of l in K4's canonical order, with s the mode-1 score above (the fma chain, fl(acc + bias),
+ * -0.0 -> +0.0), bit for bit: a like at position p of tkr_score_topk's list has rank p.  Integer and deterministic.  accuracy@k for
+ * any step / total, AUC, NDCG, MRR and MAP all follow from the ranks (top-k-rec_amd/rankmetrics.py).
+ * k <= 256: the fp32-MFMA tile loop of K4 with a counting epilogue (the sorted like scores of a user block and one counter each in
+ * LDS, a binary search per score; item ranges of a block add up in rank_out by integer atomics); k > 256: one wave per row, a lane
+ * per column.  Any number of likes per row; n_cols < 2^27.
+ * workspace (required): tkr_like_ranks_workspace_bytes(n_rows, n_cols, k, n_likes) bytes, n_likes = like_ptr[n_rows].  The call
+ * writes every rank_out[e] itself (no zeroing by the caller); a workspace sized for fewer likes than the CSR holds leaves -2 in all
+ * of them. */
+int64_t tkr_like_ranks_workspace_bytes(int32_t n_rows, int32_t n_cols, int32_t k, int64_t n_likes);
+int tkr_like_ranks(const float* U, const int32_t* user_idx, int32_t n_rows, const float* Vt, const float* bias,
+                   int32_t n_cols, int32_t k, const uint32_t* mask, int32_t mask_pitch, const int64_t* like_ptr,
+                   const int32_t* like_cols, int32_t* rank_out, void* workspace, int64_t workspace_bytes, void* stream);
 
 /* ---- multi-GPU: pack / unpack of the replicated item-side tables around the per-epoch all-reduce ---------
  * (new design, the reference is single-process: SURVEY.md §8e).  Users are sharded over the GPUs, every rank updates its

@@ -27,6 +27,9 @@ Stated differences from the reference:
   * ids are resolved to indices while parsing, so the rated set of a user is keyed by the uid's
     index and a test column by its index in the id list; the reference keys both by token.  The
     two differ only if an id file repeats a token (the re-pointing quirk of evaluate.py:5-10).
+  * ``-M/--metrics acc auc mrr ndcg map`` (not in the reference) prints, after the reference lines, one line
+    ``S.metric,%.6f[,...]`` per scenario and metric from ONE full-rank pass: the filtered rank of every liked column (K8,
+    tkr_hip.like_ranks) and rankmetrics.py.  Without the flag stdout is the reference's, byte for byte.
 """
 from __future__ import annotations
 
@@ -38,6 +41,7 @@ os.environ.setdefault('HSA_ENABLE_IPC_MODE_LEGACY', '0')     # multi-process GPU
 import numpy as np
 import torch
 
+import rankmetrics
 import textio
 import tkr_hip
 
@@ -115,8 +119,8 @@ def load_scenario(data_dir, fold, scenario, uids, umap=None):
     return Scenario(teids, users, like_ptr, lcols, rated_ptr, rated_cols)
 
 
-def rank_scenario(umat_dev, vmat, bmat, vids, sc, total, device, want_scores=False):
-    """filtered top-`total` test columns of every test line -> int32 [n_lines, total] (device)"""
+def _scenario_operands(vmat, bmat, vids, sc, device):
+    """the scenario's test-item rows, bias, user rows and rated mask on the device: the operands of K4 and K8"""
     te_rows = np.zeros(len(sc.teids), dtype=np.int64)
     for vid, col in sc.teids.items():
         te_rows[col] = vids[vid]                                     # evaluate.py:75-77
@@ -127,6 +131,12 @@ def rank_scenario(umat_dev, vmat, bmat, vids, sc, total, device, want_scores=Fal
     user_idx = torch.from_numpy(sc.users.astype(np.int32)).to(device)
     rptr, rcols = torch.from_numpy(sc.rated_ptr).to(device), torch.from_numpy(sc.rated_cols).to(device)
     mask, pitch = tkr_hip.build_rated_mask(rptr, rcols, len(sc.users), len(sc.teids))
+    return Vt, bias, user_idx, mask, pitch
+
+
+def rank_scenario(umat_dev, vmat, bmat, vids, sc, total, device, want_scores=False):
+    """filtered top-`total` test columns of every test line -> int32 [n_lines, total] (device)"""
+    Vt, bias, user_idx, mask, pitch = _scenario_operands(vmat, bmat, vids, sc, device)
     return tkr_hip.score_topk(umat_dev, Vt, total, bias=bias, user_idx=user_idx, mask=mask, mask_pitch=pitch,
                               want_scores=want_scores)
 
@@ -177,6 +187,28 @@ def evaluate_loaded(umat_dev, vmat, bmat, vids, full, step, total, device):
     return [float(h) / tcount for h in hits]                          # ZeroDivisionError like evaluate.py:112
 
 
+def rank_metrics_loaded(umat_dev, vmat, bmat, vids, full, step, total, metrics, device):
+    """{metric: list of values} (rankmetrics.py) of an already parsed Scenario from one full-rank pass: K8 gives the filtered rank of
+    every liked column of this rank's block of test lines, the metric sums and counts are all-reduced like the hits of
+    evaluate_loaded (one fp64 vector; the same on every rank afterwards)."""
+    rank, world = _world()
+    sc = shard_scenario(full, rank, world) if world > 1 else full
+    ranks = np.zeros(0, dtype=np.int32)
+    if len(sc.users):
+        Vt, bias, user_idx, mask, pitch = _scenario_operands(vmat, bmat, vids, sc, device)
+        lptr, lcols = torch.from_numpy(sc.like_ptr).to(device), torch.from_numpy(sc.like_cols).to(device)
+        ranks = tkr_hip.like_ranks(umat_dev, Vt, lptr, lcols, bias=bias, user_idx=user_idx, mask=mask, mask_pitch=pitch).cpu().numpy()
+    sums = rankmetrics.rank_sums(ranks, sc.like_ptr, sc.rated_ptr, len(sc.teids), step, total)
+    if world > 1:
+        import torch.distributed as dist
+        on_dev = dist.get_backend() == 'nccl'
+        acc = torch.from_numpy(rankmetrics.to_vector(sums))
+        acc = acc.to(device) if on_dev else acc
+        dist.all_reduce(acc, op=dist.ReduceOp.SUM)
+        sums = rankmetrics.from_vector(acc.cpu().numpy(), total // step)
+    return rankmetrics.finish(sums, metrics)
+
+
 def main(argv=None):
     parser = argparse.ArgumentParser(description="Evaluate weighted matrix factorization based methods.")
     parser.add_argument('-d', '--data', required=True, help="The data path for the evaluation")
@@ -185,6 +217,8 @@ def main(argv=None):
     parser.add_argument('-s', '--step', type=int, default=5, help="The number of evaluation step")
     parser.add_argument('-t', '--total', type=int, default=30, help="The number of total predictions")
     parser.add_argument('-sl', '--scenarios', nargs='+', default=None, help="The test scenario list")
+    parser.add_argument('-M', '--metrics', nargs='+', default=None, choices=rankmetrics.METRICS,
+                        help="Rank metrics from one full-rank pass, printed after the accuracy lines as S.metric,...")
     args = parser.parse_args(argv)
 
     if not torch.cuda.is_available():
@@ -201,9 +235,15 @@ def main(argv=None):
         bmat = read_matrix(os.path.join(args.model, 'final-B.dat'), vids)
     umat_dev = torch.from_numpy(umat).to(device)
     umap = textio.IdMap(uids)
-    results = {}
+    results, extra = {}, {}
     for scenario in args.scenarios:
-        acc = evaluate_scenario(umat_dev, vmat, bmat, uids, vids, args.data, args.fold, scenario, args.step, args.total, device, umap)
+        if args.metrics:
+            full = load_scenario(args.data, args.fold, scenario, uids, umap)
+            acc = evaluate_loaded(umat_dev, vmat, bmat, vids, full, args.step, args.total, device)
+            if scenario not in extra:                                # (a scenario listed twice: its metric lines are not doubled)
+                extra[scenario] = rank_metrics_loaded(umat_dev, vmat, bmat, vids, full, args.step, args.total, args.metrics, device)
+        else:
+            acc = evaluate_scenario(umat_dev, vmat, bmat, uids, vids, args.data, args.fold, scenario, args.step, args.total, device, umap)
         if scenario not in results:                                  # evaluate.py:109-112 ACCUMULATES per scenario name: a scenario
             results[scenario] = [0.0] * len(acc)                     # listed twice ("-sl im im") prints doubled values, twice
         for k, v in enumerate(acc):
@@ -213,6 +253,11 @@ def main(argv=None):
         lines.append(scenario + ''.join(',%.6f' % v for v in results[scenario]))
         if rank == 0:                                                # one report, like the single process
             print(lines[-1])
+    for scenario in args.scenarios if args.metrics else ():
+        for m in args.metrics:
+            lines.append('%s.%s' % (scenario, m) + ''.join(',%.6f' % v for v in extra[scenario][m]))
+            if rank == 0:
+                print(lines[-1])
     if started_group:
         import torch.distributed as dist
         dist.destroy_process_group()

@@ -16,7 +16,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get('TKR_HIP_LIB') or os.path.join(_HERE, 'libtkr_hip.so')      # the override is for A/B builds of the kernels (scripts/)
 
 _lib = None
-VERSION = 118          # TKR_VERSION of include/tkr.h this binding was written against
+VERSION = 119          # TKR_VERSION of include/tkr.h this binding was written against
 
 
 class TkrError(RuntimeError):
@@ -84,8 +84,8 @@ EXPORTS = ('tkr_version', 'tkr_plan_team', 'tkr_plan_max_blocks', 'tkr_sample_pl
            'tkr_ratings_destroy', 'tkr_matrix_read', 'tkr_matrix_sizes', 'tkr_matrix_copy', 'tkr_matrix_destroy',
            'tkr_matrix_write', 'tkr_raw_ranks', 'tkr_count_hits_rr', 'tkr_topk_set_math', 'tkr_vbpr_set_pairs', 'tkr_lab_build',
            'tkr_sync_snapshot', 'tkr_sync_pack', 'tkr_sync_unpack', 'tkr_sync_flow_snapshot', 'tkr_sync_flow_pack',
-           'tkr_sync_flow_unpack')
-EXPORTS_I64 = ('tkr_vbpr_workspace_floats', 'tkr_vbpr_colplan_lds_bytes', 'tkr_topk_workspace_bytes_for', 'tkr_topk_workspace_bytes', 'tkr_plan_workspace_bytes')
+           'tkr_sync_flow_unpack', 'tkr_like_ranks')
+EXPORTS_I64 = ('tkr_vbpr_workspace_floats', 'tkr_vbpr_colplan_lds_bytes', 'tkr_topk_workspace_bytes_for', 'tkr_topk_workspace_bytes', 'tkr_plan_workspace_bytes', 'tkr_like_ranks_workspace_bytes')
 
 
 def lib():
@@ -534,6 +534,24 @@ def count_hits_rr(ids, raw_rank, like_ptr, like_cols, step, interval):
         _call('tkr_count_hits_rr', ids, _p(ids), _p(raw_rank), C.c_int32(n_rows), C.c_int32(ids.shape[1]), _p(like_ptr),
                                        _p(like_cols), C.c_int32(step), C.c_int32(interval), _p(hit), _p(rr))
     return torch.cumsum(hit.sum(0, dtype=torch.int64)[:interval], 0), torch.cumsum(rr.sum(0)[:interval], 0)
+
+
+def like_ranks(U, Vt, like_ptr, like_cols, bias=None, user_idx=None, mask=None, mask_pitch=0):
+    """K8 -> int32 [n_likes] (device): for every entry of the like CSR (int64 ptr from 0, int32 ascending cols) the number of unmasked
+    columns in front of it in K4's canonical order, -1 where the liked column itself is masked (include/tkr.h)"""
+    assert U.dtype == torch.float32 and Vt.dtype == torch.float32 and U.shape[1] == Vt.shape[1]
+    assert like_ptr.dtype == torch.int64 and like_cols.dtype == torch.int32
+    n_rows = int(user_idx.numel()) if user_idx is not None else int(U.shape[0])
+    assert like_ptr.numel() == n_rows + 1
+    n_likes, n_cols, k = int(like_cols.numel()), int(Vt.shape[0]), int(U.shape[1])
+    out = torch.empty(n_likes, dtype=torch.int32, device=U.device)
+    if n_likes == 0:
+        return out
+    need = int(lib().tkr_like_ranks_workspace_bytes(C.c_int32(n_rows), C.c_int32(n_cols), C.c_int32(k), C.c_int64(n_likes)))
+    ws = torch.empty(need, dtype=torch.uint8, device=U.device)
+    _call('tkr_like_ranks', U, _p(U), _p(user_idx), C.c_int32(n_rows), _p(Vt), _p(bias), C.c_int32(n_cols), C.c_int32(k), _p(mask),
+          C.c_int32(mask_pitch), _p(like_ptr), _p(like_cols), _p(out), _p(ws), C.c_int64(need))
+    return out
 
 
 # ---- per-epoch exchange of replicated tables (csrc/sync.hip) ----------------------------------------
