@@ -31,7 +31,7 @@
 extern "C" {
 #endif
 
-#define TKR_VERSION 119 /* 0.1.19: K8 tkr_like_ranks + tkr_like_ranks_workspace_bytes (filtered rank of every liked test column; csrc/like_ranks.hip). 0.1.18: K4 second form of bound-and-refine (csrc/topk_refine.hip; tkr_topk_workspace_bytes_for grows by the pieces' packed lists), any k (bpr_wide_kernel, score_topk_wide_kernel), tkr_lab_build; tkr_topk_set_finish is gone, tkr_topk_set_math(0) and tkr_vbpr_set_pairs(1 | 2) need the lab library. 0.1.17: tkr_vbpr_set_pairs (tkr_vbpr_workspace_floats + 64). 0.1.16: tkr_topk_set_finish (larger tkr_topk_workspace_bytes), tkr_bpr_own_plan_run plans inside the step's launch. 0.1.15: tkr_bpr_own_owners_shared; tkr_bpr_run takes `rec` non-const. 0.1.14: per-task loss sums instead of atomics on loss_out (larger tkr_vbpr_workspace_floats; K2 writes word 15 of its records). 0.1.13: tkr_bpr_own_plan_run, K4 to k = 768. 0.1.12: tkr_bpr_own_run_between. 0.1.11: K2o (tkr_sample_plan_owned, tkr_bpr_own_run: item rows owned by one workgroup each, resident in its LDS); prec[5] = last batch of the call that updated the row. 0.1.10: tkr_topk_workspace_bytes_for (K4 stages pre-converted fp16 tiles). 0.1.9: tkr_vbpr_colplan + tkr_vbpr_run_cols (VBPR in three launches per batch). 0.1.8: tkr_sync_flow_* (exchange of the granule tables). 0.1.7: K4 bound-and-refine arithmetic (tkr_topk_set_math(2), the default; larger tkr_topk_workspace_bytes); K2f leaves its ticket words zero. 0.1.6: K2f persistent dataflow step, tkr_plan_rollback, batches above 8192 */
+#define TKR_VERSION 120 /* 0.1.20: K9 tkr_bpr_foldin (user vectors for new histories against frozen item factors; csrc/foldin.hip). 0.1.19: K8 tkr_like_ranks + tkr_like_ranks_workspace_bytes (filtered rank of every liked test column; csrc/like_ranks.hip). 0.1.18: K4 second form of bound-and-refine (csrc/topk_refine.hip; tkr_topk_workspace_bytes_for grows by the pieces' packed lists), any k (bpr_wide_kernel, score_topk_wide_kernel), tkr_lab_build; tkr_topk_set_finish is gone, tkr_topk_set_math(0) and tkr_vbpr_set_pairs(1 | 2) need the lab library. 0.1.17: tkr_vbpr_set_pairs (tkr_vbpr_workspace_floats + 64). 0.1.16: tkr_topk_set_finish (larger tkr_topk_workspace_bytes), tkr_bpr_own_plan_run plans inside the step's launch. 0.1.15: tkr_bpr_own_owners_shared; tkr_bpr_run takes `rec` non-const. 0.1.14: per-task loss sums instead of atomics on loss_out (larger tkr_vbpr_workspace_floats; K2 writes word 15 of its records). 0.1.13: tkr_bpr_own_plan_run, K4 to k = 768. 0.1.12: tkr_bpr_own_run_between. 0.1.11: K2o (tkr_sample_plan_owned, tkr_bpr_own_run: item rows owned by one workgroup each, resident in its LDS); prec[5] = last batch of the call that updated the row. 0.1.10: tkr_topk_workspace_bytes_for (K4 stages pre-converted fp16 tiles). 0.1.9: tkr_vbpr_colplan + tkr_vbpr_run_cols (VBPR in three launches per batch). 0.1.8: tkr_sync_flow_* (exchange of the granule tables). 0.1.7: K4 bound-and-refine arithmetic (tkr_topk_set_math(2), the default; larger tkr_topk_workspace_bytes); K2f leaves its ticket words zero. 0.1.6: K2f persistent dataflow step, tkr_plan_rollback, batches above 8192 */
 #define TKR_OK 0
 #define TKR_E_INVAL (-1)
 #define TKR_E_UNSUPPORTED (-2)
@@ -410,6 +410,29 @@ int64_t tkr_like_ranks_workspace_bytes(int32_t n_rows, int32_t n_cols, int32_t k
 int tkr_like_ranks(const float* U, const int32_t* user_idx, int32_t n_rows, const float* Vt, const float* bias,
                    int32_t n_cols, int32_t k, const uint32_t* mask, int32_t mask_pitch, const int64_t* like_ptr,
                    const int32_t* like_cols, int32_t* rank_out, void* workspace, int64_t workspace_bytes, void* stream);
+
+/* ---- K9: fold-in -- user vectors for histories the model was not trained on (new design: the reference can only retrain) ----
+ * For each of m users, `steps` times: the step of K2 (single/bpr.py:81-100) on a batch of `triplets` triplets that all carry this user,
+ * with the item side FROZEN --  x_p = b_i - b_j + <u, v_i - v_j>,  g = sum_p [-sigma(-x_p) (v_i - v_j) + lu u]  (mode 1: lu sign(u)),
+ * summed in the order p = 0 .. triplets-1, then one RMSProp update of u (slot from 1.0, rho 0.9, eps 1e-10 as K2).  V, b are read only.
+ *   V [n_items, k], b [n_items] (nullable)   the exported item factors and biases (fie / fib: a VBPR model folds in unchanged)
+ *   hist_ptr [m+1] int64 (starts at 0), hist_cols int32   the positives of every user as CSR, ascending and unique inside a row, every
+ *                         column in [0, n_items) (the CSR of tkr_build_rated_mask)
+ *   U0 [m, k] (nullable: zeros)   start vectors; the gradient at zero is not zero
+ *   U [m, k]                      result;  loss [m] (nullable): the objective of the LAST step at its pre-step u, as K2's loss_out with
+ *                                 lambda_i = lambda_j = lambda_b = 0: sum_p log(1 + exp(-x_p)) + triplets * lu |u|^2 / 2  (mode 1: lu |u|_1)
+ *   trip [m, steps, triplets, 2] int32 (nullable)   the drawn (i, j), for tests
+ * The draw: positive uniform over the row, negative uniform over the columns not in it -- K1's rounds, membership test and cyclic
+ * fallback (csrc/sampler_draw.h) on Philox counter (g & 0xffffffff, g >> 32, round, 1), g = ((first_row + x) * steps + t) * triplets + p
+ * (mod 2^64), key = seed: K1 has 0 in the fourth counter word, so the stream is disjoint from training under one seed, and rows
+ * [a, b) of a call with first_row = f equal a call on those rows alone with first_row = f + a.
+ * A row with no column, or with all n_items of them, has no triplet: U = U0, loss = 0, its part of trip is not written.
+ * One wave per user, the row in registers up to k = 512; above, the generic form keeps u, its slot and the gradient sum in one
+ * workgroup's LDS (12 k bytes <= 160 KB, i.e. k <= 13,653; wider: TKR_E_UNSUPPORTED).  1 <= triplets <= 64, steps >= 1; arguments are
+ * checked before any device access (TKR_E_INVAL).  Deterministic: bitwise the same U run to run. */
+int tkr_bpr_foldin(const float* V, const float* b, int32_t n_items, int32_t k, const int64_t* hist_ptr, const int32_t* hist_cols,
+                   int32_t m, const float* U0, float lu, float lr, int32_t mode, int32_t steps, int32_t triplets, uint64_t seed,
+                   uint64_t first_row, float* U, float* loss, int32_t* trip, void* stream);
 
 /* ---- multi-GPU: pack / unpack of the replicated item-side tables around the per-epoch all-reduce ---------
  * (new design, the reference is single-process: SURVEY.md §8e).  Users are sharded over the GPUs, every rank updates its

@@ -1,4 +1,5 @@
-// The (u, i, j) draw of K1, shared by the per-batch planner (sampler.hip) and the grid-wide one (planner_big.hip).
+// The (u, i, j) draw of K1, shared by the per-batch planner (sampler.hip) and the grid-wide one (planner_big.hip); its (i, j) part for a
+// fixed user is the draw of K9 (foldin.hip).
 // Replaces BPR._uniform_user_sampling (single/bpr.py:155-165); stream definition in oracle/plan_np.py.
 #pragma once
 #include "tkr_common.h"
@@ -30,20 +31,18 @@ __device__ __forceinline__ bool is_member(const int32_t* __restrict__ cols_sorte
     return (a < b && c0 == item) || (a + 1 < b && c1 == item) || (a + 2 < b && c2 == item);
 }
 
-__device__ __forceinline__ void draw_triplet(const int32_t* __restrict__ tr_users, uint32_t n_tr,
-                                             const int32_t* __restrict__ row_ptr,
-                                             const int32_t* __restrict__ pos_cols,
-                                             const int32_t* __restrict__ cols_sorted, uint32_t n_items,
-                                             uint32_t k0, uint32_t k1, uint64_t g, int& u, int& i, int& j) {
-    const uint32_t c0 = (uint32_t)g, c1 = (uint32_t)(g >> 32);
-    u32x4 w = philox4x32_10(c0, c1, 0u, 0u, k0, k1);
-    u = tr_users[mulhi64(w.x, w.y, n_tr)];
-    const int lo = row_ptr[u], hi = row_ptr[u + 1];
-    i = pos_cols[lo + (int)mulhi64(w.z, w.w, (uint32_t)(hi - lo))];
+// The (i, j) part of a draw for a user whose row is [lo, hi) of pos_cols / cols_sorted (hi > lo, and the row does not cover the whole
+// catalogue unless the caller accepts the candidate coming back unchanged): the positive from words z, w of the round-0 block `w0`,
+// the negative from rounds 1 .. kMaxRounds of the same counter (c0, c1, round, C3), two candidates a round, then the cyclic scan.
+// C3 names the stream: 0 = K1 (training), 1 = K9 (fold-in, csrc/foldin.hip) -- disjoint under one seed.
+template <uint32_t C3>
+__device__ __forceinline__ void draw_pair(const int32_t* __restrict__ pos_cols, const int32_t* __restrict__ cols_sorted, int lo, int hi,
+                                          uint32_t n_items, u32x4 w0, uint32_t c0, uint32_t c1, uint32_t k0, uint32_t k1, int& i, int& j) {
+    i = pos_cols[lo + (int)mulhi64(w0.z, w0.w, (uint32_t)(hi - lo))];
     int cand = 0;
     bool found = false;
     for (uint32_t r = 1; r <= (uint32_t)kMaxRounds && !found; ++r) {
-        w = philox4x32_10(c0, c1, r, 0u, k0, k1);
+        const u32x4 w = philox4x32_10(c0, c1, r, C3, k0, k1);
         cand = (int)mulhi64(w.x, w.y, n_items);
         if (!is_member(cols_sorted, lo, hi, cand)) { found = true; break; }
         cand = (int)mulhi64(w.z, w.w, n_items);
@@ -54,6 +53,17 @@ __device__ __forceinline__ void draw_triplet(const int32_t* __restrict__ tr_user
             cand = (cand + 1 == (int)n_items) ? 0 : cand + 1;
     }
     j = cand;
+}
+
+__device__ __forceinline__ void draw_triplet(const int32_t* __restrict__ tr_users, uint32_t n_tr,
+                                             const int32_t* __restrict__ row_ptr,
+                                             const int32_t* __restrict__ pos_cols,
+                                             const int32_t* __restrict__ cols_sorted, uint32_t n_items,
+                                             uint32_t k0, uint32_t k1, uint64_t g, int& u, int& i, int& j) {
+    const uint32_t c0 = (uint32_t)g, c1 = (uint32_t)(g >> 32);
+    const u32x4 w = philox4x32_10(c0, c1, 0u, 0u, k0, k1);
+    u = tr_users[mulhi64(w.x, w.y, n_tr)];
+    draw_pair<0u>(pos_cols, cols_sorted, row_ptr[u], row_ptr[u + 1], n_items, w, c0, c1, k0, k1, i, j);
 }
 
 }  // namespace tkr

@@ -1,0 +1,153 @@
+"""recommend.py -- write every user's top-k items and their scores, scored on MI355X; new users are folded in first.
+
+    python recommend.py -d DATA -m MODEL -f 0 -t 30 -o out.txt [-u USERS_FILE]
+                        [--new-uid FILE --new-history FILE --fold-steps 50 --fold-triplets 16 --fold-lr 0.05 --fold-lu 2.5e-3 --seed 0]
+
+Inputs as evaluate.py: ``DATA/uid``, ``DATA/vid``, ``DATA/f{fold}tr.txt`` (the histories), ``MODEL/final-U.dat``, ``final-V.dat``,
+optional ``final-B.dat``.  For every requested user -- the tokens of USERS_FILE, one per line; default: every line of ``uid`` -- the
+``-t`` best items of the whole ``vid`` catalogue, every item on the user's history line excluded whatever its like value (the
+``rated`` set of evaluate.py:30-45; a user without a line excludes nothing).  One output line per user in the ratings layout,
+
+    uid,iid:%f,iid:%f,...
+
+best first, ties in K4's order (higher catalogue index first); fewer than ``-t`` fields when the user has fewer unrated items.
+
+``--new-uid`` / ``--new-history`` (both or neither): the users of that id file are not in the model; their vectors are folded in
+from the like == 1 entries of their lines in the history file (K9, foldin.py) and ranked the same way, their own history file
+supplying the excluded items; their lines follow the model users' lines.  With ``--new-uid`` and no ``-u``, ``-u`` defaults to every
+model user as usual; an empty USERS_FILE writes the new users only.
+
+The scores, the filter and the selection run on the GPU (tkr_hip.build_rated_mask, tkr_hip.score_topk); single process.
+"""
+from __future__ import annotations
+
+import argparse
+import os
+
+import numpy as np
+import torch
+
+import foldin
+import textio
+import tkr_hip
+from evaluate import _group, read_ids, read_matrix
+
+
+def format_lines(users, ids, scores, items):
+    """users: n tokens; ids int [n, K] catalogue indices, -1 = no item; scores float [n, K]; items: index -> token
+    -> n lines 'uid,iid:%f,iid:%f,...'"""
+    out = []
+    for u, row_i, row_s in zip(users, np.asarray(ids), np.asarray(scores)):
+        out.append(','.join([u] + ['%s:%f' % (items[int(c)], float(s)) for c, s in zip(row_i, row_s) if c >= 0]))
+    return out
+
+
+def read_user_list(path, uids):
+    """the requested users: one known uid token per line -> tokens in file order"""
+    with open(path) as fh:
+        users = [ln.strip() for ln in fh if ln.strip()]
+    for u in users:
+        if u not in uids:
+            raise KeyError('%s: user %r is not in the uid list' % (path, u))
+    return users
+
+
+def rated_csr(R, rows_of_user, n_rows, n_items):
+    """the excluded items of every ranked row: all known items on the LAST line of its user in the parsed ratings file R
+    (evaluate.py:34: rated[uid] = set() per line).  rows_of_user: user index -> list of ranked rows (a user may be asked for twice)"""
+    last = {}
+    for line in np.flatnonzero(R.line_user >= 0):
+        last[int(R.line_user[line])] = int(line)
+    rr, cc = [], []
+    for user, line in last.items():
+        cols = R.item[R.line_ptr[line]:R.line_ptr[line + 1]]
+        cols = cols[cols >= 0]
+        for row in rows_of_user.get(user, ()):
+            rr.append(np.full(len(cols), row, dtype=np.int64))
+            cc.append(cols.astype(np.int64))
+    if not rr:
+        return np.zeros(n_rows + 1, dtype=np.int64), np.zeros(0, dtype=np.int32)
+    return _group(np.concatenate(rr), np.concatenate(cc), n_rows, n_items)
+
+
+def rank(U_dev, user_rows, V_dev, bias_dev, R, total):
+    """top-`total` unrated items of the users `user_rows` (indices into U_dev and into R's user numbering)
+    -> (ids int32 [n, total], scores fp32 [n, total]) as numpy"""
+    n, n_items = len(user_rows), int(V_dev.shape[0])
+    rows_of_user = {}
+    for row, user in enumerate(user_rows):
+        rows_of_user.setdefault(int(user), []).append(row)
+    ptr, cols = rated_csr(R, rows_of_user, n, n_items)
+    dev = V_dev.device
+    mask, pitch = tkr_hip.build_rated_mask(torch.from_numpy(ptr).to(dev), torch.from_numpy(cols).to(dev), n, n_items)
+    idx = torch.from_numpy(np.asarray(user_rows, dtype=np.int32)).to(dev)
+    ids, scores = tkr_hip.score_topk(U_dev, V_dev, total, bias=bias_dev, user_idx=idx, mask=mask, mask_pitch=pitch, want_scores=True)
+    return ids.cpu().numpy(), scores.cpu().numpy()
+
+
+def main(argv=None):
+    parser = argparse.ArgumentParser(description="Write the top-k items of every user, scored on the GPU.")
+    parser.add_argument('-d', '--data', required=True, help="The data path (uid, vid, f{fold}tr.txt)")
+    parser.add_argument('-m', '--model', required=True, help="The work path for the model")
+    parser.add_argument('-f', '--fold', type=int, default=0, help="The index of the fold whose train file holds the histories")
+    parser.add_argument('-t', '--total', type=int, default=30, help="The number of items per user")
+    parser.add_argument('-o', '--output', required=True, help="The file the lines are written to")
+    parser.add_argument('-u', '--users', default=None, help="A file of uid tokens, one per line (default: every user of uid)")
+    parser.add_argument('--new-uid', default=None, help="An id file of users that are not in the model: folded in, then ranked")
+    parser.add_argument('--new-history', default=None, help="The ratings file of the new users")
+    parser.add_argument('--fold-steps', type=int, default=50)
+    parser.add_argument('--fold-triplets', type=int, default=16)
+    parser.add_argument('--fold-lr', type=float, default=0.05)
+    parser.add_argument('--fold-lu', type=float, default=2.5e-3)
+    parser.add_argument('--seed', type=int, default=0)
+    args = parser.parse_args(argv)
+    if (args.new_uid is None) != (args.new_history is None):
+        parser.error('--new-uid and --new-history go together')
+    if args.total < 1:
+        parser.error('-t must be at least 1')
+
+    uids = read_ids(os.path.join(args.data, 'uid'))
+    vids = read_ids(os.path.join(args.data, 'vid'))
+    users = list(uids) if args.users is None else read_user_list(args.users, uids)
+    new_uids = {}
+    if args.new_uid is not None:
+        new_uids = read_ids(args.new_uid)
+        clash = [u for u in new_uids if u in uids]
+        if clash:
+            raise KeyError('%s: user %r is in the model already' % (args.new_uid, clash[0]))
+    if not torch.cuda.is_available():
+        raise tkr_hip.TkrError('recommend.py scores on the GPU through libtkr_hip.so; no MI355X is visible')
+    device = torch.device('cuda', torch.cuda.current_device())
+
+    items = {idx: tok for tok, idx in vids.items()}
+    vmat = read_matrix(os.path.join(args.model, 'final-V.dat'), vids)
+    bmat = None
+    if os.path.exists(os.path.join(args.model, 'final-B.dat')):
+        bmat = read_matrix(os.path.join(args.model, 'final-B.dat'), vids).reshape(-1)
+    V_dev = torch.from_numpy(vmat).to(device)
+    bias_dev = None if bmat is None else torch.from_numpy(np.ascontiguousarray(bmat)).to(device)
+    vmap = textio.IdMap(vids)
+    lines = []
+    if users:
+        umat = read_matrix(os.path.join(args.model, 'final-U.dat'), uids)
+        R = textio.parse_ratings(os.path.join(args.data, 'f%dtr.txt' % args.fold), textio.IdMap(uids), vmap)
+        ids, scores = rank(torch.from_numpy(umat).to(device), [uids[u] for u in users], V_dev, bias_dev, R, args.total)
+        lines += format_lines(users, ids, scores, items)
+    if new_uids:
+        m = max(new_uids.values()) + 1
+        R = textio.parse_ratings(args.new_history, textio.IdMap(new_uids), vmap)
+        eu = R.entry_user
+        keep = (eu >= 0) & (R.item >= 0) & (R.like == 1)
+        hist = foldin.group_history(eu[keep], R.item[keep], m, len(vmat))
+        U_new = foldin.fold_in(vmat, bmat, hist, lu=args.fold_lu, lr=args.fold_lr, steps=args.fold_steps, triplets=args.fold_triplets,
+                               seed=args.seed, device=device)
+        ids, scores = rank(torch.from_numpy(U_new).to(device), [new_uids[u] for u in new_uids], V_dev, bias_dev, R, args.total)
+        lines += format_lines(list(new_uids), ids, scores, items)
+    with open(args.output, 'w') as fh:
+        for ln in lines:
+            fh.write(ln + '\n')
+    return lines
+
+
+if __name__ == '__main__':
+    main()

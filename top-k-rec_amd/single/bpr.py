@@ -351,6 +351,47 @@ class BPR(REC):
                 print()
         return True
 
+    # ------------------------------------------------------------------ fold-in (new: the reference can only retrain)
+    def fold_in(self, uid_file: str, tr_file: str, *, steps: int = 50, triplets: int = 16, lr: float = None, lambda_u: float = None,
+                seed=None, device=None, start: str = 'zero'):
+        """User vectors for the users of ``uid_file`` from their lines in the ratings file ``tr_file``, against this model's item
+        factors: K9 (csrc/foldin.hip), the model's own step with the item side frozen.  -> (uids: dict token -> row, fue_new
+        fp32 [len(uids), width of fie]).  The model itself is not changed.
+
+        ``like == '1'`` entries of known items are the positives, as in load_training_data.  The item side is ``fie`` / ``fib`` as
+        train() collected them from the engine after its last epoch, or as import_embeddings read them; VBPR's already carry the
+        content half, so a VBPR model folds in through this same method.  ``lr`` and ``lambda_u`` default to the model's own --
+        note that a step of 0.05 on a model trained at 1e-4 produces vectors on another scale than the model's users: scores
+        of folded-in and trained users are then not comparable with each other (each user's own ranking still is).
+        ``start='zero'``: the users are new and must not be in the model's uid list; ``start='model'``: they are users of the model
+        whose history grew, and fold-in starts from their rows of ``fue`` (U0 = fue[rows])."""
+        import foldin
+        if self.fie is None or self.iids is None:
+            raise ValueError('fold_in needs item factors: train() or import_embeddings() first')
+        if start not in ('zero', 'model'):
+            raise ValueError("start must be 'zero' or 'model'")
+        uids = get_id_dict_from_file(uid_file)
+        known = [u for u in uids if u in self.uids]
+        m = max(uids.values()) + 1 if uids else 0
+        U0 = None
+        if start == 'zero' and known:
+            raise ValueError("%d users of %s are in the model already (e.g. %r): start='model' refreshes them" % (len(known), uid_file, known[0]))
+        if start == 'model':
+            if len(known) != len(uids) or self.fue is None:
+                raise ValueError("start='model' needs every user of %s in the model, and its fue" % uid_file)
+            U0 = np.zeros((m, np.asarray(self.fue).shape[1]), dtype=np.float32)
+            for u, row in uids.items():
+                U0[row] = self.fue[self.uids[u]]
+        R = textio.parse_ratings(tr_file, uids, self.iids)
+        eu = R.entry_user
+        keep = (eu >= 0) & (R.item >= 0) & (R.like == 1)
+        hist = foldin.group_history(eu[keep], R.item[keep], m, self.n_items)
+        if seed is None:
+            seed = self._eng.seed if self._eng is not None else 0
+        fue_new = foldin.fold_in(self.fie, self.fib, hist, lu=self.lu if lambda_u is None else lambda_u, lr=self.lr if lr is None else lr,
+                                 mode=self.mode, steps=steps, triplets=triplets, seed=seed, U0=U0, device=device)
+        return uids, fue_new
+
     # ------------------------------------------------------------------ sampler (bpr.py:155-165)
     def _uniform_user_sampling(self, batch_size: int):
         """Generator of (ub, ib, jb) numpy batches drawn by the device sampler (K1): u uniform over

@@ -16,7 +16,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get('TKR_HIP_LIB') or os.path.join(_HERE, 'libtkr_hip.so')      # the override is for A/B builds of the kernels (scripts/)
 
 _lib = None
-VERSION = 119          # TKR_VERSION of include/tkr.h this binding was written against
+VERSION = 120          # TKR_VERSION of include/tkr.h this binding was written against
 
 
 class TkrError(RuntimeError):
@@ -84,7 +84,7 @@ EXPORTS = ('tkr_version', 'tkr_plan_team', 'tkr_plan_max_blocks', 'tkr_sample_pl
            'tkr_ratings_destroy', 'tkr_matrix_read', 'tkr_matrix_sizes', 'tkr_matrix_copy', 'tkr_matrix_destroy',
            'tkr_matrix_write', 'tkr_raw_ranks', 'tkr_count_hits_rr', 'tkr_topk_set_math', 'tkr_vbpr_set_pairs', 'tkr_lab_build',
            'tkr_sync_snapshot', 'tkr_sync_pack', 'tkr_sync_unpack', 'tkr_sync_flow_snapshot', 'tkr_sync_flow_pack',
-           'tkr_sync_flow_unpack', 'tkr_like_ranks')
+           'tkr_sync_flow_unpack', 'tkr_like_ranks', 'tkr_bpr_foldin')
 EXPORTS_I64 = ('tkr_vbpr_workspace_floats', 'tkr_vbpr_colplan_lds_bytes', 'tkr_topk_workspace_bytes_for', 'tkr_topk_workspace_bytes', 'tkr_plan_workspace_bytes', 'tkr_like_ranks_workspace_bytes')
 
 
@@ -552,6 +552,45 @@ def like_ranks(U, Vt, like_ptr, like_cols, bias=None, user_idx=None, mask=None, 
     _call('tkr_like_ranks', U, _p(U), _p(user_idx), C.c_int32(n_rows), _p(Vt), _p(bias), C.c_int32(n_cols), C.c_int32(k), _p(mask),
           C.c_int32(mask_pitch), _p(like_ptr), _p(like_cols), _p(out), _p(ws), C.c_int64(need))
     return out
+
+
+# ---- K9: fold-in (csrc/foldin.hip) -------------------------------------------------------------------
+FOLDIN_MAX_TRIPLETS = 64     # one lane of a wave draws one triplet of a step
+FOLDIN_REG_MAX_K = 512       # rows up to here stay in registers
+
+
+def fold_in(V, b, hist_ptr, hist_cols, *, lu, lr, mode='l2', steps, triplets, seed, first_row=0, U0=None, want_loss=False,
+            want_triplets=False):
+    """K9 -> U fp32 [m, k] (and loss fp32 [m], trip int32 [m, steps, triplets, 2] when asked for, in that order): the user vectors
+    of m histories folded in against the frozen item factors V [n_items, k] / biases b [n_items] or None (include/tkr.h
+    tkr_bpr_foldin).  hist_ptr int64 [m+1] from 0, hist_cols int32 ascending and unique per row; all tensors on V's device.
+    Rows without a triplet (empty, or the whole catalogue) return U0 (zeros), loss 0 and -1 in trip."""
+    assert V.dtype == torch.float32 and V.dim() == 2 and hist_ptr.dtype == torch.int64 and hist_cols.dtype == torch.int32
+    m, (n_items, k) = int(hist_ptr.numel()) - 1, V.shape
+    if not 1 <= triplets <= FOLDIN_MAX_TRIPLETS or steps < 1 or m < 0:
+        raise ValueError('fold_in: 1 <= triplets <= %d and steps >= 1 required' % FOLDIN_MAX_TRIPLETS)
+    assert b is None or (b.dtype == torch.float32 and b.numel() == n_items)
+    assert U0 is None or (U0.dtype == torch.float32 and tuple(U0.shape) == (m, k))
+    if hist_cols.numel():           # the kernel gathers rows of V by these: checked here, once per call
+        assert int(hist_ptr[0]) == 0 and int(hist_ptr[-1]) == hist_cols.numel(), 'hist_ptr does not describe hist_cols'
+        assert 0 <= int(hist_cols.min()) and int(hist_cols.max()) < n_items, 'history column outside the catalogue'
+    else:
+        assert m == 0 or not bool(hist_ptr.any())
+        hist_cols = torch.zeros(1, dtype=torch.int32, device=V.device)
+    if k > FOLDIN_REG_MAX_K and not getattr(fold_in, '_warned_wide', False):
+        fold_in._warned_wide = True
+        warnings.warn('K9: factor width %d is above %d, where a wave no longer holds its user row in registers: the generic form runs '
+                      '(row, slot and gradient sum in LDS, two passes over the item rows per triplet: csrc/foldin.hip foldin_wide_kernel)'
+                      % (k, FOLDIN_REG_MAX_K))
+    U = torch.empty((m, k), dtype=torch.float32, device=V.device)
+    loss = torch.zeros(m, dtype=torch.float32, device=V.device) if want_loss else None
+    trip = torch.full((m, steps, triplets, 2), -1, dtype=torch.int32, device=V.device) if want_triplets else None
+    if m:
+        _call('tkr_bpr_foldin', V, _p(V), _p(b), C.c_int32(n_items), C.c_int32(k), _p(hist_ptr), _p(hist_cols), C.c_int32(m), _p(U0),
+              C.c_float(lu), C.c_float(lr), C.c_int32({'l2': 0, 'l1': 1}[mode]), C.c_int32(steps), C.c_int32(triplets),
+              C.c_uint64(seed & 0xffffffffffffffff), C.c_uint64(first_row), _p(U), _p(loss), _p(trip))
+    out = (U,) + ((loss,) if want_loss else ()) + ((trip,) if want_triplets else ())
+    return out[0] if len(out) == 1 else out
 
 
 # ---- per-epoch exchange of replicated tables (csrc/sync.hip) ----------------------------------------
