@@ -434,6 +434,39 @@ int tkr_bpr_foldin(const float* V, const float* b, int32_t n_items, int32_t k, c
                    int32_t m, const float* U0, float lu, float lr, int32_t mode, int32_t steps, int32_t triplets, uint64_t seed,
                    uint64_t first_row, float* U, float* loss, int32_t* trip, void* stream);
 
+/* ---- K10: fold-in of items -- rows and biases for items that were no line of `vid` at training time (new design, the twin of K9) ----
+ * For each of m new items x, `steps` times: the step of K2 on `triplets` triplets that all carry x, everything but (v_x, b_x) FROZEN.
+ *   role 1, x the positive of a liker u:      x_p = b_x - b_j + <u, v_x - v_j>;  grad v_x += -s u + li v_x,  grad b_x += -s + lb b_x
+ *   role 0, x the negative of a non-liker u:  x_p = b_i - b_x + <u, v_i - v_x>;  grad v_x += +s u + lj v_x,  grad b_x += +s + lb b_x
+ * with s = sigma(-x_p) (mode 1: li sign(v_x), lb sign(b_x) ...), summed in the order p = 0 .. triplets-1, then one RMSProp update of
+ * v_x and one of b_x (slots from 1.0, rho 0.9, eps 1e-10 as K2).  U, V, b are read only.
+ *   U [n_users, k], V [n_items, k], b [n_items] (nullable: no bias enters the score, none is learnt, bn = b0)
+ *   user_ptr [n_users+1] int64, user_cols int32   the users' training positives as CSR, ascending and unique inside a row, every column
+ *                         in [0, n_items) (the CSR tkr_bpr_foldin documents)
+ *   liker_ptr [m+1] int64, liker_rows int32       the user rows that like each new item, ascending and unique, in [0, n_users)
+ *   role_thresh [m] uint32   a triplet has role 1 iff the first word of its round-0 Philox block is < role_thresh[x]; 0xffffffff: always,
+ *                         0: never (foldin.fold_in_items derives it from the rates of the model's own sampler)
+ *   V0 [m, k], b0 [m] (nullable: zeros)   start values
+ *   Vn [m, k], bn [m]     results;  loss [m] (nullable): the objective of the LAST step at its pre-step values, the terms that depend on
+ *                         (v_x, b_x): sum_p log(1 + exp(-x_p)) + (n1 li + n0 lj) |v_x|^2 / 2 + (n1 + n0) lb b_x^2 / 2  (mode 1: |.|_1, |.|)
+ *   trip [m, steps, triplets, 3] int32 (nullable)   the drawn (role, u, other item), for tests
+ * The draw, on Philox counter (g & 0xffffffff, g >> 32, round, 2), g = ((first_row + x) * steps + t) * triplets + p (mod 2^64), key =
+ * seed -- K1 has 0 and K9 has 1 in the fourth word: round 0 gives the role (word 0) and a pick from a list (words 2, 3: role 1 the
+ * user among the likers, role 0 the positive in the found user's row); rounds 1 .. 64 and a cyclic scan give, role 1, the negative j
+ * not in u's row exactly as K1 does and, role 0, the user: two candidates a round over [0, n_users), legal = has a row and is not a
+ * liker.  Items [a, b) of a call with first_row = f equal a call on those items alone with first_row = f + a.
+ * A triplet without a legal draw (role 1: no liker, or u's row is the whole catalogue; role 0: every user with a row is a liker) is
+ * recorded as (-1, -1, -1) and contributes nothing; a step without any triplet changes nothing, so an item without any keeps V0, b0,
+ * loss 0.  The scan of role 0 is bounded by n_users.
+ * One wave per item, the row in registers up to k = 512, in LDS above (12 k bytes <= 160 KB; wider: TKR_E_UNSUPPORTED), as K9.
+ * 1 <= triplets <= 64, steps >= 1; arguments are checked before any device access (TKR_E_INVAL); m = 0 returns 0 and launches nothing.
+ * Deterministic: bitwise the same run to run. */
+int tkr_bpr_foldin_items(const float* U, const float* V, const float* b, int32_t n_users, int32_t n_items, int32_t k,
+                         const int64_t* user_ptr, const int32_t* user_cols, const int64_t* liker_ptr, const int32_t* liker_rows,
+                         const uint32_t* role_thresh, int32_t m, const float* V0, const float* b0, float li, float lj, float lb, float lr,
+                         int32_t mode, int32_t steps, int32_t triplets, uint64_t seed, uint64_t first_row, float* Vn, float* bn,
+                         float* loss, int32_t* trip, void* stream);
+
 /* ---- multi-GPU: pack / unpack of the replicated item-side tables around the per-epoch all-reduce ---------
  * (new design, the reference is single-process: SURVEY.md §8e).  Users are sharded over the GPUs, every rank updates its
  * own copy of the item tables and once per epoch  P <- P0 + sum_g (P_g - P0),  ms <- mean_g ms_g.  For a table

@@ -14,14 +14,11 @@
 // in groups whose loads are all issued before the first reduction of the group.
 #include <math.h>
 
+#include "fold_rows.h"
 #include "sampler_draw.h"
 #include "../../include/tkr.h"
 
 namespace tkr {
-
-constexpr float kFoldRho = 0.9f, kFoldEps = 1e-10f;      // oracle/ref_np.py RHO, EPS (TF RMSPropOptimizer defaults)
-constexpr int kFoldWaves = 4;                            // users per workgroup of the register form
-constexpr int kFoldMaxLds = 160 * 1024;                  // one workgroup's LDS on gfx950: the widest row of the generic form
 
 struct FoldArgs {
     const float* V;
@@ -38,48 +35,6 @@ struct FoldArgs {
     uint64_t first_row;
 };
 
-// lane l owns the NE contiguous elements [l NE, l NE + NE) of a row, as in K2 (csrc/bpr_step.hip load_row): VEC = full rows at a
-// 16-byte aligned base, one unpredicated vector access per lane; otherwise clamped addresses and a select, never a predicated load
-template <int NE, bool VEC>
-__device__ __forceinline__ void fold_load(const float* __restrict__ base, int k, int lane, float (&r)[NE]) {
-    const int e0 = lane * NE;
-    if constexpr (VEC && NE == 1) {
-        r[0] = base[e0];
-    } else if constexpr (VEC && NE == 2) {
-        const float2 v = *reinterpret_cast<const float2*>(base + e0);
-        r[0] = v.x; r[1] = v.y;
-    } else if constexpr (VEC && NE % 4 == 0) {
-#pragma unroll
-        for (int q = 0; q < NE; q += 4) {
-            const float4 v = *reinterpret_cast<const float4*>(base + e0 + q);
-            r[q] = v.x; r[q + 1] = v.y; r[q + 2] = v.z; r[q + 3] = v.w;
-        }
-    } else {
-#pragma unroll
-        for (int q = 0; q < NE; ++q) {
-            const float v = base[min(e0 + q, k - 1)];
-            r[q] = (e0 + q < k) ? v : 0.f;
-        }
-    }
-}
-
-template <int NE, bool VEC>
-__device__ __forceinline__ void fold_store(float* __restrict__ base, int k, int lane, const float (&r)[NE]) {
-    const int e0 = lane * NE;
-    if constexpr (VEC && NE == 1) {
-        base[e0] = r[0];
-    } else if constexpr (VEC && NE == 2) {
-        *reinterpret_cast<float2*>(base + e0) = make_float2(r[0], r[1]);
-    } else if constexpr (VEC && NE % 4 == 0) {
-#pragma unroll
-        for (int q = 0; q < NE; q += 4) *reinterpret_cast<float4*>(base + e0 + q) = make_float4(r[q], r[q + 1], r[q + 2], r[q + 3]);
-    } else {
-#pragma unroll
-        for (int q = 0; q < NE; ++q)
-            if (e0 + q < k) base[e0 + q] = r[q];
-    }
-}
-
 // the draw of step t for user x: lane p < P holds triplet p.  `cols` is the user's row (ascending, unique: positives and membership
 // test read the same array), 0 < deg < n_items.
 __device__ __forceinline__ void fold_draw(const FoldArgs& a, const int32_t* __restrict__ cols, int deg, int64_t x, int t, int lane,
@@ -94,9 +49,6 @@ __device__ __forceinline__ void fold_draw(const FoldArgs& a, const int32_t* __re
         if (a.trip) reinterpret_cast<int2*>(a.trip)[((size_t)x * a.steps + t) * a.P + lane] = make_int2(di, dj);
     }
 }
-
-// triplets whose rows are in flight together: 2 G NE registers of rows
-template <int NE> constexpr int kFoldGroup = NE == 1 ? 8 : NE == 2 ? 4 : 2;
 
 template <int NE, bool VEC>
 __global__ __launch_bounds__(kFoldWaves * TKR_WAVE) void foldin_kernel(const FoldArgs a) {

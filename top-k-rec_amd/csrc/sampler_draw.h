@@ -1,5 +1,5 @@
 // The (u, i, j) draw of K1, shared by the per-batch planner (sampler.hip) and the grid-wide one (planner_big.hip); its (i, j) part for a
-// fixed user is the draw of K9 (foldin.hip).
+// fixed user is the draw of K9 (foldin.hip), its negative part (draw_negative) also that of K10's positive role (foldin_items.hip).
 // Replaces BPR._uniform_user_sampling (single/bpr.py:155-165); stream definition in oracle/plan_np.py.
 #pragma once
 #include "tkr_common.h"
@@ -31,28 +31,48 @@ __device__ __forceinline__ bool is_member(const int32_t* __restrict__ cols_sorte
     return (a < b && c0 == item) || (a + 1 < b && c1 == item) || (a + 2 < b && c2 == item);
 }
 
-// The (i, j) part of a draw for a user whose row is [lo, hi) of pos_cols / cols_sorted (hi > lo, and the row does not cover the whole
-// catalogue unless the caller accepts the candidate coming back unchanged): the positive from words z, w of the round-0 block `w0`,
-// the negative from rounds 1 .. kMaxRounds of the same counter (c0, c1, round, C3), two candidates a round, then the cyclic scan.
-// C3 names the stream: 0 = K1 (training), 1 = K9 (fold-in, csrc/foldin.hip) -- disjoint under one seed.
-template <uint32_t C3>
-__device__ __forceinline__ void draw_pair(const int32_t* __restrict__ pos_cols, const int32_t* __restrict__ cols_sorted, int lo, int hi,
-                                          uint32_t n_items, u32x4 w0, uint32_t c0, uint32_t c1, uint32_t k0, uint32_t k1, int& i, int& j) {
-    i = pos_cols[lo + (int)mulhi64(w0.z, w0.w, (uint32_t)(hi - lo))];
+// A uniform draw over [0, n) that `rejected` does not refuse: the first of the two candidates a round (words x, y, then z, w) of rounds
+// 1 .. kMaxRounds of the counter (c0, c1, round, C3) that passes, then a cyclic scan of at most n from the last candidate.
+// -> false: nothing in [0, n) passes (`out` is then a refused candidate).
+// C3 names the stream: 0 = K1 (training), 1 = K9 (fold-in of users, csrc/foldin.hip), 2 = K10 (fold-in of items,
+// csrc/foldin_items.hip) -- disjoint under one seed.
+template <uint32_t C3, class Rejected>
+__device__ __forceinline__ bool draw_accepted(uint32_t n, uint32_t c0, uint32_t c1, uint32_t k0, uint32_t k1, Rejected rejected, int& out) {
     int cand = 0;
     bool found = false;
     for (uint32_t r = 1; r <= (uint32_t)kMaxRounds && !found; ++r) {
         const u32x4 w = philox4x32_10(c0, c1, r, C3, k0, k1);
-        cand = (int)mulhi64(w.x, w.y, n_items);
-        if (!is_member(cols_sorted, lo, hi, cand)) { found = true; break; }
-        cand = (int)mulhi64(w.z, w.w, n_items);
-        if (!is_member(cols_sorted, lo, hi, cand)) { found = true; break; }
+        cand = (int)mulhi64(w.x, w.y, n);
+        if (!rejected(cand)) { found = true; break; }
+        cand = (int)mulhi64(w.z, w.w, n);
+        if (!rejected(cand)) { found = true; break; }
     }
     if (!found) {   // cyclic scan fallback (user rated almost everything)
-        for (uint32_t s = 0; s < n_items && is_member(cols_sorted, lo, hi, cand); ++s)
-            cand = (cand + 1 == (int)n_items) ? 0 : cand + 1;
+        uint32_t s = 0;
+        for (; s < n && rejected(cand); ++s)
+            cand = (cand + 1 == (int)n) ? 0 : cand + 1;
+        found = s < n;
     }
-    j = cand;
+    out = cand;
+    return found;
+}
+
+// The negative of a draw for a user whose row is [lo, hi) of cols_sorted (hi > lo): uniform over the columns not in the row.
+// -> false: the row covers the whole catalogue.  Shared by K1, K9 and K10's positive role.
+template <uint32_t C3>
+__device__ __forceinline__ bool draw_negative(const int32_t* __restrict__ cols_sorted, int lo, int hi, uint32_t n_items, uint32_t c0,
+                                              uint32_t c1, uint32_t k0, uint32_t k1, int& j) {
+    return draw_accepted<C3>(n_items, c0, c1, k0, k1, [&](int c) { return is_member(cols_sorted, lo, hi, c); }, j);
+}
+
+// The (i, j) part of a draw for a user whose row is [lo, hi) of pos_cols / cols_sorted (hi > lo, and the row does not cover the whole
+// catalogue unless the caller accepts the candidate coming back unchanged): the positive from words z, w of the round-0 block `w0`,
+// the negative by draw_negative on the same counter.
+template <uint32_t C3>
+__device__ __forceinline__ void draw_pair(const int32_t* __restrict__ pos_cols, const int32_t* __restrict__ cols_sorted, int lo, int hi,
+                                          uint32_t n_items, u32x4 w0, uint32_t c0, uint32_t c1, uint32_t k0, uint32_t k1, int& i, int& j) {
+    i = pos_cols[lo + (int)mulhi64(w0.z, w0.w, (uint32_t)(hi - lo))];
+    draw_negative<C3>(cols_sorted, lo, hi, n_items, c0, c1, k0, k1, j);
 }
 
 __device__ __forceinline__ void draw_triplet(const int32_t* __restrict__ tr_users, uint32_t n_tr,

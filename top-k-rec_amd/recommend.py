@@ -2,6 +2,7 @@
 
     python recommend.py -d DATA -m MODEL -f 0 -t 30 -o out.txt [-u USERS_FILE]
                         [--new-uid FILE --new-history FILE --fold-steps 50 --fold-triplets 16 --fold-lr 0.05 --fold-lu 2.5e-3 --seed 0]
+                        [--new-vid FILE --new-ratings FILE --fold-li 2.5e-3 --fold-lj 2.5e-4 --fold-lb 0]
 
 Inputs as evaluate.py: ``DATA/uid``, ``DATA/vid``, ``DATA/f{fold}tr.txt`` (the histories), ``MODEL/final-U.dat``, ``final-V.dat``,
 optional ``final-B.dat``.  For every requested user -- the tokens of USERS_FILE, one per line; default: every line of ``uid`` -- the
@@ -16,6 +17,12 @@ best first, ties in K4's order (higher catalogue index first); fewer than ``-t``
 from the like == 1 entries of their lines in the history file (K9, foldin.py) and ranked the same way, their own history file
 supplying the excluded items; their lines follow the model users' lines.  With ``--new-uid`` and no ``-u``, ``-u`` defaults to every
 model user as usual; an empty USERS_FILE writes the new users only.
+
+``--new-vid`` / ``--new-ratings`` (both or neither): the items of that id file are not in the model; their rows (and biases, when the
+model has ``final-B.dat``) are folded in from the like == 1 entries of the model's users in the ratings file (K10,
+foldin.fold_in_items: the users' training positives are the like == 1 entries of ``f{fold}tr.txt``), appended to the catalogue in
+file order and ranked with it under their own tokens; what a user rated in that file is excluded for that user like the history
+line.  Together with ``--new-uid`` the items go first and the users are folded in against the grown catalogue.
 
 The scores, the filter and the selection run on the GPU (tkr_hip.build_rated_mask, tkr_hip.score_topk); single process.
 """
@@ -70,19 +77,50 @@ def rated_csr(R, rows_of_user, n_rows, n_items):
     return _group(np.concatenate(rr), np.concatenate(cc), n_rows, n_items)
 
 
-def rank(U_dev, user_rows, V_dev, bias_dev, R, total):
-    """top-`total` unrated items of the users `user_rows` (indices into U_dev and into R's user numbering)
+def rank(U_dev, user_rows, V_dev, bias_dev, R, total, also_rated=None):
+    """top-`total` unrated items of the users `user_rows` (indices into U_dev and into R's user numbering); `also_rated`: a second
+    parsed ratings file in the same numbering whose lines exclude items too
     -> (ids int32 [n, total], scores fp32 [n, total]) as numpy"""
     n, n_items = len(user_rows), int(V_dev.shape[0])
     rows_of_user = {}
     for row, user in enumerate(user_rows):
         rows_of_user.setdefault(int(user), []).append(row)
     ptr, cols = rated_csr(R, rows_of_user, n, n_items)
+    if also_rated is not None:
+        ptr2, cols2 = rated_csr(also_rated, rows_of_user, n, n_items)
+        rows = np.concatenate([np.repeat(np.arange(n), np.diff(ptr)), np.repeat(np.arange(n), np.diff(ptr2))])
+        ptr, cols = _group(rows, np.concatenate([cols, cols2]).astype(np.int64), n, n_items)
     dev = V_dev.device
     mask, pitch = tkr_hip.build_rated_mask(torch.from_numpy(ptr).to(dev), torch.from_numpy(cols).to(dev), n, n_items)
     idx = torch.from_numpy(np.asarray(user_rows, dtype=np.int32)).to(dev)
     ids, scores = tkr_hip.score_topk(U_dev, V_dev, total, bias=bias_dev, user_idx=idx, mask=mask, mask_pitch=pitch, want_scores=True)
     return ids.cpu().numpy(), scores.cpu().numpy()
+
+
+def fold_in_new_items(args, uids, vids, new_vids, vmat, bmat, device):
+    """-> (vmat, bmat, vids) grown by the items of `new_vids` in file order, their rows folded in (K10) from the model users' likes in
+    args.new_ratings against final-U.dat and the users' positives in the fold's train file, and that ratings file parsed over the
+    grown catalogue"""
+    n_users, n_items, m = len(uids), len(vmat), max(new_vids.values()) + 1
+    umap = textio.IdMap(uids)
+    umat = read_matrix(os.path.join(args.model, 'final-U.dat'), uids)
+    T = textio.parse_ratings(os.path.join(args.data, 'f%dtr.txt' % args.fold), umap, textio.IdMap(vids))
+    eu = T.entry_user
+    keep = (eu >= 0) & (T.item >= 0) & (T.like == 1)
+    user_pos = foldin.group_history(eu[keep], T.item[keep], n_users, n_items)
+    L = textio.parse_ratings(args.new_ratings, umap, textio.IdMap(new_vids))
+    eu = L.entry_user
+    keep = (eu >= 0) & (L.item >= 0) & (L.like == 1)
+    likers = foldin.group_history(L.item[keep], eu[keep], m, n_users)
+    V_new, b_new = foldin.fold_in_items(umat, vmat, bmat, user_pos, likers, li=args.fold_li, lj=args.fold_lj, lb=args.fold_lb, lr=args.fold_lr,
+                                        steps=args.fold_steps, triplets=args.fold_triplets, seed=args.seed, device=device)
+    grown = dict(vids)
+    for tok, idx in new_vids.items():
+        grown[tok] = n_items + idx
+    vmat = np.concatenate([vmat, V_new])
+    if bmat is not None:
+        bmat = np.concatenate([bmat, b_new.reshape(-1)])
+    return vmat, bmat, grown, textio.parse_ratings(args.new_ratings, umap, textio.IdMap(grown))
 
 
 def main(argv=None):
@@ -99,10 +137,17 @@ def main(argv=None):
     parser.add_argument('--fold-triplets', type=int, default=16)
     parser.add_argument('--fold-lr', type=float, default=0.05)
     parser.add_argument('--fold-lu', type=float, default=2.5e-3)
+    parser.add_argument('--new-vid', default=None, help="An id file of items that are not in the model: folded in, then ranked with the rest")
+    parser.add_argument('--new-ratings', default=None, help="The ratings file that holds the model users' likes of the new items")
+    parser.add_argument('--fold-li', type=float, default=2.5e-3)
+    parser.add_argument('--fold-lj', type=float, default=2.5e-4)
+    parser.add_argument('--fold-lb', type=float, default=0.0)
     parser.add_argument('--seed', type=int, default=0)
     args = parser.parse_args(argv)
     if (args.new_uid is None) != (args.new_history is None):
         parser.error('--new-uid and --new-history go together')
+    if (args.new_vid is None) != (args.new_ratings is None):
+        parser.error('--new-vid and --new-ratings go together')
     if args.total < 1:
         parser.error('-t must be at least 1')
 
@@ -115,15 +160,24 @@ def main(argv=None):
         clash = [u for u in new_uids if u in uids]
         if clash:
             raise KeyError('%s: user %r is in the model already' % (args.new_uid, clash[0]))
+    new_vids = {}
+    if args.new_vid is not None:
+        new_vids = read_ids(args.new_vid)
+        clash = [v for v in new_vids if v in vids]
+        if clash:
+            raise KeyError('%s: item %r is in the model already' % (args.new_vid, clash[0]))
     if not torch.cuda.is_available():
         raise tkr_hip.TkrError('recommend.py scores on the GPU through libtkr_hip.so; no MI355X is visible')
     device = torch.device('cuda', torch.cuda.current_device())
 
-    items = {idx: tok for tok, idx in vids.items()}
     vmat = read_matrix(os.path.join(args.model, 'final-V.dat'), vids)
     bmat = None
     if os.path.exists(os.path.join(args.model, 'final-B.dat')):
         bmat = read_matrix(os.path.join(args.model, 'final-B.dat'), vids).reshape(-1)
+    R_new_items = None
+    if new_vids:
+        vmat, bmat, vids, R_new_items = fold_in_new_items(args, uids, vids, new_vids, vmat, bmat, device)
+    items = {idx: tok for tok, idx in vids.items()}
     V_dev = torch.from_numpy(vmat).to(device)
     bias_dev = None if bmat is None else torch.from_numpy(np.ascontiguousarray(bmat)).to(device)
     vmap = textio.IdMap(vids)
@@ -131,7 +185,7 @@ def main(argv=None):
     if users:
         umat = read_matrix(os.path.join(args.model, 'final-U.dat'), uids)
         R = textio.parse_ratings(os.path.join(args.data, 'f%dtr.txt' % args.fold), textio.IdMap(uids), vmap)
-        ids, scores = rank(torch.from_numpy(umat).to(device), [uids[u] for u in users], V_dev, bias_dev, R, args.total)
+        ids, scores = rank(torch.from_numpy(umat).to(device), [uids[u] for u in users], V_dev, bias_dev, R, args.total, also_rated=R_new_items)
         lines += format_lines(users, ids, scores, items)
     if new_uids:
         m = max(new_uids.values()) + 1

@@ -392,6 +392,62 @@ class BPR(REC):
                                  mode=self.mode, steps=steps, triplets=triplets, seed=seed, U0=U0, device=device)
         return uids, fue_new
 
+    def fold_in_items(self, vid_file: str, ratings_file: str, *, tr_file: str = None, steps: int = None, triplets: int = None,
+                      lr: float = None, lambda_i: float = None, lambda_j: float = None, lambda_b: float = None, seed=None, device=None,
+                      roles: str = 'both', append: bool = False):
+        """Rows and biases for the items of ``vid_file`` -- items that were no line of the item list when the model was trained --
+        from the likes this model's users gave them in the ratings file ``ratings_file`` (``uid,iid:like,...``; like == '1' entries of
+        known users on the new items count, everything else on the lines is ignored): K10 (csrc/foldin_items.hip), the model's own
+        step with everything but the new row and bias frozen.  -> (iids: dict token -> row, fie_new fp32 [len(iids), width of fie],
+        fib_new fp32 [len(iids), 1]).
+
+        The users' training positives come from ``load_training_data`` or, for a model that only imported its embeddings, from
+        ``tr_file``.  ``steps`` / ``triplets`` default to foldin.ITEM_STEPS / ITEM_TRIPLETS; ``lr`` and the regularisers to the
+        model's own (see fold_in on what another step size does to the scale).  A model without ``fib`` learns no bias.
+        ``append=True`` adds the items to the model: ``iids``, ``n_items``, ``fie`` and ``fib`` grow by them in file order, so that
+        export_embeddings writes the grown model and fold_in / evaluate.py / recommend.py see the grown catalogue (the data
+        directory's ``vid`` needs the new lines appended).  The engine of a previous train() is dropped: train() again warm-starts
+        from the grown factors."""
+        import foldin
+        if self.fie is None or self.fue is None or self.iids is None or self.uids is None:
+            raise ValueError('fold_in_items needs the model: train() or import_embeddings() first')
+        new = get_id_dict_from_file(vid_file)
+        known = [v for v in new if v in self.iids]
+        if known:
+            raise ValueError('%d items of %s are in the model already (e.g. %r)' % (len(known), vid_file, known[0]))
+        m = max(new.values()) + 1 if new else 0
+        if tr_file is not None:
+            T = textio.parse_ratings(tr_file, self.uids, self.iids)
+            eu = T.entry_user
+            keep = (eu >= 0) & (T.item >= 0) & (T.like == 1)
+            rows, cols = eu[keep], T.item[keep]
+        elif self.tr_data is not None:
+            rows = np.concatenate([np.full(len(v), u, dtype=np.int64) for u, v in self.tr_data.items()] + [np.zeros(0, np.int64)])
+            cols = np.concatenate([np.asarray(v, dtype=np.int64) for v in self.tr_data.values()] + [np.zeros(0, np.int64)])
+        else:
+            raise ValueError('fold_in_items needs the training positives: load_training_data() first, or tr_file=')
+        user_pos = foldin.group_history(rows, cols, self.n_users, self.n_items)
+        L = textio.parse_ratings(ratings_file, self.uids, new)
+        eu = L.entry_user
+        keep = (eu >= 0) & (L.item >= 0) & (L.like == 1)
+        likers = foldin.group_history(L.item[keep], eu[keep], m, self.n_users)
+        if seed is None:
+            seed = self._eng.seed if self._eng is not None else 0
+        pick = lambda given, own: own if given is None else given
+        V_new, b_new = foldin.fold_in_items(self.fue, self.fie, self.fib, user_pos, likers, li=pick(lambda_i, self.li), lj=pick(lambda_j, self.lj),
+                                            lb=pick(lambda_b, self.lb), lr=pick(lr, self.lr), mode=self.mode,
+                                            steps=pick(steps, foldin.ITEM_STEPS), triplets=pick(triplets, foldin.ITEM_TRIPLETS), seed=seed,
+                                            roles=roles, device=device)
+        if append and m:
+            for tok, idx in new.items():
+                self.iids[tok] = self.n_items + idx
+            self.n_items += m
+            self.fie = np.concatenate([np.asarray(self.fie, dtype=np.float32), V_new])
+            if self.fib is not None:
+                self.fib = np.concatenate([np.asarray(self.fib, dtype=np.float32).reshape(-1, 1), b_new])
+            self._eng = self._csr = None
+        return new, V_new, b_new
+
     # ------------------------------------------------------------------ sampler (bpr.py:155-165)
     def _uniform_user_sampling(self, batch_size: int):
         """Generator of (ub, ib, jb) numpy batches drawn by the device sampler (K1): u uniform over

@@ -84,7 +84,7 @@ EXPORTS = ('tkr_version', 'tkr_plan_team', 'tkr_plan_max_blocks', 'tkr_sample_pl
            'tkr_ratings_destroy', 'tkr_matrix_read', 'tkr_matrix_sizes', 'tkr_matrix_copy', 'tkr_matrix_destroy',
            'tkr_matrix_write', 'tkr_raw_ranks', 'tkr_count_hits_rr', 'tkr_topk_set_math', 'tkr_vbpr_set_pairs', 'tkr_lab_build',
            'tkr_sync_snapshot', 'tkr_sync_pack', 'tkr_sync_unpack', 'tkr_sync_flow_snapshot', 'tkr_sync_flow_pack',
-           'tkr_sync_flow_unpack', 'tkr_like_ranks', 'tkr_bpr_foldin')
+           'tkr_sync_flow_unpack', 'tkr_like_ranks', 'tkr_bpr_foldin', 'tkr_bpr_foldin_items')
 EXPORTS_I64 = ('tkr_vbpr_workspace_floats', 'tkr_vbpr_colplan_lds_bytes', 'tkr_topk_workspace_bytes_for', 'tkr_topk_workspace_bytes', 'tkr_plan_workspace_bytes', 'tkr_like_ranks_workspace_bytes')
 
 
@@ -591,6 +591,51 @@ def fold_in(V, b, hist_ptr, hist_cols, *, lu, lr, mode='l2', steps, triplets, se
               C.c_uint64(seed & 0xffffffffffffffff), C.c_uint64(first_row), _p(U), _p(loss), _p(trip))
     out = (U,) + ((loss,) if want_loss else ()) + ((trip,) if want_triplets else ())
     return out[0] if len(out) == 1 else out
+
+
+# ---- K10: fold-in of items (csrc/foldin_items.hip) -----------------------------------------------------
+ROLE_ALWAYS_POSITIVE = 0xffffffff     # role_thresh value: every triplet carries the item as the positive of a liker
+
+
+def fold_in_items(U, V, b, user_ptr, user_cols, liker_ptr, liker_rows, role_thresh, *, li, lj, lb, lr, mode='l2', steps, triplets, seed,
+                  first_row=0, V0=None, b0=None, want_loss=False, want_triplets=False):
+    """K10 -> (Vn fp32 [m, k], bn fp32 [m]) (then loss fp32 [m], trip int32 [m, steps, triplets, 3] = (role, u, other item) when asked
+    for): rows and biases of m new items folded in against the frozen user factors U [n_users, k], item factors V [n_items, k]
+    and biases b [n_items] or None (include/tkr.h tkr_bpr_foldin_items).  user_ptr int64 [n_users+1] / user_cols int32: the users'
+    training positives; liker_ptr int64 [m+1] / liker_rows int32: the user rows that like each new item; both from 0, ascending and
+    unique per row.  role_thresh [m]: integers in [0, 2^32) (any integer tensor or sequence).  All tensors on V's device."""
+    assert U.dtype == torch.float32 and V.dtype == torch.float32 and U.dim() == 2 and V.dim() == 2 and U.shape[1] == V.shape[1]
+    assert user_ptr.dtype == torch.int64 and liker_ptr.dtype == torch.int64 and user_cols.dtype == torch.int32 and liker_rows.dtype == torch.int32
+    (n_users, k), n_items, m = U.shape, int(V.shape[0]), int(liker_ptr.numel()) - 1
+    if not 1 <= triplets <= FOLDIN_MAX_TRIPLETS or steps < 1 or m < 0:
+        raise ValueError('fold_in_items: 1 <= triplets <= %d and steps >= 1 required' % FOLDIN_MAX_TRIPLETS)
+    assert int(user_ptr.numel()) == n_users + 1
+    assert b is None or (b.dtype == torch.float32 and b.numel() == n_items)
+    assert V0 is None or (V0.dtype == torch.float32 and tuple(V0.shape) == (m, k))
+    assert b0 is None or (b0.dtype == torch.float32 and b0.numel() == m)
+    # the kernel gathers rows of V by user_cols and rows of U by liker_rows: checked here, once per call
+    for ptr, idx, bound, what in ((user_ptr, user_cols, n_items, 'user_cols'), (liker_ptr, liker_rows, n_users, 'liker_rows')):
+        assert int(ptr[0]) == 0 and int(ptr[-1]) == idx.numel() and bool((ptr[1:] >= ptr[:-1]).all()), 'the row pointer does not describe %s' % what
+        assert idx.numel() == 0 or (0 <= int(idx.min()) and int(idx.max()) < bound), '%s holds an index outside [0, %d)' % (what, bound)
+    pad = lambda idx: idx if idx.numel() else torch.zeros(1, dtype=torch.int32, device=V.device)
+    user_cols, liker_rows = pad(user_cols), pad(liker_rows)
+    thresh = torch.as_tensor(role_thresh, dtype=torch.int64).reshape(-1)
+    assert thresh.numel() == m and (m == 0 or (0 <= int(thresh.min()) and int(thresh.max()) <= ROLE_ALWAYS_POSITIVE))
+    thresh = torch.where(thresh >= 2 ** 31, thresh - 2 ** 32, thresh).to(torch.int32).to(V.device)     # the same 32 bits
+    if k > FOLDIN_REG_MAX_K and not getattr(fold_in_items, '_warned_wide', False):
+        fold_in_items._warned_wide = True
+        warnings.warn('K10: factor width %d is above %d, where a wave no longer holds its item row in registers: the generic form runs '
+                      '(row, slot and gradient sum in LDS: csrc/foldin_items.hip foldin_items_wide_kernel)' % (k, FOLDIN_REG_MAX_K))
+    Vn = torch.empty((m, k), dtype=torch.float32, device=V.device)
+    bn = torch.empty(m, dtype=torch.float32, device=V.device)
+    loss = torch.zeros(m, dtype=torch.float32, device=V.device) if want_loss else None
+    trip = torch.full((m, steps, triplets, 3), -1, dtype=torch.int32, device=V.device) if want_triplets else None
+    if m:
+        _call('tkr_bpr_foldin_items', V, _p(U), _p(V), _p(b), C.c_int32(n_users), C.c_int32(n_items), C.c_int32(k), _p(user_ptr), _p(user_cols),
+              _p(liker_ptr), _p(liker_rows), _p(thresh), C.c_int32(m), _p(V0), _p(b0), C.c_float(li), C.c_float(lj), C.c_float(lb),
+              C.c_float(lr), C.c_int32({'l2': 0, 'l1': 1}[mode]), C.c_int32(steps), C.c_int32(triplets), C.c_uint64(seed & 0xffffffffffffffff),
+              C.c_uint64(first_row), _p(Vn), _p(bn), _p(loss), _p(trip))
+    return (Vn, bn) + ((loss,) if want_loss else ()) + ((trip,) if want_triplets else ())
 
 
 # ---- per-epoch exchange of replicated tables (csrc/sync.hip) ----------------------------------------
