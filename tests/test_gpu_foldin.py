@@ -119,6 +119,31 @@ def test_default_depth_within_measured_tolerance(k):
     assert np.all(dist <= bound), float((dist - bound).max())
 
 
+@pytest.mark.parametrize('k', [128, 600])
+def test_split_by_first_row_and_two_runs_are_bitwise_equal(k):
+    """the vector rows (k = 128: workgroups of four waves, the last one partly filled) and the LDS form (k = 600: one wave a
+    workgroup): a call split at row 23 equals the call in one, and a second run the first, bitwise -- a wave carries nothing from
+    one row to the next and a user does not see who shares its call"""
+    rng = np.random.Generator(np.random.PCG64(k))
+    n_items, cut = 1200, 23
+    hist = _histories(rng, n_items, [int(x) for x in rng.integers(1, 81, 60)])
+    ptr, cols = O.csr(hist)
+    V = (rng.standard_normal((n_items, k)) * 0.1).astype(np.float32)
+    bias = (rng.standard_normal(n_items) * 0.1).astype(np.float32)
+    kw = dict(lu=2.5e-3, lr=0.05, steps=5, triplets=16, seed=9, want_loss=True, want_triplets=True)
+    import warnings
+    with warnings.catch_warnings():
+        warnings.simplefilter('ignore')                               # (k = 600: the one warning of the generic form)
+        whole = _fold(V, bias, ptr, cols, first_row=12345, **kw)
+        again = _fold(V, bias, ptr, cols, first_row=12345, **kw)
+        head = _fold(V, bias, ptr[:cut + 1], cols[:ptr[cut]], first_row=12345, **kw)
+        tail = _fold(V, bias, ptr[cut:] - ptr[cut], cols[ptr[cut]:], first_row=12345 + cut, **kw)
+    assert len(whole) == 3 and np.abs(whole[0]).max() > 1e-3 and whole[1].all() and (whole[2] >= 0).all()
+    for a, c, h, t in zip(whole, again, head, tail):
+        np.testing.assert_array_equal(a, c)
+        np.testing.assert_array_equal(a, np.concatenate([h, t]))
+
+
 EDGE_CHILD = r'''
 import sys
 sys.path[:0] = [%r, %r]
@@ -153,6 +178,9 @@ def test_wrapper_refuses_bad_arguments():
     for cols, Pn in (([3], 0), ([3], 65), ([10], 4), ([-1], 4)):
         with pytest.raises((ValueError, AssertionError)):
             tkr_hip.fold_in(V, None, ptr, torch.tensor(cols, dtype=torch.int32, device='cuda'), lu=0.1, lr=0.1, steps=1, triplets=Pn, seed=0)
+    with pytest.raises(AssertionError):                               # a row pointer that decreases: refused before any launch
+        tkr_hip.fold_in(V, None, torch.tensor([0, 2, 1, 3], dtype=torch.int64, device='cuda'), torch.tensor([1, 2, 3], dtype=torch.int32, device='cuda'),
+                        lu=0.1, lr=0.1, steps=1, triplets=4, seed=0)
 
 
 def _g4(golden_dir):

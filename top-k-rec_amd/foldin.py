@@ -40,26 +40,36 @@ def history_csr(histories, n_items):
     return group_history(np.repeat(np.arange(len(lens), dtype=np.int64), lens), cols, len(lens), n_items)
 
 
+def liked_csr(R, m, n, by='user'):
+    """a parsed ratings file (textio.parse_ratings) -> the group_history CSR of its like == 1 entries of known users and items:
+    by='user' the m users' liked items among n, by='item' the m items' likers among n users"""
+    rows, cols = {'user': (R.entry_user, R.item), 'item': (R.item, R.entry_user)}[by]
+    keep = (rows >= 0) & (cols >= 0) & (R.like == 1)
+    return group_history(rows[keep], cols[keep], m, n)
+
+
+def _device(device, who):
+    if device is None and not torch.cuda.is_available():
+        raise tkr_hip.TkrError('%s runs on the GPU through libtkr_hip.so; no MI355X is visible' % who)
+    return torch.device('cuda', torch.cuda.current_device()) if device is None else device
+
+
+def _upload(a, device, dtype=None, flat=False):
+    """an optional array -> a contiguous tensor on the device (None stays None); flat: as one dimension"""
+    return None if a is None else torch.from_numpy(np.ascontiguousarray(np.asarray(a, dtype=dtype).reshape(-1 if flat else np.shape(a)))).to(device)
+
+
 def fold_in(fie, fib, histories, *, lu, lr, mode='l2', steps=50, triplets=16, seed=0, first_row=0, U0=None, device=None,
             want_loss=False):
     """-> U fp32 [m, k] (numpy; with want_loss also the per-user objective of the last step).  Users with an empty history, or one
     that covers the catalogue, keep U0 (zeros by default: such a user is ranked by the item biases).  ``histories``: a list of
     item-index sequences, one per user, or the (ptr, cols) pair group_history returns."""
-    if device is None:
-        if not torch.cuda.is_available():
-            raise tkr_hip.TkrError('fold_in runs on the GPU through libtkr_hip.so; no MI355X is visible')
-        device = torch.device('cuda', torch.cuda.current_device())
-    fie = np.ascontiguousarray(fie, dtype=np.float32)
-    n_items = fie.shape[0]
-    ptr, cols = histories if isinstance(histories, tuple) else history_csr(histories, n_items)
-    V = torch.from_numpy(fie).to(device)
-    b = None if fib is None else torch.from_numpy(np.ascontiguousarray(np.asarray(fib, dtype=np.float32).reshape(-1))).to(device)
-    start = None if U0 is None else torch.from_numpy(np.ascontiguousarray(U0, dtype=np.float32)).to(device)
-    out = tkr_hip.fold_in(V, b, torch.from_numpy(ptr).to(device), torch.from_numpy(cols).to(device), lu=lu, lr=lr, mode=mode, steps=steps,
-                          triplets=triplets, seed=seed, first_row=first_row, U0=start, want_loss=want_loss)
-    if want_loss:
-        return out[0].cpu().numpy(), out[1].cpu().numpy()
-    return out.cpu().numpy()
+    device = _device(device, 'fold_in')
+    ptr, cols = histories if isinstance(histories, tuple) else history_csr(histories, len(fie))
+    out = tkr_hip.fold_in(_upload(fie, device, np.float32), _upload(fib, device, np.float32, flat=True), _upload(ptr, device), _upload(cols, device), lu=lu, lr=lr,
+                          mode=mode, steps=steps, triplets=triplets, seed=seed, first_row=first_row, U0=_upload(U0, device, np.float32),
+                          want_loss=want_loss)
+    return (out[0].cpu().numpy(), out[1].cpu().numpy()) if want_loss else out.cpu().numpy()
 
 
 ITEM_STEPS, ITEM_TRIPLETS, ITEM_LR = 50, 16, 0.05      # chosen by tests/test_item_foldin_cpu.py (the numbers: DESIGN.md section 4, K10)
@@ -104,21 +114,16 @@ def fold_in_items(fue, fie, fib, user_pos, likers, *, li, lj, lb, lr, mode='l2',
     uniformly (over the likers, or over the non-likers with a row), not in proportion to the weights 1 / (deg_u + 1) and
     1 / (n_items + 1 - deg_u) with which the sampler would reach x through that user.  roles='positive' never pushes x down: its
     scores are then too high for the users who do not like it.  An item nobody likes, with roles='positive', keeps V0 / b0."""
-    if device is None:
-        if not torch.cuda.is_available():
-            raise tkr_hip.TkrError('fold_in_items runs on the GPU through libtkr_hip.so; no MI355X is visible')
-        device = torch.device('cuda', torch.cuda.current_device())
-    fue, fie = np.ascontiguousarray(fue, dtype=np.float32), np.ascontiguousarray(fie, dtype=np.float32)
-    n_users, n_items = fue.shape[0], fie.shape[0]
+    device = _device(device, 'fold_in_items')
+    n_users, n_items = len(fue), len(fie)
     uptr, ucols = user_pos if isinstance(user_pos, tuple) else history_csr(user_pos, n_items)
     lptr, lrows = likers if isinstance(likers, tuple) else history_csr(likers, n_users)
     if len(uptr) != n_users + 1:
         raise ValueError('user_pos describes %d users, fue has %d rows' % (len(uptr) - 1, n_users))
-    thresh = role_thresholds(uptr, lptr, lrows, n_items, roles)
-    dev = lambda a: None if a is None else torch.from_numpy(np.ascontiguousarray(a)).to(device)
-    flat = lambda a: None if a is None else np.asarray(a, dtype=np.float32).reshape(-1)
-    out = tkr_hip.fold_in_items(dev(fue), dev(fie), dev(flat(fib)), dev(uptr), dev(ucols), dev(lptr), dev(lrows), thresh, li=li, lj=lj, lb=lb,
-                                lr=lr, mode=mode, steps=steps, triplets=triplets, seed=seed, first_row=first_row,
-                                V0=dev(None if V0 is None else np.asarray(V0, dtype=np.float32)), b0=dev(flat(b0)), want_loss=want_loss)
+    dev = lambda a, **kw: _upload(a, device, **kw)
+    out = tkr_hip.fold_in_items(dev(fue, dtype=np.float32), dev(fie, dtype=np.float32), dev(fib, dtype=np.float32, flat=True), dev(uptr), dev(ucols), dev(lptr), dev(lrows),
+                                role_thresholds(uptr, lptr, lrows, n_items, roles), li=li, lj=lj, lb=lb, lr=lr, mode=mode, steps=steps,
+                                triplets=triplets, seed=seed, first_row=first_row, V0=dev(V0, dtype=np.float32),
+                                b0=dev(b0, dtype=np.float32, flat=True), want_loss=want_loss)
     res = (out[0].cpu().numpy(), out[1].cpu().numpy().reshape(-1, 1))
     return res + (out[2].cpu().numpy(),) if want_loss else res

@@ -104,14 +104,8 @@ def fold_in_new_items(args, uids, vids, new_vids, vmat, bmat, device):
     n_users, n_items, m = len(uids), len(vmat), max(new_vids.values()) + 1
     umap = textio.IdMap(uids)
     umat = read_matrix(os.path.join(args.model, 'final-U.dat'), uids)
-    T = textio.parse_ratings(os.path.join(args.data, 'f%dtr.txt' % args.fold), umap, textio.IdMap(vids))
-    eu = T.entry_user
-    keep = (eu >= 0) & (T.item >= 0) & (T.like == 1)
-    user_pos = foldin.group_history(eu[keep], T.item[keep], n_users, n_items)
-    L = textio.parse_ratings(args.new_ratings, umap, textio.IdMap(new_vids))
-    eu = L.entry_user
-    keep = (eu >= 0) & (L.item >= 0) & (L.like == 1)
-    likers = foldin.group_history(L.item[keep], eu[keep], m, n_users)
+    user_pos = foldin.liked_csr(textio.parse_ratings(os.path.join(args.data, 'f%dtr.txt' % args.fold), umap, textio.IdMap(vids)), n_users, n_items)
+    likers = foldin.liked_csr(textio.parse_ratings(args.new_ratings, umap, textio.IdMap(new_vids)), m, n_users, by='item')
     V_new, b_new = foldin.fold_in_items(umat, vmat, bmat, user_pos, likers, li=args.fold_li, lj=args.fold_lj, lb=args.fold_lb, lr=args.fold_lr,
                                         steps=args.fold_steps, triplets=args.fold_triplets, seed=args.seed, device=device)
     grown = dict(vids)
@@ -190,9 +184,7 @@ def main(argv=None):
     if new_uids:
         m = max(new_uids.values()) + 1
         R = textio.parse_ratings(args.new_history, textio.IdMap(new_uids), vmap)
-        eu = R.entry_user
-        keep = (eu >= 0) & (R.item >= 0) & (R.like == 1)
-        hist = foldin.group_history(eu[keep], R.item[keep], m, len(vmat))
+        hist = foldin.liked_csr(R, m, len(vmat))
         U_new = foldin.fold_in(vmat, bmat, hist, lu=args.fold_lu, lr=args.fold_lr, steps=args.fold_steps, triplets=args.fold_triplets,
                                seed=args.seed, device=device)
         ids, scores = rank(torch.from_numpy(U_new).to(device), [new_uids[u] for u in new_uids], V_dev, bias_dev, R, args.total)

@@ -382,10 +382,7 @@ class BPR(REC):
             U0 = np.zeros((m, np.asarray(self.fue).shape[1]), dtype=np.float32)
             for u, row in uids.items():
                 U0[row] = self.fue[self.uids[u]]
-        R = textio.parse_ratings(tr_file, uids, self.iids)
-        eu = R.entry_user
-        keep = (eu >= 0) & (R.item >= 0) & (R.like == 1)
-        hist = foldin.group_history(eu[keep], R.item[keep], m, self.n_items)
+        hist = foldin.liked_csr(textio.parse_ratings(tr_file, uids, self.iids), m, self.n_items)
         if seed is None:
             seed = self._eng.seed if self._eng is not None else 0
         fue_new = foldin.fold_in(self.fie, self.fib, hist, lu=self.lu if lambda_u is None else lambda_u, lr=self.lr if lr is None else lr,
@@ -417,20 +414,14 @@ class BPR(REC):
             raise ValueError('%d items of %s are in the model already (e.g. %r)' % (len(known), vid_file, known[0]))
         m = max(new.values()) + 1 if new else 0
         if tr_file is not None:
-            T = textio.parse_ratings(tr_file, self.uids, self.iids)
-            eu = T.entry_user
-            keep = (eu >= 0) & (T.item >= 0) & (T.like == 1)
-            rows, cols = eu[keep], T.item[keep]
+            user_pos = foldin.liked_csr(textio.parse_ratings(tr_file, self.uids, self.iids), self.n_users, self.n_items)
         elif self.tr_data is not None:
             rows = np.concatenate([np.full(len(v), u, dtype=np.int64) for u, v in self.tr_data.items()] + [np.zeros(0, np.int64)])
             cols = np.concatenate([np.asarray(v, dtype=np.int64) for v in self.tr_data.values()] + [np.zeros(0, np.int64)])
+            user_pos = foldin.group_history(rows, cols, self.n_users, self.n_items)
         else:
             raise ValueError('fold_in_items needs the training positives: load_training_data() first, or tr_file=')
-        user_pos = foldin.group_history(rows, cols, self.n_users, self.n_items)
-        L = textio.parse_ratings(ratings_file, self.uids, new)
-        eu = L.entry_user
-        keep = (eu >= 0) & (L.item >= 0) & (L.like == 1)
-        likers = foldin.group_history(L.item[keep], eu[keep], m, self.n_users)
+        likers = foldin.liked_csr(textio.parse_ratings(ratings_file, self.uids, new), m, self.n_users, by='item')
         if seed is None:
             seed = self._eng.seed if self._eng is not None else 0
         pick = lambda given, own: own if given is None else given

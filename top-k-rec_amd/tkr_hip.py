@@ -554,9 +554,38 @@ def like_ranks(U, Vt, like_ptr, like_cols, bias=None, user_idx=None, mask=None, 
     return out
 
 
-# ---- K9: fold-in (csrc/foldin.hip) -------------------------------------------------------------------
+# ---- K9, K10: fold-in of users (csrc/foldin.hip) and of items (csrc/foldin_items.hip), one kernel body (csrc/fold_rows.h) ---------
 FOLDIN_MAX_TRIPLETS = 64     # one lane of a wave draws one triplet of a step
 FOLDIN_REG_MAX_K = 512       # rows up to here stay in registers
+ROLE_ALWAYS_POSITIVE = 0xffffffff     # K10 role_thresh value: every triplet carries the item as the positive of a liker
+
+
+def _fold_csr(ptr, idx, bound, what):
+    """a CSR whose indices the kernel gathers rows by, checked once per call: the pointer runs from 0 to idx.numel() and never
+    decreases, the indices lie in [0, bound).  -> idx, an empty one padded to one element (the kernel is handed no null pointer)"""
+    assert ptr.dtype == torch.int64 and idx.dtype == torch.int32
+    assert int(ptr[0]) == 0 and int(ptr[-1]) == idx.numel() and bool((ptr[1:] >= ptr[:-1]).all()), 'the row pointer does not describe %s' % what
+    assert idx.numel() == 0 or (0 <= int(idx.min()) and int(idx.max()) < bound), '%s holds an index outside [0, %d)' % (what, bound)
+    return idx if idx.numel() else torch.zeros(1, dtype=torch.int32, device=idx.device)
+
+
+def _fold_warn_wide(name, row, k):
+    """once per process and kernel: rows wider than the register form holds"""
+    if k > FOLDIN_REG_MAX_K and name not in _fold_warn_wide.seen:
+        _fold_warn_wide.seen.add(name)
+        warnings.warn('%s: factor width %d is above %d, where a wave no longer holds its %s row in registers: the generic form runs '
+                      '(row, slot and gradient sum in LDS, two passes over the gathered rows per triplet: csrc/fold_rows.h fold_wide_kernel)'
+                      % (name, k, FOLDIN_REG_MAX_K, row))
+
+
+_fold_warn_wide.seen = set()
+
+
+def _fold_outputs(m, steps, triplets, width, want_loss, want_triplets, device):
+    """-> (loss fp32 [m] zeros, trip int32 [m, steps, triplets, width] of -1), None where not asked for"""
+    loss = torch.zeros(m, dtype=torch.float32, device=device) if want_loss else None
+    trip = torch.full((m, steps, triplets, width), -1, dtype=torch.int32, device=device) if want_triplets else None
+    return loss, trip
 
 
 def fold_in(V, b, hist_ptr, hist_cols, *, lu, lr, mode='l2', steps, triplets, seed, first_row=0, U0=None, want_loss=False,
@@ -565,36 +594,22 @@ def fold_in(V, b, hist_ptr, hist_cols, *, lu, lr, mode='l2', steps, triplets, se
     of m histories folded in against the frozen item factors V [n_items, k] / biases b [n_items] or None (include/tkr.h
     tkr_bpr_foldin).  hist_ptr int64 [m+1] from 0, hist_cols int32 ascending and unique per row; all tensors on V's device.
     Rows without a triplet (empty, or the whole catalogue) return U0 (zeros), loss 0 and -1 in trip."""
-    assert V.dtype == torch.float32 and V.dim() == 2 and hist_ptr.dtype == torch.int64 and hist_cols.dtype == torch.int32
+    assert V.dtype == torch.float32 and V.dim() == 2
     m, (n_items, k) = int(hist_ptr.numel()) - 1, V.shape
     if not 1 <= triplets <= FOLDIN_MAX_TRIPLETS or steps < 1 or m < 0:
         raise ValueError('fold_in: 1 <= triplets <= %d and steps >= 1 required' % FOLDIN_MAX_TRIPLETS)
     assert b is None or (b.dtype == torch.float32 and b.numel() == n_items)
     assert U0 is None or (U0.dtype == torch.float32 and tuple(U0.shape) == (m, k))
-    if hist_cols.numel():           # the kernel gathers rows of V by these: checked here, once per call
-        assert int(hist_ptr[0]) == 0 and int(hist_ptr[-1]) == hist_cols.numel(), 'hist_ptr does not describe hist_cols'
-        assert 0 <= int(hist_cols.min()) and int(hist_cols.max()) < n_items, 'history column outside the catalogue'
-    else:
-        assert m == 0 or not bool(hist_ptr.any())
-        hist_cols = torch.zeros(1, dtype=torch.int32, device=V.device)
-    if k > FOLDIN_REG_MAX_K and not getattr(fold_in, '_warned_wide', False):
-        fold_in._warned_wide = True
-        warnings.warn('K9: factor width %d is above %d, where a wave no longer holds its user row in registers: the generic form runs '
-                      '(row, slot and gradient sum in LDS, two passes over the item rows per triplet: csrc/foldin.hip foldin_wide_kernel)'
-                      % (k, FOLDIN_REG_MAX_K))
+    hist_cols = _fold_csr(hist_ptr, hist_cols, n_items, 'hist_cols')
+    _fold_warn_wide('K9', 'user', k)
     U = torch.empty((m, k), dtype=torch.float32, device=V.device)
-    loss = torch.zeros(m, dtype=torch.float32, device=V.device) if want_loss else None
-    trip = torch.full((m, steps, triplets, 2), -1, dtype=torch.int32, device=V.device) if want_triplets else None
+    loss, trip = _fold_outputs(m, steps, triplets, 2, want_loss, want_triplets, V.device)
     if m:
         _call('tkr_bpr_foldin', V, _p(V), _p(b), C.c_int32(n_items), C.c_int32(k), _p(hist_ptr), _p(hist_cols), C.c_int32(m), _p(U0),
               C.c_float(lu), C.c_float(lr), C.c_int32({'l2': 0, 'l1': 1}[mode]), C.c_int32(steps), C.c_int32(triplets),
               C.c_uint64(seed & 0xffffffffffffffff), C.c_uint64(first_row), _p(U), _p(loss), _p(trip))
     out = (U,) + ((loss,) if want_loss else ()) + ((trip,) if want_triplets else ())
     return out[0] if len(out) == 1 else out
-
-
-# ---- K10: fold-in of items (csrc/foldin_items.hip) -----------------------------------------------------
-ROLE_ALWAYS_POSITIVE = 0xffffffff     # role_thresh value: every triplet carries the item as the positive of a liker
 
 
 def fold_in_items(U, V, b, user_ptr, user_cols, liker_ptr, liker_rows, role_thresh, *, li, lj, lb, lr, mode='l2', steps, triplets, seed,
@@ -605,7 +620,6 @@ def fold_in_items(U, V, b, user_ptr, user_cols, liker_ptr, liker_rows, role_thre
     training positives; liker_ptr int64 [m+1] / liker_rows int32: the user rows that like each new item; both from 0, ascending and
     unique per row.  role_thresh [m]: integers in [0, 2^32) (any integer tensor or sequence).  All tensors on V's device."""
     assert U.dtype == torch.float32 and V.dtype == torch.float32 and U.dim() == 2 and V.dim() == 2 and U.shape[1] == V.shape[1]
-    assert user_ptr.dtype == torch.int64 and liker_ptr.dtype == torch.int64 and user_cols.dtype == torch.int32 and liker_rows.dtype == torch.int32
     (n_users, k), n_items, m = U.shape, int(V.shape[0]), int(liker_ptr.numel()) - 1
     if not 1 <= triplets <= FOLDIN_MAX_TRIPLETS or steps < 1 or m < 0:
         raise ValueError('fold_in_items: 1 <= triplets <= %d and steps >= 1 required' % FOLDIN_MAX_TRIPLETS)
@@ -613,23 +627,15 @@ def fold_in_items(U, V, b, user_ptr, user_cols, liker_ptr, liker_rows, role_thre
     assert b is None or (b.dtype == torch.float32 and b.numel() == n_items)
     assert V0 is None or (V0.dtype == torch.float32 and tuple(V0.shape) == (m, k))
     assert b0 is None or (b0.dtype == torch.float32 and b0.numel() == m)
-    # the kernel gathers rows of V by user_cols and rows of U by liker_rows: checked here, once per call
-    for ptr, idx, bound, what in ((user_ptr, user_cols, n_items, 'user_cols'), (liker_ptr, liker_rows, n_users, 'liker_rows')):
-        assert int(ptr[0]) == 0 and int(ptr[-1]) == idx.numel() and bool((ptr[1:] >= ptr[:-1]).all()), 'the row pointer does not describe %s' % what
-        assert idx.numel() == 0 or (0 <= int(idx.min()) and int(idx.max()) < bound), '%s holds an index outside [0, %d)' % (what, bound)
-    pad = lambda idx: idx if idx.numel() else torch.zeros(1, dtype=torch.int32, device=V.device)
-    user_cols, liker_rows = pad(user_cols), pad(liker_rows)
+    user_cols = _fold_csr(user_ptr, user_cols, n_items, 'user_cols')
+    liker_rows = _fold_csr(liker_ptr, liker_rows, n_users, 'liker_rows')
     thresh = torch.as_tensor(role_thresh, dtype=torch.int64).reshape(-1)
     assert thresh.numel() == m and (m == 0 or (0 <= int(thresh.min()) and int(thresh.max()) <= ROLE_ALWAYS_POSITIVE))
     thresh = torch.where(thresh >= 2 ** 31, thresh - 2 ** 32, thresh).to(torch.int32).to(V.device)     # the same 32 bits
-    if k > FOLDIN_REG_MAX_K and not getattr(fold_in_items, '_warned_wide', False):
-        fold_in_items._warned_wide = True
-        warnings.warn('K10: factor width %d is above %d, where a wave no longer holds its item row in registers: the generic form runs '
-                      '(row, slot and gradient sum in LDS: csrc/foldin_items.hip foldin_items_wide_kernel)' % (k, FOLDIN_REG_MAX_K))
+    _fold_warn_wide('K10', 'item', k)
     Vn = torch.empty((m, k), dtype=torch.float32, device=V.device)
     bn = torch.empty(m, dtype=torch.float32, device=V.device)
-    loss = torch.zeros(m, dtype=torch.float32, device=V.device) if want_loss else None
-    trip = torch.full((m, steps, triplets, 3), -1, dtype=torch.int32, device=V.device) if want_triplets else None
+    loss, trip = _fold_outputs(m, steps, triplets, 3, want_loss, want_triplets, V.device)
     if m:
         _call('tkr_bpr_foldin_items', V, _p(U), _p(V), _p(b), C.c_int32(n_users), C.c_int32(n_items), C.c_int32(k), _p(user_ptr), _p(user_cols),
               _p(liker_ptr), _p(liker_rows), _p(thresh), C.c_int32(m), _p(V0), _p(b0), C.c_float(li), C.c_float(lj), C.c_float(lb),
