@@ -525,6 +525,39 @@ int tkr_matrix_copy(const void* matrix, float* dst /*[rows*cols]*/);
 int tkr_matrix_destroy(void* matrix);
 int tkr_matrix_write(const char* path, const float* data, int64_t rows, int64_t cols);
 
+/* ---- K11: tkr_ratings_parse on the device (csrc/parse_dev.hip) ------------------------------------
+ * The same four arrays as tkr_ratings_parse / tkr_ratings_copy, bit for bit, from the n_bytes bytes of the file in device memory
+ * (`text`, 16-byte aligned; NULL only for n_bytes == 0).  Same rules: lines end at '\n' only, a last line without one counts, a line
+ * is stripped of ' ' \t \n \r \v \f at both ends, every ',' opens one field, the iid token is the unstripped bytes before the
+ * field's first ':', like is the stripped decimal integer (optional sign, saturating at +-2,147,483,647) between the first and
+ * the second ':' or the field end.  All offsets and counts are 64-bit.  No kernel reads outside [0, n_bytes).
+ *
+ * Two calls with one read-back between them, because the outputs are sized by what the first one counts:
+ *   tkr_ratings_count_dev   totals_out (device int64[2]) = {n_lines, n_entries}; fills `workspace` (16-byte aligned,
+ *                           tkr_parse_dev_workspace_bytes(n_bytes, chunk_bytes) bytes) with the per-chunk offsets
+ *   tkr_ratings_emit_dev    with the SAME text, chunk_bytes and workspace and the totals read back: line_user int32[n_lines],
+ *                           line_ptr int64[n_lines + 1], item / like int32[n_entries]; line_start int64[n_lines] is scratch.
+ *                           status (device int64): -1, or the smallest start offset of a malformed field (no ':', or a like
+ *                           that is no such integer) -- the caller's TKR_E_PARSE; the arrays are then not to be used.
+ * chunk_bytes: a power of two, 64 ... 1,048,576: the piece of text one wave counts and walks.  It changes no output.
+ *
+ * Token lookup: an open-addressing table per id list.  tkr_idtable_build (HOST call, host pointers) lays it out from the blob
+ * and index array tkr_idmap_create takes: slots int32[n_slots][4] = {offset into blob, length (-1 = empty), index, hash},
+ * n_slots = tkr_idtable_slots(n) (a power of two >= 2 n, >= 8), linear probing from hash & (n_slots - 1), hash = FNV-1a of the
+ * token's bytes with h ^= h >> 15 at the end.  A token listed twice keeps its last index.  The caller uploads slots (16-byte
+ * aligned) and blob (4-byte aligned, < 2^31 bytes) and passes both to tkr_ratings_emit_dev; a hit compares the bytes.
+ * Arguments are checked before any device access (TKR_E_INVAL; the two size functions return it as their value). */
+int64_t tkr_parse_dev_workspace_bytes(int64_t n_bytes, int64_t chunk_bytes);
+int64_t tkr_idtable_slots(int64_t n);
+int tkr_idtable_build(const char* blob, int64_t blob_len, const int32_t* index, int64_t n, int32_t* slots, int64_t n_slots);
+int tkr_ratings_count_dev(const void* text, int64_t n_bytes, int64_t chunk_bytes, void* workspace, int64_t workspace_bytes,
+                          int64_t* totals_out, void* stream);
+int tkr_ratings_emit_dev(const void* text, int64_t n_bytes, int64_t chunk_bytes, void* workspace, int64_t workspace_bytes,
+                         int64_t n_lines, int64_t n_entries, const int32_t* user_slots, int64_t user_n_slots,
+                         const void* user_blob, int64_t user_blob_len, const int32_t* item_slots, int64_t item_n_slots,
+                         const void* item_blob, int64_t item_blob_len, int64_t* line_start, int32_t* line_user,
+                         int64_t* line_ptr, int32_t* item, int32_t* like, int64_t* status, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

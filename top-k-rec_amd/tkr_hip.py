@@ -84,8 +84,10 @@ EXPORTS = ('tkr_version', 'tkr_plan_team', 'tkr_plan_max_blocks', 'tkr_sample_pl
            'tkr_ratings_destroy', 'tkr_matrix_read', 'tkr_matrix_sizes', 'tkr_matrix_copy', 'tkr_matrix_destroy',
            'tkr_matrix_write', 'tkr_raw_ranks', 'tkr_count_hits_rr', 'tkr_topk_set_math', 'tkr_vbpr_set_pairs', 'tkr_lab_build',
            'tkr_sync_snapshot', 'tkr_sync_pack', 'tkr_sync_unpack', 'tkr_sync_flow_snapshot', 'tkr_sync_flow_pack',
-           'tkr_sync_flow_unpack', 'tkr_like_ranks', 'tkr_bpr_foldin', 'tkr_bpr_foldin_items')
-EXPORTS_I64 = ('tkr_vbpr_workspace_floats', 'tkr_vbpr_colplan_lds_bytes', 'tkr_topk_workspace_bytes_for', 'tkr_topk_workspace_bytes', 'tkr_plan_workspace_bytes', 'tkr_like_ranks_workspace_bytes')
+           'tkr_sync_flow_unpack', 'tkr_like_ranks', 'tkr_bpr_foldin', 'tkr_bpr_foldin_items', 'tkr_idtable_build', 'tkr_ratings_count_dev',
+           'tkr_ratings_emit_dev')
+EXPORTS_I64 = ('tkr_vbpr_workspace_floats', 'tkr_vbpr_colplan_lds_bytes', 'tkr_topk_workspace_bytes_for', 'tkr_topk_workspace_bytes', 'tkr_plan_workspace_bytes', 'tkr_like_ranks_workspace_bytes',
+               'tkr_parse_dev_workspace_bytes', 'tkr_idtable_slots')
 
 
 def lib():
@@ -642,6 +644,55 @@ def fold_in_items(U, V, b, user_ptr, user_cols, liker_ptr, liker_rows, role_thre
               C.c_float(lr), C.c_int32({'l2': 0, 'l1': 1}[mode]), C.c_int32(steps), C.c_int32(triplets), C.c_uint64(seed & 0xffffffffffffffff),
               C.c_uint64(first_row), _p(Vn), _p(bn), _p(loss), _p(trip))
     return (Vn, bn) + ((loss,) if want_loss else ()) + ((trip,) if want_triplets else ())
+
+
+# ---- K11: the ratings parser on the device (csrc/parse_dev.hip) ------------------------------------------------------------------
+PARSE_CHUNK_MIN, PARSE_CHUNK_MAX = 64, 1 << 20      # chunk_bytes: a power of two in this range
+
+
+def idtable_build(blob, index):
+    """-> int32 [n_slots, 4] host array: the open-addressing table of the len(index) '\\n'-separated tokens of `blob` (bytes) in the
+    layout tkr_ratings_emit_dev probes (include/tkr.h); a host call"""
+    import numpy as np
+    n = int(index.shape[0])
+    n_slots = int(lib().tkr_idtable_slots(C.c_int64(n)))
+    if n_slots < 0:
+        raise TkrError('tkr_idtable_slots failed: tkr error %d' % n_slots)
+    slots = np.empty((n_slots, 4), dtype=np.int32)
+    _check(lib().tkr_idtable_build(blob, C.c_int64(len(blob)), index.ctypes.data_as(C.c_void_p), C.c_int64(n),
+                                   slots.ctypes.data_as(C.c_void_p), C.c_int64(n_slots)), 'tkr_idtable_build')
+    return slots
+
+
+def parse_dev_workspace_bytes(n_bytes, chunk_bytes):
+    need = int(lib().tkr_parse_dev_workspace_bytes(C.c_int64(n_bytes), C.c_int64(chunk_bytes)))
+    if need < 0:
+        raise ValueError('parse on the device: chunk_bytes must be a power of two in [%d, %d], got %r' % (PARSE_CHUNK_MIN, PARSE_CHUNK_MAX, chunk_bytes))
+    return need
+
+
+def ratings_count_dev(text, chunk_bytes, workspace, totals):
+    """first half of K11: totals (device int64[2]) = (n_lines, n_entries) of the ratings text in `text` (device uint8)"""
+    assert text.dtype == torch.uint8 and totals.dtype == torch.int64 and totals.numel() == 2 and workspace.dtype == torch.uint8
+    _call('tkr_ratings_count_dev', workspace, _p(text), C.c_int64(text.numel()), C.c_int64(chunk_bytes), _p(workspace), C.c_int64(workspace.numel()),
+          _p(totals))
+
+
+def ratings_emit_dev(text, chunk_bytes, workspace, n_lines, n_entries, user_table, item_table, status):
+    """second half of K11 -> (line_user, line_ptr, item, like) on text's device; *_table = (slots int32 [n_slots, 4], blob uint8,
+    blob_len) on that device; status (device int64[1]) = -1 or the offset of a malformed field"""
+    dev = workspace.device
+    line_start = torch.empty(n_lines, dtype=torch.int64, device=dev)
+    line_user = torch.empty(n_lines, dtype=torch.int32, device=dev)
+    line_ptr = torch.empty(n_lines + 1, dtype=torch.int64, device=dev)
+    item = torch.empty(n_entries, dtype=torch.int32, device=dev)
+    like = torch.empty(n_entries, dtype=torch.int32, device=dev)
+    (us, ub, ul), (vs, vb, vl) = user_table, item_table
+    assert us.dtype == torch.int32 and vs.dtype == torch.int32 and ub.dtype == torch.uint8 and vb.dtype == torch.uint8 and status.dtype == torch.int64
+    _call('tkr_ratings_emit_dev', workspace, _p(text), C.c_int64(text.numel()), C.c_int64(chunk_bytes), _p(workspace), C.c_int64(workspace.numel()),
+          C.c_int64(n_lines), C.c_int64(n_entries), _p(us), C.c_int64(us.shape[0]), _p(ub), C.c_int64(ul), _p(vs), C.c_int64(vs.shape[0]), _p(vb),
+          C.c_int64(vl), _p(line_start), _p(line_user), _p(line_ptr), _p(item), _p(like), _p(status))
+    return line_user, line_ptr, item, like
 
 
 # ---- per-epoch exchange of replicated tables (csrc/sync.hip) ----------------------------------------
