@@ -411,6 +411,35 @@ int tkr_like_ranks(const float* U, const int32_t* user_idx, int32_t n_rows, cons
                    int32_t n_cols, int32_t k, const uint32_t* mask, int32_t mask_pitch, const int64_t* like_ptr,
                    const int32_t* like_cols, int32_t* rank_out, void* workspace, int64_t workspace_bytes, void* stream);
 
+/* ---- K12: score and rank per-user candidate lists (re-ranking a shortlist; evaluation against sampled negatives) -----------
+ * The opposite shape of K4 / K8: many rows, a short list of candidate columns each -- a gather of nnz item rows, no matrix product.
+ * U, user_idx, n_rows, Vt, bias, n_cols, k, mask, mask_pitch: exactly those of tkr_score_topk (user_idx, bias, mask nullable; a mask
+ * needs mask_pitch >= n_rows).  cand_ptr [n_rows+1] int64 (starts at 0, never decreases), cand_cols [cand_ptr[n_rows]] int32: the
+ * candidate columns of every row as CSR, STRICTLY ASCENDING inside a row and in [0, n_cols) (no duplicates; the caller's contract --
+ * top-k-rec_amd/tkr_hip.py rank_candidates checks the pointer, evaluate._group builds such rows).  For entry e of row r, c = cand_cols[e]:
+ *   score_out[e] = s(r, c), masked entries included: the mode-1 score of K4 (the fma chain with the two k-halves interleaved, fl(acc +
+ *                  bias), -0.0 -> +0.0; csrc/topk_parts.h exact_score, restated by oracle/ref_np.py mfma_chain_scores), at every k
+ *   rank_out[e]  = -1 when c is masked for the row, otherwise
+ *                  #{e' in row r, unmasked, e' != e : s(r, c_e') > s(r, c_e) or (s equal and c_e' > c_e)}
+ * -- K4's canonical order restricted to the list.  Integer and bit-exact; no atomics; two runs give the same bits, and a block of rows
+ * ranked alone gives what it gives inside a larger call.  When a row lists every column 0 .. n_cols-1, the entry with rank p < K is
+ * position p of tkr_score_topk's list with the same score bits (k <= 256 and k > 768; the slab kernels in between chain slab by slab),
+ * and the rank of every liked column is tkr_like_ranks's rank (every k).  A column outside [0, n_cols) is never dereferenced: score
+ * -inf, rank -1.  A score that is NaN has no defined rank.
+ * Shapes: any k, empty rows, any n_rows, a row of any length up to n_cols.  A row of at most TKR_CANDIDATES_RESIDENT entries belongs to
+ * one wave from first score to last rank (a lane per candidate on the chain; the item rows of 64 candidates at a time come through LDS
+ * in slabs of k when k % 8 == 0, otherwise every lane gathers its own; the list's 32-bit ordered keys stay in LDS and lane e counts
+ * the keys ahead of its own) -- lists of tens to a few thousand are the design point.  A longer row is still right
+ * but slow: a whole workgroup scores it, then counts it in tiles of TKR_CANDIDATES_RESIDENT keys rebuilt from score_out, quadratic in
+ * its length (40,000 entries: tens of milliseconds).  A caller that ranks most of the catalogue for a row wants tkr_score_topk /
+ * tkr_like_ranks instead.
+ * Arguments are checked before any device access and before any launch (TKR_E_INVAL): null U / Vt / cand_ptr / cand_cols / outputs,
+ * n_rows <= 0, n_cols <= 0, k <= 0, a mask with mask_pitch < n_rows. */
+#define TKR_CANDIDATES_RESIDENT 2048
+int tkr_rank_candidates(const float* U, const int32_t* user_idx, int32_t n_rows, const float* Vt, const float* bias,
+                        int32_t n_cols, int32_t k, const int64_t* cand_ptr, const int32_t* cand_cols, const uint32_t* mask,
+                        int32_t mask_pitch, float* score_out, int32_t* rank_out, void* stream);
+
 /* ---- K9: fold-in -- user vectors for histories the model was not trained on (new design: the reference can only retrain) ----
  * For each of m users, `steps` times: the step of K2 (single/bpr.py:81-100) on a batch of `triplets` triplets that all carry this user,
  * with the item side FROZEN --  x_p = b_i - b_j + <u, v_i - v_j>,  g = sum_p [-sigma(-x_p) (v_i - v_j) + lu u]  (mode 1: lu sign(u)),

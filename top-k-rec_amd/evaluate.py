@@ -30,6 +30,11 @@ Stated differences from the reference:
   * ``-M/--metrics acc auc mrr ndcg map`` (not in the reference) prints, after the reference lines, one line
     ``S.metric,%.6f[,...]`` per scenario and metric from ONE full-rank pass: the filtered rank of every liked column (K8,
     tkr_hip.like_ranks) and rankmetrics.py.  Without the flag stdout is the reference's, byte for byte.
+  * ``-M ... --negatives N [--neg-seed S]`` (not in the reference) adds, after those, ``S.negN.hr,...``, ``S.negN.ndcg,...`` and
+    ``S.negN.mrr,...`` for the metrics of ``hr ndcg mrr`` that ``-M`` names: the sampled-negatives protocol of the BPR / NCF
+    literature.  Every liked test column the user did not rate in training is ranked among N columns drawn without replacement from
+    those the user neither rated in training nor has on that test line (rankmetrics.sample_negatives, seeded by S; all of them when
+    fewer than N are eligible), by K12 (tkr_hip.rank_candidates).  ``hr`` exists only with ``--negatives``.
 """
 from __future__ import annotations
 
@@ -69,9 +74,10 @@ class Scenario:
     ``like_ptr``/``like_cols``: its liked test columns, ascending (evaluate.py:84-95); ``rated_ptr``/``rated_cols``:
     the test columns on the user's train line, like 0 or 1 (evaluate.py:30-45,98); ``tcount`` = sum of |likes|."""
 
-    def __init__(self, teids, users, like_ptr, like_cols, rated_ptr, rated_cols):
+    def __init__(self, teids, users, like_ptr, like_cols, rated_ptr, rated_cols, seen_ptr=None, seen_cols=None):
         self.teids, self.users = teids, users
         self.like_ptr, self.like_cols, self.rated_ptr, self.rated_cols = like_ptr, like_cols, rated_ptr, rated_cols
+        self.seen_ptr, self.seen_cols = seen_ptr, seen_cols          # every known column on the test line, whatever its like value
         self.tcount = int(like_ptr[-1])
 
 
@@ -116,7 +122,19 @@ def load_scenario(data_dir, fold, scenario, uids, umap=None):
     item = H.item[pos]
     keep = item >= 0                                                                         # only test columns matter
     rated_ptr, rated_cols = _group(row[keep], item[keep], len(lines), n_te)
-    return Scenario(teids, users, like_ptr, lcols, rated_ptr, rated_cols)
+    known = T.item >= 0
+    sptr_all, scols_all = _group(T.entry_line[known], T.item[known], len(T.line_user), n_te)
+    seen_ptr, seen_cols = _take_rows(sptr_all, scols_all, lines)
+    return Scenario(teids, users, like_ptr, lcols, rated_ptr, rated_cols, seen_ptr, seen_cols)
+
+
+def _take_rows(ptr, cols, rows):
+    """the rows `rows` of a CSR, in that order -> (ptr, cols)"""
+    seg = ptr[rows + 1] - ptr[rows]
+    out = np.zeros(len(rows) + 1, dtype=np.int64)
+    np.cumsum(seg, out=out[1:])
+    pos = np.arange(int(out[-1]), dtype=np.int64) - np.repeat(out[:-1], seg) + np.repeat(ptr[rows], seg)
+    return out, cols[pos]
 
 
 def _scenario_operands(vmat, bmat, vids, sc, device):
@@ -146,8 +164,10 @@ def shard_scenario(sc, rank, world):
     n = len(sc.users)
     lo, hi = rank * n // world, (rank + 1) * n // world
     lp, rp = sc.like_ptr, sc.rated_ptr
+    sp = sc.seen_ptr
+    seen = (None, None) if sp is None else (sp[lo:hi + 1] - sp[lo], sc.seen_cols[sp[lo]:sp[hi]])
     return Scenario(sc.teids, sc.users[lo:hi], lp[lo:hi + 1] - lp[lo], sc.like_cols[lp[lo]:lp[hi]],
-                    rp[lo:hi + 1] - rp[lo], sc.rated_cols[rp[lo]:rp[hi]])
+                    rp[lo:hi + 1] - rp[lo], sc.rated_cols[rp[lo]:rp[hi]], *seen)
 
 
 def _world():
@@ -209,6 +229,53 @@ def rank_metrics_loaded(umat_dev, vmat, bmat, vids, full, step, total, metrics, 
     return rankmetrics.finish(sums, metrics)
 
 
+def negative_rows(sc, n_neg, seed):
+    """the candidate rows of the sampled-negatives protocol for a parsed Scenario: one row per liked column that is not train-rated
+    -> (line of every row, cand_ptr, cand_cols, like_at) (rankmetrics.sample_negatives)"""
+    n, n_te = len(sc.users), max(len(sc.teids), 1)
+    line = np.repeat(np.arange(n, dtype=np.int64), np.diff(sc.like_ptr))
+    rated_line = np.repeat(np.arange(n, dtype=np.int64), np.diff(sc.rated_ptr))
+    rated = np.isin(line * n_te + sc.like_cols, rated_line * n_te + sc.rated_cols)
+    lptr, lcols = _group(line[~rated], sc.like_cols[~rated], n, n_te)
+    seen_line = np.repeat(np.arange(n, dtype=np.int64), np.diff(sc.seen_ptr))
+    xptr, xcols = _group(np.concatenate([rated_line, seen_line]), np.concatenate([sc.rated_cols, sc.seen_cols]).astype(np.int64), n, n_te)
+    cand_ptr, cand_cols, like_at = rankmetrics.sample_negatives(lptr, lcols, xptr, xcols, len(sc.teids), n_neg, seed)
+    return np.repeat(np.arange(n, dtype=np.int64), np.diff(lptr)), cand_ptr, cand_cols, like_at
+
+
+def negative_metrics_loaded(umat_dev, vmat, bmat, vids, full, step, total, n_neg, seed, metrics, device):
+    """{metric: list of values} of hr / ndcg / mrr against sampled negatives.  The rows are drawn for the whole scenario on every rank
+    (a host function of the seed: the same rows whatever the number of ranks); a rank scores the rows of its block of test lines --
+    the block shard_scenario gives it -- with K12, and the sums are all-reduced like those of rank_metrics_loaded."""
+    rank, world = _world()
+    line, cand_ptr, cand_cols, like_at = negative_rows(full, n_neg, seed)
+    n = len(full.users)
+    lo, hi = (rank * n // world, (rank + 1) * n // world) if world > 1 else (0, n)
+    q0, q1 = int(np.searchsorted(line, lo)), int(np.searchsorted(line, hi))
+    like_ranks = np.zeros(0, dtype=np.int32)
+    if q1 > q0:
+        te_rows = np.zeros(len(full.teids), dtype=np.int64)
+        for vid, col in full.teids.items():
+            te_rows[col] = vids[vid]
+        Vt = torch.from_numpy(np.ascontiguousarray(vmat[te_rows])).to(device)
+        bias = None if bmat is None else torch.from_numpy(np.ascontiguousarray(bmat.reshape(-1)[te_rows])).to(device)
+        user_idx = torch.from_numpy(full.users[line[q0:q1]].astype(np.int32)).to(device)
+        ptr = cand_ptr[q0:q1 + 1] - cand_ptr[q0]
+        cols = cand_cols[cand_ptr[q0]:cand_ptr[q1]]
+        _, ranks = tkr_hip.rank_candidates(umat_dev, Vt, torch.from_numpy(ptr).to(device), torch.from_numpy(cols).to(device), bias=bias,
+                                           user_idx=user_idx)
+        like_ranks = ranks.cpu().numpy()[like_at[q0:q1] - cand_ptr[q0]]
+    sums = rankmetrics.negative_sums(like_ranks, step, total)
+    if world > 1:
+        import torch.distributed as dist
+        on_dev = dist.get_backend() == 'nccl'
+        acc = torch.from_numpy(rankmetrics.neg_to_vector(sums))
+        acc = acc.to(device) if on_dev else acc
+        dist.all_reduce(acc, op=dist.ReduceOp.SUM)
+        sums = rankmetrics.neg_from_vector(acc.cpu().numpy(), total // step)
+    return rankmetrics.finish(sums, metrics)
+
+
 def main(argv=None):
     parser = argparse.ArgumentParser(description="Evaluate weighted matrix factorization based methods.")
     parser.add_argument('-d', '--data', required=True, help="The data path for the evaluation")
@@ -217,9 +284,20 @@ def main(argv=None):
     parser.add_argument('-s', '--step', type=int, default=5, help="The number of evaluation step")
     parser.add_argument('-t', '--total', type=int, default=30, help="The number of total predictions")
     parser.add_argument('-sl', '--scenarios', nargs='+', default=None, help="The test scenario list")
-    parser.add_argument('-M', '--metrics', nargs='+', default=None, choices=rankmetrics.METRICS,
-                        help="Rank metrics from one full-rank pass, printed after the accuracy lines as S.metric,...")
+    parser.add_argument('-M', '--metrics', nargs='+', default=None, choices=rankmetrics.METRICS + ('hr',),
+                        help="Rank metrics from one full-rank pass, printed after the accuracy lines as S.metric,... (hr: only with --negatives)")
+    parser.add_argument('--negatives', type=int, default=None, metavar='N',
+                        help="With -M: also rank every held-out like among N sampled unrated columns; prints S.negN.hr / .ndcg / .mrr")
+    parser.add_argument('--neg-seed', type=int, default=0, help="The seed of the negatives' draw")
     args = parser.parse_args(argv)
+    if args.negatives is not None and not args.metrics:
+        parser.error('--negatives needs -M (hr, ndcg and / or mrr)')
+    if args.negatives is not None and args.negatives < 1:
+        parser.error('--negatives must be at least 1')
+    if args.metrics and 'hr' in args.metrics and args.negatives is None:
+        parser.error('-M hr is defined against sampled negatives only: add --negatives N')
+    full_metrics = [m for m in args.metrics or () if m in rankmetrics.METRICS]
+    neg_metrics = [m for m in args.metrics or () if m in rankmetrics.NEG_METRICS] if args.negatives is not None else []
 
     if not torch.cuda.is_available():
         raise tkr_hip.TkrError('evaluate.py scores on the GPU through libtkr_hip.so; no MI355X is visible')
@@ -235,13 +313,16 @@ def main(argv=None):
         bmat = read_matrix(os.path.join(args.model, 'final-B.dat'), vids)
     umat_dev = torch.from_numpy(umat).to(device)
     umap = textio.IdMap(uids)
-    results, extra = {}, {}
+    results, extra, negs = {}, {}, {}
     for scenario in args.scenarios:
         if args.metrics:
             full = load_scenario(args.data, args.fold, scenario, uids, umap)
             acc = evaluate_loaded(umat_dev, vmat, bmat, vids, full, args.step, args.total, device)
             if scenario not in extra:                                # (a scenario listed twice: its metric lines are not doubled)
-                extra[scenario] = rank_metrics_loaded(umat_dev, vmat, bmat, vids, full, args.step, args.total, args.metrics, device)
+                extra[scenario] = rank_metrics_loaded(umat_dev, vmat, bmat, vids, full, args.step, args.total, full_metrics, device)
+                if neg_metrics:
+                    negs[scenario] = negative_metrics_loaded(umat_dev, vmat, bmat, vids, full, args.step, args.total, args.negatives,
+                                                             args.neg_seed, neg_metrics, device)
         else:
             acc = evaluate_scenario(umat_dev, vmat, bmat, uids, vids, args.data, args.fold, scenario, args.step, args.total, device, umap)
         if scenario not in results:                                  # evaluate.py:109-112 ACCUMULATES per scenario name: a scenario
@@ -254,8 +335,13 @@ def main(argv=None):
         if rank == 0:                                                # one report, like the single process
             print(lines[-1])
     for scenario in args.scenarios if args.metrics else ():
-        for m in args.metrics:
+        for m in full_metrics:
             lines.append('%s.%s' % (scenario, m) + ''.join(',%.6f' % v for v in extra[scenario][m]))
+            if rank == 0:
+                print(lines[-1])
+    for scenario in args.scenarios if neg_metrics else ():
+        for m in neg_metrics:
+            lines.append('%s.neg%d.%s' % (scenario, args.negatives, m) + ''.join(',%.6f' % v for v in negs[scenario][m]))
             if rank == 0:
                 print(lines[-1])
     if started_group:

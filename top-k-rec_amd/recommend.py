@@ -1,6 +1,6 @@
 """recommend.py -- write every user's top-k items and their scores, scored on MI355X; new users are folded in first.
 
-    python recommend.py -d DATA -m MODEL -f 0 -t 30 -o out.txt [-u USERS_FILE]
+    python recommend.py -d DATA -m MODEL -f 0 -t 30 -o out.txt [-u USERS_FILE | --candidates FILE]
                         [--new-uid FILE --new-history FILE --fold-steps 50 --fold-triplets 16 --fold-lr 0.05 --fold-lu 2.5e-3 --seed 0]
                         [--new-vid FILE --new-ratings FILE --fold-li 2.5e-3 --fold-lj 2.5e-4 --fold-lb 0]
 
@@ -23,6 +23,13 @@ model has ``final-B.dat``) are folded in from the like == 1 entries of the model
 foldin.fold_in_items: the users' training positives are the like == 1 entries of ``f{fold}tr.txt``), appended to the catalogue in
 file order and ranked with it under their own tokens; what a user rated in that file is excluded for that user like the history
 line.  Together with ``--new-uid`` the items go first and the users are folded in against the grown catalogue.
+
+``--candidates FILE`` (not with ``-u``): re-rank shortlists instead of the catalogue.  FILE is in the ratings layout,
+``uid,iid:like,...``; every known item on a line is a candidate of that line's user whatever its like value, unknown items are dropped
+as in the history, an item listed twice counts once.  Every line gives one output line in the format above -- the ``-t`` best of ITS
+candidates, the history excluded as always; a user may appear on several lines.  The lines of the model's users come first, in file
+order, then those of the ``--new-uid`` users; a uid that is in neither id list raises KeyError.  After ``--new-vid`` the candidates are
+looked up in the grown catalogue.  Scores and order are those the full ranking gives the same items (K12, tkr_hip.rank_candidates).
 
 The scores, the filter and the selection run on the GPU (tkr_hip.build_rated_mask, tkr_hip.score_topk); single process.
 """
@@ -77,9 +84,22 @@ def rated_csr(R, rows_of_user, n_rows, n_items):
     return _group(np.concatenate(rr), np.concatenate(cc), n_rows, n_items)
 
 
-def rank(U_dev, user_rows, V_dev, bias_dev, R, total, also_rated=None):
+def candidate_lines(path, umap, vmap, n_items):
+    """the lines of the candidates file whose uid `umap` knows -> (known: bool per line of the file, the user index of each known line,
+    and the CSR of their known items: ascending, unique)"""
+    Cf = textio.parse_ratings(path, umap, vmap)
+    lines = np.flatnonzero(Cf.line_user >= 0)
+    row_of_line = np.full(len(Cf.line_user), -1, dtype=np.int64)
+    row_of_line[lines] = np.arange(len(lines))
+    keep = (Cf.item >= 0) & (row_of_line[Cf.entry_line] >= 0)
+    ptr, cols = _group(row_of_line[Cf.entry_line[keep]], Cf.item[keep].astype(np.int64), len(lines), max(n_items, 1))
+    return Cf.line_user >= 0, Cf.line_user[lines].astype(np.int64), ptr, cols
+
+
+def rank(U_dev, user_rows, V_dev, bias_dev, R, total, also_rated=None, candidates=None):
     """top-`total` unrated items of the users `user_rows` (indices into U_dev and into R's user numbering); `also_rated`: a second
-    parsed ratings file in the same numbering whose lines exclude items too
+    parsed ratings file in the same numbering whose lines exclude items too; `candidates`: (ptr, cols), a CSR over the ranked rows --
+    then only these items of a row are ranked (K12) instead of the catalogue (K4)
     -> (ids int32 [n, total], scores fp32 [n, total]) as numpy"""
     n, n_items = len(user_rows), int(V_dev.shape[0])
     rows_of_user = {}
@@ -93,7 +113,12 @@ def rank(U_dev, user_rows, V_dev, bias_dev, R, total, also_rated=None):
     dev = V_dev.device
     mask, pitch = tkr_hip.build_rated_mask(torch.from_numpy(ptr).to(dev), torch.from_numpy(cols).to(dev), n, n_items)
     idx = torch.from_numpy(np.asarray(user_rows, dtype=np.int32)).to(dev)
-    ids, scores = tkr_hip.score_topk(U_dev, V_dev, total, bias=bias_dev, user_idx=idx, mask=mask, mask_pitch=pitch, want_scores=True)
+    if candidates is not None:
+        cptr, ccols = torch.from_numpy(candidates[0]).to(dev), torch.from_numpy(candidates[1]).to(dev)
+        s, r = tkr_hip.rank_candidates(U_dev, V_dev, cptr, ccols, bias=bias_dev, user_idx=idx, mask=mask, mask_pitch=pitch)
+        ids, scores = tkr_hip.topk_from_ranks(cptr, ccols, s, r, total)
+    else:
+        ids, scores = tkr_hip.score_topk(U_dev, V_dev, total, bias=bias_dev, user_idx=idx, mask=mask, mask_pitch=pitch, want_scores=True)
     return ids.cpu().numpy(), scores.cpu().numpy()
 
 
@@ -125,6 +150,7 @@ def main(argv=None):
     parser.add_argument('-t', '--total', type=int, default=30, help="The number of items per user")
     parser.add_argument('-o', '--output', required=True, help="The file the lines are written to")
     parser.add_argument('-u', '--users', default=None, help="A file of uid tokens, one per line (default: every user of uid)")
+    parser.add_argument('--candidates', default=None, help="A ratings-layout file of shortlists: every line is re-ranked on its own (not with -u)")
     parser.add_argument('--new-uid', default=None, help="An id file of users that are not in the model: folded in, then ranked")
     parser.add_argument('--new-history', default=None, help="The ratings file of the new users")
     parser.add_argument('--fold-steps', type=int, default=50)
@@ -144,6 +170,8 @@ def main(argv=None):
         parser.error('--new-vid and --new-ratings go together')
     if args.total < 1:
         parser.error('-t must be at least 1')
+    if args.candidates is not None and args.users is not None:
+        parser.error('--candidates names its users line by line: it does not go with -u')
 
     uids = read_ids(os.path.join(args.data, 'uid'))
     vids = read_ids(os.path.join(args.data, 'vid'))
@@ -176,10 +204,23 @@ def main(argv=None):
     bias_dev = None if bmat is None else torch.from_numpy(np.ascontiguousarray(bmat)).to(device)
     vmap = textio.IdMap(vids)
     lines = []
+    cand_model = cand_new = None
+    if args.candidates is not None:
+        cand_model = candidate_lines(args.candidates, textio.IdMap(uids), vmap, len(vmat))
+        cand_new = candidate_lines(args.candidates, textio.IdMap(new_uids), vmap, len(vmat)) if new_uids else None
+        stray = np.flatnonzero(~(cand_model[0] | cand_new[0]) if cand_new else ~cand_model[0])
+        if len(stray):
+            with open(args.candidates) as fh:
+                tokens = [ln.split(',')[0].strip() for ln in fh]
+            who = repr(tokens[stray[0]]) if len(tokens) == len(cand_model[0]) else 'on line %d' % (stray[0] + 1)
+            raise KeyError('%s: user %s is neither in the uid list nor a new user' % (args.candidates, who))
+        tok = {idx: t for t, idx in uids.items()}
+        users = [tok[int(x)] for x in cand_model[1]]
     if users:
         umat = read_matrix(os.path.join(args.model, 'final-U.dat'), uids)
         R = textio.parse_ratings(os.path.join(args.data, 'f%dtr.txt' % args.fold), textio.IdMap(uids), vmap)
-        ids, scores = rank(torch.from_numpy(umat).to(device), [uids[u] for u in users], V_dev, bias_dev, R, args.total, also_rated=R_new_items)
+        ids, scores = rank(torch.from_numpy(umat).to(device), [uids[u] for u in users], V_dev, bias_dev, R, args.total, also_rated=R_new_items,
+                           candidates=cand_model[2:] if cand_model else None)
         lines += format_lines(users, ids, scores, items)
     if new_uids:
         m = max(new_uids.values()) + 1
@@ -187,8 +228,14 @@ def main(argv=None):
         hist = foldin.liked_csr(R, m, len(vmat))
         U_new = foldin.fold_in(vmat, bmat, hist, lu=args.fold_lu, lr=args.fold_lr, steps=args.fold_steps, triplets=args.fold_triplets,
                                seed=args.seed, device=device)
-        ids, scores = rank(torch.from_numpy(U_new).to(device), [new_uids[u] for u in new_uids], V_dev, bias_dev, R, args.total)
-        lines += format_lines(list(new_uids), ids, scores, items)
+        new_users = list(new_uids)
+        if cand_new is not None:
+            tok = {idx: t for t, idx in new_uids.items()}
+            new_users = [tok[int(x)] for x in cand_new[1]]
+        if new_users:
+            ids, scores = rank(torch.from_numpy(U_new).to(device), [new_uids[u] for u in new_users], V_dev, bias_dev, R, args.total,
+                               candidates=cand_new[2:] if cand_new else None)
+            lines += format_lines(new_users, ids, scores, items)
     with open(args.output, 'w') as fh:
         for ln in lines:
             fh.write(ln + '\n')

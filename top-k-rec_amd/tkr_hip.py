@@ -85,7 +85,7 @@ EXPORTS = ('tkr_version', 'tkr_plan_team', 'tkr_plan_max_blocks', 'tkr_sample_pl
            'tkr_matrix_write', 'tkr_raw_ranks', 'tkr_count_hits_rr', 'tkr_topk_set_math', 'tkr_vbpr_set_pairs', 'tkr_lab_build',
            'tkr_sync_snapshot', 'tkr_sync_pack', 'tkr_sync_unpack', 'tkr_sync_flow_snapshot', 'tkr_sync_flow_pack',
            'tkr_sync_flow_unpack', 'tkr_like_ranks', 'tkr_bpr_foldin', 'tkr_bpr_foldin_items', 'tkr_idtable_build', 'tkr_ratings_count_dev',
-           'tkr_ratings_emit_dev')
+           'tkr_ratings_emit_dev', 'tkr_rank_candidates')
 EXPORTS_I64 = ('tkr_vbpr_workspace_floats', 'tkr_vbpr_colplan_lds_bytes', 'tkr_topk_workspace_bytes_for', 'tkr_topk_workspace_bytes', 'tkr_plan_workspace_bytes', 'tkr_like_ranks_workspace_bytes',
                'tkr_parse_dev_workspace_bytes', 'tkr_idtable_slots')
 
@@ -554,6 +554,72 @@ def like_ranks(U, Vt, like_ptr, like_cols, bias=None, user_idx=None, mask=None, 
     _call('tkr_like_ranks', U, _p(U), _p(user_idx), C.c_int32(n_rows), _p(Vt), _p(bias), C.c_int32(n_cols), C.c_int32(k), _p(mask),
           C.c_int32(mask_pitch), _p(like_ptr), _p(like_cols), _p(out), _p(ws), C.c_int64(need))
     return out
+
+
+# ---- K12: per-user candidate lists (csrc/candidates.hip) ----------------------------------------------------------------------------
+CANDIDATES_RESIDENT = 2048   # TKR_CANDIDATES_RESIDENT of include/tkr.h: a longer row is ranked by the slow whole-workgroup form
+
+
+def _cand_args(U, Vt, cand_ptr, cand_cols, bias, user_idx, mask, mask_pitch):
+    """refuse what tkr_rank_candidates cannot take, the tensors' properties first (no device access), then the row pointer
+    -> (n_rows, n_cols, k, nnz)"""
+    named = dict(U=(U, torch.float32), Vt=(Vt, torch.float32), cand_ptr=(cand_ptr, torch.int64), cand_cols=(cand_cols, torch.int32),
+                 bias=(bias, torch.float32), user_idx=(user_idx, torch.int32), mask=(mask, torch.int32))
+    for name, (t, dtype) in named.items():
+        if t is None and name in ('bias', 'user_idx', 'mask'):
+            continue
+        if not isinstance(t, torch.Tensor):
+            raise TypeError('rank_candidates: %s must be a tensor' % name)
+        if t.dtype != dtype:
+            raise TypeError('rank_candidates: %s must be %s, not %s' % (name, dtype, t.dtype))
+        if not t.is_contiguous():
+            raise ValueError('rank_candidates: %s must be contiguous' % name)
+    for name, (t, _) in named.items():
+        if t is not None and (not t.is_cuda or t.device != U.device):
+            raise ValueError('rank_candidates: %s must live on the GPU that holds U, not on %s' % (name, t.device))
+    if U.dim() != 2 or Vt.dim() != 2 or U.shape[1] != Vt.shape[1] or U.shape[1] < 1 or Vt.shape[0] < 1:
+        raise ValueError('rank_candidates: U [*, k] and Vt [n_cols, k] must share k >= 1')
+    n_rows = int(user_idx.numel()) if user_idx is not None else int(U.shape[0])
+    n_cols, k, nnz = int(Vt.shape[0]), int(U.shape[1]), int(cand_cols.numel())
+    if cand_ptr.dim() != 1 or cand_cols.dim() != 1 or cand_ptr.numel() != n_rows + 1:
+        raise ValueError('rank_candidates: cand_ptr must hold n_rows + 1 = %d entries' % (n_rows + 1))
+    if bias is not None and bias.numel() != n_cols:
+        raise ValueError('rank_candidates: bias must hold one value per column')
+    if mask is not None and (mask_pitch < n_rows or mask.numel() < ((n_cols + 31) // 32) * mask_pitch):
+        raise ValueError('rank_candidates: the mask is not the bitmap of build_rated_mask for %d rows and %d columns' % (n_rows, n_cols))
+    if n_rows and not (int(cand_ptr[0]) == 0 and int(cand_ptr[-1]) == nnz and bool((cand_ptr[1:] >= cand_ptr[:-1]).all())):
+        raise ValueError('rank_candidates: cand_ptr must run from 0 to len(cand_cols) = %d and never decrease' % nnz)
+    return n_rows, n_cols, k, nnz
+
+
+def rank_candidates(U, Vt, cand_ptr, cand_cols, bias=None, user_idx=None, mask=None, mask_pitch=0):
+    """K12 -> (scores fp32 [nnz], ranks int32 [nnz]) on the device: for every entry of the candidate CSR (int64 ptr from 0, int32 columns
+    strictly ascending inside a row and in [0, n_cols) -- evaluate._group builds such rows) the score of K4's fp32 arithmetic and the
+    number of unmasked candidates of the same row in front of it in K4's canonical order, -1 where the candidate itself is masked
+    (include/tkr.h).  Rows longer than CANDIDATES_RESIDENT are right but slow: rank most of a catalogue with score_topk / like_ranks."""
+    n_rows, n_cols, k, nnz = _cand_args(U, Vt, cand_ptr, cand_cols, bias, user_idx, mask, mask_pitch)
+    scores = torch.empty(nnz, dtype=torch.float32, device=U.device)
+    ranks = torch.empty(nnz, dtype=torch.int32, device=U.device)
+    if nnz == 0 or n_rows == 0:
+        return scores, ranks
+    _call('tkr_rank_candidates', U, _p(U), _p(user_idx), C.c_int32(n_rows), _p(Vt), _p(bias), C.c_int32(n_cols), C.c_int32(k),
+          _p(cand_ptr), _p(cand_cols), _p(mask), C.c_int32(mask_pitch), _p(scores), _p(ranks))
+    return scores, ranks
+
+
+def topk_from_ranks(cand_ptr, cand_cols, scores, ranks, K):
+    """the K best candidates of every row from rank_candidates' output -> (ids int32 [n_rows, K], -1 padded; scores fp32 [n_rows, K],
+    -inf padded), the padding of score_topk: the entry with rank p < K goes to position p (a torch scatter, no kernel)"""
+    n_rows = int(cand_ptr.numel()) - 1
+    dev = cand_cols.device
+    ids = torch.full((n_rows, K), -1, dtype=torch.int32, device=dev)
+    out = torch.full((n_rows, K), float('-inf'), dtype=torch.float32, device=dev)
+    keep = (ranks >= 0) & (ranks < K)
+    row = torch.repeat_interleave(torch.arange(n_rows, device=dev), cand_ptr[1:] - cand_ptr[:-1])[keep]
+    at = row * K + ranks[keep].long()
+    ids.view(-1)[at] = cand_cols[keep]
+    out.view(-1)[at] = scores[keep]
+    return ids, out
 
 
 # ---- K9, K10: fold-in of users (csrc/foldin.hip) and of items (csrc/foldin_items.hip), one kernel body (csrc/fold_rows.h) ---------
