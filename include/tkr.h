@@ -31,7 +31,7 @@
 extern "C" {
 #endif
 
-#define TKR_VERSION 120 /* 0.1.20: K9 tkr_bpr_foldin (user vectors for new histories against frozen item factors; csrc/foldin.hip). 0.1.19: K8 tkr_like_ranks + tkr_like_ranks_workspace_bytes (filtered rank of every liked test column; csrc/like_ranks.hip). 0.1.18: K4 second form of bound-and-refine (csrc/topk_refine.hip; tkr_topk_workspace_bytes_for grows by the pieces' packed lists), any k (bpr_wide_kernel, score_topk_wide_kernel), tkr_lab_build; tkr_topk_set_finish is gone, tkr_topk_set_math(0) and tkr_vbpr_set_pairs(1 | 2) need the lab library. 0.1.17: tkr_vbpr_set_pairs (tkr_vbpr_workspace_floats + 64). 0.1.16: tkr_topk_set_finish (larger tkr_topk_workspace_bytes), tkr_bpr_own_plan_run plans inside the step's launch. 0.1.15: tkr_bpr_own_owners_shared; tkr_bpr_run takes `rec` non-const. 0.1.14: per-task loss sums instead of atomics on loss_out (larger tkr_vbpr_workspace_floats; K2 writes word 15 of its records). 0.1.13: tkr_bpr_own_plan_run, K4 to k = 768. 0.1.12: tkr_bpr_own_run_between. 0.1.11: K2o (tkr_sample_plan_owned, tkr_bpr_own_run: item rows owned by one workgroup each, resident in its LDS); prec[5] = last batch of the call that updated the row. 0.1.10: tkr_topk_workspace_bytes_for (K4 stages pre-converted fp16 tiles). 0.1.9: tkr_vbpr_colplan + tkr_vbpr_run_cols (VBPR in three launches per batch). 0.1.8: tkr_sync_flow_* (exchange of the granule tables). 0.1.7: K4 bound-and-refine arithmetic (tkr_topk_set_math(2), the default; larger tkr_topk_workspace_bytes); K2f leaves its ticket words zero. 0.1.6: K2f persistent dataflow step, tkr_plan_rollback, batches above 8192 */
+#define TKR_VERSION 120 /* (additions that change no existing entry point keep the number: K10 tkr_bpr_foldin_items, K11 tkr_ratings_*_dev, K12 tkr_rank_candidates, K13 tkr_lists_format_* / tkr_matrix_format_*.) 0.1.20: K9 tkr_bpr_foldin (user vectors for new histories against frozen item factors; csrc/foldin.hip). 0.1.19: K8 tkr_like_ranks + tkr_like_ranks_workspace_bytes (filtered rank of every liked test column; csrc/like_ranks.hip). 0.1.18: K4 second form of bound-and-refine (csrc/topk_refine.hip; tkr_topk_workspace_bytes_for grows by the pieces' packed lists), any k (bpr_wide_kernel, score_topk_wide_kernel), tkr_lab_build; tkr_topk_set_finish is gone, tkr_topk_set_math(0) and tkr_vbpr_set_pairs(1 | 2) need the lab library. 0.1.17: tkr_vbpr_set_pairs (tkr_vbpr_workspace_floats + 64). 0.1.16: tkr_topk_set_finish (larger tkr_topk_workspace_bytes), tkr_bpr_own_plan_run plans inside the step's launch. 0.1.15: tkr_bpr_own_owners_shared; tkr_bpr_run takes `rec` non-const. 0.1.14: per-task loss sums instead of atomics on loss_out (larger tkr_vbpr_workspace_floats; K2 writes word 15 of its records). 0.1.13: tkr_bpr_own_plan_run, K4 to k = 768. 0.1.12: tkr_bpr_own_run_between. 0.1.11: K2o (tkr_sample_plan_owned, tkr_bpr_own_run: item rows owned by one workgroup each, resident in its LDS); prec[5] = last batch of the call that updated the row. 0.1.10: tkr_topk_workspace_bytes_for (K4 stages pre-converted fp16 tiles). 0.1.9: tkr_vbpr_colplan + tkr_vbpr_run_cols (VBPR in three launches per batch). 0.1.8: tkr_sync_flow_* (exchange of the granule tables). 0.1.7: K4 bound-and-refine arithmetic (tkr_topk_set_math(2), the default; larger tkr_topk_workspace_bytes); K2f leaves its ticket words zero. 0.1.6: K2f persistent dataflow step, tkr_plan_rollback, batches above 8192 */
 #define TKR_OK 0
 #define TKR_E_INVAL (-1)
 #define TKR_E_UNSUPPORTED (-2)
@@ -586,6 +586,42 @@ int tkr_ratings_emit_dev(const void* text, int64_t n_bytes, int64_t chunk_bytes,
                          const void* user_blob, int64_t user_blob_len, const int32_t* item_slots, int64_t item_n_slots,
                          const void* item_blob, int64_t item_blob_len, int64_t* line_start, int32_t* line_user,
                          int64_t* line_ptr, int32_t* item, int32_t* like, int64_t* status, void* stream);
+
+/* ---- K13: the text writers on the device (csrc/format_dev.hip) --------------------------------------------------------------
+ * Replace the per-field Python formatting of recommend.py:50-56 (format_lines: one '%s:%f' expression and one dict lookup per list
+ * entry) with the write loop of recommend.py:239-241, and the one-thread sprintf("%f ") loop of tkr_matrix_write
+ * (csrc/textio.hip:263-283; utils.py:47-55 in the reference).  The bytes are those of glibc printf / Python's '%f' % float(x) for
+ * every fp32 bit pattern: round half to even on the exact binary value, a set sign bit always prints '-', +-inf as inf / -inf,
+ * every NaN as nan; computed with integers only, |x| >= 2^64 included (no host fall-back).  A value takes at most 47 bytes.
+ *
+ * lists: row r of ids int32[n][K] / scores fp32[n][K] becomes "uid,iid:%f,iid:%f,...\n", uid = token row_user[r] of the user table,
+ *   iid = token ids[r][j] of the item table; a negative id is skipped wherever it stands; a row without a valid entry is the uid alone.
+ *   A token table is addressed by index: token i = blob[start[i], start[i] + len[i]), len[i] = -1: no token has index i; blob_len
+ *   <= 2^29.  A row_user or a non-negative id outside its table, one that names an empty slot, or a token outside its blob sets
+ *   the status word to the row number (atomic min: the first such row); the text is then not to be used.
+ * matrix: row r of data fp32[rows][cols] becomes "%f " per element and '\n' (cols = 0: the '\n' alone), as tkr_matrix_write.
+ *
+ * Two calls with one read-back between them, because the text is sized by what the first one counts:
+ *   *_sizes_dev   line_ptr (device int64[n + 1]) = the offset of every row in the text, line_ptr[n] = its size; totals (device
+ *                 int64[2]) = {size of the text, status: -1 or the first offending row}.  No workspace: the row lengths are summed
+ *                 in place in line_ptr by one workgroup (no library scan).
+ *   *_emit_dev    with the SAME inputs and line_ptr: rows [first_row, first_row + n_rows) of the text into out[0, out_bytes)
+ *                 (16-byte aligned), the byte at offset q of the whole text at out[q - line_ptr[first_row]].  status (device int64):
+ *                 -1, or a row whose line_ptr entries do not lie in the block or do not match its text.  Nothing is stored outside
+ *                 [line_ptr[r] - line_ptr[first_row], line_ptr[r + 1] - line_ptr[first_row]) of a row, whatever the arrays hold.
+ * All offsets are 64-bit.  Arguments are checked before any device access (TKR_E_INVAL).  Deterministic. */
+int tkr_lists_format_sizes_dev(const int32_t* ids, const float* scores, const int32_t* row_user, int64_t n, int32_t K,
+                               const void* user_blob, int64_t user_blob_len, const int64_t* user_start, const int32_t* user_len,
+                               int64_t n_users, const void* item_blob, int64_t item_blob_len, const int64_t* item_start,
+                               const int32_t* item_len, int64_t n_items, int64_t* line_ptr, int64_t* totals, void* stream);
+int tkr_lists_format_emit_dev(const int32_t* ids, const float* scores, const int32_t* row_user, int64_t n, int32_t K,
+                              const void* user_blob, int64_t user_blob_len, const int64_t* user_start, const int32_t* user_len,
+                              int64_t n_users, const void* item_blob, int64_t item_blob_len, const int64_t* item_start,
+                              const int32_t* item_len, int64_t n_items, const int64_t* line_ptr, int64_t first_row, int64_t n_rows,
+                              void* out, int64_t out_bytes, int64_t* status, void* stream);
+int tkr_matrix_format_sizes_dev(const float* data, int64_t rows, int64_t cols, int64_t* line_ptr, int64_t* totals, void* stream);
+int tkr_matrix_format_emit_dev(const float* data, int64_t rows, int64_t cols, const int64_t* line_ptr, int64_t first_row,
+                               int64_t n_rows, void* out, int64_t out_bytes, int64_t* status, void* stream);
 
 #ifdef __cplusplus
 }

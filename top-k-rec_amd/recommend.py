@@ -45,15 +45,15 @@ import foldin
 import textio
 import tkr_hip
 from evaluate import _group, read_ids, read_matrix
+from textio import format_lines      # noqa: F401  (the host formatter of the output lines; textio.write_lists writes them)
 
 
-def format_lines(users, ids, scores, items):
-    """users: n tokens; ids int [n, K] catalogue indices, -1 = no item; scores float [n, K]; items: index -> token
-    -> n lines 'uid,iid:%f,iid:%f,...'"""
-    out = []
-    for u, row_i, row_s in zip(users, np.asarray(ids), np.asarray(scores)):
-        out.append(','.join([u] + ['%s:%f' % (items[int(c)], float(s)) for c, s in zip(row_i, row_s) if c >= 0]))
-    return out
+def row_tokens(users):
+    """the uid tokens of the ranked rows (a user may be asked for twice) -> (IdMap of the distinct tokens, its index per row): the
+    table textio.write_lists prints the rows' uids from"""
+    table = {}
+    rows = np.fromiter((table.setdefault(u, len(table)) for u in users), dtype=np.int32, count=len(users))
+    return textio.IdMap(table), rows
 
 
 def read_user_list(path, uids):
@@ -96,11 +96,11 @@ def candidate_lines(path, umap, vmap, n_items):
     return Cf.line_user >= 0, Cf.line_user[lines].astype(np.int64), ptr, cols
 
 
-def rank(U_dev, user_rows, V_dev, bias_dev, R, total, also_rated=None, candidates=None):
+def rank(U_dev, user_rows, V_dev, bias_dev, R, total, also_rated=None, candidates=None, on_device=False):
     """top-`total` unrated items of the users `user_rows` (indices into U_dev and into R's user numbering); `also_rated`: a second
     parsed ratings file in the same numbering whose lines exclude items too; `candidates`: (ptr, cols), a CSR over the ranked rows --
     then only these items of a row are ranked (K12) instead of the catalogue (K4)
-    -> (ids int32 [n, total], scores fp32 [n, total]) as numpy"""
+    -> (ids int32 [n, total], scores fp32 [n, total]) as numpy, with on_device=True as tensors left on the GPU"""
     n, n_items = len(user_rows), int(V_dev.shape[0])
     rows_of_user = {}
     for row, user in enumerate(user_rows):
@@ -119,6 +119,8 @@ def rank(U_dev, user_rows, V_dev, bias_dev, R, total, also_rated=None, candidate
         ids, scores = tkr_hip.topk_from_ranks(cptr, ccols, s, r, total)
     else:
         ids, scores = tkr_hip.score_topk(U_dev, V_dev, total, bias=bias_dev, user_idx=idx, mask=mask, mask_pitch=pitch, want_scores=True)
+    if on_device:
+        return ids, scores
     return ids.cpu().numpy(), scores.cpu().numpy()
 
 
@@ -163,6 +165,8 @@ def main(argv=None):
     parser.add_argument('--fold-lj', type=float, default=2.5e-4)
     parser.add_argument('--fold-lb', type=float, default=0.0)
     parser.add_argument('--seed', type=int, default=0)
+    parser.add_argument('--format', default=None, choices=textio.FORMAT_WHERE,
+                        help="Where the output lines are formatted (default: TKR_FORMAT, else auto: on the GPU from TKR_FORMAT_DEVICE_FROM list entries upward)")
     args = parser.parse_args(argv)
     if (args.new_uid is None) != (args.new_history is None):
         parser.error('--new-uid and --new-history go together')
@@ -199,11 +203,10 @@ def main(argv=None):
     R_new_items = None
     if new_vids:
         vmat, bmat, vids, R_new_items = fold_in_new_items(args, uids, vids, new_vids, vmat, bmat, device)
-    items = {idx: tok for tok, idx in vids.items()}
     V_dev = torch.from_numpy(vmat).to(device)
     bias_dev = None if bmat is None else torch.from_numpy(np.ascontiguousarray(bmat)).to(device)
     vmap = textio.IdMap(vids)
-    lines = []
+    wrote = False                                                   # one output file: the model users' lines, then the new users'
     cand_model = cand_new = None
     if args.candidates is not None:
         cand_model = candidate_lines(args.candidates, textio.IdMap(uids), vmap, len(vmat))
@@ -220,8 +223,10 @@ def main(argv=None):
         umat = read_matrix(os.path.join(args.model, 'final-U.dat'), uids)
         R = textio.parse_ratings(os.path.join(args.data, 'f%dtr.txt' % args.fold), textio.IdMap(uids), vmap)
         ids, scores = rank(torch.from_numpy(umat).to(device), [uids[u] for u in users], V_dev, bias_dev, R, args.total, also_rated=R_new_items,
-                           candidates=cand_model[2:] if cand_model else None)
-        lines += format_lines(users, ids, scores, items)
+                           candidates=cand_model[2:] if cand_model else None, on_device=True)
+        tokens, rows = row_tokens(users)
+        textio.write_lists(args.output, tokens, ids, scores, rows, vmap, where=args.format)
+        wrote = True
     if new_uids:
         m = max(new_uids.values()) + 1
         R = textio.parse_ratings(args.new_history, textio.IdMap(new_uids), vmap)
@@ -234,12 +239,14 @@ def main(argv=None):
             new_users = [tok[int(x)] for x in cand_new[1]]
         if new_users:
             ids, scores = rank(torch.from_numpy(U_new).to(device), [new_uids[u] for u in new_users], V_dev, bias_dev, R, args.total,
-                               candidates=cand_new[2:] if cand_new else None)
-            lines += format_lines(new_users, ids, scores, items)
-    with open(args.output, 'w') as fh:
-        for ln in lines:
-            fh.write(ln + '\n')
-    return lines
+                               candidates=cand_new[2:] if cand_new else None, on_device=True)
+            tokens, rows = row_tokens(new_users)
+            textio.write_lists(args.output, tokens, ids, scores, rows, vmap, where=args.format, append=wrote)
+            wrote = True
+    if not wrote:
+        open(args.output, 'wb').close()
+    with open(args.output, 'rb') as fh:
+        return fh.read().decode().split('\n')[:-1]               # the lines as written (one C-level call each, not one per line)
 
 
 if __name__ == '__main__':

@@ -7,7 +7,12 @@
     parse_ratings_device(path, users, items, device=None, chunk_bytes=None)
                                       the same arrays parsed by HIP kernels, left on the device (RatingsDevice)
     read_matrix(path)                 '%f ' text matrix -> fp32 [lines, cols]   (+ stamped .npy copy)
-    write_matrix(path, array)         fp32 array -> '%f ' text, byte-identical to utils.py:47-55
+    write_matrix(path, array, where=None)
+                                      fp32 array -> '%f ' text, byte-identical to utils.py:47-55
+    write_lists(path, users, ids, scores, row_user, items, where=None, block_bytes=None, append=False)
+                                      top-k lists -> "uid,iid:%f,iid:%f,..." lines, the bytes of format_lines
+    format_lists_device(ids, scores, row_user, users, items)
+                                      the same text formatted by HIP kernels, left on the device with its line offsets
 
 The text files stay authoritative.  ``read_matrix`` keeps a binary copy ``<path>.npy`` of what
 it parsed and ``parse_ratings`` a copy ``<path>.csr.npz`` of its flat arrays (n1).  A copy is used
@@ -21,6 +26,11 @@ Which parser reads a ratings file (``where`` / TKR_PARSE): 'host' -- one thread 
 the file's bytes are copied to the GPU and parsed there (K11), the four arrays come back in one copy; 'auto' (the default) -- the
 device for files of at least TKR_PARSE_DEVICE_FROM bytes when a GPU is visible and the text fits beside its outputs, else the host.
 Both produce the same arrays bit for bit and raise for the same files.
+
+Which writer formats a matrix or the lists (``where`` / TKR_FORMAT): 'host' -- tkr_matrix_write / format_lines, needs no GPU; 'device'
+-- the text is formatted on the GPU (K13, csrc/format_dev.hip) in blocks of at most ``block_bytes``, each downloaded and appended to
+the file; 'auto' (the default) -- the device from TKR_FORMAT_DEVICE_FROM fields (list entries, matrix elements) upward when a GPU is
+visible, else the host.  Both write the same bytes.
 """
 from __future__ import annotations
 
@@ -62,7 +72,7 @@ class IdMap:
         _check(tkr_hip.lib().tkr_idmap_create(blob, C.c_int64(len(blob)), index.ctypes.data_as(C.c_void_p),
                                               C.c_int64(len(keys)), C.byref(self._h)), 'tkr_idmap_create')
         self.size = len(keys)
-        self._blob, self._index, self._dev = blob, index, {}
+        self._blob, self._index, self._dev, self._dev_tokens, self._by_index = blob, index, {}, {}, None
 
     def device_table(self, device):
         """-> (slots int32 [n_slots, 4], blob uint8, blob_len) on `device`: the open-addressing table K11 probes, laid out on the host
@@ -75,8 +85,35 @@ class IdMap:
             self._dev[device] = (slots, torch.from_numpy(blob).to(device), len(self._blob))
         return self._dev[device]
 
+    def tokens_by_index(self):
+        """-> {index: token}, the later token where two share an index (the reference's own inversion of its dict)"""
+        if self._by_index is None:
+            self._by_index = {int(i): t for t, i in zip(self._blob.decode().split('\n'), self._index)}
+        return self._by_index
+
+    def device_tokens(self, device):
+        """-> (blob uint8, blob_len, start int64 [n], length int32 [n]) on `device`, n = the largest index + 1: token i is
+        blob[start[i], start[i] + length[i]), length[i] = -1 where no token has index i (a negative index is left out; of two tokens
+        with one index the later wins).  What K13 writes ids with; laid out on the host once and kept per device"""
+        device = torch.device(device)
+        if device not in self._dev_tokens:
+            n = len(self._index)
+            raw = np.frombuffer(self._blob, dtype=np.uint8)
+            ends = np.append(np.flatnonzero(raw == 10), len(raw))[:n].astype(np.int64)      # n tokens, n - 1 separators
+            starts = np.append(0, ends[:-1] + 1)[:n].astype(np.int64)
+            keep = self._index >= 0
+            size = int(self._index[keep].max()) + 1 if keep.any() else 0
+            start, length = np.zeros(size, dtype=np.int64), np.full(size, -1, dtype=np.int32)
+            start[self._index[keep]] = starts[keep]
+            length[self._index[keep]] = (ends - starts)[keep]
+            blob = np.zeros(max(len(raw), 4), dtype=np.uint8)
+            blob[:len(raw)] = raw
+            self._dev_tokens[device] = (torch.from_numpy(blob).to(device), len(raw), torch.from_numpy(start).to(device),
+                                        torch.from_numpy(length).to(device))
+        return self._dev_tokens[device]
+
     def __del__(self):
-        if getattr(self, '_h', None) and tkr_hip is not None:      # (module globals are gone at interpreter shutdown)
+        if getattr(self, '_h', None) and getattr(tkr_hip, 'lib', None) is not None:      # (module globals are gone at interpreter shutdown)
             tkr_hip.lib().tkr_idmap_destroy(self._h)
             self._h = None
 
@@ -292,12 +329,207 @@ def _store_cache(path, parsed, stamp):
         pass                                   # read-only data directory: the text stays the only copy
 
 
-def write_matrix(path: str, array) -> None:
-    array = np.ascontiguousarray(array, dtype=np.float32)
-    if array.ndim != 2:
+FORMAT_WHERE = ('host', 'device', 'auto')
+FORMAT_DEFAULT = 'auto'
+FORMAT_DEVICE_FROM = 65536           # fields: 'auto' formats fewer on the host (TKR_FORMAT_DEVICE_FROM; DESIGN.md §4 K13 has the crossover)
+FORMAT_BLOCK_BYTES = 256 << 20       # text formatted, downloaded and written at a time (any value from the longest line up gives the same file)
+format_counts = {'host': 0, 'device': 0}     # files (or appended parts) written per writer in this process
+
+
+def _format_where(where):
+    where = os.environ.get('TKR_FORMAT', '') or FORMAT_DEFAULT if where is None else where
+    if where not in FORMAT_WHERE:
+        raise ValueError('where / TKR_FORMAT must be one of %s, got %r' % (', '.join(FORMAT_WHERE), where))
+    return where
+
+
+def _format_on_device(where, n_fields):
+    """'device', or 'auto' with a GPU and enough fields; 'device' without a GPU raises"""
+    if where == 'device' and not torch.cuda.is_available():
+        raise tkr_hip.TkrError('formatting on the device runs through libtkr_hip.so; no MI355X is visible')
+    from_fields = int(os.environ.get('TKR_FORMAT_DEVICE_FROM', '') or FORMAT_DEVICE_FROM)
+    return where == 'device' or (where == 'auto' and torch.cuda.is_available() and n_fields >= from_fields)
+
+
+def format_lines(users, ids, scores, items):
+    """users: n tokens; ids int [n, K] catalogue indices, -1 = no item; scores float [n, K]; items: index -> token
+    -> n lines 'uid,iid:%f,iid:%f,...'"""
+    out = []
+    for u, row_i, row_s in zip(users, np.asarray(ids), np.asarray(scores)):
+        out.append(','.join([u] + ['%s:%f' % (items[int(c)], float(s)) for c, s in zip(row_i, row_s) if c >= 0]))
+    return out
+
+
+def _host_array(x, dtype):
+    return np.ascontiguousarray(x.detach().cpu().numpy() if isinstance(x, torch.Tensor) else x, dtype=dtype)
+
+
+def _device_array(x, dtype, device):
+    if isinstance(x, torch.Tensor):
+        return x.detach().to(device=device, dtype=dtype).contiguous()
+    return torch.from_numpy(np.ascontiguousarray(x, dtype={torch.int32: np.int32, torch.float32: np.float32}[dtype])).to(device)
+
+
+def _format_device_of(*arrays):
+    for x in arrays:
+        if isinstance(x, torch.Tensor) and x.is_cuda:
+            return x.device
+    return torch.device('cuda', torch.cuda.current_device())
+
+
+class _Timer:
+    """device time of the kernels between start() and stop() (events, read at the end), host time of the download and the file
+    write, summed into the caller's dict"""
+
+    def __init__(self, into):
+        self.into, self.pairs = into, []
+
+    def kernels(self):
+        if self.into is None:
+            return None
+        pair = (torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True))
+        self.pairs.append(pair)
+        pair[0].record()
+        return pair[1]
+
+    def host(self, name, since):
+        if self.into is not None:
+            import time
+            self.into[name] = self.into.get(name, 0.0) + time.perf_counter() - since
+
+    def close(self):
+        if self.into is not None:
+            torch.cuda.synchronize()
+            self.into['kernels'] = self.into.get('kernels', 0.0) + sum(a.elapsed_time(b) for a, b in self.pairs) * 1e-3
+
+
+def _emit_blocks(path, append, line_ptr, totals, emit, block_bytes, what, timing=None):
+    """the second half of K13 for a whole file: read back the line offsets (the one round trip between the two calls), cut the rows into
+    blocks of at most block_bytes of text, format each into one device buffer, download it and append it to the file -> bytes written"""
+    import time
+    timer = _Timer(timing)
+    t0 = time.perf_counter()
+    host = torch.cat([line_ptr, totals]).cpu().numpy()
+    timer.host('download', t0)
+    lp = host[:-2]
+    total = tkr_hip.format_totals(host[-2:], what)
+    n = len(lp) - 1
+    longest = int(np.diff(lp).max()) if n else 0
+    device = line_ptr.device
+    if block_bytes is None:
+        block_bytes = max(min(FORMAT_BLOCK_BYTES, torch.cuda.mem_get_info(device)[0] // 2), longest)
+    if block_bytes < longest:
+        raise ValueError('%s: block_bytes must be at least %d, the longest line (got %d)' % (path, longest, block_bytes))
+    _fits(min(block_bytes, total) + 64, device, 'a block of the text', path)
+    buf = torch.empty(min(block_bytes, total), dtype=torch.uint8, device=device)
+    with open(path, 'ab' if append else 'wb') as fh:
+        first = 0
+        while first < n:
+            last = int(np.searchsorted(lp, lp[first] + block_bytes, side='right')) - 1      # the rows [first, last) fit
+            size = int(lp[last] - lp[first])
+            done = timer.kernels()
+            status = emit(first, last - first, buf)
+            if done is not None:
+                done.record()
+            t0 = time.perf_counter()
+            text = buf[:size].cpu().numpy()
+            tkr_hip.format_emit_check(status, what)
+            timer.host('download', t0)
+            t0 = time.perf_counter()
+            fh.write(memoryview(text))
+            timer.host('write', t0)
+            first = last
+    timer.close()
+    return total
+
+
+def format_lists_device(ids, scores, row_user, users: IdMap, items: IdMap):
+    """-> (text uint8 [bytes], line_ptr int64 [n + 1]) on the device: the lines of format_lines for the rows of ids / scores [n, K]
+    (negative id = no entry), row r under token row_user[r] of `users`, the items under their tokens of `items`, each with its '\n';
+    line r is text[line_ptr[r] : line_ptr[r + 1]].  An index that names no token raises TkrError"""
+    if not torch.cuda.is_available():
+        raise tkr_hip.TkrError('formatting on the device runs through libtkr_hip.so; no MI355X is visible')
+    device = _format_device_of(ids, scores, row_user)
+    ids, scores, row_user = _device_array(ids, torch.int32, device), _device_array(scores, torch.float32, device), _device_array(row_user, torch.int32, device)
+    if ids.dim() != 2 or ids.shape != scores.shape or row_user.numel() != ids.shape[0]:
+        raise ValueError('ids and scores [n, K] and row_user [n] required')
+    args = (ids, scores, row_user.reshape(-1), users.device_tokens(device), items.device_tokens(device))
+    line_ptr, totals = tkr_hip.lists_format_sizes(*args)
+    total = tkr_hip.format_totals(totals.tolist(), 'tkr_lists_format_sizes_dev')       # the one round trip: the text is sized by it
+    _fits(total + 64, device, 'the text', 'format_lists_device')
+    text = torch.empty(total, dtype=torch.uint8, device=device)
+    tkr_hip.format_emit_check(tkr_hip.lists_format_emit(*args, line_ptr, 0, ids.shape[0], text), 'tkr_lists_format_emit_dev')
+    return text, line_ptr
+
+
+def write_lists(path, users: IdMap, ids, scores, row_user, items: IdMap, where=None, block_bytes=None, append=False, timing=None):
+    """write (or append) the top-k lines of ids / scores [n, K] -> bytes written; row r is the list of user index row_user[r].
+    The bytes are '\n'.join(format_lines(...)) + '\n' whichever writer runs; see the module text for `where`.  On the device the text is
+    formatted in blocks of at most block_bytes (at least the longest line, else ValueError before anything is written)"""
+    where = _format_where(where)
+    shape = tuple(ids.shape)
+    if len(shape) != 2 or shape != tuple(scores.shape) or len(row_user) != shape[0]:
+        raise ValueError('ids and scores [n, K] and row_user [n] required')
+    if _format_on_device(where, shape[0] * shape[1]):
+        device = _format_device_of(ids, scores, row_user)
+        try:
+            args = (_device_array(ids, torch.int32, device), _device_array(scores, torch.float32, device),
+                    _device_array(row_user, torch.int32, device).reshape(-1), users.device_tokens(device), items.device_tokens(device))
+            timer = _Timer(timing)
+            done = timer.kernels()
+            line_ptr, totals = tkr_hip.lists_format_sizes(*args)
+            if done is not None:
+                done.record()
+            timer.close()
+            size = _emit_blocks(path, append, line_ptr, totals, lambda first, count, out: tkr_hip.lists_format_emit(*args, line_ptr, first, count, out),
+                                block_bytes, 'tkr_lists_format', timing)
+            format_counts['device'] += 1
+            return size
+        except DeviceParseTooLarge:
+            if where == 'device':
+                raise
+    utok, itok = users.tokens_by_index(), items.tokens_by_index()
+    lines = format_lines([utok[int(u)] for u in _host_array(row_user, np.int64).reshape(-1)], _host_array(ids, np.int64), _host_array(scores, np.float32), itok)
+    text = ('\n'.join(lines) + '\n').encode() if lines else b''
+    with open(path, 'ab' if append else 'wb') as fh:
+        fh.write(text)
+    format_counts['host'] += 1
+    return len(text)
+
+
+def _write_matrix_device(path, array, block_bytes, timing):
+    device = _format_device_of(array)
+    data = _device_array(array, torch.float32, device)
+    timer = _Timer(timing)
+    done = timer.kernels()
+    line_ptr, totals = tkr_hip.matrix_format_sizes(data)
+    if done is not None:
+        done.record()
+    timer.close()
+    return _emit_blocks(path, False, line_ptr, totals, lambda first, count, out: tkr_hip.matrix_format_emit(data, line_ptr, first, count, out),
+                        block_bytes, 'tkr_matrix_format', timing)
+
+
+def write_matrix(path: str, array, where=None, block_bytes=None, timing=None) -> None:
+    where = _format_where(where)
+    shape = tuple(array.shape) if hasattr(array, 'shape') else np.shape(array)
+    if len(shape) != 2:
         raise ValueError('2-D array required')
-    _check(tkr_hip.lib().tkr_matrix_write(os.fsencode(path), array.ctypes.data_as(C.c_void_p),
-                                          C.c_int64(array.shape[0]), C.c_int64(array.shape[1])), 'tkr_matrix_write', path)
+    rows, cols = (int(v) for v in shape)
+    written = False
+    if _format_on_device(where, rows * cols):
+        try:
+            _write_matrix_device(path, array, block_bytes, timing)
+            format_counts['device'] += 1
+            written = True
+        except DeviceParseTooLarge:
+            if where == 'device':
+                raise
+    if not written:
+        array = _host_array(array, np.float32)
+        _check(tkr_hip.lib().tkr_matrix_write(os.fsencode(path), array.ctypes.data_as(C.c_void_p),
+                                              C.c_int64(array.shape[0]), C.c_int64(array.shape[1])), 'tkr_matrix_write', path)
+        format_counts['host'] += 1
     if _cache_enabled():
         stamp = _stamp(path)
         _store_cache(path, _parse_matrix(path), stamp)      # the 6-decimal text is authoritative: cache what IT says

@@ -85,7 +85,8 @@ EXPORTS = ('tkr_version', 'tkr_plan_team', 'tkr_plan_max_blocks', 'tkr_sample_pl
            'tkr_matrix_write', 'tkr_raw_ranks', 'tkr_count_hits_rr', 'tkr_topk_set_math', 'tkr_vbpr_set_pairs', 'tkr_lab_build',
            'tkr_sync_snapshot', 'tkr_sync_pack', 'tkr_sync_unpack', 'tkr_sync_flow_snapshot', 'tkr_sync_flow_pack',
            'tkr_sync_flow_unpack', 'tkr_like_ranks', 'tkr_bpr_foldin', 'tkr_bpr_foldin_items', 'tkr_idtable_build', 'tkr_ratings_count_dev',
-           'tkr_ratings_emit_dev', 'tkr_rank_candidates')
+           'tkr_ratings_emit_dev', 'tkr_rank_candidates', 'tkr_lists_format_sizes_dev', 'tkr_lists_format_emit_dev',
+           'tkr_matrix_format_sizes_dev', 'tkr_matrix_format_emit_dev')
 EXPORTS_I64 = ('tkr_vbpr_workspace_floats', 'tkr_vbpr_colplan_lds_bytes', 'tkr_topk_workspace_bytes_for', 'tkr_topk_workspace_bytes', 'tkr_plan_workspace_bytes', 'tkr_like_ranks_workspace_bytes',
                'tkr_parse_dev_workspace_bytes', 'tkr_idtable_slots')
 
@@ -759,6 +760,72 @@ def ratings_emit_dev(text, chunk_bytes, workspace, n_lines, n_entries, user_tabl
           C.c_int64(n_lines), C.c_int64(n_entries), _p(us), C.c_int64(us.shape[0]), _p(ub), C.c_int64(ul), _p(vs), C.c_int64(vs.shape[0]), _p(vb),
           C.c_int64(vl), _p(line_start), _p(line_user), _p(line_ptr), _p(item), _p(like), _p(status))
     return line_user, line_ptr, item, like
+
+
+# ---- K13: the text writers on the device (csrc/format_dev.hip) -------------------------------------------------------------------
+def format_totals(totals, what):
+    """what the host reads between the two calls, (size of the text, status) as a pair of ints -> the size; an index that names no token
+    raises"""
+    size, bad = (int(v) for v in totals)
+    if bad != -1:
+        raise TkrError('%s: row %d holds an index that names no token of its table' % (what, bad))
+    return size
+
+
+def _list_args(ids, scores, row_user, user_tokens, item_tokens):
+    assert ids.dtype == torch.int32 and scores.dtype == torch.float32 and row_user.dtype == torch.int32
+    assert ids.dim() == 2 and ids.shape == scores.shape and row_user.numel() == ids.shape[0]
+    args = [_p(ids), _p(scores), _p(row_user), C.c_int64(ids.shape[0]), C.c_int32(ids.shape[1])]
+    for blob, blob_len, start, length in (user_tokens, item_tokens):
+        assert blob.dtype == torch.uint8 and start.dtype == torch.int64 and length.dtype == torch.int32 and start.numel() == length.numel()
+        assert blob_len <= blob.numel()
+        args += [_p(blob), C.c_int64(blob_len), _p(start), _p(length), C.c_int64(length.numel())]
+    return args
+
+
+def lists_format_sizes(ids, scores, row_user, user_tokens, item_tokens):
+    """first half of K13 for the top-k lists -> (line_ptr int64 [n + 1], totals int64 [2]) on the device, nothing read back yet
+    (format_totals(totals.tolist(), ...) is the round trip); *_tokens = (blob uint8, blob_len, start int64, length int32) on ids' device
+    (textio.IdMap.device_tokens)"""
+    n = int(ids.shape[0])
+    line_ptr = torch.empty(n + 1, dtype=torch.int64, device=ids.device)
+    totals = torch.empty(2, dtype=torch.int64, device=ids.device)
+    _call('tkr_lists_format_sizes_dev', line_ptr, *_list_args(ids, scores, row_user, user_tokens, item_tokens), _p(line_ptr), _p(totals))
+    return line_ptr, totals
+
+
+def format_emit_check(status, what):
+    """the status word of an emit call, read after the block's text has been used or downloaded"""
+    bad = int(status.item())
+    if bad != -1:
+        raise TkrError('%s: line_ptr does not describe the text of row %d' % (what, bad))
+
+
+def lists_format_emit(ids, scores, row_user, user_tokens, item_tokens, line_ptr, first_row, n_rows, out):
+    """second half: rows [first_row, first_row + n_rows) of the text into `out` (device uint8, at least their bytes)"""
+    assert out.dtype == torch.uint8 and line_ptr.dtype == torch.int64 and line_ptr.numel() == ids.shape[0] + 1
+    status = torch.empty(1, dtype=torch.int64, device=ids.device)
+    _call('tkr_lists_format_emit_dev', line_ptr, *_list_args(ids, scores, row_user, user_tokens, item_tokens), _p(line_ptr),
+          C.c_int64(first_row), C.c_int64(n_rows), _p(out), C.c_int64(out.numel()), _p(status))
+    return status
+
+
+def matrix_format_sizes(data):
+    """first half of K13 for a '%f ' matrix (fp32 [rows, cols] on the device) -> (line_ptr int64 [rows + 1], totals int64 [2])"""
+    assert data.dtype == torch.float32 and data.dim() == 2
+    line_ptr = torch.empty(data.shape[0] + 1, dtype=torch.int64, device=data.device)
+    totals = torch.empty(2, dtype=torch.int64, device=data.device)
+    _call('tkr_matrix_format_sizes_dev', line_ptr, _p(data) if data.numel() else C.c_void_p(0), C.c_int64(data.shape[0]), C.c_int64(data.shape[1]),
+          _p(line_ptr), _p(totals))
+    return line_ptr, totals
+
+
+def matrix_format_emit(data, line_ptr, first_row, n_rows, out):
+    assert out.dtype == torch.uint8 and line_ptr.dtype == torch.int64 and line_ptr.numel() == data.shape[0] + 1
+    status = torch.empty(1, dtype=torch.int64, device=data.device)
+    _call('tkr_matrix_format_emit_dev', line_ptr, _p(data) if data.numel() else C.c_void_p(0), C.c_int64(data.shape[0]), C.c_int64(data.shape[1]),
+          _p(line_ptr), C.c_int64(first_row), C.c_int64(n_rows), _p(out), C.c_int64(out.numel()), _p(status))
+    return status
 
 
 # ---- per-epoch exchange of replicated tables (csrc/sync.hip) ----------------------------------------
