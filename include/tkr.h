@@ -623,6 +623,53 @@ int tkr_matrix_format_sizes_dev(const float* data, int64_t rows, int64_t cols, i
 int tkr_matrix_format_emit_dev(const float* data, int64_t rows, int64_t cols, const int64_t* line_ptr, int64_t first_row,
                                int64_t n_rows, void* out, int64_t out_bytes, int64_t* status, void* stream);
 
+/* ---- K14: tkr_matrix_read on the device (csrc/scan_dev.hip, csrc/scan_num.h) ---------------------------------------------------
+ * The same fp32 array as tkr_matrix_read / tkr_matrix_copy, bit for bit, from the n_bytes bytes of the file in device memory (`text`,
+ * 16-byte aligned; NULL only for n_bytes == 0).  The rules are the host reader's: lines end at '\n' only, a last line without one
+ * counts, a line is stripped of ' ' \t \n \r \v \f at both ends, tokens are split on ' ' only (an empty token is TKR_E_PARSE), every
+ * token goes through strtod, must be consumed whole and is narrowed with (float) -- two roundings, decimal -> 53 bits -> 24 bits,
+ * both to nearest even ("1.0000000596046448" is 0x3f800000, not 0x3f800001) --, cols is the first line's token count and any
+ * other count is TKR_E_PARSE.  The device decides nothing about malformed input.  It does two jobs:
+ *
+ * Layout.  A file is CANONICAL when it holds none of \t \r \v \f, its first byte is a token byte (anything but ' ' and '\n'), it
+ *   holds none of the pairs "  ", "\n ", "\n\n", and every line has as many tokens as the first.  Then a token starts at p when
+ *   byte[p] is a token byte and p == 0 or byte[p - 1] is ' ' or '\n', and runs to the next ' ', '\n' or the end: the host's
+ *   tokenisation.  The empty file is canonical, shape (0, 0).  For any other file the status word holds the smallest offset that
+ *   breaks a rule (-1: none); the caller then hands the WHOLE file to tkr_matrix_read, which returns the array or TKR_E_PARSE.
+ * Tokens.  A token is PLAIN when it is [+-]? digits* ('.' digits*)? with at least one digit, at most 19 digits from its first
+ *   non-zero digit to its last and at most 19 behind the '.': w / 10^f with w < 10^19 and 10^f < 2^64, converted exactly with
+ *   64-bit integers (a 64-step restoring division, the remainder as the sticky bit, the two roundings above).  Its value is 0
+ *   (keeping its sign: "-0.000000" is 0x80000000) or lies in [1e-19, 1e19).  Every other token is HARD (exponent forms, inf, nan,
+ *   hex floats, longer digit strings, garbage): its bit in `hard` is set, data holds 0 there, and the caller runs
+ *   tkr_matrix_tokens_host on those tokens -- the very check of tkr_matrix_read -- and patches the results in.
+ *
+ * Two calls with one read-back between them, because the outputs are sized by what the first one counts:
+ *   tkr_matrix_count_dev    totals_out (device int64[3]) = {n_lines, n_tokens, layout status}; fills `workspace` (16-byte aligned,
+ *                           tkr_scan_dev_workspace_bytes(n_bytes, chunk_bytes) bytes) with the per-chunk offsets
+ *   tkr_matrix_emit_dev     with the SAME text, chunk_bytes and workspace, the totals read back and cols = the token count of the
+ *                           first line (the host counts it): tok_start int64[n_tokens] = the offset of every token, data
+ *                           fp32[n_tokens] = row-major values, hard uint64[(n_tokens + 63) / 64] = bit (i & 63) of word i >> 6
+ *                           for token i, counts (device int64[2]) = {layout status, n_hard}.  The status is set here when a line
+ *                           does not start at token line * cols (its start offset), or n_lines * cols != n_tokens (n_bytes).
+ * chunk_bytes: a power of two, 64 ... 1,048,576: the piece of text one wave counts and walks.  It changes no output.
+ * A token or a line may straddle any number of chunks.  All offsets are 64-bit.  No kernel reads outside [0, n_bytes).  The only
+ * atomic is the status word's atomic min.  Deterministic.  Arguments are checked before any device access (TKR_E_INVAL; the size
+ * function returns it as its value).
+ *
+ * HOST calls (host pointers, no GPU):
+ *   tkr_matrix_token_host   the device's classify-and-convert routine run on the CPU on tok[0, len): 1 = plain, *out converted;
+ *                           0 = hard, *out untouched; TKR_E_INVAL on bad arguments
+ *   tkr_matrix_tokens_host  for k < n the token of text[0, n_bytes) that starts at start[k] and runs to the next ' ', '\n' or the
+ *                           end: out[k] = (float)strtod(token), TKR_E_PARSE where tkr_matrix_read would return it */
+int64_t tkr_scan_dev_workspace_bytes(int64_t n_bytes, int64_t chunk_bytes);
+int tkr_matrix_count_dev(const void* text, int64_t n_bytes, int64_t chunk_bytes, void* workspace, int64_t workspace_bytes,
+                         int64_t* totals_out, void* stream);
+int tkr_matrix_emit_dev(const void* text, int64_t n_bytes, int64_t chunk_bytes, void* workspace, int64_t workspace_bytes,
+                        int64_t n_lines, int64_t n_tokens, int64_t cols, int64_t* tok_start, float* data, uint64_t* hard,
+                        int64_t* counts, void* stream);
+int tkr_matrix_token_host(const char* tok, int64_t len, float* out);
+int tkr_matrix_tokens_host(const char* text, int64_t n_bytes, const int64_t* start, int64_t n, float* out);
+
 #ifdef __cplusplus
 }
 #endif

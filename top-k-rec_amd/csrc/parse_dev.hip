@@ -23,20 +23,17 @@
 // Token lookup: one open-addressing table per id list, laid out on the host (tkr_idtable_build) and uploaded by the caller: slots
 // of {offset into the blob, length, index, hash}, length -1 = empty, linear probing from hash & (n_slots - 1).  A hit compares the
 // bytes.  The empty token is a key like any other.
+//
+// The byte helpers, the chunk scan and the workspace layout are shared with K14 (csrc/scan_dev.hip): csrc/text_bytes.h.
 #include <string.h>
 
 #include "tkr_common.h"
+#include "text_bytes.h"
 #include "../../include/tkr.h"
 
 namespace tkr {
 namespace {
 
-constexpr int kParseBlock = 256;                                  // 4 waves = 4 chunks per workgroup
-constexpr int64_t kMinChunk = 64, kMaxChunk = 1 << 20;
-constexpr int64_t kWaveBytes = 64 * 16;                            // one step of a wave
-constexpr int64_t kMaxChunks = (int64_t)1 << 30;
-constexpr int kScanThreads = 1024;
-constexpr unsigned kMaxLaneGrid = 1u << 20;                        // entries / lines beyond 2^28 are taken by a grid-stride loop
 
 // FNV-1a over the token's bytes, folded once: the same function lays the table out on the host and probes it on the device
 constexpr uint32_t kHashSeed = 2166136261u;
@@ -44,51 +41,6 @@ __host__ __device__ inline uint32_t hash_step(uint32_t h, uint32_t byte) { retur
 __host__ __device__ inline uint32_t hash_finish(uint32_t h) { return h ^ (h >> 15); }
 
 __device__ __forceinline__ bool is_space(uint32_t c) { return c == ' ' || (c >= 9 && c <= 13); }      // ' ' \t \n \v \f \r
-
-// n bytes at a 4-byte aligned p.  word(w) = bytes [4w, 4w + 4) as a little-endian word; bytes at or past n are never touched and read as 0
-struct Bytes {
-    const uint8_t* p;
-    int64_t n;
-    __device__ __forceinline__ uint32_t word(int64_t w) const {
-        const int64_t o = w * 4;
-        if (o + 4 <= n) return *reinterpret_cast<const uint32_t*>(p + o);
-        uint32_t v = 0;
-        for (int j = 0; j < 4; ++j)
-            if (o + j < n) v |= (uint32_t)p[o + j] << (8 * j);
-        return v;
-    }
-};
-
-// a lane's reader: at(i), 0 <= i < n, keeps the word it last loaded
-struct Cursor {
-    Bytes t;
-    int64_t w = -1;
-    uint32_t v = 0;
-    __device__ __forceinline__ uint32_t at(int64_t i) {
-        if ((i >> 2) != w) {
-            w = i >> 2;
-            v = t.word(w);
-        }
-        return (v >> ((i & 3) * 8)) & 0xffu;
-    }
-};
-
-// bytes [g, g + 16) of t, g a multiple of 16 below t.n
-__device__ __forceinline__ void load16(const Bytes& t, int64_t g, uint32_t (&w)[4]) {
-    if (g + 16 <= t.n) {
-        const uint4 q = *reinterpret_cast<const uint4*>(t.p + g);
-        w[0] = q.x; w[1] = q.y; w[2] = q.z; w[3] = q.w;
-    } else {
-#pragma unroll
-        for (int k = 0; k < 4; ++k) w[k] = g + 4 * k < t.n ? t.word((g >> 2) + k) : 0u;
-    }
-}
-
-// number of bytes of w equal to c (exact: no borrow runs between the bytes)
-__device__ __forceinline__ uint32_t count_eq(uint32_t w, uint32_t c) {
-    const uint32_t x = w ^ (c * 0x01010101u);
-    return __popc(~(((x & 0x7f7f7f7fu) + 0x7f7f7f7fu) | x) & 0x80808080u);
-}
 
 // (newlines << 16 | commas) of 16 bytes
 __device__ __forceinline__ uint32_t count16(const uint32_t (&w)[4]) {
@@ -120,45 +72,6 @@ __global__ __launch_bounds__(kParseBlock) void parse_count_kernel(Bytes t, int64
         cm += __shfl_down(cm, off);
     }
     if (lane == 0) counts[c] = make_uint2(nl, cm);
-}
-
-// exclusive prefixes of the chunk pairs and the totals; thread x takes a contiguous run of chunks
-__global__ __launch_bounds__(kScanThreads) void parse_scan_kernel(Bytes t, const uint2* __restrict__ counts, int64_t n_chunks,
-                                                                 int64_t* __restrict__ off_nl, int64_t* __restrict__ off_cm,
-                                                                 int64_t* __restrict__ totals) {
-    __shared__ int64_t s_nl[2][kScanThreads], s_cm[2][kScanThreads];
-    const int x = threadIdx.x;
-    const int64_t per = (n_chunks + kScanThreads - 1) / kScanThreads;
-    const int64_t lo = x * per < n_chunks ? x * per : n_chunks;
-    const int64_t hi = lo + per < n_chunks ? lo + per : n_chunks;
-    int64_t nl = 0, cm = 0;
-    for (int64_t c = lo; c < hi; ++c) {
-        const uint2 v = counts[c];
-        nl += v.x;
-        cm += v.y;
-    }
-    int cur = 0;
-    s_nl[0][x] = nl;
-    s_cm[0][x] = cm;
-    __syncthreads();
-    for (int d = 1; d < kScanThreads; d <<= 1) {                   // inclusive, double-buffered
-        s_nl[cur ^ 1][x] = s_nl[cur][x] + (x >= d ? s_nl[cur][x - d] : 0);
-        s_cm[cur ^ 1][x] = s_cm[cur][x] + (x >= d ? s_cm[cur][x - d] : 0);
-        cur ^= 1;
-        __syncthreads();
-    }
-    int64_t run_nl = s_nl[cur][x] - nl, run_cm = s_cm[cur][x] - cm;
-    for (int64_t c = lo; c < hi; ++c) {
-        const uint2 v = counts[c];
-        off_nl[c] = run_nl;
-        off_cm[c] = run_cm;
-        run_nl += v.x;
-        run_cm += v.y;
-    }
-    if (x == kScanThreads - 1) {
-        totals[0] = s_nl[cur][x] + ((t.n > 0 && t.p[t.n - 1] != '\n') ? 1 : 0);      // a last line without a terminator counts
-        totals[1] = s_cm[cur][x];
-    }
 }
 
 __global__ __launch_bounds__(kParseBlock) void parse_positions_kernel(Bytes t, int64_t chunk, int64_t n_chunks,
@@ -326,31 +239,11 @@ __global__ __launch_bounds__(kParseBlock) void parse_lines_kernel(Bytes t, Table
     }
 }
 
-inline bool chunk_ok(int64_t chunk) { return chunk >= kMinChunk && chunk <= kMaxChunk && (chunk & (chunk - 1)) == 0; }
-inline int64_t chunks_of(int64_t n_bytes, int64_t chunk) { return (n_bytes + chunk - 1) / chunk; }
 inline bool pow2(int64_t v) { return v > 0 && (v & (v - 1)) == 0; }
 inline bool table_ok(const void* slots, int64_t n_slots, const void* blob, int64_t blob_len) {
     return slots && ((uintptr_t)slots & 15) == 0 && pow2(n_slots) && n_slots <= ((int64_t)1 << 30) && blob_len >= 0 &&
            blob_len <= 2147483647LL && (blob_len == 0 || (blob && ((uintptr_t)blob & 3) == 0));
 }
-inline unsigned lane_grid(int64_t n) {
-    const int64_t blocks = (n + kParseBlock - 1) / kParseBlock;
-    return (unsigned)(blocks < (int64_t)kMaxLaneGrid ? blocks : (int64_t)kMaxLaneGrid);
-}
-
-// the three arrays in front of the workspace, each 256-byte aligned
-struct Workspace {
-    uint2* counts;
-    int64_t *off_nl, *off_cm;
-    static int64_t part(int64_t n_chunks) { return (n_chunks * 8 + 255) / 256 * 256; }
-    static int64_t bytes(int64_t n_chunks) { return 3 * part(n_chunks) + 256; }
-    Workspace(void* ws, int64_t n_chunks) {
-        char* p = static_cast<char*>(ws);
-        counts = reinterpret_cast<uint2*>(p);
-        off_nl = reinterpret_cast<int64_t*>(p + part(n_chunks));
-        off_cm = reinterpret_cast<int64_t*>(p + 2 * part(n_chunks));
-    }
-};
 
 }  // namespace
 }  // namespace tkr
@@ -419,7 +312,7 @@ extern "C" int tkr_ratings_count_dev(const void* text, int64_t n_bytes, int64_t 
     const unsigned blocks = (unsigned)((n_chunks + tkr::kParseBlock / 64 - 1) / (tkr::kParseBlock / 64));
     hipLaunchKernelGGL(tkr::parse_count_kernel, dim3(blocks), dim3(tkr::kParseBlock), 0, s, t, chunk_bytes, n_chunks, ws.counts);
     TKR_LAUNCH_CHECK();
-    hipLaunchKernelGGL(tkr::parse_scan_kernel, dim3(1), dim3(tkr::kScanThreads), 0, s, t, ws.counts, n_chunks, ws.off_nl, ws.off_cm, totals_out);
+    hipLaunchKernelGGL(tkr::chunk_scan_kernel, dim3(1), dim3(tkr::kScanThreads), 0, s, t, ws.counts, n_chunks, ws.off_x, ws.off_y, totals_out);
     TKR_LAUNCH_CHECK();
     return TKR_OK;
 }
@@ -447,7 +340,7 @@ extern "C" int tkr_ratings_emit_dev(const void* text, int64_t n_bytes, int64_t c
     const tkr::Table users{reinterpret_cast<const int4*>(user_slots), user_n_slots, {static_cast<const uint8_t*>(user_blob), user_blob_len}};
     const tkr::Table items{reinterpret_cast<const int4*>(item_slots), item_n_slots, {static_cast<const uint8_t*>(item_blob), item_blob_len}};
     const unsigned blocks = (unsigned)((n_chunks + tkr::kParseBlock / 64 - 1) / (tkr::kParseBlock / 64));
-    hipLaunchKernelGGL(tkr::parse_positions_kernel, dim3(blocks), dim3(tkr::kParseBlock), 0, s, t, chunk_bytes, n_chunks, ws.off_nl, ws.off_cm,
+    hipLaunchKernelGGL(tkr::parse_positions_kernel, dim3(blocks), dim3(tkr::kParseBlock), 0, s, t, chunk_bytes, n_chunks, ws.off_x, ws.off_y,
                        n_lines, n_entries, line_start, line_ptr, item, like);
     TKR_LAUNCH_CHECK();
     if (n_entries > 0) {

@@ -98,6 +98,18 @@ inline bool parse_int(const char* b, const char* e, int32_t& out) {
     return true;
 }
 
+// one matrix element [b, e): float(str) then narrowing, like np.float32(str); the whole token must be a number.  `tok` is scratch.
+// The one check both matrix readers apply: tkr_matrix_read to every token, K14 (csrc/scan_dev.hip) to the tokens it left to the host
+inline bool parse_element(const char* b, const char* e, std::string& tok, float& out) {
+    tok.assign(b, (size_t)(e - b));
+    char* stop = nullptr;
+    errno = 0;
+    const double v = strtod(tok.c_str(), &stop);
+    if (tok.empty() || stop != tok.c_str() + tok.size()) return false;
+    out = (float)v;
+    return true;
+}
+
 }  // namespace
 
 extern "C" int tkr_idmap_create(const char* blob, int64_t blob_len, const int32_t* index, int64_t n, void** out) {
@@ -219,12 +231,9 @@ extern "C" int tkr_matrix_read(const char* path, void** out) {
             while (b < e) {                                         // terms = line.strip().split(' ')
                 const char* sp = static_cast<const char*>(memchr(b, ' ', (size_t)(e - b)));
                 const char* te = sp ? sp : e;
-                tok.assign(b, (size_t)(te - b));
-                char* stop = nullptr;
-                errno = 0;
-                const double v = strtod(tok.c_str(), &stop);        // float(str) then narrowing, like np.float32(str)
-                if (tok.empty() || stop != tok.c_str() + tok.size()) return TKR_E_PARSE;
-                m->data.push_back((float)v);
+                float v;
+                if (!parse_element(b, te, tok, v)) return TKR_E_PARSE;
+                m->data.push_back(v);
                 ++cols;
                 b = sp ? sp + 1 : e;
             }
@@ -234,6 +243,23 @@ extern "C" int tkr_matrix_read(const char* path, void** out) {
             p = nl ? nl + 1 : end;
         }
         *out = m.release();
+        return TKR_OK;
+    } catch (...) {
+        return TKR_E_NOMEM;                                       // nothing throws across the C ABI
+    }
+}
+
+extern "C" int tkr_matrix_tokens_host(const char* text, int64_t n_bytes, const int64_t* start, int64_t n, float* out) {
+    try {
+        if (n_bytes < 0 || n < 0 || (n > 0 && (!text || !start || !out))) return TKR_E_INVAL;
+        std::string tok;
+        for (int64_t k = 0; k < n; ++k) {
+            if (start[k] < 0 || start[k] >= n_bytes) return TKR_E_INVAL;
+            const char* b = text + start[k];
+            const char* e = b;
+            while (e < text + n_bytes && *e != ' ' && *e != '\n') ++e;      // a token of a canonical file: to the next ' ', '\n' or the end
+            if (!parse_element(b, e, tok, out[k])) return TKR_E_PARSE;
+        }
         return TKR_OK;
     } catch (...) {
         return TKR_E_NOMEM;                                       // nothing throws across the C ABI

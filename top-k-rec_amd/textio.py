@@ -1,12 +1,14 @@
 """Bulk readers/writers of the reference's text formats on top of the native parsers of libtkr_hip.so
-(csrc/textio.hip on the host, csrc/parse_dev.hip on the GPU).
+(csrc/textio.hip on the host; csrc/parse_dev.hip, csrc/scan_dev.hip and csrc/format_dev.hip on the GPU).
 
     IdMap(dict)                       the reference's token -> index dict, handed to the parser
     parse_ratings(path, users, items, where=None)
                                       "uid,iid:like,..." lines -> flat arrays (Ratings)   (+ stamped .csr.npz copy)
     parse_ratings_device(path, users, items, device=None, chunk_bytes=None)
                                       the same arrays parsed by HIP kernels, left on the device (RatingsDevice)
-    read_matrix(path)                 '%f ' text matrix -> fp32 [lines, cols]   (+ stamped .npy copy)
+    read_matrix(path, where=None)     '%f ' text matrix -> fp32 [lines, cols]   (+ stamped .npy copy)
+    read_matrix_device(path, device=None, chunk_bytes=None)
+                                      the same array read by HIP kernels, left on the device
     write_matrix(path, array, where=None)
                                       fp32 array -> '%f ' text, byte-identical to utils.py:47-55
     write_lists(path, users, ids, scores, row_user, items, where=None, block_bytes=None, append=False)
@@ -26,6 +28,14 @@ Which parser reads a ratings file (``where`` / TKR_PARSE): 'host' -- one thread 
 the file's bytes are copied to the GPU and parsed there (K11), the four arrays come back in one copy; 'auto' (the default) -- the
 device for files of at least TKR_PARSE_DEVICE_FROM bytes when a GPU is visible and the text fits beside its outputs, else the host.
 Both produce the same arrays bit for bit and raise for the same files.
+
+Which reader reads a matrix (``where`` / TKR_MATRIX): 'host' -- tkr_matrix_read, one thread over the mapped file, needs no GPU;
+'device' -- the file's bytes are copied to the GPU (K14, csrc/scan_dev.hip), which checks that the text has the canonical layout
+("%f %f ... %f \\n" lines: no \\t \\r \\v \\f, no empty token, no blank line, equal token counts) and converts every plain decimal
+token exactly; the tokens it cannot (exponent forms, inf, nan, more than 19 digits) are parsed by the host reader's own strtod
+check from the mapped file and patched in.  A file in any other layout is read by the host reader as a whole, so both readers
+return the same array bit for bit and raise TextFormatError for the same files.  'auto' (the default) -- the device for files of
+at least TKR_MATRIX_DEVICE_FROM bytes when a GPU is visible and the text fits beside its outputs, else the host.
 
 Which writer formats a matrix or the lists (``where`` / TKR_FORMAT): 'host' -- tkr_matrix_write / format_lines, needs no GPU; 'device'
 -- the text is formatted on the GPU (K13, csrc/format_dev.hip) in blocks of at most ``block_bytes``, each downloaded and appended to
@@ -291,8 +301,107 @@ def _cache_writer():
     return os.environ.get('RANK', '0') == '0'
 
 
-def read_matrix(path: str) -> np.ndarray:
-    """every line of a '%f ' text matrix -> fp32 [n_lines, n_cols]"""
+class MatrixNotCanonical(TextFormatError):
+    """the text does not have the layout K14 reads on the device (read_matrix then hands the whole file to the host reader, which
+    returns the array or raises its own TextFormatError); ``offset`` is the first byte that breaks a rule"""
+
+    def __init__(self, path, offset):
+        super().__init__('%s: not the canonical layout of a \'%%f \' matrix at byte %d' % (path, offset))
+        self.offset = offset
+
+
+MATRIX_WHERE = ('host', 'device', 'auto')
+MATRIX_DEFAULT = 'auto'
+MATRIX_DEVICE_FROM = 1 << 20         # bytes of text: 'auto' reads smaller files on the host (TKR_MATRIX_DEVICE_FROM; DESIGN.md §4 K14 has the sweep)
+MATRIX_CHUNK_BYTES = 16384           # the piece of text one wave counts and walks (any power of two 64 ... 2^20 gives the same array)
+scan_counts = {'host': 0, 'device': 0}       # matrices read from text per reader in this process (what 'auto' chose is read off here)
+
+
+def _matrix_where(where):
+    where = os.environ.get('TKR_MATRIX', '') or MATRIX_DEFAULT if where is None else where
+    if where not in MATRIX_WHERE:
+        raise ValueError('where / TKR_MATRIX must be one of %s, got %r' % (', '.join(MATRIX_WHERE), where))
+    return where
+
+
+def _matrix_device_from():
+    return int(os.environ.get('TKR_MATRIX_DEVICE_FROM', '') or MATRIX_DEVICE_FROM)
+
+
+def _first_line_cols(host):
+    """the token count of the first line of the mapped text, as the host reader counts it"""
+    end, step = 0, 1 << 16
+    while True:
+        hit = np.flatnonzero(host[end:end + step] == 10)
+        if hit.size:
+            end += int(hit[0])
+            break
+        end += step
+        if end >= host.size:
+            end = int(host.size)
+            break
+    line = bytes(host[:end]).strip(b' \t\n\r\v\f')
+    return len(line.split(b' ')) if line else 0
+
+
+def _read_matrix_device(path, device=None, chunk_bytes=None, timing=None):
+    """K14 -> fp32 [rows, cols] on the device.  timing: a dict that receives the seconds of 'upload', 'kernels' (with the two
+    read-backs of a few words), 'patch' (the hard tokens: their offsets down, the host's strtod, their values up)"""
+    if not torch.cuda.is_available():
+        raise tkr_hip.TkrError('read_matrix on the device runs through libtkr_hip.so; no MI355X is visible')
+    import time
+    chunk_bytes = MATRIX_CHUNK_BYTES if chunk_bytes is None else chunk_bytes
+    host = np.memmap(path, dtype=np.uint8, mode='c') if os.stat(path).st_size else np.empty(0, dtype=np.uint8)
+    n_bytes = int(host.size)
+    need_ws = tkr_hip.scan_dev_workspace_bytes(n_bytes, chunk_bytes)
+    device = torch.device('cuda', torch.cuda.current_device()) if device is None else torch.device(device)
+
+    def lap(name, since):
+        if timing is not None:
+            torch.cuda.synchronize(device)
+            timing[name] = timing.get(name, 0.0) + time.perf_counter() - since
+        return time.perf_counter()
+
+    # the limit: text + workspace, then 12 bytes and a bit per token beside them, must fit the free device memory
+    _fits(n_bytes + need_ws, device, 'the text', path)
+    t0 = time.perf_counter()
+    text = torch.from_numpy(host).to(device)                       # mapped, copied once
+    t0 = lap('upload', t0)
+    ws = torch.empty(need_ws, dtype=torch.uint8, device=device)
+    totals = torch.empty(3, dtype=torch.int64, device=device)
+    tkr_hip.matrix_count_dev(text, chunk_bytes, ws, totals)
+    n_lines, n_tokens, status = totals.tolist()                    # the one round trip: the outputs are sized by it
+    if status != -1:
+        raise MatrixNotCanonical(path, status)
+    cols = _first_line_cols(host)
+    _fits(12 * n_tokens + n_tokens // 8 + 64, device, 'the parsed array', path)
+    tok_start, data, hard, counts = tkr_hip.matrix_emit_dev(text, chunk_bytes, ws, n_lines, n_tokens, cols)
+    status, n_hard = counts.tolist()
+    if status != -1:
+        raise MatrixNotCanonical(path, status)
+    t0 = lap('kernels', t0)
+    if n_hard:
+        bits = np.unpackbits(hard.cpu().numpy().view(np.uint8), bitorder='little')[:n_tokens]
+        index = torch.from_numpy(np.flatnonzero(bits)).to(device)
+        rc, values = tkr_hip.matrix_tokens_host(host, tok_start[index].cpu().numpy())
+        _check(rc, 'tkr_matrix_tokens_host', path)
+        data[index] = torch.from_numpy(values).to(device)
+        lap('patch', t0)
+    return data.view(n_lines, cols)
+
+
+def read_matrix_device(path: str, device=None, chunk_bytes=None, timing=None) -> torch.Tensor:
+    """the array of read_matrix, read on `device` (default: the current GPU) by K14 and left there, the tokens the device leaves to
+    the host's strtod already patched in; no stamped copy is read or written.  A text that is not in the canonical layout raises
+    MatrixNotCanonical, a token that is no number TextFormatError"""
+    out = _read_matrix_device(path, device, chunk_bytes, timing)
+    scan_counts['device'] += 1
+    return out
+
+
+def read_matrix(path: str, where=None) -> np.ndarray:
+    """every line of a '%f ' text matrix -> fp32 [n_lines, n_cols]; see the module text for `where`"""
+    where = _matrix_where(where)
     cache = _cache_path(path)
     if _cache_enabled() and os.path.isfile(cache) and os.path.isfile(cache + '.stamp'):
         try:
@@ -303,7 +412,16 @@ def read_matrix(path: str) -> np.ndarray:
         except (OSError, ValueError):
             pass
     stamp = _stamp(path) if _cache_enabled() else None
-    out = _parse_matrix(path)
+    out = None
+    if where == 'device' or (where == 'auto' and torch.cuda.is_available() and os.path.getsize(path) >= _matrix_device_from()):
+        try:
+            out = _read_matrix_device(path).cpu().numpy()
+            scan_counts['device'] += 1
+        except (MatrixNotCanonical, DeviceParseTooLarge):
+            pass                               # the host reader takes the whole file: it returns the array or raises as it always did
+    if out is None:
+        out = _parse_matrix(path)
+        scan_counts['host'] += 1
     _store_cache(path, out, stamp)
     return out
 

@@ -86,9 +86,10 @@ EXPORTS = ('tkr_version', 'tkr_plan_team', 'tkr_plan_max_blocks', 'tkr_sample_pl
            'tkr_sync_snapshot', 'tkr_sync_pack', 'tkr_sync_unpack', 'tkr_sync_flow_snapshot', 'tkr_sync_flow_pack',
            'tkr_sync_flow_unpack', 'tkr_like_ranks', 'tkr_bpr_foldin', 'tkr_bpr_foldin_items', 'tkr_idtable_build', 'tkr_ratings_count_dev',
            'tkr_ratings_emit_dev', 'tkr_rank_candidates', 'tkr_lists_format_sizes_dev', 'tkr_lists_format_emit_dev',
-           'tkr_matrix_format_sizes_dev', 'tkr_matrix_format_emit_dev')
+           'tkr_matrix_format_sizes_dev', 'tkr_matrix_format_emit_dev', 'tkr_matrix_count_dev', 'tkr_matrix_emit_dev', 'tkr_matrix_token_host',
+           'tkr_matrix_tokens_host')
 EXPORTS_I64 = ('tkr_vbpr_workspace_floats', 'tkr_vbpr_colplan_lds_bytes', 'tkr_topk_workspace_bytes_for', 'tkr_topk_workspace_bytes', 'tkr_plan_workspace_bytes', 'tkr_like_ranks_workspace_bytes',
-               'tkr_parse_dev_workspace_bytes', 'tkr_idtable_slots')
+               'tkr_parse_dev_workspace_bytes', 'tkr_idtable_slots', 'tkr_scan_dev_workspace_bytes')
 
 
 def lib():
@@ -826,6 +827,53 @@ def matrix_format_emit(data, line_ptr, first_row, n_rows, out):
     _call('tkr_matrix_format_emit_dev', line_ptr, _p(data) if data.numel() else C.c_void_p(0), C.c_int64(data.shape[0]), C.c_int64(data.shape[1]),
           _p(line_ptr), C.c_int64(first_row), C.c_int64(n_rows), _p(out), C.c_int64(out.numel()), _p(status))
     return status
+
+
+# ---- K14: the matrix reader on the device (csrc/scan_dev.hip) --------------------------------------------------------------------
+def scan_dev_workspace_bytes(n_bytes, chunk_bytes):
+    need = int(lib().tkr_scan_dev_workspace_bytes(C.c_int64(n_bytes), C.c_int64(chunk_bytes)))
+    if need < 0:
+        raise ValueError('read on the device: chunk_bytes must be a power of two in [%d, %d], got %r' % (PARSE_CHUNK_MIN, PARSE_CHUNK_MAX, chunk_bytes))
+    return need
+
+
+def matrix_count_dev(text, chunk_bytes, workspace, totals):
+    """first half of K14: totals (device int64[3]) = (n_lines, n_tokens, layout status) of the matrix text in `text` (device uint8)"""
+    assert text.dtype == torch.uint8 and totals.dtype == torch.int64 and totals.numel() == 3 and workspace.dtype == torch.uint8
+    _call('tkr_matrix_count_dev', workspace, _p(text), C.c_int64(text.numel()), C.c_int64(chunk_bytes), _p(workspace), C.c_int64(workspace.numel()),
+          _p(totals))
+
+
+def matrix_emit_dev(text, chunk_bytes, workspace, n_lines, n_tokens, cols):
+    """second half of K14 -> (tok_start int64 [n_tokens], data fp32 [n_tokens], hard int64 [(n_tokens + 63) // 64] (bit i & 63 of word
+    i >> 6: token i is left to the host), counts int64 [2] = (layout status, n_hard)) on text's device, nothing read back yet"""
+    dev = workspace.device
+    tok_start = torch.empty(n_tokens, dtype=torch.int64, device=dev)
+    data = torch.empty(n_tokens, dtype=torch.float32, device=dev)
+    hard = torch.empty((n_tokens + 63) // 64, dtype=torch.int64, device=dev)
+    counts = torch.empty(2, dtype=torch.int64, device=dev)
+    _call('tkr_matrix_emit_dev', workspace, _p(text), C.c_int64(text.numel()), C.c_int64(chunk_bytes), _p(workspace), C.c_int64(workspace.numel()),
+          C.c_int64(n_lines), C.c_int64(n_tokens), C.c_int64(cols), _p(tok_start), _p(data), _p(hard), _p(counts))
+    return tok_start, data, hard, counts
+
+
+def matrix_token_host(token: bytes):
+    """the device's classify-and-convert routine of K14 run on the CPU -> the fp32 as 4 little-endian bytes, or None for a hard token"""
+    out = C.c_float()
+    rc = lib().tkr_matrix_token_host(token, C.c_int64(len(token)), C.byref(out))
+    if rc < 0:
+        raise TkrError('tkr_matrix_token_host failed: tkr error %d' % rc)
+    return bytes(memoryview(out).cast('B')) if rc == 1 else None
+
+
+def matrix_tokens_host(text, start):
+    """the host reader's own check on the tokens of `text` (host uint8 array) that start at `start` (host int64 array) -> (rc, fp32
+    array): rc -4 where tkr_matrix_read would refuse the file"""
+    import numpy as np
+    out = np.empty(len(start), dtype=np.float32)
+    rc = lib().tkr_matrix_tokens_host(C.c_void_p(text.ctypes.data), C.c_int64(text.size), C.c_void_p(start.ctypes.data), C.c_int64(len(start)),
+                                      C.c_void_p(out.ctypes.data))
+    return rc, out
 
 
 # ---- per-epoch exchange of replicated tables (csrc/sync.hip) ----------------------------------------
