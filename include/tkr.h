@@ -31,7 +31,7 @@
 extern "C" {
 #endif
 
-#define TKR_VERSION 120 /* (additions that change no existing entry point keep the number: K10 tkr_bpr_foldin_items, K11 tkr_ratings_*_dev, K12 tkr_rank_candidates, K13 tkr_lists_format_* / tkr_matrix_format_*.) 0.1.20: K9 tkr_bpr_foldin (user vectors for new histories against frozen item factors; csrc/foldin.hip). 0.1.19: K8 tkr_like_ranks + tkr_like_ranks_workspace_bytes (filtered rank of every liked test column; csrc/like_ranks.hip). 0.1.18: K4 second form of bound-and-refine (csrc/topk_refine.hip; tkr_topk_workspace_bytes_for grows by the pieces' packed lists), any k (bpr_wide_kernel, score_topk_wide_kernel), tkr_lab_build; tkr_topk_set_finish is gone, tkr_topk_set_math(0) and tkr_vbpr_set_pairs(1 | 2) need the lab library. 0.1.17: tkr_vbpr_set_pairs (tkr_vbpr_workspace_floats + 64). 0.1.16: tkr_topk_set_finish (larger tkr_topk_workspace_bytes), tkr_bpr_own_plan_run plans inside the step's launch. 0.1.15: tkr_bpr_own_owners_shared; tkr_bpr_run takes `rec` non-const. 0.1.14: per-task loss sums instead of atomics on loss_out (larger tkr_vbpr_workspace_floats; K2 writes word 15 of its records). 0.1.13: tkr_bpr_own_plan_run, K4 to k = 768. 0.1.12: tkr_bpr_own_run_between. 0.1.11: K2o (tkr_sample_plan_owned, tkr_bpr_own_run: item rows owned by one workgroup each, resident in its LDS); prec[5] = last batch of the call that updated the row. 0.1.10: tkr_topk_workspace_bytes_for (K4 stages pre-converted fp16 tiles). 0.1.9: tkr_vbpr_colplan + tkr_vbpr_run_cols (VBPR in three launches per batch). 0.1.8: tkr_sync_flow_* (exchange of the granule tables). 0.1.7: K4 bound-and-refine arithmetic (tkr_topk_set_math(2), the default; larger tkr_topk_workspace_bytes); K2f leaves its ticket words zero. 0.1.6: K2f persistent dataflow step, tkr_plan_rollback, batches above 8192 */
+#define TKR_VERSION 120 /* (additions that change no existing entry point keep the number: K10 tkr_bpr_foldin_items, K11 tkr_ratings_*_dev, K12 tkr_rank_candidates, K13 tkr_lists_format_* / tkr_matrix_format_*, K15 tkr_group_*_dev / tkr_last_line_of_user_dev / tkr_compact_rows_*_dev.) 0.1.20: K9 tkr_bpr_foldin (user vectors for new histories against frozen item factors; csrc/foldin.hip). 0.1.19: K8 tkr_like_ranks + tkr_like_ranks_workspace_bytes (filtered rank of every liked test column; csrc/like_ranks.hip). 0.1.18: K4 second form of bound-and-refine (csrc/topk_refine.hip; tkr_topk_workspace_bytes_for grows by the pieces' packed lists), any k (bpr_wide_kernel, score_topk_wide_kernel), tkr_lab_build; tkr_topk_set_finish is gone, tkr_topk_set_math(0) and tkr_vbpr_set_pairs(1 | 2) need the lab library. 0.1.17: tkr_vbpr_set_pairs (tkr_vbpr_workspace_floats + 64). 0.1.16: tkr_topk_set_finish (larger tkr_topk_workspace_bytes), tkr_bpr_own_plan_run plans inside the step's launch. 0.1.15: tkr_bpr_own_owners_shared; tkr_bpr_run takes `rec` non-const. 0.1.14: per-task loss sums instead of atomics on loss_out (larger tkr_vbpr_workspace_floats; K2 writes word 15 of its records). 0.1.13: tkr_bpr_own_plan_run, K4 to k = 768. 0.1.12: tkr_bpr_own_run_between. 0.1.11: K2o (tkr_sample_plan_owned, tkr_bpr_own_run: item rows owned by one workgroup each, resident in its LDS); prec[5] = last batch of the call that updated the row. 0.1.10: tkr_topk_workspace_bytes_for (K4 stages pre-converted fp16 tiles). 0.1.9: tkr_vbpr_colplan + tkr_vbpr_run_cols (VBPR in three launches per batch). 0.1.8: tkr_sync_flow_* (exchange of the granule tables). 0.1.7: K4 bound-and-refine arithmetic (tkr_topk_set_math(2), the default; larger tkr_topk_workspace_bytes); K2f leaves its ticket words zero. 0.1.6: K2f persistent dataflow step, tkr_plan_rollback, batches above 8192 */
 #define TKR_OK 0
 #define TKR_E_INVAL (-1)
 #define TKR_E_UNSUPPORTED (-2)
@@ -669,6 +669,49 @@ int tkr_matrix_emit_dev(const void* text, int64_t n_bytes, int64_t chunk_bytes, 
                         int64_t* counts, void* stream);
 int tkr_matrix_token_host(const char* tok, int64_t len, float* out);
 int tkr_matrix_tokens_host(const char* text, int64_t n_bytes, const int64_t* start, int64_t n, float* out);
+
+/* ---- K15: parsed ratings -> CSR rows on the device (csrc/group_dev.hip) ---------------------------------------------------------
+ * What evaluate._group builds for rows that arrive grouped.  A SOURCE is a set of n_seg segments over n_entries entries: segment g is
+ * the entries [seg_ptr[g], seg_ptr[g + 1]) of item (and like) -- the lines of a parsed ratings file (seg_ptr = line_ptr of
+ * tkr_ratings_emit_dev) or the rows of a CSR -- and seg_of_row[r] names the segment that feeds row r: -1 none, NULL the identity
+ * (then n_seg >= n_rows).  An entry counts when item >= 0 and, with like_only != 0, like == 1 (like may be NULL without like_only).
+ * Row r of the result is the ascending, duplicate-free union of the counted items of its segment in each of the n_src (1 or 2)
+ * sources; ptr is the 64-bit exclusive prefix of the row sizes.  All pointers but `src` itself are device pointers.
+ *
+ * Two calls with one read-back between them, because cols is sized by what the first one counts:
+ *   tkr_group_count_dev   ptr int64[n_rows + 1]; totals (device int64[2]) = {ptr[n_rows], status}
+ *   tkr_group_emit_dev    with the SAME sources and ptr: cols int32[n_out], n_out = ptr[n_rows]; status (device int64)
+ * A row's set is a bitmap of n_cols bits in LDS (no sort): one wave per row while n_cols <= TKR_GROUP_WAVE_COLS, one workgroup per row
+ * up to TKR_GROUP_MAX_COLS (what the 160 KB of a CU hold); above that both return TKR_E_UNSUPPORTED.  Rows of any length run.
+ * The input is not trusted.  status: -1, or the smallest 4 * index + kind of what was refused: kind 0 -- seg_of_row[index] outside
+ * [-1, n_seg); 1 -- seg_ptr decreases at segment `index`, or leaves [0, n_entries] (every segment is checked; kind 1 with a row as
+ * index when the row met it first); 2 -- row `index` holds a counted item >= n_cols; 3 (emit) -- ptr is not the ptr of these
+ * sources at row `index`.  What is refused is never used as an index; the outputs are then not to be used.  Deterministic.
+ *
+ *   tkr_last_line_of_user_dev   last int64[n_users]: the largest line i with line_user[i] == u, -1 where none (a line_user outside
+ *                               [0, n_users) belongs to nobody)
+ *   tkr_compact_rows_count_dev  pos int64[n_rows + 1]: exclusive count of the rows of the CSR `ptr` with at least one element;
+ *                               pos[n_rows] = n_kept, which the caller reads back
+ *   tkr_compact_rows_emit_dev   rows int64[n_kept]: those rows, ascending; out_ptr int64[n_kept + 1]: the ptr of the CSR that keeps
+ *                               only them (the same cols); status: -1, or 4 * row + 3 when pos is not the pos of this ptr
+ * Arguments are checked before any device access (TKR_E_INVAL: a NULL that is not allowed, n_rows / n_cols / n_lines / n_users < 1). */
+#define TKR_GROUP_WAVE_COLS 32768
+#define TKR_GROUP_MAX_COLS 1308672
+typedef struct tkr_group_source {
+    const int64_t* seg_ptr;    /* [n_seg + 1] */
+    const int32_t* item;       /* [n_entries] */
+    const int32_t* like;       /* [n_entries] or NULL */
+    const int64_t* seg_of_row; /* [n_rows] or NULL */
+    int64_t n_seg, n_entries;
+} tkr_group_source;
+int tkr_group_count_dev(const tkr_group_source* src, int32_t n_src, int64_t n_rows, int32_t n_cols, int32_t like_only,
+                        int64_t* ptr, int64_t* totals, void* stream);
+int tkr_group_emit_dev(const tkr_group_source* src, int32_t n_src, int64_t n_rows, int32_t n_cols, int32_t like_only,
+                       const int64_t* ptr, int32_t* cols, int64_t n_out, int64_t* status, void* stream);
+int tkr_last_line_of_user_dev(const int32_t* line_user, int64_t n_lines, int64_t n_users, int64_t* last, void* stream);
+int tkr_compact_rows_count_dev(const int64_t* ptr, int64_t n_rows, int64_t* pos, void* stream);
+int tkr_compact_rows_emit_dev(const int64_t* ptr, const int64_t* pos, int64_t n_rows, int64_t n_kept, int64_t* rows,
+                              int64_t* out_ptr, int64_t* status, void* stream);
 
 #ifdef __cplusplus
 }

@@ -10,7 +10,8 @@ Same inputs: ``DATA/uid``, ``DATA/vid``, ``DATA/f{fold}tr.txt``, ``MODEL/final-U
 
 What runs where: the text files are parsed by the native host parsers of libtkr_hip.so
 (textio.py; one pass per file, flat arrays instead of dicts of sets -- SURVEY.md §8f n2; the
-'%f ' matrices keep a binary ``.npy`` copy beside them, n1); the scores, the rated-item filter,
+'%f ' matrices keep a binary ``.npy`` copy beside them, n1); the flat arrays are grouped into the like / rated / seen CSRs on the host or, from
+TKR_GROUP_DEVICE_FROM parsed entries upward, on the GPU (K15, ``TKR_GROUP=host|device|auto``: the same arrays); the scores, the rated-item filter,
 the top-``total`` selection (K4) and the hit counting (K5) run on the GPU -- the
 [n_users, n_items] score matrix and its argsort (evaluate.py:78-81) are never materialised.
 
@@ -89,13 +90,39 @@ def _group(rows, cols, n_rows, n_cols):
     return ptr, (key % n_cols).astype(np.int32)
 
 
-def load_scenario(data_dir, fold, scenario, uids, umap=None):
+def load_scenario(data_dir, fold, scenario, uids, umap=None, where=None):
+    """the Scenario of one test file.  where / TKR_GROUP: 'host' -- the arrays are grouped by numpy; 'device' -- by K15
+    (tkr_hip.group_segments), and the Scenario also carries them as device tensors (``dev``) for K4 / K5 / K8; 'auto' (the default) -- the
+    device when a GPU is visible, the two files hold at least TKR_GROUP_DEVICE_FROM entries, the arrays fit and the id list has at most
+    tkr_hip.GROUP_MAX_COLS ids, else the host.  Same arrays, same KeyErrors either way"""
+    where = textio._group_where(where)
     umap = umap or textio.IdMap(uids)
     teids = read_ids(os.path.join(data_dir, 'f%dte.%s.idl' % (fold, scenario)))
     temap = textio.IdMap(teids)
     n_te = max(len(teids), 1)
     te_path = os.path.join(data_dir, 'f%dte.%s.txt' % (fold, scenario))
-    T = textio.parse_ratings(te_path, umap, temap)
+    hist_path = os.path.join(data_dir, 'f%dtr.txt' % fold)
+    T = H = None
+    if textio.group_on_device(where, textio._group_device_from() if where == 'auto' else 0, n_te):      # 'auto': a GPU and an id list that fits
+        T = textio.parse_ratings_for_group(te_path, umap, temap, where)
+        n = textio.n_entries_of(T)
+        if where == 'auto' and n < textio._group_device_from():
+            try:                                                     # 'auto' decides by both files; what is wrong with the train file is
+                H = textio.parse_ratings_for_group(hist_path, umap, temap, where)       # raised where the host path raises it
+                n += textio.n_entries_of(H)
+            except (OSError, ValueError):
+                H = None
+        if textio.group_on_device(where, n, n_te):
+            try:
+                sc = _load_scenario_device(T, H, te_path, hist_path, teids, temap, n_te, uids, umap, where)
+                textio.group_counts['device'] += 1
+                return sc
+            except textio.DeviceGroupTooLarge:
+                if where == 'device':
+                    raise
+        T, H = textio.ratings_to_host(T), None if H is None else textio.ratings_to_host(H)
+    textio.group_counts['host'] += 1
+    T = textio.parse_ratings(te_path, umap, temap) if T is None else T
     liked = T.like == 1
     if np.any(liked & (T.item < 0)):
         raise KeyError('%s likes an id that is not in the scenario id list' % te_path)        # teids[vid], :93
@@ -107,8 +134,7 @@ def load_scenario(data_dir, fold, scenario, uids, umap=None):
     like_ptr = np.zeros(len(lines) + 1, dtype=np.int64)
     np.cumsum(np.diff(lptr_all)[lines], out=like_ptr[1:])
     # history: the LAST train line of a user is its rated set (rated[uid] = set() per line, :34)
-    hist_path = os.path.join(data_dir, 'f%dtr.txt' % fold)
-    H = textio.parse_ratings(hist_path, umap, temap)
+    H = textio.parse_ratings(hist_path, umap, temap) if H is None else H
     n_users = max(int(max(uids.values())) + 1 if uids else 0, 1)
     last = np.full(n_users, -1, dtype=np.int64)
     known = np.flatnonzero(H.line_user >= 0)
@@ -126,6 +152,53 @@ def load_scenario(data_dir, fold, scenario, uids, umap=None):
     sptr_all, scols_all = _group(T.entry_line[known], T.item[known], len(T.line_user), n_te)
     seen_ptr, seen_cols = _take_rows(sptr_all, scols_all, lines)
     return Scenario(teids, users, like_ptr, lcols, rated_ptr, rated_cols, seen_ptr, seen_cols)
+
+
+def _load_scenario_device(T, H, te_path, hist_path, teids, temap, n_te, uids, umap, where, timing=None):
+    """load_scenario with the grouping on the GPU (K15): T (and H, when 'auto' has parsed it already) are Ratings or RatingsDevice.  The
+    checks are the host path's, in its order, each computed on the device and read back as one word.  timing: a dict that receives the
+    seconds of 'download', the seven arrays to numpy at the end (scripts/time_group.py)"""
+    dev = T.item.device if isinstance(T, textio.RatingsDevice) else torch.device('cuda', torch.cuda.current_device())
+    T = textio.ratings_to_device(T, dev)
+    n_lines, n_entries = int(T.line_user.numel()), int(T.item.numel())
+    textio.group_fits(8 * n_entries + 40 * n_lines + 64, dev, 'the CSRs of %s' % te_path)
+    lptr_all, lcols = tkr_hip.group_segments([(T.line_ptr, T.item, T.like, None)], n_lines, n_te, like_only=True)
+    lines, like_ptr = tkr_hip.scenario_lines(lptr_all)               # len(likes) != 0, :95
+    users = T.line_user[lines].to(torch.int64)
+    bad = torch.stack([((T.like == 1) & (T.item < 0)).any(), (users < 0).any()]).tolist()
+    if bad[0]:
+        raise KeyError('%s likes an id that is not in the scenario id list' % te_path)        # teids[vid], :93
+    if bad[1]:
+        raise KeyError('%s: test user missing from the uid list' % te_path)                   # uids[uid], :98
+    H = textio.ratings_to_device(textio.parse_ratings_for_group(hist_path, umap, temap, where) if H is None else H, dev)
+    n_users = max(int(max(uids.values())) + 1 if uids else 0, 1)
+    last = tkr_hip.last_line_of_user(H.line_user, n_users)           # the LAST train line of a user is its rated set, :34
+    hl = last[users]
+    if bool((hl < 0).any().item()):
+        raise KeyError('%s: test user without a line in %s' % (te_path, hist_path))           # rated[uid], :98
+    n = int(lines.numel())
+    textio.group_fits(4 * int(H.item.numel()) + 4 * n_entries + 16 * n + 64, dev, 'the CSRs of %s' % te_path)
+    rated_ptr, rated_cols = tkr_hip.group_segments([(H.line_ptr, H.item, None, hl.contiguous())], n, n_te)
+    seen_ptr, seen_cols = tkr_hip.group_segments([(T.line_ptr, T.item, None, lines)], n, n_te)
+    if timing is not None:
+        import time
+        torch.cuda.synchronize(dev)
+        t0 = time.perf_counter()
+    host = [t.cpu().numpy() for t in (users, like_ptr, lcols, rated_ptr, rated_cols, seen_ptr, seen_cols)]
+    if timing is not None:
+        timing['download'] = time.perf_counter() - t0
+    sc = Scenario(teids, *host)
+    sc.dev = dict(users=users, like_ptr=like_ptr, like_cols=lcols, rated_ptr=rated_ptr, rated_cols=rated_cols, seen_ptr=seen_ptr,
+                  seen_cols=seen_cols)
+    return sc
+
+
+def _on_device(sc, device, *names):
+    """the arrays `names` of a Scenario on `device`: the tensors K15 left there, else uploaded"""
+    kept = getattr(sc, 'dev', None)
+    if kept is not None and kept[names[0]].device == torch.device(device):
+        return tuple(kept[n] for n in names)
+    return tuple(torch.from_numpy(getattr(sc, n)).to(device) for n in names)
 
 
 def _take_rows(ptr, cols, rows):
@@ -146,8 +219,8 @@ def _scenario_operands(vmat, bmat, vids, sc, device):
     bias = None
     if bmat is not None:
         bias = torch.from_numpy(np.ascontiguousarray(bmat.reshape(-1)[te_rows])).to(device)
-    user_idx = torch.from_numpy(sc.users.astype(np.int32)).to(device)
-    rptr, rcols = torch.from_numpy(sc.rated_ptr).to(device), torch.from_numpy(sc.rated_cols).to(device)
+    users, rptr, rcols = _on_device(sc, device, 'users', 'rated_ptr', 'rated_cols')
+    user_idx = users.to(torch.int32)
     mask, pitch = tkr_hip.build_rated_mask(rptr, rcols, len(sc.users), len(sc.teids))
     return Vt, bias, user_idx, mask, pitch
 
@@ -193,7 +266,7 @@ def evaluate_loaded(umat_dev, vmat, bmat, vids, full, step, total, device):
     hits = np.zeros(interval, dtype=np.int64)
     if len(sc.users):
         ids = rank_scenario(umat_dev, vmat, bmat, vids, sc, total, device)
-        lptr, lcols = torch.from_numpy(sc.like_ptr).to(device), torch.from_numpy(sc.like_cols).to(device)
+        lptr, lcols = _on_device(sc, device, 'like_ptr', 'like_cols')
         hits = tkr_hip.count_hits(ids, lptr, lcols, step, interval).cpu().numpy()
     tcount = sc.tcount
     if world > 1:
@@ -216,7 +289,7 @@ def rank_metrics_loaded(umat_dev, vmat, bmat, vids, full, step, total, metrics, 
     ranks = np.zeros(0, dtype=np.int32)
     if len(sc.users):
         Vt, bias, user_idx, mask, pitch = _scenario_operands(vmat, bmat, vids, sc, device)
-        lptr, lcols = torch.from_numpy(sc.like_ptr).to(device), torch.from_numpy(sc.like_cols).to(device)
+        lptr, lcols = _on_device(sc, device, 'like_ptr', 'like_cols')
         ranks = tkr_hip.like_ranks(umat_dev, Vt, lptr, lcols, bias=bias, user_idx=user_idx, mask=mask, mask_pitch=pitch).cpu().numpy()
     sums = rankmetrics.rank_sums(ranks, sc.like_ptr, sc.rated_ptr, len(sc.teids), step, total)
     if world > 1:

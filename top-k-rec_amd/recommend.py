@@ -84,10 +84,37 @@ def rated_csr(R, rows_of_user, n_rows, n_items):
     return _group(np.concatenate(rr), np.concatenate(cc), n_rows, n_items)
 
 
-def candidate_lines(path, umap, vmap, n_items):
+def _rated_csr_device(sources, user_rows, n_items, dev):
+    """rated_csr (and the union over a second file) by K15 -> (ptr, cols) on the device.  sources: parsed ratings files"""
+    n = len(user_rows)
+    rows = torch.from_numpy(np.asarray(user_rows, dtype=np.int64)).to(dev)
+    n_users = int(max(user_rows)) + 1 if n else 0
+    segs = []
+    for R in sources:
+        Rd = textio.ratings_to_device(R, dev)
+        last = tkr_hip.last_line_of_user(Rd.line_user, n_users)      # a user without a line: -1, excludes nothing
+        segs.append((Rd.line_ptr, Rd.item, None, last[rows].contiguous()))
+    textio.group_fits(4 * sum(int(s[1].numel()) for s in segs) + 8 * n + 64, dev, 'the excluded items')
+    return tkr_hip.group_segments(segs, n, max(n_items, 1))
+
+
+def candidate_lines(path, umap, vmap, n_items, where=None):
     """the lines of the candidates file whose uid `umap` knows -> (known: bool per line of the file, the user index of each known line,
-    and the CSR of their known items: ascending, unique)"""
+    and the CSR of their known items: ascending, unique).  where / TKR_GROUP: which code groups them (textio.group_on_device)"""
+    where = textio._group_where(where)
     Cf = textio.parse_ratings(path, umap, vmap)
+    if textio.group_on_device(where, len(Cf.item), max(n_items, 1)):
+        try:
+            dev = torch.device('cuda', torch.cuda.current_device())
+            Cd = textio.ratings_to_device(Cf, dev)
+            lines = torch.nonzero(Cd.line_user >= 0).reshape(-1)
+            ptr, cols = tkr_hip.group_segments([(Cd.line_ptr, Cd.item, None, lines)], int(lines.numel()), max(n_items, 1))
+            textio.group_counts['device'] += 1
+            return Cf.line_user >= 0, Cd.line_user[lines].to(torch.int64).cpu().numpy(), ptr.cpu().numpy(), cols.cpu().numpy()
+        except textio.DeviceGroupTooLarge:
+            if where == 'device':
+                raise
+    textio.group_counts['host'] += 1
     lines = np.flatnonzero(Cf.line_user >= 0)
     row_of_line = np.full(len(Cf.line_user), -1, dtype=np.int64)
     row_of_line[lines] = np.arange(len(lines))
@@ -96,22 +123,37 @@ def candidate_lines(path, umap, vmap, n_items):
     return Cf.line_user >= 0, Cf.line_user[lines].astype(np.int64), ptr, cols
 
 
-def rank(U_dev, user_rows, V_dev, bias_dev, R, total, also_rated=None, candidates=None, on_device=False):
+def rank(U_dev, user_rows, V_dev, bias_dev, R, total, also_rated=None, candidates=None, on_device=False, where=None):
     """top-`total` unrated items of the users `user_rows` (indices into U_dev and into R's user numbering); `also_rated`: a second
     parsed ratings file in the same numbering whose lines exclude items too; `candidates`: (ptr, cols), a CSR over the ranked rows --
     then only these items of a row are ranked (K12) instead of the catalogue (K4)
-    -> (ids int32 [n, total], scores fp32 [n, total]) as numpy, with on_device=True as tensors left on the GPU"""
+    -> (ids int32 [n, total], scores fp32 [n, total]) as numpy, with on_device=True as tensors left on the GPU.  where / TKR_GROUP:
+    which code builds the excluded-items CSR (textio.group_on_device); on the device it goes to the mask without a download"""
+    where = textio._group_where(where)
     n, n_items = len(user_rows), int(V_dev.shape[0])
-    rows_of_user = {}
-    for row, user in enumerate(user_rows):
-        rows_of_user.setdefault(int(user), []).append(row)
-    ptr, cols = rated_csr(R, rows_of_user, n, n_items)
-    if also_rated is not None:
-        ptr2, cols2 = rated_csr(also_rated, rows_of_user, n, n_items)
-        rows = np.concatenate([np.repeat(np.arange(n), np.diff(ptr)), np.repeat(np.arange(n), np.diff(ptr2))])
-        ptr, cols = _group(rows, np.concatenate([cols, cols2]).astype(np.int64), n, n_items)
     dev = V_dev.device
-    mask, pitch = tkr_hip.build_rated_mask(torch.from_numpy(ptr).to(dev), torch.from_numpy(cols).to(dev), n, n_items)
+    sources = [R] if also_rated is None else [R, also_rated]
+    ptr_dev = None
+    if n and textio.group_on_device(where, sum(textio.n_entries_of(S) for S in sources), n_items):
+        try:
+            ptr_dev, cols_dev = _rated_csr_device(sources, user_rows, n_items, dev)
+            textio.group_counts['device'] += 1
+        except textio.DeviceGroupTooLarge:
+            if where == 'device':
+                raise
+    if ptr_dev is None:
+        textio.group_counts['host'] += 1
+        rows_of_user = {}
+        for row, user in enumerate(user_rows):
+            rows_of_user.setdefault(int(user), []).append(row)
+        R, also_rated = textio.ratings_to_host(R), None if also_rated is None else textio.ratings_to_host(also_rated)
+        ptr, cols = rated_csr(R, rows_of_user, n, n_items)
+        if also_rated is not None:
+            ptr2, cols2 = rated_csr(also_rated, rows_of_user, n, n_items)
+            rows = np.concatenate([np.repeat(np.arange(n), np.diff(ptr)), np.repeat(np.arange(n), np.diff(ptr2))])
+            ptr, cols = _group(rows, np.concatenate([cols, cols2]).astype(np.int64), n, n_items)
+        ptr_dev, cols_dev = torch.from_numpy(ptr).to(dev), torch.from_numpy(cols).to(dev)
+    mask, pitch = tkr_hip.build_rated_mask(ptr_dev, cols_dev, n, n_items)
     idx = torch.from_numpy(np.asarray(user_rows, dtype=np.int32)).to(dev)
     if candidates is not None:
         cptr, ccols = torch.from_numpy(candidates[0]).to(dev), torch.from_numpy(candidates[1]).to(dev)
@@ -167,6 +209,8 @@ def main(argv=None):
     parser.add_argument('--seed', type=int, default=0)
     parser.add_argument('--format', default=None, choices=textio.FORMAT_WHERE,
                         help="Where the output lines are formatted (default: TKR_FORMAT, else auto: on the GPU from TKR_FORMAT_DEVICE_FROM list entries upward)")
+    parser.add_argument('--group', default=None, choices=textio.GROUP_WHERE,
+                        help="Where the excluded items and the candidates are grouped into rows (default: TKR_GROUP, else auto: on the GPU from TKR_GROUP_DEVICE_FROM parsed entries upward)")
     args = parser.parse_args(argv)
     if (args.new_uid is None) != (args.new_history is None):
         parser.error('--new-uid and --new-history go together')
@@ -209,8 +253,8 @@ def main(argv=None):
     wrote = False                                                   # one output file: the model users' lines, then the new users'
     cand_model = cand_new = None
     if args.candidates is not None:
-        cand_model = candidate_lines(args.candidates, textio.IdMap(uids), vmap, len(vmat))
-        cand_new = candidate_lines(args.candidates, textio.IdMap(new_uids), vmap, len(vmat)) if new_uids else None
+        cand_model = candidate_lines(args.candidates, textio.IdMap(uids), vmap, len(vmat), where=args.group)
+        cand_new = candidate_lines(args.candidates, textio.IdMap(new_uids), vmap, len(vmat), where=args.group) if new_uids else None
         stray = np.flatnonzero(~(cand_model[0] | cand_new[0]) if cand_new else ~cand_model[0])
         if len(stray):
             with open(args.candidates) as fh:
@@ -223,7 +267,7 @@ def main(argv=None):
         umat = read_matrix(os.path.join(args.model, 'final-U.dat'), uids)
         R = textio.parse_ratings(os.path.join(args.data, 'f%dtr.txt' % args.fold), textio.IdMap(uids), vmap)
         ids, scores = rank(torch.from_numpy(umat).to(device), [uids[u] for u in users], V_dev, bias_dev, R, args.total, also_rated=R_new_items,
-                           candidates=cand_model[2:] if cand_model else None, on_device=True)
+                           candidates=cand_model[2:] if cand_model else None, on_device=True, where=args.group)
         tokens, rows = row_tokens(users)
         textio.write_lists(args.output, tokens, ids, scores, rows, vmap, where=args.format)
         wrote = True
@@ -239,7 +283,7 @@ def main(argv=None):
             new_users = [tok[int(x)] for x in cand_new[1]]
         if new_users:
             ids, scores = rank(torch.from_numpy(U_new).to(device), [new_uids[u] for u in new_users], V_dev, bias_dev, R, args.total,
-                               candidates=cand_new[2:] if cand_new else None, on_device=True)
+                               candidates=cand_new[2:] if cand_new else None, on_device=True, where=args.group)
             tokens, rows = row_tokens(new_users)
             textio.write_lists(args.output, tokens, ids, scores, rows, vmap, where=args.format, append=wrote)
             wrote = True

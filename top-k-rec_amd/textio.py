@@ -9,6 +9,8 @@
     read_matrix(path, where=None)     '%f ' text matrix -> fp32 [lines, cols]   (+ stamped .npy copy)
     read_matrix_device(path, device=None, chunk_bytes=None)
                                       the same array read by HIP kernels, left on the device
+    parse_ratings_for_group(path, users, items, where)
+                                      the arrays of parse_ratings where the grouping (K15) wants them: host or device
     write_matrix(path, array, where=None)
                                       fp32 array -> '%f ' text, byte-identical to utils.py:47-55
     write_lists(path, users, ids, scores, row_user, items, where=None, block_bytes=None, append=False)
@@ -36,6 +38,13 @@ token exactly; the tokens it cannot (exponent forms, inf, nan, more than 19 digi
 check from the mapped file and patched in.  A file in any other layout is read by the host reader as a whole, so both readers
 return the same array bit for bit and raise TextFormatError for the same files.  'auto' (the default) -- the device for files of
 at least TKR_MATRIX_DEVICE_FROM bytes when a GPU is visible and the text fits beside its outputs, else the host.
+
+Which code groups parsed arrays into CSR rows (``where`` / TKR_GROUP; evaluate.load_scenario, recommend.rank, recommend.candidate_lines):
+'host' -- numpy (evaluate._group), needs no GPU; 'device' -- K15 (csrc/group_dev.hip, tkr_hip.group_segments): the arrays K11 left on
+the GPU, or the uploaded arrays of a stamped copy, are grouped there and the CSRs go to the kernels that read them without a download;
+'auto' (the default) -- the device from TKR_GROUP_DEVICE_FROM parsed entries upward when a GPU is visible, the arrays fit and a row's
+bitmap of columns fits LDS (tkr_hip.GROUP_MAX_COLS), else the host.  Both build the same arrays and raise the same errors;
+``group_counts`` tells which ran.
 
 Which writer formats a matrix or the lists (``where`` / TKR_FORMAT): 'host' -- tkr_matrix_write / format_lines, needs no GPU; 'device'
 -- the text is formatted on the GPU (K13, csrc/format_dev.hip) in blocks of at most ``block_bytes``, each downloaded and appended to
@@ -181,19 +190,28 @@ def _device_from():
     return int(os.environ.get('TKR_PARSE_DEVICE_FROM', '') or PARSE_DEVICE_FROM)
 
 
-def parse_ratings(path: str, users, items, where=None) -> Ratings:
-    where = _parse_where(where)
-    users = users if isinstance(users, IdMap) else IdMap(users)
-    items = items if isinstance(items, IdMap) else IdMap(items)
+def _cached_ratings(path, users, items):
+    """-> (the stamp the text carries now, or None when copies are off; the arrays of its valid stamped copy, or None)"""
     cache = path + '.csr.npz'
     stamp = _stamp(path, users.digest + '/' + items.digest) if _cache_enabled() else None
     if stamp is not None and os.path.isfile(cache):
         try:
             with np.load(cache, allow_pickle=False) as z:
                 if str(z['stamp']) == stamp:
-                    return Ratings(z['line_user'], z['line_ptr'], z['item'], z['like'])
+                    return stamp, Ratings(z['line_user'], z['line_ptr'], z['item'], z['like'])
         except (OSError, ValueError, KeyError):
             pass
+    return stamp, None
+
+
+def parse_ratings(path: str, users, items, where=None) -> Ratings:
+    where = _parse_where(where)
+    users = users if isinstance(users, IdMap) else IdMap(users)
+    items = items if isinstance(items, IdMap) else IdMap(items)
+    cache = path + '.csr.npz'
+    stamp, cached = _cached_ratings(path, users, items)
+    if cached is not None:
+        return cached
     out = None
     if where == 'device' or (where == 'auto' and torch.cuda.is_available() and os.path.getsize(path) >= _device_from()):
         try:
@@ -272,6 +290,75 @@ def _parse_ratings(path, users, items) -> Ratings:
     finally:
         lib.tkr_ratings_destroy(h)
     return Ratings(line_user, line_ptr, item, like)
+
+
+# ---- K15: where the parsed arrays are grouped into CSRs (evaluate.load_scenario, recommend.rank / candidate_lines) --------------------
+DeviceGroupTooLarge = tkr_hip.DeviceGroupTooLarge
+GROUP_WHERE = ('host', 'device', 'auto')
+GROUP_DEFAULT = 'auto'
+GROUP_DEVICE_FROM = 262144           # entries: 'auto' groups fewer on the host (TKR_GROUP_DEVICE_FROM; DESIGN.md §4 K15 has the sweep)
+group_counts = {'host': 0, 'device': 0}      # scenarios / rated sets / candidate files grouped per path in this process (what 'auto' chose)
+
+
+def _group_where(where):
+    where = os.environ.get('TKR_GROUP', '') or GROUP_DEFAULT if where is None else where
+    if where not in GROUP_WHERE:
+        raise ValueError('where / TKR_GROUP must be one of %s, got %r' % (', '.join(GROUP_WHERE), where))
+    return where
+
+
+def _group_device_from():
+    return int(os.environ.get('TKR_GROUP_DEVICE_FROM', '') or GROUP_DEVICE_FROM)
+
+
+def group_on_device(where, n_entries, n_cols):
+    """whether K15 groups `n_entries` parsed entries over `n_cols` columns: 'device' -- yes, and without a GPU that raises; 'auto' -- with
+    a GPU, from TKR_GROUP_DEVICE_FROM entries upward, while a row's bitmap fits (tkr_hip.GROUP_MAX_COLS); 'host' -- no"""
+    if where == 'device' and not torch.cuda.is_available():
+        raise tkr_hip.TkrError('grouping on the device runs through libtkr_hip.so; no MI355X is visible')
+    return where == 'device' or (where == 'auto' and torch.cuda.is_available() and n_entries >= _group_device_from()
+                                 and n_cols <= tkr_hip.GROUP_MAX_COLS)
+
+
+def group_fits(need, device, what):
+    """K15 keeps the parsed arrays beside the CSRs it writes: raise DeviceGroupTooLarge unless `need` more bytes fit"""
+    free = torch.cuda.mem_get_info(device)[0]
+    if need > free:
+        raise DeviceGroupTooLarge('%s needs %d bytes of device memory, %d are free' % (what, need, free))
+
+
+def n_entries_of(R):
+    return int(R.item.numel()) if isinstance(R, RatingsDevice) else int(len(R.item))
+
+
+def ratings_to_device(R, device=None) -> RatingsDevice:
+    """a Ratings uploaded (a RatingsDevice is returned as it is)"""
+    if isinstance(R, RatingsDevice):
+        return R
+    device = torch.device('cuda', torch.cuda.current_device()) if device is None else torch.device(device)
+    group_fits(12 * len(R.item) + 20 * len(R.line_user) + 64, device, 'the parsed arrays')
+    return RatingsDevice(*(torch.from_numpy(np.ascontiguousarray(a)).to(device) for a in (R.line_user, R.line_ptr, R.item, R.like)))
+
+
+def ratings_to_host(R) -> Ratings:
+    return R.host() if isinstance(R, RatingsDevice) else R
+
+
+def parse_ratings_for_group(path: str, users, items, where):
+    """the arrays of parse_ratings where the grouping wants them -> Ratings or RatingsDevice.  A valid stamped copy is answered from the
+    host as always; otherwise, when K11 parses the file (TKR_PARSE 'device', or 'auto' and a file of TKR_PARSE_DEVICE_FROM bytes -- under
+    where='device' any file), its arrays stay on the device and no copy is written; everything else is parse_ratings itself"""
+    users = users if isinstance(users, IdMap) else IdMap(users)
+    items = items if isinstance(items, IdMap) else IdMap(items)
+    if where != 'host' and torch.cuda.is_available() and _cached_ratings(path, users, items)[1] is None:
+        parser = _parse_where(None)
+        if parser == 'device' or (parser == 'auto' and (where == 'device' or os.path.getsize(path) >= _device_from())):
+            try:
+                return _parse_ratings_device(path, users, items)
+            except DeviceParseTooLarge:
+                if parser == 'device':
+                    raise
+    return parse_ratings(path, users, items)
 
 
 def _parse_matrix(path):

@@ -87,7 +87,8 @@ EXPORTS = ('tkr_version', 'tkr_plan_team', 'tkr_plan_max_blocks', 'tkr_sample_pl
            'tkr_sync_flow_unpack', 'tkr_like_ranks', 'tkr_bpr_foldin', 'tkr_bpr_foldin_items', 'tkr_idtable_build', 'tkr_ratings_count_dev',
            'tkr_ratings_emit_dev', 'tkr_rank_candidates', 'tkr_lists_format_sizes_dev', 'tkr_lists_format_emit_dev',
            'tkr_matrix_format_sizes_dev', 'tkr_matrix_format_emit_dev', 'tkr_matrix_count_dev', 'tkr_matrix_emit_dev', 'tkr_matrix_token_host',
-           'tkr_matrix_tokens_host')
+           'tkr_matrix_tokens_host', 'tkr_group_count_dev', 'tkr_group_emit_dev', 'tkr_last_line_of_user_dev', 'tkr_compact_rows_count_dev',
+           'tkr_compact_rows_emit_dev')
 EXPORTS_I64 = ('tkr_vbpr_workspace_floats', 'tkr_vbpr_colplan_lds_bytes', 'tkr_topk_workspace_bytes_for', 'tkr_topk_workspace_bytes', 'tkr_plan_workspace_bytes', 'tkr_like_ranks_workspace_bytes',
                'tkr_parse_dev_workspace_bytes', 'tkr_idtable_slots', 'tkr_scan_dev_workspace_bytes')
 
@@ -874,6 +875,132 @@ def matrix_tokens_host(text, start):
     rc = lib().tkr_matrix_tokens_host(C.c_void_p(text.ctypes.data), C.c_int64(text.size), C.c_void_p(start.ctypes.data), C.c_int64(len(start)),
                                       C.c_void_p(out.ctypes.data))
     return rc, out
+
+
+# ---- K15: parsed ratings -> CSR rows on the device (csrc/group_dev.hip) ----------------------------------------------------------
+GROUP_WAVE_COLS = 32768      # TKR_GROUP_WAVE_COLS of include/tkr.h: up to here a wave builds a row, above it a workgroup
+GROUP_MAX_COLS = 1308672     # TKR_GROUP_MAX_COLS: the bitmap of one row must fit the LDS of one workgroup
+_GROUP_REFUSED = ('seg_of_row[%d] is outside [-1, n_seg)', 'seg_ptr decreases or leaves [0, len(item)] at segment / row %d',
+                  'row %d holds an item >= n_cols', 'ptr does not describe the sources at row %d')
+
+
+class DeviceGroupTooLarge(TkrError):
+    """more columns than the bitmap of one row can hold in LDS (GROUP_MAX_COLS), or arrays that do not fit the free memory of the
+    device ('auto' then groups on the host)"""
+
+
+class GroupSource(C.Structure):
+    """mirror of tkr_group_source (include/tkr.h)"""
+    _fields_ = [('seg_ptr', C.c_void_p), ('item', C.c_void_p), ('like', C.c_void_p), ('seg_of_row', C.c_void_p), ('n_seg', C.c_int64),
+                ('n_entries', C.c_int64)]
+
+
+def _group_tensor(what, name, t, dtype, device, optional=False):
+    if t is None and optional:
+        return
+    if not isinstance(t, torch.Tensor):
+        raise TypeError('%s: %s must be a tensor' % (what, name))
+    if t.dtype != dtype:
+        raise TypeError('%s: %s must be %s, not %s' % (what, name, dtype, t.dtype))
+    if t.dim() != 1 or not t.is_contiguous():
+        raise ValueError('%s: %s must be contiguous and one-dimensional' % (what, name))
+    if not t.is_cuda or (device is not None and t.device != device):
+        raise ValueError('%s: %s must live on the GPU%s, not on %s' % (what, name, '' if device is None else ' that holds seg_ptr', t.device))
+
+
+def _group_status(word, what):
+    if word != -1:
+        raise ValueError('%s: %s' % (what, _GROUP_REFUSED[word & 3] % (word >> 2)))
+
+
+def group_segments(sources, n_rows, n_cols, like_only=False):
+    """K15 -> (ptr int64 [n_rows + 1], cols int32 [ptr[-1]]) on the device: row r is the ascending, duplicate-free union of the counted
+    items of its segments.  sources: one or two tuples (seg_ptr int64 [n_seg + 1], item int32, like int32 | None, seg_of_row int64
+    [n_rows] | None) of device tensors; seg_of_row[r] is the segment that feeds row r, -1 none, None the identity.  An entry counts
+    when item >= 0 and, with like_only, like == 1 (include/tkr.h).  Input the kernels refuse raises ValueError, more than
+    GROUP_MAX_COLS columns DeviceGroupTooLarge"""
+    what = 'group_segments'
+    sources = list(sources)
+    if not 1 <= len(sources) <= 2:
+        raise ValueError('%s: one or two sources required, got %d' % (what, len(sources)))
+    n_rows, n_cols = int(n_rows), int(n_cols)
+    if n_rows < 0 or n_cols < 1:
+        raise ValueError('%s: n_rows >= 0 and n_cols >= 1 required' % what)
+    device = None
+    structs = (GroupSource * len(sources))()
+    for k, source in enumerate(sources):
+        if not isinstance(source, (tuple, list)) or len(source) != 4:
+            raise TypeError('%s: a source is (seg_ptr, item, like | None, seg_of_row | None)' % what)
+        seg_ptr, item, like, seg_of_row = source
+        _group_tensor(what, 'seg_ptr', seg_ptr, torch.int64, device)
+        device = seg_ptr.device
+        _group_tensor(what, 'item', item, torch.int32, device)
+        _group_tensor(what, 'like', like, torch.int32, device, optional=True)
+        _group_tensor(what, 'seg_of_row', seg_of_row, torch.int64, device, optional=True)
+        n_seg, n_entries = int(seg_ptr.numel()) - 1, int(item.numel())
+        if n_seg < 0:
+            raise ValueError('%s: seg_ptr must hold n_seg + 1 >= 1 entries' % what)
+        if like is None and like_only:
+            raise ValueError('%s: like_only needs the like array of every source' % what)
+        if like is not None and like.numel() != n_entries:
+            raise ValueError('%s: item and like must have one length' % what)
+        if seg_of_row is None and n_seg < n_rows:
+            raise ValueError('%s: without seg_of_row a source needs a segment per row (%d < %d)' % (what, n_seg, n_rows))
+        if seg_of_row is not None and seg_of_row.numel() != n_rows:
+            raise ValueError('%s: seg_of_row must hold n_rows = %d entries' % (what, n_rows))
+        structs[k] = GroupSource(seg_ptr.data_ptr(), item.data_ptr() if n_entries else None, like.data_ptr() if like is not None and n_entries else None,
+                                 seg_of_row.data_ptr() if seg_of_row is not None and n_rows else None, n_seg, n_entries)
+    if n_cols > GROUP_MAX_COLS:
+        raise DeviceGroupTooLarge('%s: %d columns, the bitmap of a row holds at most %d' % (what, n_cols, GROUP_MAX_COLS))
+    ptr = torch.zeros(n_rows + 1, dtype=torch.int64, device=device)
+    if n_rows == 0:
+        return ptr, torch.empty(0, dtype=torch.int32, device=device)
+    totals = torch.empty(2, dtype=torch.int64, device=device)
+    args = (C.byref(structs), C.c_int32(len(sources)), C.c_int64(n_rows), C.c_int32(n_cols), C.c_int32(1 if like_only else 0))
+    _call('tkr_group_count_dev', ptr, *args, _p(ptr), _p(totals))
+    total, word = totals.tolist()                                   # the one round trip: cols is sized by it
+    _group_status(word, what)
+    cols = torch.empty(total, dtype=torch.int32, device=device)
+    status = torch.empty(1, dtype=torch.int64, device=device)
+    _call('tkr_group_emit_dev', ptr, *args, _p(ptr), _p(cols) if total else C.c_void_p(0), C.c_int64(total), _p(status))
+    _group_status(int(status.item()), what)
+    return ptr, cols
+
+
+def last_line_of_user(line_user, n_users):
+    """-> int64 [n_users] on the device: the last line of every user in line_user (int32 [n_lines], -1 = unknown user), -1 = no line"""
+    what = 'last_line_of_user'
+    _group_tensor(what, 'line_user', line_user, torch.int32, None)
+    n_users = int(n_users)
+    if n_users < 0:
+        raise ValueError('%s: n_users >= 0 required' % what)
+    last = torch.full((n_users,), -1, dtype=torch.int64, device=line_user.device)
+    if n_users and line_user.numel():
+        _call('tkr_last_line_of_user_dev', line_user, _p(line_user), C.c_int64(line_user.numel()), C.c_int64(n_users), _p(last))
+    return last
+
+
+def scenario_lines(ptr):
+    """the rows of the CSR `ptr` (device int64 [n_rows + 1]) with at least one element -> (rows int64 [n_kept], ascending; the ptr
+    int64 [n_kept + 1] of the CSR that keeps only them -- its cols are the same array)"""
+    what = 'scenario_lines'
+    _group_tensor(what, 'ptr', ptr, torch.int64, None)
+    n_rows = int(ptr.numel()) - 1
+    if n_rows < 0:
+        raise ValueError('%s: ptr must hold n_rows + 1 >= 1 entries' % what)
+    dev = ptr.device
+    if n_rows == 0:
+        return torch.empty(0, dtype=torch.int64, device=dev), ptr.clone()
+    pos = torch.empty(n_rows + 1, dtype=torch.int64, device=dev)
+    _call('tkr_compact_rows_count_dev', ptr, _p(ptr), C.c_int64(n_rows), _p(pos))
+    n_kept = int(pos[-1].item())                                    # the one round trip
+    rows = torch.empty(n_kept, dtype=torch.int64, device=dev)
+    out_ptr = torch.empty(n_kept + 1, dtype=torch.int64, device=dev)
+    status = torch.empty(1, dtype=torch.int64, device=dev)
+    _call('tkr_compact_rows_emit_dev', ptr, _p(ptr), _p(pos), C.c_int64(n_rows), C.c_int64(n_kept), _p(rows) if n_kept else C.c_void_p(0),
+          _p(out_ptr), _p(status))
+    _group_status(int(status.item()), what)
+    return rows, out_ptr
 
 
 # ---- per-epoch exchange of replicated tables (csrc/sync.hip) ----------------------------------------
