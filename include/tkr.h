@@ -31,7 +31,7 @@
 extern "C" {
 #endif
 
-#define TKR_VERSION 120 /* (additions that change no existing entry point keep the number: K10 tkr_bpr_foldin_items, K11 tkr_ratings_*_dev, K12 tkr_rank_candidates, K13 tkr_lists_format_* / tkr_matrix_format_*, K15 tkr_group_*_dev / tkr_last_line_of_user_dev / tkr_compact_rows_*_dev.) 0.1.20: K9 tkr_bpr_foldin (user vectors for new histories against frozen item factors; csrc/foldin.hip). 0.1.19: K8 tkr_like_ranks + tkr_like_ranks_workspace_bytes (filtered rank of every liked test column; csrc/like_ranks.hip). 0.1.18: K4 second form of bound-and-refine (csrc/topk_refine.hip; tkr_topk_workspace_bytes_for grows by the pieces' packed lists), any k (bpr_wide_kernel, score_topk_wide_kernel), tkr_lab_build; tkr_topk_set_finish is gone, tkr_topk_set_math(0) and tkr_vbpr_set_pairs(1 | 2) need the lab library. 0.1.17: tkr_vbpr_set_pairs (tkr_vbpr_workspace_floats + 64). 0.1.16: tkr_topk_set_finish (larger tkr_topk_workspace_bytes), tkr_bpr_own_plan_run plans inside the step's launch. 0.1.15: tkr_bpr_own_owners_shared; tkr_bpr_run takes `rec` non-const. 0.1.14: per-task loss sums instead of atomics on loss_out (larger tkr_vbpr_workspace_floats; K2 writes word 15 of its records). 0.1.13: tkr_bpr_own_plan_run, K4 to k = 768. 0.1.12: tkr_bpr_own_run_between. 0.1.11: K2o (tkr_sample_plan_owned, tkr_bpr_own_run: item rows owned by one workgroup each, resident in its LDS); prec[5] = last batch of the call that updated the row. 0.1.10: tkr_topk_workspace_bytes_for (K4 stages pre-converted fp16 tiles). 0.1.9: tkr_vbpr_colplan + tkr_vbpr_run_cols (VBPR in three launches per batch). 0.1.8: tkr_sync_flow_* (exchange of the granule tables). 0.1.7: K4 bound-and-refine arithmetic (tkr_topk_set_math(2), the default; larger tkr_topk_workspace_bytes); K2f leaves its ticket words zero. 0.1.6: K2f persistent dataflow step, tkr_plan_rollback, batches above 8192 */
+#define TKR_VERSION 120 /* (additions that change no existing entry point keep the number: K10 tkr_bpr_foldin_items, K11 tkr_ratings_*_dev, K12 tkr_rank_candidates, K13 tkr_lists_format_* / tkr_matrix_format_*, K15 tkr_group_*_dev / tkr_last_line_of_user_dev / tkr_compact_rows_*_dev, K16 tkr_fusion_*.) 0.1.20: K9 tkr_bpr_foldin (user vectors for new histories against frozen item factors; csrc/foldin.hip). 0.1.19: K8 tkr_like_ranks + tkr_like_ranks_workspace_bytes (filtered rank of every liked test column; csrc/like_ranks.hip). 0.1.18: K4 second form of bound-and-refine (csrc/topk_refine.hip; tkr_topk_workspace_bytes_for grows by the pieces' packed lists), any k (bpr_wide_kernel, score_topk_wide_kernel), tkr_lab_build; tkr_topk_set_finish is gone, tkr_topk_set_math(0) and tkr_vbpr_set_pairs(1 | 2) need the lab library. 0.1.17: tkr_vbpr_set_pairs (tkr_vbpr_workspace_floats + 64). 0.1.16: tkr_topk_set_finish (larger tkr_topk_workspace_bytes), tkr_bpr_own_plan_run plans inside the step's launch. 0.1.15: tkr_bpr_own_owners_shared; tkr_bpr_run takes `rec` non-const. 0.1.14: per-task loss sums instead of atomics on loss_out (larger tkr_vbpr_workspace_floats; K2 writes word 15 of its records). 0.1.13: tkr_bpr_own_plan_run, K4 to k = 768. 0.1.12: tkr_bpr_own_run_between. 0.1.11: K2o (tkr_sample_plan_owned, tkr_bpr_own_run: item rows owned by one workgroup each, resident in its LDS); prec[5] = last batch of the call that updated the row. 0.1.10: tkr_topk_workspace_bytes_for (K4 stages pre-converted fp16 tiles). 0.1.9: tkr_vbpr_colplan + tkr_vbpr_run_cols (VBPR in three launches per batch). 0.1.8: tkr_sync_flow_* (exchange of the granule tables). 0.1.7: K4 bound-and-refine arithmetic (tkr_topk_set_math(2), the default; larger tkr_topk_workspace_bytes); K2f leaves its ticket words zero. 0.1.6: K2f persistent dataflow step, tkr_plan_rollback, batches above 8192 */
 #define TKR_OK 0
 #define TKR_E_INVAL (-1)
 #define TKR_E_UNSUPPORTED (-2)
@@ -712,6 +712,54 @@ int tkr_last_line_of_user_dev(const int32_t* line_user, int64_t n_lines, int64_t
 int tkr_compact_rows_count_dev(const int64_t* ptr, int64_t n_rows, int64_t* pos, void* stream);
 int tkr_compact_rows_emit_dev(const int64_t* ptr, const int64_t* pos, int64_t n_rows, int64_t n_kept, int64_t* rows,
                               int64_t* out_ptr, int64_t* status, void* stream);
+
+/* ---- K16: the weights of a linear fusion of several trained models (csrc/fusion.hip) ----------------------------------------------
+ * Replaces the learning half of the reference's old/methods/bfusion.py + ranking_fusion.py and efusion.py.  (Serving a fused model
+ * needs no entry point: top-k-rec_amd/fusion.py concatenates the tables.)  The models arrive in one struct: n_models <= 16 table pairs
+ * over the same n_users and n_items, each with its own width k (= its row pitch) and an optional bias [n_items].  All pointers inside
+ * are device pointers; the struct itself is read on the host.
+ * The per-model score s_m(u, c) is the score of tkr_rank_candidates / tkr_score_topk bit for bit (csrc/topk_parts.h exact_score: the
+ * fma chain with the two k-halves interleaved, fl(acc + bias), -0.0 -> +0.0; oracle/ref_np.py mfma_chain_scores), one lane per score.
+ *
+ *   tkr_fusion_features      triplet g = first_triplet + t, t < count, is K1's draw (tkr_sample_plan's stream under `seed`:
+ *                            oracle/plan_np.py sample_triplets) on the CSR tr_users / row_ptr / pos_cols / cols_sorted;
+ *                            D_out[t, m] = fl(s_m(u, i) - s_m(u, j)), fp32 [count, n_models]; trip_out (nullable) int32 [count, 3] =
+ *                            (u, i, j).  A lane per triplet; no atomics, no workspace.  A drawn id outside the tables is never used
+ *                            as an index (the row of D is NaN).
+ *   tkr_fusion_sgd           the loop of ranking_fusion.py:48-54 on D [n_rows, n_models]: for batch z = 0 .. n_batches-1 (rows
+ *                            [z * batch, (z + 1) * batch); n_batches * batch <= n_rows), with x_t = sum_m W[m] D[t, m] (an fma chain, m
+ *                            ascending) on the W from before the update:
+ *                              loss_out[z] = sum_t log(1 + e^-x_t) + lambda_w / 2 * sum_m W[m]^2         (nullable)
+ *                              W[m] += lr * (sum_t sigma(-x_t) D[t, m] - lambda_w W[m])
+ *                            W fp32 [n_models] in/out.  ONE workgroup walks the batches; every sum goes through one fixed tree (DPP
+ *                            inside a wave, the waves in wave order), and the thread of a row depends on the row's place in its batch
+ *                            alone: two runs give the same bits, and so does a call cut into calls of whole batches with W carried.
+ *   tkr_fusion_user_weights  efusion.py:57-82 on the CSR of the users' training likes (like_ptr int64 [n_users + 1] from 0, like_cols
+ *                            int32, a SET per row):  r[u, m] = sqrt(sum_{c in likes(u)} (s_m(u, c) - 1)^2 / max(|likes(u)|, 1)),
+ *                            w[u, m] = exp(-(r[u, m] - mean_m r[u, .])), and 1.0 where that mean is exactly 0 (an empty row; the
+ *                            reference leaves 0 there).  rmse_out, w_out fp32 [n_users, n_models].  A wave per user, rows of any
+ *                            length.  A column outside [0, n_items) is never dereferenced (the user's figures are NaN).
+ * Arguments are checked before any device access and before any launch (TKR_E_INVAL): a NULL that is not allowed, n_models outside
+ * [1, 16], a model without U or V or with k < 1, n_items / n_users that differ from the struct's, count / batch / n_batches < 1,
+ * n_batches * batch > n_rows. */
+#define TKR_FUSION_MAX_MODELS 16
+typedef struct tkr_fusion_model {
+    const float* U;    /* [n_users, k] */
+    const float* V;    /* [n_items, k] */
+    const float* bias; /* [n_items] or NULL */
+    int32_t k, reserved;
+} tkr_fusion_model;
+typedef struct tkr_fusion_models {
+    tkr_fusion_model m[TKR_FUSION_MAX_MODELS];
+    int32_t n_models, n_users, n_items, reserved;
+} tkr_fusion_models;
+int tkr_fusion_features(const tkr_fusion_models* models, const int32_t* tr_users, int32_t n_tr, const int32_t* row_ptr,
+                        const int32_t* pos_cols, const int32_t* cols_sorted, int32_t n_items, uint64_t seed, uint64_t first_triplet,
+                        int64_t count, float* D_out, int32_t* trip_out, void* stream);
+int tkr_fusion_sgd(const float* D, int64_t n_rows, int32_t n_models, int32_t batch, int64_t n_batches, float lr, float lambda_w, float* W,
+                   float* loss_out, void* stream);
+int tkr_fusion_user_weights(const tkr_fusion_models* models, const int64_t* like_ptr, const int32_t* like_cols, int32_t n_users,
+                            float* rmse_out, float* w_out, void* stream);
 
 #ifdef __cplusplus
 }

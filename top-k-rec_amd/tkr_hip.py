@@ -88,7 +88,7 @@ EXPORTS = ('tkr_version', 'tkr_plan_team', 'tkr_plan_max_blocks', 'tkr_sample_pl
            'tkr_ratings_emit_dev', 'tkr_rank_candidates', 'tkr_lists_format_sizes_dev', 'tkr_lists_format_emit_dev',
            'tkr_matrix_format_sizes_dev', 'tkr_matrix_format_emit_dev', 'tkr_matrix_count_dev', 'tkr_matrix_emit_dev', 'tkr_matrix_token_host',
            'tkr_matrix_tokens_host', 'tkr_group_count_dev', 'tkr_group_emit_dev', 'tkr_last_line_of_user_dev', 'tkr_compact_rows_count_dev',
-           'tkr_compact_rows_emit_dev')
+           'tkr_compact_rows_emit_dev', 'tkr_fusion_features', 'tkr_fusion_sgd', 'tkr_fusion_user_weights')
 EXPORTS_I64 = ('tkr_vbpr_workspace_floats', 'tkr_vbpr_colplan_lds_bytes', 'tkr_topk_workspace_bytes_for', 'tkr_topk_workspace_bytes', 'tkr_plan_workspace_bytes', 'tkr_like_ranks_workspace_bytes',
                'tkr_parse_dev_workspace_bytes', 'tkr_idtable_slots', 'tkr_scan_dev_workspace_bytes')
 
@@ -1001,6 +1001,146 @@ def scenario_lines(ptr):
           _p(out_ptr), _p(status))
     _group_status(int(status.item()), what)
     return rows, out_ptr
+
+
+# ---- K16: the weights of a linear fusion of several models (csrc/fusion.hip) -------------------------------------------------------
+FUSION_MAX_MODELS = 16       # TKR_FUSION_MAX_MODELS of include/tkr.h
+
+
+class FusionModel(C.Structure):
+    """mirror of tkr_fusion_model (include/tkr.h)"""
+    _fields_ = [('U', C.c_void_p), ('V', C.c_void_p), ('bias', C.c_void_p), ('k', C.c_int32), ('reserved', C.c_int32)]
+
+
+class FusionModels(C.Structure):
+    """mirror of tkr_fusion_models (include/tkr.h)"""
+    _fields_ = [('m', FusionModel * FUSION_MAX_MODELS), ('n_models', C.c_int32), ('n_users', C.c_int32), ('n_items', C.c_int32),
+                ('reserved', C.c_int32)]
+
+
+def _fusion_table(what, name, t, dim):
+    if not isinstance(t, torch.Tensor):
+        raise TkrError('%s: %s must be a tensor' % (what, name))
+    if t.dtype != torch.float32:
+        raise TkrError('%s: %s must be torch.float32, not %s' % (what, name, t.dtype))
+    if not t.is_contiguous():
+        raise TkrError('%s: %s must be contiguous' % (what, name))
+    if dim is not None and t.dim() != dim:
+        raise TkrError('%s: %s must have %d dimensions' % (what, name, dim))
+
+
+def _fusion_int(what, name, t, dtype, device):
+    if not isinstance(t, torch.Tensor) or t.dtype != dtype or t.dim() != 1 or not t.is_contiguous():
+        raise TkrError('%s: %s must be a contiguous one-dimensional %s tensor' % (what, name, dtype))
+    if not t.is_cuda or t.device != device:
+        raise TkrError('%s: %s must live on the GPU that holds the models, not on %s' % (what, name, t.device))
+
+
+def fusion_models(what, models):
+    """a list of (U [n_users, k_m], V [n_items, k_m], bias [n_items] | [n_items, 1] | None) -> (FusionModels, n_users, n_items, device).
+    Refuses with TkrError, the tensors' properties first (no device access): more than FUSION_MAX_MODELS models, a table that is not
+    fp32 or not contiguous, row counts or widths that do not match, tensors that are not on one GPU."""
+    models = list(models)
+    if not 1 <= len(models) <= FUSION_MAX_MODELS:
+        raise TkrError('%s: 1 .. %d models required, got %d' % (what, FUSION_MAX_MODELS, len(models)))
+    st = FusionModels()
+    n_users = n_items = None
+    for m, model in enumerate(models):
+        if not isinstance(model, (tuple, list)) or len(model) != 3:
+            raise TkrError('%s: a model is (U, V, bias | None)' % what)
+        U, V, b = model
+        _fusion_table(what, 'U of model %d' % m, U, 2)
+        _fusion_table(what, 'V of model %d' % m, V, 2)
+        if b is not None:
+            _fusion_table(what, 'bias of model %d' % m, b, None)
+        if U.shape[1] != V.shape[1] or U.shape[1] < 1:
+            raise TkrError('%s: U and V of model %d must share k >= 1 (%d, %d)' % (what, m, U.shape[1], V.shape[1]))
+        if n_users is None:
+            n_users, n_items = int(U.shape[0]), int(V.shape[0])
+        if int(U.shape[0]) != n_users or int(V.shape[0]) != n_items or n_users < 1 or n_items < 1:
+            raise TkrError('%s: model %d has %d user and %d item rows, model 0 has %d and %d' % (what, m, U.shape[0], V.shape[0], n_users, n_items))
+        if b is not None and b.numel() != n_items:
+            raise TkrError('%s: the bias of model %d must hold one value per item' % (what, m))
+    device = models[0][0].device
+    for m, model in enumerate(models):
+        for t in model:
+            if t is not None and (not t.is_cuda or t.device != device):
+                raise TkrError('%s: the tables of model %d must live on one GPU, not on %s' % (what, m, t.device))
+        U, V, b = model
+        st.m[m] = FusionModel(U.data_ptr(), V.data_ptr(), b.data_ptr() if b is not None else None, int(U.shape[1]), 0)
+    st.n_models, st.n_users, st.n_items = len(models), n_users, n_items
+    return st, n_users, n_items, device
+
+
+def fusion_features(models, csr, n_items, seed, first_triplet, count, want_triplets=False):
+    """K16 -> D fp32 [count, M] on the device (with want_triplets also int32 [count, 3]): triplet first_triplet + t of K1's stream
+    under `seed` on the training CSR `csr` (tr_users, row_ptr, pos_cols, cols_sorted: single/_engine.py TrainingCSR),
+    D[t, m] = fl(s_m(u, i) - s_m(u, j)) on the score bits of rank_candidates (include/tkr.h tkr_fusion_features)"""
+    what = 'fusion_features'
+    st, n_users, n_items_m, device = fusion_models(what, models)
+    count = int(count)
+    if int(n_items) != n_items_m:
+        raise TkrError('%s: n_items = %d, the models have %d item rows' % (what, n_items, n_items_m))
+    if count < 1:
+        raise TkrError('%s: count >= 1 required' % what)
+    for name in ('tr_users', 'row_ptr', 'pos_cols', 'cols_sorted'):
+        _fusion_int(what, name, getattr(csr, name), torch.int32, device)
+    if csr.row_ptr.numel() != n_users + 1 or csr.tr_users.numel() < 1:
+        raise TkrError('%s: the CSR must describe the models\' %d users and hold at least one row' % (what, n_users))
+    M = st.n_models
+    D = torch.empty((count, M), dtype=torch.float32, device=device)
+    trip = torch.empty((count, 3), dtype=torch.int32, device=device) if want_triplets else None
+    _call('tkr_fusion_features', D, C.byref(st), _p(csr.tr_users), C.c_int32(csr.tr_users.numel()), _p(csr.row_ptr), _p(csr.pos_cols),
+          _p(csr.cols_sorted), C.c_int32(n_items), C.c_uint64(int(seed) & 0xFFFFFFFFFFFFFFFF), C.c_uint64(int(first_triplet)),
+          C.c_int64(count), _p(D), _p(trip))
+    return (D, trip) if want_triplets else D
+
+
+def fusion_sgd(D, batch, n_batches, lr, lambda_w, W, want_loss=False):
+    """K16: n_batches steps of ranking_fusion.py:48-54 on the rows of D [n_rows, M], batch after batch from row 0; W fp32 [M] is
+    updated in place -> W (with want_loss: (W, loss fp32 [n_batches])).  One workgroup, bitwise repeatable, and the same bits whether
+    the batches run in one call or in several with W carried across (include/tkr.h tkr_fusion_sgd)"""
+    what = 'fusion_sgd'
+    _fusion_table(what, 'D', D, 2)
+    _fusion_table(what, 'W', W, 1)
+    n_rows, M = int(D.shape[0]), int(D.shape[1])
+    batch, n_batches = int(batch), int(n_batches)
+    if not 1 <= M <= FUSION_MAX_MODELS:
+        raise TkrError('%s: 1 .. %d models required, D has %d columns' % (what, FUSION_MAX_MODELS, M))
+    if batch < 1:
+        raise TkrError('%s: batch >= 1 required, got %d' % (what, batch))
+    if W.numel() != M:
+        raise TkrError('%s: W must hold one weight per column of D (%d, %d)' % (what, W.numel(), M))
+    if n_batches < 0 or n_batches * batch > n_rows:
+        raise TkrError('%s: %d batches of %d rows do not fit the %d rows of D' % (what, n_batches, batch, n_rows))
+    if not D.is_cuda or W.device != D.device:
+        raise TkrError('%s: D and W must live on one GPU' % what)
+    loss = torch.empty(n_batches, dtype=torch.float32, device=D.device) if want_loss else None
+    if n_batches:
+        _call('tkr_fusion_sgd', D, _p(D), C.c_int64(n_rows), C.c_int32(M), C.c_int32(batch), C.c_int64(n_batches), C.c_float(lr),
+              C.c_float(lambda_w), _p(W), _p(loss))
+    return (W, loss) if want_loss else W
+
+
+def fusion_user_weights(models, like_ptr, like_cols):
+    """K16 -> (rmse fp32 [n_users, M], w fp32 [n_users, M]) on the device: efusion.py:57-82 on the CSR of the users' training likes
+    (like_ptr int64 [n_users + 1] from 0, like_cols int32, a set per row: foldin.liked_csr) -- include/tkr.h tkr_fusion_user_weights"""
+    what = 'fusion_user_weights'
+    st, n_users, n_items, device = fusion_models(what, models)
+    _fusion_int(what, 'like_ptr', like_ptr, torch.int64, device)
+    _fusion_int(what, 'like_cols', like_cols, torch.int32, device)
+    if like_ptr.numel() != n_users + 1:
+        raise TkrError('%s: like_ptr must hold n_users + 1 = %d entries' % (what, n_users + 1))
+    nnz = int(like_cols.numel())
+    if not (int(like_ptr[0]) == 0 and int(like_ptr[-1]) == nnz and bool((like_ptr[1:] >= like_ptr[:-1]).all())):
+        raise TkrError('%s: like_ptr must run from 0 to len(like_cols) = %d and never decrease' % (what, nnz))
+    if nnz == 0:
+        like_cols = torch.zeros(1, dtype=torch.int32, device=device)      # never read: every row is empty
+    M = st.n_models
+    rmse = torch.empty((n_users, M), dtype=torch.float32, device=device)
+    w = torch.empty((n_users, M), dtype=torch.float32, device=device)
+    _call('tkr_fusion_user_weights', rmse, C.byref(st), _p(like_ptr), _p(like_cols), C.c_int32(n_users), _p(rmse), _p(w))
+    return rmse, w
 
 
 # ---- per-epoch exchange of replicated tables (csrc/sync.hip) ----------------------------------------
