@@ -31,7 +31,7 @@
 extern "C" {
 #endif
 
-#define TKR_VERSION 120 /* (additions that change no existing entry point keep the number: K10 tkr_bpr_foldin_items, K11 tkr_ratings_*_dev, K12 tkr_rank_candidates, K13 tkr_lists_format_* / tkr_matrix_format_*, K15 tkr_group_*_dev / tkr_last_line_of_user_dev / tkr_compact_rows_*_dev, K16 tkr_fusion_*.) 0.1.20: K9 tkr_bpr_foldin (user vectors for new histories against frozen item factors; csrc/foldin.hip). 0.1.19: K8 tkr_like_ranks + tkr_like_ranks_workspace_bytes (filtered rank of every liked test column; csrc/like_ranks.hip). 0.1.18: K4 second form of bound-and-refine (csrc/topk_refine.hip; tkr_topk_workspace_bytes_for grows by the pieces' packed lists), any k (bpr_wide_kernel, score_topk_wide_kernel), tkr_lab_build; tkr_topk_set_finish is gone, tkr_topk_set_math(0) and tkr_vbpr_set_pairs(1 | 2) need the lab library. 0.1.17: tkr_vbpr_set_pairs (tkr_vbpr_workspace_floats + 64). 0.1.16: tkr_topk_set_finish (larger tkr_topk_workspace_bytes), tkr_bpr_own_plan_run plans inside the step's launch. 0.1.15: tkr_bpr_own_owners_shared; tkr_bpr_run takes `rec` non-const. 0.1.14: per-task loss sums instead of atomics on loss_out (larger tkr_vbpr_workspace_floats; K2 writes word 15 of its records). 0.1.13: tkr_bpr_own_plan_run, K4 to k = 768. 0.1.12: tkr_bpr_own_run_between. 0.1.11: K2o (tkr_sample_plan_owned, tkr_bpr_own_run: item rows owned by one workgroup each, resident in its LDS); prec[5] = last batch of the call that updated the row. 0.1.10: tkr_topk_workspace_bytes_for (K4 stages pre-converted fp16 tiles). 0.1.9: tkr_vbpr_colplan + tkr_vbpr_run_cols (VBPR in three launches per batch). 0.1.8: tkr_sync_flow_* (exchange of the granule tables). 0.1.7: K4 bound-and-refine arithmetic (tkr_topk_set_math(2), the default; larger tkr_topk_workspace_bytes); K2f leaves its ticket words zero. 0.1.6: K2f persistent dataflow step, tkr_plan_rollback, batches above 8192 */
+#define TKR_VERSION 120 /* (additions that change no existing entry point keep the number: K10 tkr_bpr_foldin_items, K11 tkr_ratings_*_dev, K12 tkr_rank_candidates, K13 tkr_lists_format_* / tkr_matrix_format_*, K15 tkr_group_*_dev / tkr_last_line_of_user_dev / tkr_compact_rows_*_dev, K16 tkr_fusion_*, K17 tkr_mmr_select / tkr_list_pair_sums.) 0.1.20: K9 tkr_bpr_foldin (user vectors for new histories against frozen item factors; csrc/foldin.hip). 0.1.19: K8 tkr_like_ranks + tkr_like_ranks_workspace_bytes (filtered rank of every liked test column; csrc/like_ranks.hip). 0.1.18: K4 second form of bound-and-refine (csrc/topk_refine.hip; tkr_topk_workspace_bytes_for grows by the pieces' packed lists), any k (bpr_wide_kernel, score_topk_wide_kernel), tkr_lab_build; tkr_topk_set_finish is gone, tkr_topk_set_math(0) and tkr_vbpr_set_pairs(1 | 2) need the lab library. 0.1.17: tkr_vbpr_set_pairs (tkr_vbpr_workspace_floats + 64). 0.1.16: tkr_topk_set_finish (larger tkr_topk_workspace_bytes), tkr_bpr_own_plan_run plans inside the step's launch. 0.1.15: tkr_bpr_own_owners_shared; tkr_bpr_run takes `rec` non-const. 0.1.14: per-task loss sums instead of atomics on loss_out (larger tkr_vbpr_workspace_floats; K2 writes word 15 of its records). 0.1.13: tkr_bpr_own_plan_run, K4 to k = 768. 0.1.12: tkr_bpr_own_run_between. 0.1.11: K2o (tkr_sample_plan_owned, tkr_bpr_own_run: item rows owned by one workgroup each, resident in its LDS); prec[5] = last batch of the call that updated the row. 0.1.10: tkr_topk_workspace_bytes_for (K4 stages pre-converted fp16 tiles). 0.1.9: tkr_vbpr_colplan + tkr_vbpr_run_cols (VBPR in three launches per batch). 0.1.8: tkr_sync_flow_* (exchange of the granule tables). 0.1.7: K4 bound-and-refine arithmetic (tkr_topk_set_math(2), the default; larger tkr_topk_workspace_bytes); K2f leaves its ticket words zero. 0.1.6: K2f persistent dataflow step, tkr_plan_rollback, batches above 8192 */
 #define TKR_OK 0
 #define TKR_E_INVAL (-1)
 #define TKR_E_UNSUPPORTED (-2)
@@ -760,6 +760,36 @@ int tkr_fusion_sgd(const float* D, int64_t n_rows, int32_t n_models, int32_t bat
                    float* loss_out, void* stream);
 int tkr_fusion_user_weights(const tkr_fusion_models* models, const int64_t* like_ptr, const int32_t* like_cols, int32_t n_users,
                             float* rmse_out, float* w_out, void* stream);
+
+/* ---- K17: diversify a pool into a list (greedy MMR) and the pair sums of list diversity (csrc/diversity.hip) ----------------------
+ * New design: the reference sorts every list by score alone.  Both entry points are built on the similarity of two entries of a row,
+ *   sim(a, b) = chain(S[id_a], S[id_b]),   S fp32 [n_items, k]: whatever the caller measures similarity in (row-normalised item factors
+ * for cosine, the factors themselves for dot; top-k-rec_amd/diversity.py prepare), chain = the mode-1 score of K4 / K12 without a bias
+ * (csrc/topk_parts.h exact_score; oracle/ref_np.py mfma_chain_scores): symmetric bit for bit.
+ *
+ *   tkr_mmr_select      ids int32 [n_rows, N]: a pool per row, valid up to the first negative id (the -1 padding of tkr_score_topk);
+ *                       rel fp32 [n_rows, N]: the relevance of every entry.  sel_pos int32 [n_rows, t]: pool POSITIONS in pick order,
+ *                       -1 where the row has fewer than t valid entries.  With lam32 = (float)lam, mu32 = 1.0f - lam32 (fp32) and
+ *                       a_e = fl(lam32 * rel_e) (one fp32 multiply, kept): pick 0 = argmax a_e; before pick r > 0, pen_e = the maximum
+ *                       over the r picked entries s of sim(e, s) (it may be negative), obj_e = fma(-mu32, pen_e, a_e), pick r = argmax
+ *                       of obj_e over the unpicked valid entries; every tie goes to the lower pool position (-0.0 counts as +0.0).
+ *                       t * N similarities per row, never an N x N matrix.  1 <= t <= N <= TKR_MMR_MAX_POOL (above: TKR_E_UNSUPPORTED).
+ *                       One workgroup per row, a thread per entry; the valid rows of S are staged once in LDS when N rows of it fit
+ *                       the 160 KB of a CU, otherwise both rows of every chain are read through L2; any k.
+ *   tkr_list_pair_sums  ids int32 [n_rows, t]: the final lists, the same prefix rule; pair_sum float64 [n_rows, t]:
+ *                       pair_sum[r, b] = sum over a < b of (1 - sim(a, b)), the subtraction and the sum (a ascending) in float64, 0
+ *                       behind the valid prefix.  Intra-list diversity at every cut-off is a prefix sum of a row.
+ *                       t <= TKR_MMR_MAX_POOL.
+ * An id >= n_items is never dereferenced: it ends its row like a negative id, and the row is reported in `status` (device int64[1],
+ * written by the call; K15's convention): -1, or 4 * row + 1 for the smallest such row (bit 0: an id outside the table).  Only the
+ * entry that ENDS a row is looked at; what follows it is ignored.  Arguments are checked before any device access and before any
+ * launch (TKR_E_INVAL): a null S / ids / rel / output / status, n_items / k / n_rows / N / t < 1, t > N, lam not finite or outside
+ * [0, 1].  Deterministic; no atomics but the status word's minimum.  S and every row of it 16-byte aligned when k % 8 == 0. */
+#define TKR_MMR_MAX_POOL 1024
+int tkr_mmr_select(const float* S, int32_t n_items, int32_t k, const int32_t* ids, const float* rel, int32_t n_rows, int32_t N,
+                   double lam, int32_t t, int32_t* sel_pos, int64_t* status, void* stream);
+int tkr_list_pair_sums(const float* S, int32_t n_items, int32_t k, const int32_t* ids, int32_t n_rows, int32_t t, double* pair_sum,
+                       int64_t* status, void* stream);
 
 #ifdef __cplusplus
 }

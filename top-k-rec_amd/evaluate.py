@@ -36,6 +36,12 @@ Stated differences from the reference:
     literature.  Every liked test column the user did not rate in training is ranked among N columns drawn without replacement from
     those the user neither rated in training nor has on that test line (rankmetrics.sample_negatives, seeded by S; all of them when
     fewer than N are eligible), by K12 (tkr_hip.rank_candidates).  ``hr`` exists only with ``--negatives``.
+  * ``-M ... ild cov gini`` (not in the reference) prints, after all of those, ``S.ild,...``, ``S.cov,...`` and ``S.gini,...``: the
+    intra-list diversity (1 - similarity of two items' factors, averaged over the pairs of a list and then over the lists), the share
+    of the scenario's id list the lists reach and the Gini index of item exposure, of the scenario's ordinary top-``total`` lists at
+    every cut-off step, 2 step, ... (K17, diversity.list_metrics).  ``--diversify LAMBDA [--pool N] [--similarity cosine|dot]`` adds,
+    after those, ``S.mmr.acc,...`` -- the accuracy lines' hit counting on the lists re-ranked by greedy MMR from the ``--pool`` best
+    (diversity.rerank) -- and ``S.mmr.ild`` / ``.cov`` / ``.gini`` for those of the three that ``-M`` names.  Single process only.
 """
 from __future__ import annotations
 
@@ -47,6 +53,7 @@ os.environ.setdefault('HSA_ENABLE_IPC_MODE_LEGACY', '0')     # multi-process GPU
 import numpy as np
 import torch
 
+import diversity
 import rankmetrics
 import textio
 import tkr_hip
@@ -349,6 +356,35 @@ def negative_metrics_loaded(umat_dev, vmat, bmat, vids, full, step, total, n_neg
     return rankmetrics.finish(sums, metrics)
 
 
+def list_metrics_loaded(umat_dev, vmat, bmat, vids, sc, step, total, metrics, div, device):
+    """the list metrics of an already parsed Scenario (single process) -> (plain, mmr): {metric: values at step, 2 step, ...} of the
+    ordinary top-`total` lists for the `metrics` of diversity.LIST_METRICS, and -- with div, the arguments of --diversify -- the same of
+    the lists K17 re-ranks out of the div['pool'] best, plus 'acc': K5's hit count on them as evaluate_loaded reports it (else None)"""
+    interval = total // step
+    grid = [step * (q + 1) for q in range(interval)]
+    plain = {m: [0.0] * interval for m in metrics}
+    mmr = dict(plain, acc=[0.0] * interval) if div else None
+    if not len(sc.users):
+        return plain, mmr
+    Vt, bias, user_idx, mask, pitch = _scenario_operands(vmat, bmat, vids, sc, device)
+    S = diversity.similarity_table(Vt, div['similarity'] if div else 'cosine')
+    n_cols = len(sc.teids)
+    ids, scores = tkr_hip.score_topk(umat_dev, Vt, div['pool'] if div else total, bias=bias, user_idx=user_idx, mask=mask, mask_pitch=pitch,
+                                     want_scores=True)
+    if metrics:
+        every = diversity.list_metrics(S, ids[:, :total].contiguous(), n_cols, grid)
+        plain = {m: every[m] for m in metrics}
+    if div:
+        picked, _ = diversity.rerank(S, diversity.relevance(ids, scores), ids, scores, div['diversify'], total)
+        lptr, lcols = _on_device(sc, device, 'like_ptr', 'like_cols')
+        hits = tkr_hip.count_hits(picked, lptr, lcols, step, interval).cpu().numpy()
+        mmr = {'acc': [float(h) / sc.tcount for h in hits]}
+        if metrics:
+            every = diversity.list_metrics(S, picked, n_cols, grid)
+            mmr.update({m: every[m] for m in metrics})
+    return plain, mmr
+
+
 def main(argv=None):
     parser = argparse.ArgumentParser(description="Evaluate weighted matrix factorization based methods.")
     parser.add_argument('-d', '--data', required=True, help="The data path for the evaluation")
@@ -357,12 +393,18 @@ def main(argv=None):
     parser.add_argument('-s', '--step', type=int, default=5, help="The number of evaluation step")
     parser.add_argument('-t', '--total', type=int, default=30, help="The number of total predictions")
     parser.add_argument('-sl', '--scenarios', nargs='+', default=None, help="The test scenario list")
-    parser.add_argument('-M', '--metrics', nargs='+', default=None, choices=rankmetrics.METRICS + ('hr',),
-                        help="Rank metrics from one full-rank pass, printed after the accuracy lines as S.metric,... (hr: only with --negatives)")
+    parser.add_argument('-M', '--metrics', nargs='+', default=None, choices=rankmetrics.METRICS + ('hr',) + diversity.LIST_METRICS,
+                        help="Rank metrics from one full-rank pass, printed after the accuracy lines as S.metric,... (hr: only with --negatives); "
+                             "ild cov gini: diversity, coverage and exposure Gini of the top-k lists")
     parser.add_argument('--negatives', type=int, default=None, metavar='N',
                         help="With -M: also rank every held-out like among N sampled unrated columns; prints S.negN.hr / .ndcg / .mrr")
     parser.add_argument('--neg-seed', type=int, default=0, help="The seed of the negatives' draw")
+    diversity.add_arguments(parser)
     args = parser.parse_args(argv)
+    div = diversity.check_arguments(parser, args)
+    list_metrics = [m for m in args.metrics or () if m in diversity.LIST_METRICS]
+    if (div or list_metrics) and int(os.environ.get('WORLD_SIZE', '1')) > 1:
+        parser.error('ild / cov / gini and --diversify look at whole lists and are not sharded over ranks yet: run them in a single process')
     if args.negatives is not None and not args.metrics:
         parser.error('--negatives needs -M (hr, ndcg and / or mrr)')
     if args.negatives is not None and args.negatives < 1:
@@ -386,9 +428,9 @@ def main(argv=None):
         bmat = read_matrix(os.path.join(args.model, 'final-B.dat'), vids)
     umat_dev = torch.from_numpy(umat).to(device)
     umap = textio.IdMap(uids)
-    results, extra, negs = {}, {}, {}
+    results, extra, negs, lists = {}, {}, {}, {}
     for scenario in args.scenarios:
-        if args.metrics:
+        if args.metrics or div:
             full = load_scenario(args.data, args.fold, scenario, uids, umap)
             acc = evaluate_loaded(umat_dev, vmat, bmat, vids, full, args.step, args.total, device)
             if scenario not in extra:                                # (a scenario listed twice: its metric lines are not doubled)
@@ -396,6 +438,8 @@ def main(argv=None):
                 if neg_metrics:
                     negs[scenario] = negative_metrics_loaded(umat_dev, vmat, bmat, vids, full, args.step, args.total, args.negatives,
                                                              args.neg_seed, neg_metrics, device)
+                if list_metrics or div:
+                    lists[scenario] = list_metrics_loaded(umat_dev, vmat, bmat, vids, full, args.step, args.total, list_metrics, div, device)
         else:
             acc = evaluate_scenario(umat_dev, vmat, bmat, uids, vids, args.data, args.fold, scenario, args.step, args.total, device, umap)
         if scenario not in results:                                  # evaluate.py:109-112 ACCUMULATES per scenario name: a scenario
@@ -417,6 +461,11 @@ def main(argv=None):
             lines.append('%s.neg%d.%s' % (scenario, args.negatives, m) + ''.join(',%.6f' % v for v in negs[scenario][m]))
             if rank == 0:
                 print(lines[-1])
+    for which, names in ((0, list_metrics), (1, (['acc'] + list_metrics) if div else [])):
+        for scenario in args.scenarios if names else ():
+            for m in names:
+                lines.append('%s.%s%s' % (scenario, 'mmr.' if which else '', m) + ''.join(',%.6f' % v for v in lists[scenario][which][m]))
+                print(lines[-1])                                     # (single process: refused above otherwise)
     if started_group:
         import torch.distributed as dist
         dist.destroy_process_group()

@@ -3,6 +3,7 @@
     python recommend.py -d DATA -m MODEL -f 0 -t 30 -o out.txt [-u USERS_FILE | --candidates FILE]
                         [--new-uid FILE --new-history FILE --fold-steps 50 --fold-triplets 16 --fold-lr 0.05 --fold-lu 2.5e-3 --seed 0]
                         [--new-vid FILE --new-ratings FILE --fold-li 2.5e-3 --fold-lj 2.5e-4 --fold-lb 0]
+                        [--diversify LAMBDA --pool 100 --similarity cosine|dot]
 
 Inputs as evaluate.py: ``DATA/uid``, ``DATA/vid``, ``DATA/f{fold}tr.txt`` (the histories), ``MODEL/final-U.dat``, ``final-V.dat``,
 optional ``final-B.dat``.  For every requested user -- the tokens of USERS_FILE, one per line; default: every line of ``uid`` -- the
@@ -31,6 +32,13 @@ candidates, the history excluded as always; a user may appear on several lines. 
 order, then those of the ``--new-uid`` users; a uid that is in neither id list raises KeyError.  After ``--new-vid`` the candidates are
 looked up in the grown catalogue.  Scores and order are those the full ranking gives the same items (K12, tkr_hip.rank_candidates).
 
+``--diversify LAMBDA`` (0 <= LAMBDA <= 1): every line is re-ranked by greedy Maximal Marginal Relevance (K17, diversity.py).  The
+``--pool`` best items of the line (default max(100, -t); at most 1024) are ranked as above, their scores scaled onto [0, 1] per line, and
+``-t`` of them are picked one by one, each time the item with the largest  LAMBDA * relevance - (1 - LAMBDA) * (its largest similarity to
+an item already picked);  ``--similarity``: the cosine (default) or the dot product of the item factors.  The format is unchanged and
+the scores are the model's own, so they are no longer monotone along a line.  LAMBDA = 1 writes the file written without the flag.
+It applies to every kind of line: model users, ``--new-uid``, ``--new-vid`` and ``--candidates``.
+
 The scores, the filter and the selection run on the GPU (tkr_hip.build_rated_mask, tkr_hip.score_topk); single process.
 """
 from __future__ import annotations
@@ -41,6 +49,7 @@ import os
 import numpy as np
 import torch
 
+import diversity
 import foldin
 import textio
 import tkr_hip
@@ -123,13 +132,21 @@ def candidate_lines(path, umap, vmap, n_items, where=None):
     return Cf.line_user >= 0, Cf.line_user[lines].astype(np.int64), ptr, cols
 
 
-def rank(U_dev, user_rows, V_dev, bias_dev, R, total, also_rated=None, candidates=None, on_device=False, where=None):
+def rank(U_dev, user_rows, V_dev, bias_dev, R, total, also_rated=None, candidates=None, on_device=False, where=None, diversify=None,
+         pool=None, similarity='cosine'):
     """top-`total` unrated items of the users `user_rows` (indices into U_dev and into R's user numbering); `also_rated`: a second
     parsed ratings file in the same numbering whose lines exclude items too; `candidates`: (ptr, cols), a CSR over the ranked rows --
     then only these items of a row are ranked (K12) instead of the catalogue (K4)
     -> (ids int32 [n, total], scores fp32 [n, total]) as numpy, with on_device=True as tensors left on the GPU.  where / TKR_GROUP:
-    which code builds the excluded-items CSR (textio.group_on_device); on the device it goes to the mask without a download"""
+    which code builds the excluded-items CSR (textio.group_on_device); on the device it goes to the mask without a download.
+    diversify: a lambda in [0, 1] -- the `pool` best (default diversity.default_pool(total)) are ranked instead and `total` of them
+    picked by greedy MMR under `similarity` (K17, diversity.rerank); the scores stay the model's own, in pick order"""
     where = textio._group_where(where)
+    want = total
+    if diversify is not None:
+        total = diversity.default_pool(want) if pool is None else int(pool)
+        if not want <= total <= tkr_hip.MMR_MAX_POOL:
+            raise ValueError('rank: the pool must hold between total = %d and %d entries, got %d' % (want, tkr_hip.MMR_MAX_POOL, total))
     n, n_items = len(user_rows), int(V_dev.shape[0])
     dev = V_dev.device
     sources = [R] if also_rated is None else [R, also_rated]
@@ -161,6 +178,9 @@ def rank(U_dev, user_rows, V_dev, bias_dev, R, total, also_rated=None, candidate
         ids, scores = tkr_hip.topk_from_ranks(cptr, ccols, s, r, total)
     else:
         ids, scores = tkr_hip.score_topk(U_dev, V_dev, total, bias=bias_dev, user_idx=idx, mask=mask, mask_pitch=pitch, want_scores=True)
+    if diversify is not None:
+        S, rel = diversity.prepare(V_dev, ids, scores, similarity)
+        ids, scores = diversity.rerank(S, rel, ids, scores, diversify, want)
     if on_device:
         return ids, scores
     return ids.cpu().numpy(), scores.cpu().numpy()
@@ -207,6 +227,7 @@ def main(argv=None):
     parser.add_argument('--fold-lj', type=float, default=2.5e-4)
     parser.add_argument('--fold-lb', type=float, default=0.0)
     parser.add_argument('--seed', type=int, default=0)
+    diversity.add_arguments(parser)
     parser.add_argument('--format', default=None, choices=textio.FORMAT_WHERE,
                         help="Where the output lines are formatted (default: TKR_FORMAT, else auto: on the GPU from TKR_FORMAT_DEVICE_FROM list entries upward)")
     parser.add_argument('--group', default=None, choices=textio.GROUP_WHERE,
@@ -220,6 +241,7 @@ def main(argv=None):
         parser.error('-t must be at least 1')
     if args.candidates is not None and args.users is not None:
         parser.error('--candidates names its users line by line: it does not go with -u')
+    div = diversity.check_arguments(parser, args)
 
     uids = read_ids(os.path.join(args.data, 'uid'))
     vids = read_ids(os.path.join(args.data, 'vid'))
@@ -267,7 +289,7 @@ def main(argv=None):
         umat = read_matrix(os.path.join(args.model, 'final-U.dat'), uids)
         R = textio.parse_ratings(os.path.join(args.data, 'f%dtr.txt' % args.fold), textio.IdMap(uids), vmap)
         ids, scores = rank(torch.from_numpy(umat).to(device), [uids[u] for u in users], V_dev, bias_dev, R, args.total, also_rated=R_new_items,
-                           candidates=cand_model[2:] if cand_model else None, on_device=True, where=args.group)
+                           candidates=cand_model[2:] if cand_model else None, on_device=True, where=args.group, **div)
         tokens, rows = row_tokens(users)
         textio.write_lists(args.output, tokens, ids, scores, rows, vmap, where=args.format)
         wrote = True
@@ -283,7 +305,7 @@ def main(argv=None):
             new_users = [tok[int(x)] for x in cand_new[1]]
         if new_users:
             ids, scores = rank(torch.from_numpy(U_new).to(device), [new_uids[u] for u in new_users], V_dev, bias_dev, R, args.total,
-                               candidates=cand_new[2:] if cand_new else None, on_device=True, where=args.group)
+                               candidates=cand_new[2:] if cand_new else None, on_device=True, where=args.group, **div)
             tokens, rows = row_tokens(new_users)
             textio.write_lists(args.output, tokens, ids, scores, rows, vmap, where=args.format, append=wrote)
             wrote = True

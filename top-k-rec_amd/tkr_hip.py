@@ -88,7 +88,8 @@ EXPORTS = ('tkr_version', 'tkr_plan_team', 'tkr_plan_max_blocks', 'tkr_sample_pl
            'tkr_ratings_emit_dev', 'tkr_rank_candidates', 'tkr_lists_format_sizes_dev', 'tkr_lists_format_emit_dev',
            'tkr_matrix_format_sizes_dev', 'tkr_matrix_format_emit_dev', 'tkr_matrix_count_dev', 'tkr_matrix_emit_dev', 'tkr_matrix_token_host',
            'tkr_matrix_tokens_host', 'tkr_group_count_dev', 'tkr_group_emit_dev', 'tkr_last_line_of_user_dev', 'tkr_compact_rows_count_dev',
-           'tkr_compact_rows_emit_dev', 'tkr_fusion_features', 'tkr_fusion_sgd', 'tkr_fusion_user_weights')
+           'tkr_compact_rows_emit_dev', 'tkr_fusion_features', 'tkr_fusion_sgd', 'tkr_fusion_user_weights',
+           'tkr_mmr_select', 'tkr_list_pair_sums')
 EXPORTS_I64 = ('tkr_vbpr_workspace_floats', 'tkr_vbpr_colplan_lds_bytes', 'tkr_topk_workspace_bytes_for', 'tkr_topk_workspace_bytes', 'tkr_plan_workspace_bytes', 'tkr_like_ranks_workspace_bytes',
                'tkr_parse_dev_workspace_bytes', 'tkr_idtable_slots', 'tkr_scan_dev_workspace_bytes')
 
@@ -1141,6 +1142,73 @@ def fusion_user_weights(models, like_ptr, like_cols):
     w = torch.empty((n_users, M), dtype=torch.float32, device=device)
     _call('tkr_fusion_user_weights', rmse, C.byref(st), _p(like_ptr), _p(like_cols), C.c_int32(n_users), _p(rmse), _p(w))
     return rmse, w
+
+
+# ---- K17: diversify a pool into a list, the pair sums of list diversity (csrc/diversity.hip) -------------------------------------------
+MMR_MAX_POOL = 1024          # TKR_MMR_MAX_POOL of include/tkr.h: a thread per pool entry
+
+
+def _div_args(what, S, ids, rel=None):
+    """refuse what the K17 entry points cannot take, the tensors' properties only (no device access) -> (n_items, k, n_rows, width)"""
+    named = dict(S=(S, torch.float32, 2), ids=(ids, torch.int32, 2))
+    if rel is not None:
+        named['rel'] = (rel, torch.float32, 2)
+    for name, (t, dtype, dim) in named.items():
+        if not isinstance(t, torch.Tensor):
+            raise TkrError('%s: %s must be a tensor' % (what, name))
+        if t.dtype != dtype or t.dim() != dim or not t.is_contiguous():
+            raise TkrError('%s: %s must be a contiguous %d-dimensional %s tensor' % (what, name, dim, dtype))
+    for name, (t, _, _) in named.items():
+        if not t.is_cuda or t.device != S.device:
+            raise TkrError('%s: %s must live on the GPU that holds S, not on %s' % (what, name, t.device))
+    if S.shape[0] < 1 or S.shape[1] < 1:
+        raise TkrError('%s: S [n_items, k] needs n_items >= 1 and k >= 1' % what)
+    if rel is not None and rel.shape != ids.shape:
+        raise TkrError('%s: ids and rel must have one shape' % what)
+    if ids.shape[1] > MMR_MAX_POOL:
+        raise TkrError('%s: %d entries per row, at most %d are supported' % (what, ids.shape[1], MMR_MAX_POOL))
+    return int(S.shape[0]), int(S.shape[1]), int(ids.shape[0]), int(ids.shape[1])
+
+
+def _div_status(status, what, n_items):
+    word = int(status.item())
+    if word != -1:
+        raise TkrError('%s: row %d holds an id outside [0, %d) in front of its padding' % (what, word >> 2, n_items))
+
+
+def mmr_select(S, ids, rel, lam, t):
+    """K17 -> sel_pos int32 [n_rows, t] on the device: greedy Maximal Marginal Relevance over the pool `ids` (int32 [n_rows, N], valid up
+    to the first negative id) with relevance `rel` (fp32 [n_rows, N]) and similarity chain(S[a], S[b]) -- the pool positions in pick
+    order, -1 where a row has fewer than t valid entries (include/tkr.h tkr_mmr_select).  An id >= n_items raises TkrError"""
+    what = 'mmr_select'
+    n_items, k, n_rows, N = _div_args(what, S, ids, rel)
+    lam, t = float(lam), int(t)
+    if not 0.0 <= lam <= 1.0:                                        # (a NaN fails both comparisons)
+        raise TkrError('%s: lambda must lie in [0, 1], got %r' % (what, lam))
+    if not 1 <= t <= N:
+        raise TkrError('%s: 1 <= t <= N = %d required, got %d' % (what, N, t))
+    sel = torch.empty((n_rows, t), dtype=torch.int32, device=S.device)
+    if n_rows == 0:
+        return sel
+    status = torch.empty(1, dtype=torch.int64, device=S.device)
+    _call('tkr_mmr_select', S, _p(S), C.c_int32(n_items), C.c_int32(k), _p(ids), _p(rel), C.c_int32(n_rows), C.c_int32(N), C.c_double(lam),
+          C.c_int32(t), _p(sel), _p(status))
+    _div_status(status, what, n_items)
+    return sel
+
+
+def list_pair_sums(S, ids):
+    """K17 -> pair_sum float64 [n_rows, t] on the device: pair_sum[r, b] = sum over a < b of 1 - chain(S[ids[r, a]], S[ids[r, b]]) inside
+    the valid prefix of row r (up to the first negative id), 0 behind it (include/tkr.h tkr_list_pair_sums)"""
+    what = 'list_pair_sums'
+    n_items, k, n_rows, t = _div_args(what, S, ids)
+    out = torch.zeros((n_rows, t), dtype=torch.float64, device=S.device)
+    if n_rows == 0 or t == 0:
+        return out
+    status = torch.empty(1, dtype=torch.int64, device=S.device)
+    _call('tkr_list_pair_sums', S, _p(S), C.c_int32(n_items), C.c_int32(k), _p(ids), C.c_int32(n_rows), C.c_int32(t), _p(out), _p(status))
+    _div_status(status, what, n_items)
+    return out
 
 
 # ---- per-epoch exchange of replicated tables (csrc/sync.hip) ----------------------------------------
