@@ -290,7 +290,13 @@ int tkr_vbpr_set_pairs(int32_t mode);
  * any batch_size (batches above 8192 are planned grid-wide, see tkr_sample_plan; above 65,536 the first four triplet indices of a
  * launch record are read from occt); kh <= 128 holds rows in registers, kh > 128 runs the generic form of the sparse view
  * (csrc/vbpr_wide.hip: factors walked in passes) and needs the CSR view (st->f_ptr): the dense MFMA view at kh > 128 is
- * TKR_E_UNSUPPORTED; loss_out as in tkr_bpr_run */
+ * TKR_E_UNSUPPORTED; loss_out as in tkr_bpr_run.
+ * RANGE (this entry point and tkr_vbpr_run_cols): a pair term sigma(-(alpha_a + beta_b)), alpha_a = irb_i - irb_j + (f_i - f_j).icb of
+ * triplet a, beta_b = x_ui - x_uj of triplet b, is evaluated as 1 / (1 + e^alpha_a * e^beta_b) with alpha and beta EACH clamped to
+ * [-80, 80] before its exponential (csrc/tkr_common.h pair_exp).  With |alpha| <= 80 and |beta| <= 80 for every triplet of the batch
+ * the step is the reference's (a product that overflows or underflows gives the saturated 0 or 1, which is the fp32 value).  Outside
+ * that range it is not: alpha = 100, beta = -85 is scored as sigma(0) = 0.5 where the objective has sigma(-15) = 3e-7.  Nothing
+ * checks the range; tables set from outside are the caller's to keep inside it. */
 int tkr_vbpr_run(const tkr_vbpr_state* st, const int32_t* tri_i, const int32_t* tri_j, const int32_t* rec,
                  const int32_t* occ, const int32_t* hdr, const int32_t* occt, const int32_t* tri_u /*nullable*/,
                  const int32_t* tpar /*nullable*/, int32_t batch_size,
