@@ -797,6 +797,52 @@ int tkr_mmr_select(const float* S, int32_t n_items, int32_t k, const int32_t* id
 int tkr_list_pair_sums(const float* S, int32_t n_items, int32_t k, const int32_t* ids, int32_t n_rows, int32_t t, double* pair_sum,
                        int64_t* status, void* stream);
 
+/* ---- K18: the metric values of every test line, and their sums over resampled lines (csrc/line_metrics.hip) ---------------------
+ * New design: the reference reports one mean per scenario.  What a bootstrap needs on the device, next to K8's output.
+ *
+ *   tkr_line_metrics    ranks int32 [n_likes]: tkr_like_ranks' output in the order of the like CSR (-1: a rated like); like_ptr,
+ *                       rated_ptr int64 [n_lines + 1] (only the row SIZES of the rated CSR are used); gain float64 [total],
+ *                       gain[r] = 1 / log2(r + 2); ideal float64 [total + 1], ideal[d] = gain[0] + ... + gain[d - 1] -- both made by the
+ *                       caller: the device calls no logarithm.  X float64 [n_lines, C], C = 3 * interval + 5, interval = total / step
+ *                       (0 is legal).  For line r with ranks >= 0 rho_0 < rho_1 < ... (P of them), K_b = step * (b + 1) and
+ *                       N = n_cols - |rated_r| - P:
+ *                         X[r, b]                    = #{q : rho_q < K_b}                                          b < interval
+ *                         X[r, interval]             = the line's likes, rated ones included
+ *                         X[r, interval + 1], [+ 2]  = 1 - (sum rho_q - P (P - 1) / 2) / (P N) and 1.0 where P >= 1 and N >= 1, else 0, 0
+ *                                                      (numerator and P N exact in int64; one division, one subtraction)
+ *                         X[r, interval + 3], [+ 4]  = 1 / (rho_0 + 1) and 1.0 where P >= 1, else 0, 0
+ *                         X[r, interval + 5 + b]     = (sum_{rho_q < K_b} gain[rho_q]) / ideal[min(P, K_b)], 0 where P = 0
+ *                         X[r, 2 interval + 5 + b]   = (sum_{rho_q < K_b} (q + 1) / (rho_q + 1)) / min(P, K_b), 0 where P = 0
+ *                       both sums added in ascending q from 0.0, no fused multiply-add: X is defined bit for bit.
+ *                       A wave per line, the line's ranks as a bitmap in LDS; a line of any length is two passes over its ranks.
+ *                       total <= TKR_LINE_MAX_TOTAL, n_cols <= TKR_LINE_MAX_COLS (above: TKR_E_UNSUPPORTED).
+ *                       The input is not trusted.  status (device int64[1], written by the call; K15's convention): -1, or the smallest
+ *                       4 * line + kind of what was refused: kind 0 -- a rank below -1; 1 -- a rank >= n_cols - |rated_line|; 2 -- a rank
+ *                       >= 0 named twice in the line; 3 -- like_ptr / rated_ptr do not start at 0, descend at this line, leave
+ *                       [0, n_likes], or give the line more than n_cols rated columns.  Nothing refused is used as an index; X is then
+ *                       not to be used.
+ *   tkr_bootstrap_sums  X float64 [n, C], row r at X + r * pitch (pitch >= C doubles); out float64 [R, C]: out[r, c] = sum over t < n of X[idx(r, t), c] -- R resamples of n lines
+ *                       with replacement, each applied to all columns.  The draw, on the library's Philox stream with stream word 3
+ *                       (0 / 1 / 2: K1 / K9 / K10): w = philox4x32_10(c0 = low word of t >> 1, c1 = its high word, c2 = r, c3 = 3,
+ *                       k0 = low word of seed, k1 = high word); idx = mulhi64(w.x, w.y, n) for even t, mulhi64(w.z, w.w, n) for odd t
+ *                       (oracle/plan_np.py).  The order of the sum is fixed by (n, C): a wave sums TKR_BOOT_CHUNK consecutive draws
+ *                       (L = the power of two >= max(C, 8) lanes read a row; lane group g adds the draws t with t mod (64 / L) = g in
+ *                       ascending order; the groups are added in a butterfly), the chunks are added in ascending order.  Two calls
+ *                       give the same bits, whatever the pitch; no float atomics.  A pitch of whole 64- or 128-byte lines (8, 16, 32,
+ *                       48, 64 doubles) reads faster than rows that straddle lines.  workspace: 8-byte aligned, at least
+ *                       R * ceil(n / TKR_BOOT_CHUNK) * C * 8 bytes.  1 <= C <= TKR_BOOT_MAX_COLUMNS, 1 <= n < 2^31, 1 <= R.
+ * Arguments are checked before any device access and before any launch (TKR_E_INVAL): a null or misaligned pointer (ranks may be
+ * null when n_likes = 0), n_likes < 0, n_lines / n_cols / step / total < 1, C, n or R outside their limits, pitch < C, a workspace too small. */
+#define TKR_LINE_MAX_TOTAL 1024
+#define TKR_LINE_MAX_COLS 1308672
+#define TKR_BOOT_MAX_COLUMNS 64
+#define TKR_BOOT_CHUNK 8192
+int tkr_line_metrics(const int32_t* ranks, int64_t n_likes, const int64_t* like_ptr, const int64_t* rated_ptr, int64_t n_lines,
+                     int32_t n_cols, int32_t step, int32_t total, const double* gain, const double* ideal, double* X, int64_t* status,
+                     void* stream);
+int tkr_bootstrap_sums(const double* X, int64_t n, int32_t C, int64_t pitch, int32_t R, uint64_t seed, double* out, void* workspace,
+                       int64_t workspace_bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -42,6 +42,12 @@ Stated differences from the reference:
     every cut-off step, 2 step, ... (K17, diversity.list_metrics).  ``--diversify LAMBDA [--pool N] [--similarity cosine|dot]`` adds,
     after those, ``S.mmr.acc,...`` -- the accuracy lines' hit counting on the lists re-ranked by greedy MMR from the ``--pool`` best
     (diversity.rerank) -- and ``S.mmr.ild`` / ``.cov`` / ``.gini`` for those of the three that ``-M`` names.  Single process only.
+  * ``-M ... --bootstrap R [--boot-seed S] [--level L]`` (not in the reference) prints, after all of those, ``S.m.lo,...`` and
+    ``S.m.hi,...`` for every m of ``acc auc mrr ndcg map`` that ``-M`` names: the percentile interval at level L (0.95) of the metric
+    over R resamples of the scenario's test lines with replacement.  The ranks stay on the device from K8 to the resample sums (K18,
+    significance.py); only the [R, columns] sums come down.  ``--compare MODEL_B`` ranks a second model directory on the same lines,
+    resamples both together (a paired bootstrap) and adds ``S.vs.m`` (B's values), ``S.diff.m`` (this model - B), ``S.diff.m.lo`` /
+    ``.hi`` and ``S.diff.m.p`` (two-sided).  Single process only.
 """
 from __future__ import annotations
 
@@ -55,6 +61,7 @@ import torch
 
 import diversity
 import rankmetrics
+import significance
 import textio
 import tkr_hip
 
@@ -287,17 +294,26 @@ def evaluate_loaded(umat_dev, vmat, bmat, vids, full, step, total, device):
     return [float(h) / tcount for h in hits]                          # ZeroDivisionError like evaluate.py:112
 
 
-def rank_metrics_loaded(umat_dev, vmat, bmat, vids, full, step, total, metrics, device):
+def like_ranks_loaded(umat_dev, vmat, bmat, vids, sc, device):
+    """K8 on an already parsed Scenario with at least one line -> the filtered rank of every liked column, int32 [n_likes] (device)"""
+    Vt, bias, user_idx, mask, pitch = _scenario_operands(vmat, bmat, vids, sc, device)
+    lptr, lcols = _on_device(sc, device, 'like_ptr', 'like_cols')
+    return tkr_hip.like_ranks(umat_dev, Vt, lptr, lcols, bias=bias, user_idx=user_idx, mask=mask, mask_pitch=pitch)
+
+
+def rank_metrics_loaded(umat_dev, vmat, bmat, vids, full, step, total, metrics, device, keep=None):
     """{metric: list of values} (rankmetrics.py) of an already parsed Scenario from one full-rank pass: K8 gives the filtered rank of
     every liked column of this rank's block of test lines, the metric sums and counts are all-reduced like the hits of
-    evaluate_loaded (one fp64 vector; the same on every rank afterwards)."""
+    evaluate_loaded (one fp64 vector; the same on every rank afterwards).  keep: a dict that receives K8's output, still on the device,
+    as 'ranks' (None without a test line)."""
     rank, world = _world()
     sc = shard_scenario(full, rank, world) if world > 1 else full
-    ranks = np.zeros(0, dtype=np.int32)
+    ranks, ranks_dev = np.zeros(0, dtype=np.int32), None
     if len(sc.users):
-        Vt, bias, user_idx, mask, pitch = _scenario_operands(vmat, bmat, vids, sc, device)
-        lptr, lcols = _on_device(sc, device, 'like_ptr', 'like_cols')
-        ranks = tkr_hip.like_ranks(umat_dev, Vt, lptr, lcols, bias=bias, user_idx=user_idx, mask=mask, mask_pitch=pitch).cpu().numpy()
+        ranks_dev = like_ranks_loaded(umat_dev, vmat, bmat, vids, sc, device)
+        ranks = ranks_dev.cpu().numpy()
+    if keep is not None:
+        keep['ranks'] = ranks_dev
     sums = rankmetrics.rank_sums(ranks, sc.like_ptr, sc.rated_ptr, len(sc.teids), step, total)
     if world > 1:
         import torch.distributed as dist
@@ -307,6 +323,21 @@ def rank_metrics_loaded(umat_dev, vmat, bmat, vids, full, step, total, metrics, 
         dist.all_reduce(acc, op=dist.ReduceOp.SUM)
         sums = rankmetrics.from_vector(acc.cpu().numpy(), total // step)
     return rankmetrics.finish(sums, metrics)
+
+
+def significance_loaded(ranks_dev, umat_b, vmat_b, bmat_b, vids, sc, step, total, metrics, boot, device):
+    """the bootstrap figures of an already parsed Scenario (single process) -> significance.report's dict.  ranks_dev: K8's ranks of the
+    model under evaluation (device); umat_b (device) / vmat_b / bmat_b: the model of --compare, or None; boot: dict(R, seed, level).
+    The line tables of both models are built, joined and resampled on the device (K18); only the column sums come down"""
+    if ranks_dev is None:
+        raise ZeroDivisionError('--bootstrap: no test line to resample')
+    lptr, rptr = _on_device(sc, device, 'like_ptr', 'rated_ptr')
+    X = significance.line_table(ranks_dev, lptr, rptr, len(sc.teids), step, total)
+    if umat_b is not None:
+        ranks_b = like_ranks_loaded(umat_b, vmat_b, bmat_b, vids, sc, device)
+        X = torch.cat([X, significance.line_table(ranks_b, lptr, rptr, len(sc.teids), step, total)], dim=1).contiguous()
+    reps = significance.bootstrap_sums(X, boot['R'], boot['seed']).cpu().numpy()
+    return significance.report(X.sum(dim=0).cpu().numpy(), reps, total // step, metrics, boot['level'], 2 if umat_b is not None else 1)
 
 
 def negative_rows(sc, n_neg, seed):
@@ -400,6 +431,14 @@ def main(argv=None):
                         help="With -M: also rank every held-out like among N sampled unrated columns; prints S.negN.hr / .ndcg / .mrr")
     parser.add_argument('--neg-seed', type=int, default=0, help="The seed of the negatives' draw")
     diversity.add_arguments(parser)
+    parser.add_argument('--bootstrap', type=int, default=None, metavar='R',
+                        help="With -M acc auc mrr ndcg map: the percentile interval of every metric over R resamples of the test lines; "
+                             "prints S.metric.lo / .hi")
+    parser.add_argument('--boot-seed', type=int, default=0, help="The seed of the resampling")
+    parser.add_argument('--level', type=float, default=0.95, help="The level of the bootstrap intervals, inside (0, 1)")
+    parser.add_argument('--compare', default=None, metavar='MODEL_B',
+                        help="With --bootstrap: a second model directory, resampled on the same lines; prints S.vs.metric, S.diff.metric, "
+                             "its interval and its two-sided p")
     args = parser.parse_args(argv)
     div = diversity.check_arguments(parser, args)
     list_metrics = [m for m in args.metrics or () if m in diversity.LIST_METRICS]
@@ -412,6 +451,19 @@ def main(argv=None):
     if args.metrics and 'hr' in args.metrics and args.negatives is None:
         parser.error('-M hr is defined against sampled negatives only: add --negatives N')
     full_metrics = [m for m in args.metrics or () if m in rankmetrics.METRICS]
+    if args.compare is not None and args.bootstrap is None:
+        parser.error('--compare needs --bootstrap R')
+    if args.bootstrap is not None and not full_metrics:
+        parser.error('--bootstrap needs -M with at least one of acc auc mrr ndcg map')
+    if args.bootstrap is not None and not 1 <= args.bootstrap < 2 ** 31:
+        parser.error('--bootstrap must be at least 1')
+    if not 0 <= args.boot_seed < 2 ** 64:
+        parser.error('--boot-seed must be a 64-bit unsigned integer')
+    if not 0.0 < args.level < 1.0:
+        parser.error('--level must lie inside (0, 1)')
+    if args.bootstrap is not None and int(os.environ.get('WORLD_SIZE', '1')) > 1:
+        parser.error('--bootstrap and --compare look at whole lists and are not sharded over ranks yet: run them in a single process')
+    boot = dict(R=args.bootstrap, seed=args.boot_seed, level=args.level) if args.bootstrap is not None else None
     neg_metrics = [m for m in args.metrics or () if m in rankmetrics.NEG_METRICS] if args.negatives is not None else []
 
     if not torch.cuda.is_available():
@@ -428,13 +480,23 @@ def main(argv=None):
         bmat = read_matrix(os.path.join(args.model, 'final-B.dat'), vids)
     umat_dev = torch.from_numpy(umat).to(device)
     umap = textio.IdMap(uids)
-    results, extra, negs, lists = {}, {}, {}, {}
+    umat_b = vmat_b = bmat_b = None
+    if args.compare is not None:                                     # model B: the same uid / vid lists
+        umat_b = torch.from_numpy(read_matrix(os.path.join(args.compare, 'final-U.dat'), uids)).to(device)
+        vmat_b = read_matrix(os.path.join(args.compare, 'final-V.dat'), vids)
+        if os.path.exists(os.path.join(args.compare, 'final-B.dat')):
+            bmat_b = read_matrix(os.path.join(args.compare, 'final-B.dat'), vids)
+    results, extra, negs, lists, boots = {}, {}, {}, {}, {}
     for scenario in args.scenarios:
         if args.metrics or div:
             full = load_scenario(args.data, args.fold, scenario, uids, umap)
             acc = evaluate_loaded(umat_dev, vmat, bmat, vids, full, args.step, args.total, device)
             if scenario not in extra:                                # (a scenario listed twice: its metric lines are not doubled)
-                extra[scenario] = rank_metrics_loaded(umat_dev, vmat, bmat, vids, full, args.step, args.total, full_metrics, device)
+                kept = {} if boot else None
+                extra[scenario] = rank_metrics_loaded(umat_dev, vmat, bmat, vids, full, args.step, args.total, full_metrics, device, kept)
+                if boot:
+                    boots[scenario] = significance_loaded(kept['ranks'], umat_b, vmat_b, bmat_b, vids, full, args.step, args.total,
+                                                          full_metrics, boot, device)
                 if neg_metrics:
                     negs[scenario] = negative_metrics_loaded(umat_dev, vmat, bmat, vids, full, args.step, args.total, args.negatives,
                                                              args.neg_seed, neg_metrics, device)
@@ -465,6 +527,14 @@ def main(argv=None):
         for scenario in args.scenarios if names else ():
             for m in names:
                 lines.append('%s.%s%s' % (scenario, 'mmr.' if which else '', m) + ''.join(',%.6f' % v for v in lists[scenario][which][m]))
+                print(lines[-1])                                     # (single process: refused above otherwise)
+    named = [('%s.lo', 'lo'), ('%s.hi', 'hi')]                       # (the line's name after 'S.', significance.report's key)
+    if args.compare is not None:
+        named += [('vs.%s', 'vs'), ('diff.%s', 'diff'), ('diff.%s.lo', 'diff.lo'), ('diff.%s.hi', 'diff.hi'), ('diff.%s.p', 'diff.p')]
+    for scenario in args.scenarios if boot else ():
+        for m in full_metrics:
+            for name, key in named:
+                lines.append('%s.%s' % (scenario, name % m) + ''.join(',%.6f' % v for v in boots[scenario][m][key]))
                 print(lines[-1])                                     # (single process: refused above otherwise)
     if started_group:
         import torch.distributed as dist

@@ -89,7 +89,7 @@ EXPORTS = ('tkr_version', 'tkr_plan_team', 'tkr_plan_max_blocks', 'tkr_sample_pl
            'tkr_matrix_format_sizes_dev', 'tkr_matrix_format_emit_dev', 'tkr_matrix_count_dev', 'tkr_matrix_emit_dev', 'tkr_matrix_token_host',
            'tkr_matrix_tokens_host', 'tkr_group_count_dev', 'tkr_group_emit_dev', 'tkr_last_line_of_user_dev', 'tkr_compact_rows_count_dev',
            'tkr_compact_rows_emit_dev', 'tkr_fusion_features', 'tkr_fusion_sgd', 'tkr_fusion_user_weights',
-           'tkr_mmr_select', 'tkr_list_pair_sums')
+           'tkr_mmr_select', 'tkr_list_pair_sums', 'tkr_line_metrics', 'tkr_bootstrap_sums')
 EXPORTS_I64 = ('tkr_vbpr_workspace_floats', 'tkr_vbpr_colplan_lds_bytes', 'tkr_topk_workspace_bytes_for', 'tkr_topk_workspace_bytes', 'tkr_plan_workspace_bytes', 'tkr_like_ranks_workspace_bytes',
                'tkr_parse_dev_workspace_bytes', 'tkr_idtable_slots', 'tkr_scan_dev_workspace_bytes')
 
@@ -1208,6 +1208,90 @@ def list_pair_sums(S, ids):
     status = torch.empty(1, dtype=torch.int64, device=S.device)
     _call('tkr_list_pair_sums', S, _p(S), C.c_int32(n_items), C.c_int32(k), _p(ids), C.c_int32(n_rows), C.c_int32(t), _p(out), _p(status))
     _div_status(status, what, n_items)
+    return out
+
+
+# ---- K18: the metric values of every test line, their sums over resampled lines (csrc/line_metrics.hip) -------------------------------
+LINE_MAX_TOTAL = 1024        # TKR_LINE_MAX_TOTAL of include/tkr.h
+LINE_MAX_COLS = 1308672      # TKR_LINE_MAX_COLS: the bitmap of one line must fit the LDS of one workgroup
+BOOT_MAX_COLUMNS = 64        # TKR_BOOT_MAX_COLUMNS: a lane per column of a row
+BOOT_CHUNK = 8192            # TKR_BOOT_CHUNK: the draws one wave sums
+_LINE_REFUSED = ('line %d holds a rank below -1', 'line %d holds a rank that is not below its number of unrated columns',
+                 'line %d names a rank twice', 'like_ptr / rated_ptr do not ascend from 0 inside their arrays at line %d')
+
+
+def _sig_tensor(what, name, t, dtype, dim, device=None):
+    if not isinstance(t, torch.Tensor):
+        raise TkrError('%s: %s must be a tensor' % (what, name))
+    if t.dtype != dtype or t.dim() != dim or not t.is_contiguous():
+        raise TkrError('%s: %s must be a contiguous %d-dimensional %s tensor' % (what, name, dim, dtype))
+    if not t.is_cuda or (device is not None and t.device != device):
+        raise TkrError('%s: %s must live on the GPU%s, not on %s' % (what, name, '' if device is None else ' that holds ranks', t.device))
+
+
+def line_metrics(ranks, like_ptr, rated_ptr, n_cols, step, total, gain, ideal):
+    """K18 -> X float64 [n_lines, 3 * (total // step) + 5] on the device: per test line the hit counts, the like count, AUC / reciprocal
+    rank with their flags, NDCG and average precision at every cut-off (include/tkr.h tkr_line_metrics; the columns:
+    significance.columns).  ranks int32 [n_likes] as tkr_hip.like_ranks returns them, like_ptr / rated_ptr int64 [n_lines + 1], gain
+    float64 [total], ideal float64 [total + 1], all on one GPU.  Ranks or pointers that cannot come from K8 raise TkrError"""
+    what = 'line_metrics'
+    _sig_tensor(what, 'ranks', ranks, torch.int32, 1)
+    for name, t, dtype in (('like_ptr', like_ptr, torch.int64), ('rated_ptr', rated_ptr, torch.int64), ('gain', gain, torch.float64),
+                           ('ideal', ideal, torch.float64)):
+        _sig_tensor(what, name, t, dtype, 1, ranks.device)
+    n_cols, step, total = int(n_cols), int(step), int(total)
+    n_lines = int(like_ptr.numel()) - 1
+    if n_lines < 0 or rated_ptr.numel() != n_lines + 1:
+        raise TkrError('%s: like_ptr and rated_ptr must both hold n_lines + 1 entries' % what)
+    if n_cols < 1 or step < 1 or total < 1:
+        raise TkrError('%s: n_cols, step and total must be at least 1' % what)
+    if total > LINE_MAX_TOTAL or n_cols > LINE_MAX_COLS:
+        raise TkrError('%s: total = %d, n_cols = %d; at most %d and %d are supported' % (what, total, n_cols, LINE_MAX_TOTAL, LINE_MAX_COLS))
+    if gain.numel() != total or ideal.numel() != total + 1:
+        raise TkrError('%s: gain must hold total and ideal total + 1 entries' % what)
+    X = torch.empty((n_lines, 3 * (total // step) + 5), dtype=torch.float64, device=ranks.device)
+    if n_lines == 0:
+        return X
+    status = torch.empty(1, dtype=torch.int64, device=ranks.device)
+    _call('tkr_line_metrics', ranks, _p(ranks) if ranks.numel() else C.c_void_p(0), C.c_int64(ranks.numel()), _p(like_ptr), _p(rated_ptr),
+          C.c_int64(n_lines), C.c_int32(n_cols), C.c_int32(step), C.c_int32(total), _p(gain), _p(ideal), _p(X), _p(status))
+    word = int(status.item())
+    if word != -1:
+        raise TkrError('%s: %s' % (what, _LINE_REFUSED[word & 3] % (word >> 2)))
+    return X
+
+
+def boot_pitch(width):
+    """the row pitch (doubles) bootstrap_sums copies a table of `width` columns to: whole 64- / 128-byte lines, the same lanes per row"""
+    return next(p for p in (8, 16, 32, 48, 64) if width <= p)
+
+
+def bootstrap_sums(X, R, seed, pad=True):
+    """K18 -> float64 [R, C] on the device: row r = the column sums of n = len(X) rows of X (float64 [n, C], C <= 64) drawn with
+    replacement, the draw a function of (seed, r, n) alone (include/tkr.h tkr_bootstrap_sums).  Bitwise repeatable.  pad: gather from
+    a copy of X at a row pitch of whole cache lines (boot_pitch: faster, the same bits; one more table in memory)"""
+    what = 'bootstrap_sums'
+    _sig_tensor(what, 'X', X, torch.float64, 2)
+    n, width = int(X.shape[0]), int(X.shape[1])
+    R, seed = int(R), int(seed)
+    if not 1 <= width <= BOOT_MAX_COLUMNS:
+        raise TkrError('%s: X has %d columns, 1 to %d are supported' % (what, width, BOOT_MAX_COLUMNS))
+    if not 1 <= n < 2 ** 31:
+        raise TkrError('%s: X needs 1 to 2^31 - 1 rows, got %d' % (what, n))
+    if not 1 <= R < 2 ** 31:
+        raise TkrError('%s: 1 <= R < 2^31 required, got %d' % (what, R))
+    if not 0 <= seed < 2 ** 64:
+        raise TkrError('%s: the seed must fit 64 bits' % what)
+    out = torch.empty((R, width), dtype=torch.float64, device=X.device)
+    workspace = torch.empty(R * ((n + BOOT_CHUNK - 1) // BOOT_CHUNK) * width, dtype=torch.float64, device=X.device)
+    pitch = boot_pitch(width) if pad else width
+    if pitch != width:
+        table = torch.zeros((n, pitch), dtype=torch.float64, device=X.device)
+        table[:, :width] = X
+    else:
+        table = X
+    _call('tkr_bootstrap_sums', X, _p(table), C.c_int64(n), C.c_int32(width), C.c_int64(pitch), C.c_int32(R), C.c_uint64(seed), _p(out),
+          _p(workspace), C.c_int64(workspace.numel() * 8))
     return out
 
 
