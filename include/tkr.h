@@ -843,6 +843,44 @@ int tkr_line_metrics(const int32_t* ranks, int64_t n_likes, const int64_t* like_
 int tkr_bootstrap_sums(const double* X, int64_t n, int32_t C, int64_t pitch, int32_t R, uint64_t seed, double* out, void* workspace,
                        int64_t workspace_bytes, void* stream);
 
+/* ---- K19: the nearest anchors of every list entry (csrc/explain.hip) ---------------------------------------------------------------
+ * New design: the reference writes lists and nothing about them.  "Why is this item on my list?" -- because of the user's own likes
+ * whose factors are closest to it; "is the list more of the same?" -- 1 - the similarity of an entry to the nearest item of the
+ * history (unexpectedness).  Both are one operation: for every entry of a row's list, the e most similar items of a second, per-row
+ * set, the ANCHORS.  sim(a, b) = chain(S[a], S[b]) is K17's similarity exactly: S fp32 [n_items, k] is whatever the caller measures
+ * similarity in (top-k-rec_amd/diversity.py similarity_table), chain = the mode-1 score of K4 / K12 without a bias (csrc/topk_parts.h
+ * exact_score; oracle/ref_np.py mfma_chain_scores), -0.0 mapped to +0.0, symmetric bit for bit; any k.
+ *
+ *   tkr_nearest_anchors  ids int32 [n_rows, t]: a list per row, valid up to the first id that is negative or >= n_items (K17's prefix
+ *                        rule).  Row r's anchors are anchor_cols[anchor_ptr[r] : anchor_ptr[r + 1]] (anchor_ptr int64 [n_rows + 1]
+ *                        from 0, anchor_cols int32 [n_anchors]); they need not be sorted or unique, and their POSITIONS, counted from
+ *                        the row's start, are what is ranked: a column named twice is two anchors.  For entry (r, p) inside the valid
+ *                        prefix the eligible anchors are the positions q with 0 <= anchor_cols[q] < n_items and anchor_cols[q] !=
+ *                        ids[r, p] (an item does not explain itself).  best_pos int32 [n_rows, t, e]: the eligible positions in
+ *                        descending sim, ties to the lower position; best_sim fp32 [n_rows, t, e]: their similarities, the chain's
+ *                        bits.  Where fewer than e anchors are eligible, and everywhere behind the valid prefix: -1 and -inf.
+ *                        Similarities are compared through the ordered 32-bit key K12 keeps its scores in (the bits of a float with
+ *                        the sign bit set are inverted, all others get the sign bit), so the order is total: NaNs with the sign bit
+ *                        < -inf < the negative numbers < +0.0 < the positive numbers < +inf < NaNs without the sign bit (-0.0 does
+ *                        not occur).  t <= TKR_ANCHOR_MAX_T, e <= TKR_ANCHOR_MAX_E (above: TKR_E_UNSUPPORTED).
+ *                        One workgroup per row; its threads are cut into groups of t, so that a lane holds one (entry, anchor) pair
+ *                        at a time and owns its entry's e best as packed 64-bit (key, inverted position) words; the list's rows of S
+ *                        are staged once in LDS when t + 8 rows of it fit the 160 KB of a CU, and the anchors' rows stream through LDS
+ *                        behind them in tiles (a row of any length, 0 to more than n_items anchors); otherwise both rows of every
+ *                        chain are read through L2.
+ * The input is not trusted.  status (device int64[1], written by the call; K15's convention): -1, or the smallest 4 * row + kind of
+ * what was found: kind 0 -- a list id >= n_items ended the row (only the entry that ENDS a row is looked at); 1 -- an anchor column
+ * outside [0, n_items) was skipped; 3 -- anchor_ptr does not start at 0, descends at this row, leaves [0, n_anchors] or gives the row
+ * 2^31 anchors or more: that row gets padding only and its anchors are not looked at.  Nothing refused is ever used as an index.
+ * Arguments are checked before any device access and before any launch (TKR_E_INVAL): a null S / ids / anchor_ptr / output / status,
+ * a null anchor_cols when n_anchors > 0, n_items / k / n_rows / t / e < 1, n_anchors < 0.  Deterministic: two calls give the same
+ * bits; no float atomics, the only atomic is the status word's minimum.  S and every row of it 16-byte aligned when k % 8 == 0. */
+#define TKR_ANCHOR_MAX_E 8
+#define TKR_ANCHOR_MAX_T 1024          /* = TKR_MMR_MAX_POOL */
+int tkr_nearest_anchors(const float* S, int32_t n_items, int32_t k, const int32_t* ids, int32_t n_rows, int32_t t,
+                        const int64_t* anchor_ptr, const int32_t* anchor_cols, int64_t n_anchors,
+                        int32_t e, int32_t* best_pos, float* best_sim, int64_t* status, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

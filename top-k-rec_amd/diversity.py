@@ -33,14 +33,14 @@ def add_arguments(parser):
                         help="Re-rank every list by greedy MMR: LAMBDA in [0, 1] weighs relevance against similarity to the items already "
                              "picked (1: no change).  The scores written are the model's own and no longer monotone along a line")
     parser.add_argument('--pool', type=int, default=None, help="With --diversify: the best items of a list that are re-ranked (default max(100, -t); at most 1024)")
-    parser.add_argument('--similarity', default=None, choices=SIMILARITIES, help="With --diversify: similarity of two items' factors (default cosine)")
+    parser.add_argument('--similarity', default=None, choices=SIMILARITIES, help="With --diversify (and recommend.py --explain): similarity of two items' factors (default cosine)")
 
 
 def check_arguments(parser, args):
     """the arguments of add_arguments -> the keyword arguments of recommend.rank they stand for ({} without --diversify); parser.error
     on what cannot be served"""
     if args.diversify is None:
-        if args.pool is not None or args.similarity is not None:
+        if args.pool is not None or (args.similarity is not None and getattr(args, 'explain', None) is None):     # (--explain: recommend.py's)
             parser.error('--pool and --similarity need --diversify')
         return {}
     if not 0.0 <= args.diversify <= 1.0:                             # (a NaN fails both comparisons)

@@ -39,9 +39,12 @@ Stated differences from the reference:
   * ``-M ... ild cov gini`` (not in the reference) prints, after all of those, ``S.ild,...``, ``S.cov,...`` and ``S.gini,...``: the
     intra-list diversity (1 - similarity of two items' factors, averaged over the pairs of a list and then over the lists), the share
     of the scenario's id list the lists reach and the Gini index of item exposure, of the scenario's ordinary top-``total`` lists at
-    every cut-off step, 2 step, ... (K17, diversity.list_metrics).  ``--diversify LAMBDA [--pool N] [--similarity cosine|dot]`` adds,
-    after those, ``S.mmr.acc,...`` -- the accuracy lines' hit counting on the lists re-ranked by greedy MMR from the ``--pool`` best
-    (diversity.rerank) -- and ``S.mmr.ild`` / ``.cov`` / ``.gini`` for those of the three that ``-M`` names.  Single process only.
+    every cut-off step, 2 step, ... (K17, diversity.list_metrics).  ``-M ... unexp`` prints, after those, ``S.unexp,...``: the
+    unexpectedness of the same lists -- 1 - the similarity of an item to the nearest item its user liked in the fold's training file,
+    averaged over a list and then over the lists (K19, explain.py; the similarity table is the whole ``final-V.dat``'s, so scenarios
+    whose items are outside the training matrix work); not with ``--bootstrap`` / ``--compare``.
+    ``--diversify LAMBDA [--pool N] [--similarity cosine|dot]`` adds, after those, ``S.mmr.acc,...`` -- the accuracy lines' hit counting on the lists re-ranked by greedy MMR from the ``--pool`` best
+    (diversity.rerank) -- and ``S.mmr.ild`` / ``.cov`` / ``.gini`` / ``.unexp`` for those of the four that ``-M`` names.  Single process only.
   * ``-M ... --bootstrap R [--boot-seed S] [--level L]`` (not in the reference) prints, after all of those, ``S.m.lo,...`` and
     ``S.m.hi,...`` for every m of ``acc auc mrr ndcg map`` that ``-M`` names: the percentile interval at level L (0.95) of the metric
     over R resamples of the scenario's test lines with replacement.  The ranks stay on the device from K8 to the resample sums (K18,
@@ -60,6 +63,7 @@ import numpy as np
 import torch
 
 import diversity
+import explain
 import rankmetrics
 import significance
 import textio
@@ -387,16 +391,30 @@ def negative_metrics_loaded(umat_dev, vmat, bmat, vids, full, step, total, n_neg
     return rankmetrics.finish(sums, metrics)
 
 
-def list_metrics_loaded(umat_dev, vmat, bmat, vids, sc, step, total, metrics, div, device):
+def list_metrics_loaded(umat_dev, vmat, bmat, vids, sc, step, total, metrics, div, device, anchors=None):
     """the list metrics of an already parsed Scenario (single process) -> (plain, mmr): {metric: values at step, 2 step, ...} of the
     ordinary top-`total` lists for the `metrics` of diversity.LIST_METRICS, and -- with div, the arguments of --diversify -- the same of
-    the lists K17 re-ranks out of the div['pool'] best, plus 'acc': K5's hit count on them as evaluate_loaded reports it (else None)"""
+    the lists K17 re-ranks out of the div['pool'] best, plus 'acc': K5's hit count on them as evaluate_loaded reports it (else None).
+    anchors: (ptr, cols) on the device, the training likes of every test line's user in the `vid` numbering -- both dicts then also
+    hold 'unexp', the unexpectedness of the lists against them (K19, explain.list_unexpectedness): the similarity table is the whole
+    final-V.dat's, and the lists' test columns are mapped to its rows first"""
     interval = total // step
     grid = [step * (q + 1) for q in range(interval)]
-    plain = {m: [0.0] * interval for m in metrics}
+    plain = {m: [0.0] * interval for m in list(metrics) + (['unexp'] if anchors is not None else [])}
     mmr = dict(plain, acc=[0.0] * interval) if div else None
     if not len(sc.users):
         return plain, mmr
+    unexp = None
+    if anchors is not None:
+        te_rows = np.zeros(len(sc.teids), dtype=np.int64)
+        for vid, col in sc.teids.items():
+            te_rows[col] = vids[vid]
+        te_rows = torch.from_numpy(te_rows.astype(np.int32)).to(device)
+        S_full = diversity.similarity_table(torch.from_numpy(vmat).to(device), div['similarity'] if div else 'cosine')
+
+        def unexp(lists):
+            as_vid = torch.where(lists >= 0, te_rows[lists.clamp(min=0).long()], torch.full_like(lists, -1)).contiguous()
+            return explain.list_unexpectedness(S_full, as_vid, anchors[0], anchors[1], grid)
     Vt, bias, user_idx, mask, pitch = _scenario_operands(vmat, bmat, vids, sc, device)
     S = diversity.similarity_table(Vt, div['similarity'] if div else 'cosine')
     n_cols = len(sc.teids)
@@ -405,6 +423,8 @@ def list_metrics_loaded(umat_dev, vmat, bmat, vids, sc, step, total, metrics, di
     if metrics:
         every = diversity.list_metrics(S, ids[:, :total].contiguous(), n_cols, grid)
         plain = {m: every[m] for m in metrics}
+    if unexp:
+        plain['unexp'] = unexp(ids[:, :total])
     if div:
         picked, _ = diversity.rerank(S, diversity.relevance(ids, scores), ids, scores, div['diversify'], total)
         lptr, lcols = _on_device(sc, device, 'like_ptr', 'like_cols')
@@ -413,6 +433,8 @@ def list_metrics_loaded(umat_dev, vmat, bmat, vids, sc, step, total, metrics, di
         if metrics:
             every = diversity.list_metrics(S, picked, n_cols, grid)
             mmr.update({m: every[m] for m in metrics})
+        if unexp:
+            mmr['unexp'] = unexp(picked)
     return plain, mmr
 
 
@@ -424,9 +446,10 @@ def main(argv=None):
     parser.add_argument('-s', '--step', type=int, default=5, help="The number of evaluation step")
     parser.add_argument('-t', '--total', type=int, default=30, help="The number of total predictions")
     parser.add_argument('-sl', '--scenarios', nargs='+', default=None, help="The test scenario list")
-    parser.add_argument('-M', '--metrics', nargs='+', default=None, choices=rankmetrics.METRICS + ('hr',) + diversity.LIST_METRICS,
+    parser.add_argument('-M', '--metrics', nargs='+', default=None, choices=rankmetrics.METRICS + ('hr',) + diversity.LIST_METRICS + explain.METRICS,
                         help="Rank metrics from one full-rank pass, printed after the accuracy lines as S.metric,... (hr: only with --negatives); "
-                             "ild cov gini: diversity, coverage and exposure Gini of the top-k lists")
+                             "ild cov gini: diversity, coverage and exposure Gini of the top-k lists; unexp: their unexpectedness against the "
+                             "users' training likes")
     parser.add_argument('--negatives', type=int, default=None, metavar='N',
                         help="With -M: also rank every held-out like among N sampled unrated columns; prints S.negN.hr / .ndcg / .mrr")
     parser.add_argument('--neg-seed', type=int, default=0, help="The seed of the negatives' draw")
@@ -444,6 +467,11 @@ def main(argv=None):
     list_metrics = [m for m in args.metrics or () if m in diversity.LIST_METRICS]
     if (div or list_metrics) and int(os.environ.get('WORLD_SIZE', '1')) > 1:
         parser.error('ild / cov / gini and --diversify look at whole lists and are not sharded over ranks yet: run them in a single process')
+    unexp = 'unexp' in (args.metrics or ())
+    if unexp and int(os.environ.get('WORLD_SIZE', '1')) > 1:
+        parser.error('unexp looks at whole lists and is not sharded over ranks yet: run it in a single process')
+    if unexp and (args.bootstrap is not None or args.compare is not None):
+        parser.error('unexp looks at whole lists and is not resampled yet: run it without --bootstrap / --compare')
     if args.negatives is not None and not args.metrics:
         parser.error('--negatives needs -M (hr, ndcg and / or mrr)')
     if args.negatives is not None and args.negatives < 1:
@@ -487,6 +515,7 @@ def main(argv=None):
         if os.path.exists(os.path.join(args.compare, 'final-B.dat')):
             bmat_b = read_matrix(os.path.join(args.compare, 'final-B.dat'), vids)
     results, extra, negs, lists, boots = {}, {}, {}, {}, {}
+    liked = textio.parse_ratings(os.path.join(args.data, 'f%dtr.txt' % args.fold), umap, textio.IdMap(vids)) if unexp else None
     for scenario in args.scenarios:
         if args.metrics or div:
             full = load_scenario(args.data, args.fold, scenario, uids, umap)
@@ -500,8 +529,10 @@ def main(argv=None):
                 if neg_metrics:
                     negs[scenario] = negative_metrics_loaded(umat_dev, vmat, bmat, vids, full, args.step, args.total, args.negatives,
                                                              args.neg_seed, neg_metrics, device)
-                if list_metrics or div:
-                    lists[scenario] = list_metrics_loaded(umat_dev, vmat, bmat, vids, full, args.step, args.total, list_metrics, div, device)
+                if list_metrics or div or unexp:
+                    anchors = explain.anchors_csr([liked], full.users, len(vmat), device) if unexp else None
+                    lists[scenario] = list_metrics_loaded(umat_dev, vmat, bmat, vids, full, args.step, args.total, list_metrics, div, device,
+                                                          anchors)
         else:
             acc = evaluate_scenario(umat_dev, vmat, bmat, uids, vids, args.data, args.fold, scenario, args.step, args.total, device, umap)
         if scenario not in results:                                  # evaluate.py:109-112 ACCUMULATES per scenario name: a scenario
@@ -523,7 +554,8 @@ def main(argv=None):
             lines.append('%s.neg%d.%s' % (scenario, args.negatives, m) + ''.join(',%.6f' % v for v in negs[scenario][m]))
             if rank == 0:
                 print(lines[-1])
-    for which, names in ((0, list_metrics), (1, (['acc'] + list_metrics) if div else [])):
+    list_names = list_metrics + (['unexp'] if unexp else [])
+    for which, names in ((0, list_names), (1, (['acc'] + list_names) if div else [])):
         for scenario in args.scenarios if names else ():
             for m in names:
                 lines.append('%s.%s%s' % (scenario, 'mmr.' if which else '', m) + ''.join(',%.6f' % v for v in lists[scenario][which][m]))

@@ -4,6 +4,7 @@
                         [--new-uid FILE --new-history FILE --fold-steps 50 --fold-triplets 16 --fold-lr 0.05 --fold-lu 2.5e-3 --seed 0]
                         [--new-vid FILE --new-ratings FILE --fold-li 2.5e-3 --fold-lj 2.5e-4 --fold-lb 0]
                         [--diversify LAMBDA --pool 100 --similarity cosine|dot]
+                        [--explain E --explain-output FILE --similarity cosine|dot]
 
 Inputs as evaluate.py: ``DATA/uid``, ``DATA/vid``, ``DATA/f{fold}tr.txt`` (the histories), ``MODEL/final-U.dat``, ``final-V.dat``,
 optional ``final-B.dat``.  For every requested user -- the tokens of USERS_FILE, one per line; default: every line of ``uid`` -- the
@@ -39,6 +40,17 @@ an item already picked);  ``--similarity``: the cosine (default) or the dot prod
 the scores are the model's own, so they are no longer monotone along a line.  LAMBDA = 1 writes the file written without the flag.
 It applies to every kind of line: model users, ``--new-uid``, ``--new-vid`` and ``--candidates``.
 
+``--explain E --explain-output FILE`` (both or neither, 1 <= E <= 8): FILE gets one line per output line, in the same order,
+
+    uid,iid:aid:%f:aid:%f,iid:aid:%f,...
+
+one comma field per recommended item in list order: the item's token, then up to E (anchor token, similarity) pairs, best first -- the
+user's own liked items whose factors are most similar to the item's (K19, explain.py; ``--similarity`` as above, default cosine, on the
+catalogue the lists were ranked against).  The anchors of a line are the like == 1 entries of exactly the sources whose items the
+line excludes: the user's last line of ``f{fold}tr.txt``, with ``--new-vid`` also of ``--new-ratings``, for ``--new-uid`` users
+``--new-history``.  An item never explains itself; an item without an anchor is its bare token.  With ``--diversify`` the final lists
+are explained.  The main output is byte for byte what it is without the two flags.
+
 The scores, the filter and the selection run on the GPU (tkr_hip.build_rated_mask, tkr_hip.score_topk); single process.
 """
 from __future__ import annotations
@@ -50,6 +62,7 @@ import numpy as np
 import torch
 
 import diversity
+import explain as expl
 import foldin
 import textio
 import tkr_hip
@@ -133,14 +146,17 @@ def candidate_lines(path, umap, vmap, n_items, where=None):
 
 
 def rank(U_dev, user_rows, V_dev, bias_dev, R, total, also_rated=None, candidates=None, on_device=False, where=None, diversify=None,
-         pool=None, similarity='cosine'):
+         pool=None, similarity='cosine', explain=None):
     """top-`total` unrated items of the users `user_rows` (indices into U_dev and into R's user numbering); `also_rated`: a second
     parsed ratings file in the same numbering whose lines exclude items too; `candidates`: (ptr, cols), a CSR over the ranked rows --
     then only these items of a row are ranked (K12) instead of the catalogue (K4)
     -> (ids int32 [n, total], scores fp32 [n, total]) as numpy, with on_device=True as tensors left on the GPU.  where / TKR_GROUP:
     which code builds the excluded-items CSR (textio.group_on_device); on the device it goes to the mask without a download.
     diversify: a lambda in [0, 1] -- the `pool` best (default diversity.default_pool(total)) are ranked instead and `total` of them
-    picked by greedy MMR under `similarity` (K17, diversity.rerank); the scores stay the model's own, in pick order"""
+    picked by greedy MMR under `similarity` (K17, diversity.rerank); the scores stay the model's own, in pick order.
+    explain: a number of anchors E -- a third value is returned, (cols int32 [n, total, E], sims fp32 [n, total, E]): for every entry of
+    the final lists the E like == 1 items of the row's user in R (and also_rated) that are most similar to it under `similarity`, -1 /
+    -inf padded (K19, explain.explain)"""
     where = textio._group_where(where)
     want = total
     if diversify is not None:
@@ -178,9 +194,17 @@ def rank(U_dev, user_rows, V_dev, bias_dev, R, total, also_rated=None, candidate
         ids, scores = tkr_hip.topk_from_ranks(cptr, ccols, s, r, total)
     else:
         ids, scores = tkr_hip.score_topk(U_dev, V_dev, total, bias=bias_dev, user_idx=idx, mask=mask, mask_pitch=pitch, want_scores=True)
+    S = None
     if diversify is not None:
         S, rel = diversity.prepare(V_dev, ids, scores, similarity)
         ids, scores = diversity.rerank(S, rel, ids, scores, diversify, want)
+    if explain is not None:
+        S = diversity.similarity_table(V_dev, similarity) if S is None else S
+        aptr, acols = expl.anchors_csr(sources, user_rows, n_items, dev, where)
+        why = expl.explain(S, ids, aptr, acols, explain)
+        if on_device:
+            return ids, scores, why
+        return ids.cpu().numpy(), scores.cpu().numpy(), tuple(x.cpu().numpy() for x in why)
     if on_device:
         return ids, scores
     return ids.cpu().numpy(), scores.cpu().numpy()
@@ -228,6 +252,7 @@ def main(argv=None):
     parser.add_argument('--fold-lb', type=float, default=0.0)
     parser.add_argument('--seed', type=int, default=0)
     diversity.add_arguments(parser)
+    expl.add_arguments(parser)
     parser.add_argument('--format', default=None, choices=textio.FORMAT_WHERE,
                         help="Where the output lines are formatted (default: TKR_FORMAT, else auto: on the GPU from TKR_FORMAT_DEVICE_FROM list entries upward)")
     parser.add_argument('--group', default=None, choices=textio.GROUP_WHERE,
@@ -241,7 +266,8 @@ def main(argv=None):
         parser.error('-t must be at least 1')
     if args.candidates is not None and args.users is not None:
         parser.error('--candidates names its users line by line: it does not go with -u')
-    div = diversity.check_arguments(parser, args)
+    div = dict(diversity.check_arguments(parser, args), **expl.check_arguments(parser, args))
+    why_path = args.explain_output
 
     uids = read_ids(os.path.join(args.data, 'uid'))
     vids = read_ids(os.path.join(args.data, 'vid'))
@@ -288,10 +314,12 @@ def main(argv=None):
     if users:
         umat = read_matrix(os.path.join(args.model, 'final-U.dat'), uids)
         R = textio.parse_ratings(os.path.join(args.data, 'f%dtr.txt' % args.fold), textio.IdMap(uids), vmap)
-        ids, scores = rank(torch.from_numpy(umat).to(device), [uids[u] for u in users], V_dev, bias_dev, R, args.total, also_rated=R_new_items,
-                           candidates=cand_model[2:] if cand_model else None, on_device=True, where=args.group, **div)
+        ids, scores, *why = rank(torch.from_numpy(umat).to(device), [uids[u] for u in users], V_dev, bias_dev, R, args.total, also_rated=R_new_items,
+                                 candidates=cand_model[2:] if cand_model else None, on_device=True, where=args.group, **div)
         tokens, rows = row_tokens(users)
         textio.write_lists(args.output, tokens, ids, scores, rows, vmap, where=args.format)
+        if why:
+            expl.write_lines(why_path, tokens, ids, *why[0], rows, vmap)
         wrote = True
     if new_uids:
         m = max(new_uids.values()) + 1
@@ -304,13 +332,17 @@ def main(argv=None):
             tok = {idx: t for t, idx in new_uids.items()}
             new_users = [tok[int(x)] for x in cand_new[1]]
         if new_users:
-            ids, scores = rank(torch.from_numpy(U_new).to(device), [new_uids[u] for u in new_users], V_dev, bias_dev, R, args.total,
-                               candidates=cand_new[2:] if cand_new else None, on_device=True, where=args.group, **div)
+            ids, scores, *why = rank(torch.from_numpy(U_new).to(device), [new_uids[u] for u in new_users], V_dev, bias_dev, R, args.total,
+                                     candidates=cand_new[2:] if cand_new else None, on_device=True, where=args.group, **div)
             tokens, rows = row_tokens(new_users)
             textio.write_lists(args.output, tokens, ids, scores, rows, vmap, where=args.format, append=wrote)
+            if why:
+                expl.write_lines(why_path, tokens, ids, *why[0], rows, vmap, append=wrote)
             wrote = True
     if not wrote:
         open(args.output, 'wb').close()
+        if why_path is not None:
+            open(why_path, 'wb').close()
     with open(args.output, 'rb') as fh:
         return fh.read().decode().split('\n')[:-1]               # the lines as written (one C-level call each, not one per line)
 

@@ -89,7 +89,7 @@ EXPORTS = ('tkr_version', 'tkr_plan_team', 'tkr_plan_max_blocks', 'tkr_sample_pl
            'tkr_matrix_format_sizes_dev', 'tkr_matrix_format_emit_dev', 'tkr_matrix_count_dev', 'tkr_matrix_emit_dev', 'tkr_matrix_token_host',
            'tkr_matrix_tokens_host', 'tkr_group_count_dev', 'tkr_group_emit_dev', 'tkr_last_line_of_user_dev', 'tkr_compact_rows_count_dev',
            'tkr_compact_rows_emit_dev', 'tkr_fusion_features', 'tkr_fusion_sgd', 'tkr_fusion_user_weights',
-           'tkr_mmr_select', 'tkr_list_pair_sums', 'tkr_line_metrics', 'tkr_bootstrap_sums')
+           'tkr_mmr_select', 'tkr_list_pair_sums', 'tkr_line_metrics', 'tkr_bootstrap_sums', 'tkr_nearest_anchors')
 EXPORTS_I64 = ('tkr_vbpr_workspace_floats', 'tkr_vbpr_colplan_lds_bytes', 'tkr_topk_workspace_bytes_for', 'tkr_topk_workspace_bytes', 'tkr_plan_workspace_bytes', 'tkr_like_ranks_workspace_bytes',
                'tkr_parse_dev_workspace_bytes', 'tkr_idtable_slots', 'tkr_scan_dev_workspace_bytes')
 
@@ -1209,6 +1209,44 @@ def list_pair_sums(S, ids):
     _call('tkr_list_pair_sums', S, _p(S), C.c_int32(n_items), C.c_int32(k), _p(ids), C.c_int32(n_rows), C.c_int32(t), _p(out), _p(status))
     _div_status(status, what, n_items)
     return out
+
+
+# ---- K19: the nearest anchors of every list entry (csrc/explain.hip) ---------------------------------------------------------------------
+ANCHOR_MAX_E = 8             # TKR_ANCHOR_MAX_E of include/tkr.h: the best anchors kept per entry
+ANCHOR_MAX_T = 1024          # TKR_ANCHOR_MAX_T (= MMR_MAX_POOL)
+_ANCHOR_REFUSED = ('row %d holds an id outside [0, n_items) in front of its padding', 'row %d holds an anchor outside [0, n_items)', None,
+                   'anchor_ptr does not start at 0, decreases or leaves [0, len(anchor_cols)] at row %d')
+
+
+def nearest_anchors(S, ids, anchor_ptr, anchor_cols, e):
+    """K19 -> (pos int32 [n_rows, t, e], sim fp32 [n_rows, t, e]) on the device: for every entry of the lists `ids` (int32 [n_rows, t],
+    valid up to the first negative id) the e anchors of its row -- anchor_cols[anchor_ptr[r] : anchor_ptr[r + 1]], int64 / int32, any
+    order, repeats allowed -- that are most similar to it under chain(S[a], S[b]) and are not the entry's own item: their positions
+    from the row's start, best first, ties to the lower position, and the similarities; -1 / -inf where fewer than e exist and behind
+    a row's end (include/tkr.h tkr_nearest_anchors).  An id or an anchor outside the table raises TkrError, a bad anchor_ptr ValueError"""
+    what = 'nearest_anchors'
+    n_items, k, n_rows, t = _div_args(what, S, ids)
+    e = int(e)
+    if not 1 <= e <= ANCHOR_MAX_E:
+        raise TkrError('%s: 1 <= e <= %d required, got %d' % (what, ANCHOR_MAX_E, e))
+    if t < 1:
+        raise TkrError('%s: ids [n_rows, t] needs t >= 1' % what)
+    _group_tensor(what, 'anchor_ptr', anchor_ptr, torch.int64, S.device)
+    _group_tensor(what, 'anchor_cols', anchor_cols, torch.int32, S.device)
+    if anchor_ptr.numel() != n_rows + 1:
+        raise ValueError('%s: anchor_ptr must hold n_rows + 1 = %d entries, not %d' % (what, n_rows + 1, anchor_ptr.numel()))
+    pos = torch.empty((n_rows, t, e), dtype=torch.int32, device=S.device)
+    sim = torch.empty((n_rows, t, e), dtype=torch.float32, device=S.device)
+    if n_rows == 0:
+        return pos, sim
+    n_anchors = int(anchor_cols.numel())
+    status = torch.empty(1, dtype=torch.int64, device=S.device)
+    _call('tkr_nearest_anchors', S, _p(S), C.c_int32(n_items), C.c_int32(k), _p(ids), C.c_int32(n_rows), C.c_int32(t), _p(anchor_ptr),
+          _p(anchor_cols) if n_anchors else C.c_void_p(0), C.c_int64(n_anchors), C.c_int32(e), _p(pos), _p(sim), _p(status))
+    word = int(status.item())
+    if word != -1:
+        raise (ValueError if word & 3 == 3 else TkrError)('%s: %s' % (what, _ANCHOR_REFUSED[word & 3] % (word >> 2)))
+    return pos, sim
 
 
 # ---- K18: the metric values of every test line, their sums over resampled lines (csrc/line_metrics.hip) -------------------------------
