@@ -881,6 +881,50 @@ int tkr_nearest_anchors(const float* S, int32_t n_items, int32_t k, const int32_
                         const int64_t* anchor_ptr, const int32_t* anchor_cols, int64_t n_anchors,
                         int32_t e, int32_t* best_pos, float* best_sim, int64_t* status, void* stream);
 
+/* ---- K20: the two halves of an ALS step, implicit feedback (csrc/als.hip) -------------------------------------------------------------
+ * Replaces the loops of the reference's single/wmf.py:70-97 (np.dot for the shared Gram, np.linalg.solve per row); the semantics are
+ * those of dpm.py:36-58, every stored like r = 1 (top-k-rec_amd/als.py).  Y fp32 [n, k] is the table that is
+ * held fixed in a half-step, X fp32 [n_x, k] the one that is solved for; 1 <= k <= TKR_ALS_MAX_K (wider: TKR_E_UNSUPPORTED).
+ *
+ *   tkr_als_gram        G fp32 [k, k]: G[p, q] = fp32(scale * sum_t Y[rows[t], p] * Y[rows[t], q] + (p == q ? ridge : 0)), t < n_listed;
+ *                       rows int32 [n_listed], or NULL: all n rows (n_listed is then not looked at).  n_listed = 0 gives ridge * I.  A
+ *                       workgroup sums a slab of TKR_ALS_GRAM_SLAB listed rows on the exact-fp32 MFMA (v_mfma_f32_32x32x2_f32 over
+ *                       tiles of 32 rows staged in LDS: per element one fp32 fma chain in list order from +0.0) into an fp32 partial in
+ *                       the workspace; a second launch adds the partials in ascending slab order in fp64, applies scale and ridge and
+ *                       rounds once.  workspace: at least tkr_als_workspace_bytes(0, k, ceil(n_listed / TKR_ALS_GRAM_SLAB)) bytes.
+ *                       status: -1, or 4 * t + 1 for the smallest t whose rows[t] lies outside [0, n): that row is skipped.
+ *   tkr_als_solve_rows  like_ptr int64 [n_x + 1] from 0, like_cols int32 [n_likes]: row r's likes, rows of Y, in any order; a column
+ *                       named twice counts twice.  For every r with m_r > 0 likes, y running over them:
+ *                         A = G + w_like * sum y y^T,  rhs = w_rhs * sum y,  X[r] = (A + ridge I)^-1 rhs
+ *                         row_loss[r] = 1/2 x^T A x - w_rhs * sum y.x + 1/2 w_rhs m_r        (float64 [n_x], or NULL; the new x, A
+ *                                       without ridge; fp32 products added in fp64)
+ *                       Rows with m_r = 0: X[r] untouched, row_loss[r] = 0.  One workgroup per row: sum y y^T as in tkr_als_gram, A =
+ *                       fp32(G + w_like * sum) in LDS, Cholesky in fp32 with the lower triangle in the workgroup's registers and one
+ *                       barrier per column (the right-hand side rides along as row k), the back substitution in one wave, one store
+ *                       of the row.  A row with m_r >= heavy_from likes (>= 1) does not sum its own
+ *                       likes: a launch before the solve sums its slabs of TKR_ALS_GRAM_SLAB likes, one workgroup each, into the
+ *                       workspace, and the solve adds them in ascending order in fp64.  workspace: 16-byte aligned;
+ *                       tkr_als_workspace_bytes(n_x, k, n_slabs) bytes hold the heavy rows' n_slabs = sum ceil(m_r / TKR_ALS_GRAM_SLAB)
+ *                       slabs; a heavy row whose slabs do not fit sums its own likes after all (same result up to the order of the
+ *                       sum).  It may be NULL when heavy_from > n_likes, else it holds at least tkr_als_workspace_bytes(n_x, k, 0).
+ *                       status: -1, or the smallest 4 * r + kind: kind 1 -- a like column outside [0, n_y) was skipped (m_r counts the
+ *                       others; none left: as m_r = 0); 2 -- a pivot of the factorisation is not positive and finite, or the solution is
+ *                       not finite: X[r] is left as it is, no NaN is written, row_loss[r] = 0; 3 -- like_ptr does not start at 0,
+ *                       descends at this row, leaves [0, n_likes] or gives the row 2^31 likes or more: left as it is, row_loss[r] = 0.
+ *   tkr_als_workspace_bytes  the size above (a multiple of 16), or TKR_E_INVAL.
+ * The input is not trusted: nothing refused is ever used as an index.  Arguments are checked before any device access and before any
+ * launch (TKR_E_INVAL): a null Y / G / X / like_ptr / status, a null like_cols with n_likes > 0, a misaligned status / row_loss /
+ * workspace, k / n / n_y / n_x < 1, n_x >= 2^31, n_listed / n_likes < 0, heavy_from < 1, ridge < 0 (solve), a weight that is not finite,
+ * a workspace too small.  Deterministic: two calls give the same bits; no float atomics, the only atomic is the status word's minimum. */
+#define TKR_ALS_MAX_K 128
+#define TKR_ALS_GRAM_SLAB 1024
+int64_t tkr_als_workspace_bytes(int64_t n_x, int32_t k, int64_t n_slabs);
+int tkr_als_gram(const float* Y, int32_t n, int32_t k, const int32_t* rows, int64_t n_listed, double scale, double ridge, float* G,
+                 void* workspace, int64_t workspace_bytes, int64_t* status, void* stream);
+int tkr_als_solve_rows(const float* Y, int32_t n_y, int32_t k, const float* G, const int64_t* like_ptr, const int32_t* like_cols,
+                       int64_t n_likes, int64_t n_x, double w_like, double w_rhs, double ridge, int64_t heavy_from, float* X,
+                       double* row_loss, void* workspace, int64_t workspace_bytes, int64_t* status, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -2,7 +2,7 @@
 
 REC, BPR and VBPR are the MI355X-native implementations of this repo.  The reference's other
 five exports are ALS / MLP models outside the BPR/VBPR hot path (SURVEY.md §2 rows 7-9);
-they are present as names only and raise on construction.
+they are present as names only and raise on construction.  WMF is built, but not here: ``from als import WMF`` (top-k-rec_amd/als.py).
 """
 from .rec import REC
 from .bpr import BPR
@@ -13,7 +13,8 @@ def _out_of_scope(name):
     class _Stub:
         def __init__(self, *a, **kw):
             raise NotImplementedError('%s (ALS/MLP family) is outside the BPR/VBPR hot path this '
-                                      'build accelerates; use the reference implementation' % name)
+                                      'build accelerates; use the reference implementation%s'
+                                      % (name, ' -- or als.WMF, the GPU build of WMF (from als import WMF)' if name == 'WMF' else ''))
     _Stub.__name__ = name
     return _Stub
 

@@ -89,9 +89,10 @@ EXPORTS = ('tkr_version', 'tkr_plan_team', 'tkr_plan_max_blocks', 'tkr_sample_pl
            'tkr_matrix_format_sizes_dev', 'tkr_matrix_format_emit_dev', 'tkr_matrix_count_dev', 'tkr_matrix_emit_dev', 'tkr_matrix_token_host',
            'tkr_matrix_tokens_host', 'tkr_group_count_dev', 'tkr_group_emit_dev', 'tkr_last_line_of_user_dev', 'tkr_compact_rows_count_dev',
            'tkr_compact_rows_emit_dev', 'tkr_fusion_features', 'tkr_fusion_sgd', 'tkr_fusion_user_weights',
-           'tkr_mmr_select', 'tkr_list_pair_sums', 'tkr_line_metrics', 'tkr_bootstrap_sums', 'tkr_nearest_anchors')
+           'tkr_mmr_select', 'tkr_list_pair_sums', 'tkr_line_metrics', 'tkr_bootstrap_sums', 'tkr_nearest_anchors', 'tkr_als_gram',
+           'tkr_als_solve_rows')
 EXPORTS_I64 = ('tkr_vbpr_workspace_floats', 'tkr_vbpr_colplan_lds_bytes', 'tkr_topk_workspace_bytes_for', 'tkr_topk_workspace_bytes', 'tkr_plan_workspace_bytes', 'tkr_like_ranks_workspace_bytes',
-               'tkr_parse_dev_workspace_bytes', 'tkr_idtable_slots', 'tkr_scan_dev_workspace_bytes')
+               'tkr_parse_dev_workspace_bytes', 'tkr_idtable_slots', 'tkr_scan_dev_workspace_bytes', 'tkr_als_workspace_bytes')
 
 
 def lib():
@@ -1247,6 +1248,117 @@ def nearest_anchors(S, ids, anchor_ptr, anchor_cols, e):
     if word != -1:
         raise (ValueError if word & 3 == 3 else TkrError)('%s: %s' % (what, _ANCHOR_REFUSED[word & 3] % (word >> 2)))
     return pos, sim
+
+
+# ---- K20: the two halves of an ALS step (csrc/als.hip) -------------------------------------------------------------------------------------
+ALS_MAX_K = 128              # TKR_ALS_MAX_K of include/tkr.h: A (k x k) lives in the LDS of one workgroup
+ALS_GRAM_SLAB = 1024         # TKR_ALS_GRAM_SLAB: the listed rows one workgroup sums
+ALS_NO_HEAVY = 1 << 62       # heavy_from: no row is heavy
+_ALS_REFUSED = (None, 'row %d holds a like outside [0, n_y)', 'the system of row %d is not positive definite in fp32',
+                'like_ptr does not start at 0, decreases or leaves [0, len(like_cols)] at row %d')
+
+
+class AlsRefused(TkrError):
+    """a status word of K20 that is not -1; .row and .kind say what it holds (include/tkr.h)"""
+
+    def __init__(self, what, word):
+        self.word, self.row, self.kind = word, word >> 2, word & 3
+        super().__init__('%s: %s (kind %d)' % (what, _ALS_REFUSED[self.kind] % self.row, self.kind))
+
+
+def _als_table(what, name, t, k=None):
+    if not isinstance(t, torch.Tensor) or t.dtype != torch.float32 or t.dim() != 2 or not t.is_contiguous() or not t.is_cuda:
+        raise TkrError('%s: %s must be a contiguous two-dimensional float32 tensor on the GPU' % (what, name))
+    if t.shape[0] < 1 or (k is not None and t.shape[1] != k):
+        raise TkrError('%s: %s has shape %s' % (what, name, tuple(t.shape)))
+    if not 1 <= t.shape[1] <= ALS_MAX_K:
+        raise ValueError('%s: k = %d, 1 <= k <= %d is supported' % (what, t.shape[1], ALS_MAX_K))
+    return int(t.shape[0]), int(t.shape[1])
+
+
+def als_workspace_bytes(n_x, k, n_slabs):
+    need = int(lib().tkr_als_workspace_bytes(C.c_int64(n_x), C.c_int32(k), C.c_int64(n_slabs)))
+    if need < 0:
+        raise TkrError('tkr_als_workspace_bytes(%d, %d, %d) failed: tkr error %d' % (n_x, k, n_slabs, need))
+    return need
+
+
+def als_heavy_slabs(like_ptr, heavy_from):
+    """the slabs the heavy rows of a like CSR have together (like_ptr: a host array or a tensor)"""
+    import numpy as np
+    m = np.diff(like_ptr.cpu().numpy() if isinstance(like_ptr, torch.Tensor) else np.asarray(like_ptr, dtype=np.int64))
+    m = m[(m >= heavy_from) & (m > 0)]
+    return int(((m + ALS_GRAM_SLAB - 1) // ALS_GRAM_SLAB).sum())
+
+
+def _als_workspace(workspace, need, device):
+    if workspace is not None and workspace.numel() * workspace.element_size() >= need and workspace.device == device:
+        return workspace
+    return torch.empty(max(need, 16) // 8, dtype=torch.int64, device=device)
+
+
+def als_gram(Y, rows=None, scale=1.0, ridge=0.0, workspace=None, out=None, check=True):
+    """K20 -> G fp32 [k, k] on the device: scale * sum over the listed rows (int32 tensor; None: all) of y y^T + ridge I
+    (include/tkr.h tkr_als_gram).  A listed row outside [0, n) raises AlsRefused (after G is written without it); check=False
+    returns (G, status tensor) and reads nothing back"""
+    what = 'als_gram'
+    n, k = _als_table(what, 'Y', Y)
+    if rows is not None:
+        _group_tensor(what, 'rows', rows, torch.int32, Y.device)
+    n_listed = n if rows is None else int(rows.numel())
+    n_slabs = (n_listed + ALS_GRAM_SLAB - 1) // ALS_GRAM_SLAB
+    need = als_workspace_bytes(0, k, n_slabs)
+    workspace = _als_workspace(workspace, need, Y.device)
+    G = torch.empty((k, k), dtype=torch.float32, device=Y.device) if out is None else out
+    status = torch.empty(1, dtype=torch.int64, device=Y.device)
+    # (an empty list is still a list: its tensor may have no address, so any that is not null stands in for it)
+    rows_p = C.c_void_p(0) if rows is None else _p(rows if n_listed else Y)
+    _call('tkr_als_gram', Y, _p(Y), C.c_int32(n), C.c_int32(k), rows_p, C.c_int64(n_listed), C.c_double(scale), C.c_double(ridge), _p(G), _p(workspace), C.c_int64(workspace.numel() * workspace.element_size()),
+          _p(status))
+    if not check:
+        return G, status
+    word = int(status.item())
+    if word != -1:
+        raise AlsRefused(what, word)
+    return G
+
+
+def als_solve_rows(Y, G, like_ptr, like_cols, X, *, w_like, w_rhs, ridge, heavy_from=None, want_loss=False, workspace=None, heavy_slabs=None,
+                   check=True):
+    """K20, in place on X fp32 [n_x, k]: X[r] = (G + w_like sum y y^T + ridge I)^-1 (w_rhs sum y) over row r's likes, rows of Y; rows
+    without likes are left as they are (include/tkr.h tkr_als_solve_rows).  -> row_loss float64 [n_x] with want_loss, else None.
+    heavy_from: None = ALS_HEAVY_FROM; heavy_slabs: what als_heavy_slabs gives for this CSR (computed when it is not handed in).
+    A refusal raises AlsRefused naming row and kind; check=False returns (row_loss, status tensor) instead and reads nothing back"""
+    what = 'als_solve_rows'
+    n_y, k = _als_table(what, 'Y', Y)
+    n_x, _ = _als_table(what, 'X', X, k)
+    _als_table(what, 'G', G, k)
+    if G.shape[0] != k or X.device != Y.device or G.device != Y.device:
+        raise TkrError('%s: G must be [k, k], and Y, G and X on one GPU' % what)
+    _group_tensor(what, 'like_ptr', like_ptr, torch.int64, Y.device)
+    _group_tensor(what, 'like_cols', like_cols, torch.int32, Y.device)
+    if like_ptr.numel() != n_x + 1:
+        raise ValueError('%s: like_ptr must hold n_x + 1 = %d entries, not %d' % (what, n_x + 1, like_ptr.numel()))
+    heavy_from = ALS_HEAVY_FROM if heavy_from is None else int(heavy_from)
+    n_likes = int(like_cols.numel())
+    need = 0
+    if heavy_from <= n_likes:
+        need = als_workspace_bytes(n_x, k, als_heavy_slabs(like_ptr, heavy_from) if heavy_slabs is None else heavy_slabs)
+    workspace = _als_workspace(workspace, need, Y.device)
+    loss = torch.empty(n_x, dtype=torch.float64, device=Y.device) if want_loss else None
+    status = torch.empty(1, dtype=torch.int64, device=Y.device)
+    _call('tkr_als_solve_rows', Y, _p(Y), C.c_int32(n_y), C.c_int32(k), _p(G), _p(like_ptr), _p(like_cols) if n_likes else C.c_void_p(0),
+          C.c_int64(n_likes), C.c_int64(n_x), C.c_double(w_like), C.c_double(w_rhs), C.c_double(ridge), C.c_int64(heavy_from), _p(X), _p(loss),
+          _p(workspace), C.c_int64(workspace.numel() * workspace.element_size()), _p(status))
+    if not check:
+        return loss, status
+    word = int(status.item())
+    if word != -1:
+        raise AlsRefused(what, word)
+    return loss
+
+
+ALS_HEAVY_FROM = 4 * ALS_GRAM_SLAB       # a row with this many likes is shared by several workgroups (scripts/time_als.py)
 
 
 # ---- K18: the metric values of every test line, their sums over resampled lines (csrc/line_metrics.hip) -------------------------------
