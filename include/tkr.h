@@ -359,9 +359,9 @@ int tkr_vbpr_run_cols(const tkr_vbpr_state* st, const int32_t* tri_i, const int3
  *   On gfx950 the fp32 MFMA runs at the vector-ALU rate and overlaps nothing; mode 2 is 1.5-2.1x faster than mode 1.
  * K <= 32 per launch (larger K: rank 32, add the found columns to the mask with tkr_build_rated_mask, rank
  * again -- top-k-rec_amd/tkr_hip.py score_topk does this); any k (above 768: score_topk_wide_kernel, one wave per row, a lane per item,
- * the same fma chain; 256 < k <= 768: mode 1 with the k dimension in slabs of 256 --
- * the chain of a score runs slab after slab, halves [256 s, 256 s + 128) and [256 s + 128, 256 s + 256) in place of the two
- * halves of k; 63 % of the fp32-MFMA peak at k = 512, register spills above 512). */
+ * the same fma chain; 256 < k <= 768: mode 1 with the k dimension in slabs -- 128 factors of each half of k per slab, so
+ * the chain of a score is the one above, the two halves of the WHOLE width interleaved, at these widths too; 60 % of the
+ * fp32-MFMA peak at k = 512, register spills above 512). */
 int64_t tkr_topk_workspace_bytes(int32_t n_rows, int32_t K);
 /* the same + room for the item factors of mode 2 pre-converted to scaled fp16 (k <= 128), laid out as the LDS image of every
  * 32-item tile: with a workspace of at least this size a K4 call converts V once (a ~5 us pre-pass) and every workgroup stages
@@ -429,7 +429,7 @@ int tkr_like_ranks(const float* U, const int32_t* user_idx, int32_t n_rows, cons
  *                  #{e' in row r, unmasked, e' != e : s(r, c_e') > s(r, c_e) or (s equal and c_e' > c_e)}
  * -- K4's canonical order restricted to the list.  Integer and bit-exact; no atomics; two runs give the same bits, and a block of rows
  * ranked alone gives what it gives inside a larger call.  When a row lists every column 0 .. n_cols-1, the entry with rank p < K is
- * position p of tkr_score_topk's list with the same score bits (k <= 256 and k > 768; the slab kernels in between chain slab by slab),
+ * position p of tkr_score_topk's list with the same score bits (every k; tests/test_gpu_score_chain.py),
  * and the rank of every liked column is tkr_like_ranks's rank (every k).  A column outside [0, n_cols) is never dereferenced: score
  * -inf, rank -1.  A score that is NaN has no defined rank.
  * Shapes: any k, empty rows, any n_rows, a row of any length up to n_cols.  A row of at most TKR_CANDIDATES_RESIDENT entries belongs to

@@ -84,11 +84,15 @@ def _random_case(seed, n_items, k, N, rows):
     return V, ids, scores
 
 
-@pytest.mark.parametrize('seed,n_items,k,N,t,rows,lam', [(1, 600, 50, 96, 30, 300, 0.7), (2, 600, 128, 64, 30, 300, 0.5), (3, 600, 24, 130, 40, 300, 0.7)])
+@pytest.mark.parametrize('seed,n_items,k,N,t,rows,lam', [(1, 600, 50, 96, 30, 300, 0.7), (2, 600, 128, 64, 30, 300, 0.5), (3, 600, 24, 130, 40, 300, 0.7),
+                                                         # wide tables on generic floats: an odd width above one tile, a fused width
+                                                         # (three k = 128 models with bias), and one whose 64 rows do not fit the LDS
+                                                         (4, 600, 129, 96, 30, 300, 0.7), (5, 600, 387, 64, 30, 300, 0.5), (6, 600, 1032, 64, 30, 300, 0.7)])
 def test_random_floats_match_oracle_outside_ambiguous_rows(seed, n_items, k, N, t, rows, lam):
     """cosine S and rel from diversity.prepare, downloaded and handed to the oracle: every row without a near-tie (a gap <= 2^-20 between
     the two best objectives of a pick) equals the oracle exactly, and at most 2 % of the rows may have one (a float64 NumPy probe at
-    these shapes marked 2, 0 and 0 of 300; the oracle on these pools marks 0, 1 and 1).  The pick order differs from the score order in most rows, lambda = 1 gives the pool's
+    these shapes marked 2, 0 and 0 of 300; the oracle on these pools marks 0, 1 and 1; at k = 129, 387 and 1032 a CPU run of the oracle
+    marked 0, 2 and 1).  The pick order differs from the score order in most rows, lambda = 1 gives the pool's
     first t entries back, and the pair sums of the picked lists match the float64 oracle."""
     V, ids, scores = _random_case(seed, n_items, k, N, rows)
     ids_d, scores_d = _dev(ids), _dev(scores)
@@ -96,7 +100,8 @@ def test_random_floats_match_oracle_outside_ambiguous_rows(seed, n_items, k, N, 
     S, rel = S_d.cpu().numpy(), rel_d.cpu().numpy()
     np.testing.assert_allclose(np.linalg.norm(S, axis=1), 1.0, rtol=1e-6)
     assert rel.min() == 0.0 and rel.max() == 1.0 and np.all(rel[:, 0] == 1.0)
-    want, amb = O.mmr(S, ids, rel, lam, t, n_items)
+    full = R.mfma_chain_scores(S, S) if k > 256 else None             # wide tables: the oracle's similarities once, not per row
+    want, amb = O.mmr(S, ids, rel, lam, t, n_items, full=full)
     print('ambiguous rows: %d of %d' % (amb.sum(), rows))
     assert amb.sum() <= 0.02 * rows
     got = tkr_hip.mmr_select(S_d, ids_d, rel_d, lam, t).cpu().numpy()
@@ -109,7 +114,7 @@ def test_random_floats_match_oracle_outside_ambiguous_rows(seed, n_items, k, N, 
     np.testing.assert_array_equal(same_ids.cpu().numpy(), ids[:, :t])
     np.testing.assert_array_equal(same_scores.cpu().numpy(), scores[:, :t])
     ps = tkr_hip.list_pair_sums(S_d, out_ids).cpu().numpy()
-    np.testing.assert_allclose(ps, O.pair_sums(S, out_ids.cpu().numpy(), n_items), rtol=0, atol=1e-9)
+    np.testing.assert_allclose(ps, O.pair_sums(S, out_ids.cpu().numpy(), n_items, full=full), rtol=0, atol=1e-9)
     m = diversity.list_metrics(S_d, out_ids, n_items, [5, 10, t])
     w = O.metrics_loop(ps, out_ids.cpu().numpy(), n_items, [5, 10, t])
     for name in m:

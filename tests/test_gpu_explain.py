@@ -103,11 +103,15 @@ def _random_case(seed, k, t, rows, longest):
     return V, ids, ptr, np.concatenate(hist).astype(np.int32)
 
 
-@pytest.mark.parametrize('seed,k,t,rows,longest,e', [(1, 50, 30, 300, 40, 3), (2, 128, 30, 300, 150, 3), (3, 24, 40, 300, 7, 8)])
+@pytest.mark.parametrize('seed,k,t,rows,longest,e', [(1, 50, 30, 300, 40, 3), (2, 128, 30, 300, 150, 3), (3, 24, 40, 300, 7, 8),
+                                                     # wide tables on generic floats: an odd width above one tile, a fused width (three
+                                                     # k = 128 models with bias), and one above every MFMA form of K4
+                                                     (4, 129, 30, 300, 40, 3), (5, 387, 30, 300, 150, 3), (6, 1032, 40, 300, 7, 8)])
 def test_random_floats_match_oracle_outside_ambiguous_entries(seed, k, t, rows, longest, e):
     """cosine S from diversity.similarity_table, downloaded and handed to the oracle: every entry without a near-tie (a gap <= 2^-20
     between neighbours among its best e + 1 similarities) has the oracle's positions and the oracle's similarity bits, and at most 0.5 %
-    of the entries may have one (a CPU probe of the oracle at these cases marked 1, 0 and 0 of 9,000, 9,000 and 12,000).  In most rows
+    of the entries may have one (a CPU probe of the oracle at these cases marked 1, 0 and 0 of 9,000, 9,000 and 12,000; at k = 129, 387
+    and 1032: 3, 5 and 1).  In most rows
     the nearest like is not the same for every entry of the list, and a second call returns the same bits."""
     V, ids, ptr, cols = _random_case(seed, k, t, rows, longest)
     S_d = diversity.similarity_table(_dev(V), 'cosine')

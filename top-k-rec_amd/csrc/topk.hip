@@ -664,8 +664,12 @@ __global__ __launch_bounds__((WAVES * TKR_WAVE)) void score_topk_kernel(
 // row in registers (128 at k = 256) and a 32-item tile of the full width in LDS (2 x 33 KB at k = 256): neither scales.  Here the
 // user operand of EVERY slab stays in registers (SLABS x 128: the 512-register file of a one-wave-per-SIMD workgroup holds two or
 // three slabs) and the item tiles go through the same two LDS buffers one slab at a time -- unit (tile, slab) is staged while unit
-// (tile, slab - 1) is multiplied; the accumulator runs over a tile's slabs and the filter sees it after the last.  Same fp32 MFMA
-// chain, same lists, trims and merge as score_topk_kernel.
+// (tile, slab - 1) is multiplied; the accumulator runs over a tile's slabs and the filter sees it after the last.  Same lists, trims
+// and merge as score_topk_kernel, and the same fma chain as exact_score (topk_parts.h): the two k-halves are the halves of the WHOLE
+// width, KH = ceil(k / 2) -- half-wave h, slab s, element kk holds factor h KH + 128 s + kk, zero beyond its half -- so the chain is
+// (j, KH + j) for j = 0 .. KH-1, what K8, K12, K16, K17, K19 and the wave-per-row form below run.  A slab of 256 CONSECUTIVE
+// factors, 128 per half-wave, would be simpler to stage but interleaves the halves per slab: a few ulp away from every other kernel
+// in most score bits (tests/test_gpu_score_chain.py holds the kernel to the one chain).
 template <int SLABS, typename IdT>
 __global__ __launch_bounds__(256) void score_topk_slab_kernel(
     const float* __restrict__ U, const int32_t* __restrict__ uidx, int n_rows, const float* __restrict__ Vt,
@@ -693,7 +697,8 @@ __global__ __launch_bounds__(256) void score_topk_slab_kernel(
     const int row = ws.block * users + uw;
     const bool user_ok = row < n_rows;
 
-    float breg[SLABS * KHP];                                     // element (slab s, kk) = factor 256 s + 128 h + kk of this lane's user
+    const int KH = (k + 1) >> 1;                                 // the halves of the WHOLE width, as in exact_score: half h starts at h * KH
+    float breg[SLABS * KHP];                                     // element (slab s, kk) = factor h KH + 128 s + kk of this lane's user, 0 beyond its half
     {
         const int urow = user_ok ? (uidx ? uidx[row] : row) : 0;
         const float* up = U + (size_t)urow * k;
@@ -701,8 +706,8 @@ __global__ __launch_bounds__(256) void score_topk_slab_kernel(
         for (int sl = 0; sl < SLABS; ++sl)
 #pragma unroll
             for (int kk = 0; kk < KHP; ++kk) {
-                const int e = sl * SW + h * KHP + kk;
-                breg[sl * KHP + kk] = (user_ok && e < k) ? up[e] : 0.f;
+                const int j = sl * KHP + kk, e = h * KH + j;
+                breg[sl * KHP + kk] = (user_ok && j < KH && e < k) ? up[e] : 0.f;
             }
     }
     for (int s = tid; s < users; s += NT_) sm.cnt[s] = 0;
@@ -713,16 +718,35 @@ __global__ __launch_bounds__(256) void score_topk_slab_kernel(
 
     // ---- staging of unit (tile t, slab sl): global -> registers -> LDS buffer (unit index & 1)
     constexpr int NC = 32 * SW / 4 / NT_;                        // 8 float4 per thread
-    const bool vec = (k & 3) == 0;                               // every item row and slab starts 16-byte aligned
+    // LDS row of an item in a slab: [h * KHP + kk] = factor h KH + 128 sl + kk, 0 beyond the half.  The second half of an item row
+    // starts at KH: 16-byte aligned when k % 8 == 0 (then KH % 4 == 0 and no float4 chunk straddles the end of a half: one float4
+    // load per chunk, the rule of exact_score's aligned path), 8-byte aligned when k % 4 == 0 (KH even: two float2 loads per chunk,
+    // the second one beyond the half in the half's last chunk); scalar staging for every other width
+    const bool vec = (k & 3) == 0, vec4 = (k & 7) == 0;
     float4 stg[NC];
     float stg_bias = 0.f;
     auto stage_load = [&](int t, int sl) {
         if (vec) {
 #pragma unroll
             for (int q = 0; q < NC; ++q) {
-                const int c = tid + q * NT_, item = c >> 6, e = sl * SW + (c & 63) * 4;
+                const int c = tid + q * NT_, item = c >> 6, p = (c & 63) * 4;
+                const int j = sl * KHP + (p & (KHP - 1)), e = (p >> 7) * KH + j;
                 stg[q] = make_float4(0.f, 0.f, 0.f, 0.f);
-                if (e < k && t * 32 + item < n_cols) stg[q] = *reinterpret_cast<const float4*>(Vt + (size_t)(t * 32 + item) * k + e);
+                if (j < KH && t * 32 + item < n_cols) {            // j % 4 == 0 and KH even: j + 1 < KH; e + 1 < k
+                    const float* src = Vt + (size_t)(t * 32 + item) * k + e;
+                    if (vec4) {
+                        stg[q] = *reinterpret_cast<const float4*>(src);
+                    } else {
+                        const float2 lo = *reinterpret_cast<const float2*>(src);
+                        stg[q].x = lo.x;
+                        stg[q].y = lo.y;
+                        if (j + 2 < KH) {                            // then j + 3 < KH too
+                            const float2 hi = *reinterpret_cast<const float2*>(src + 2);
+                            stg[q].z = hi.x;
+                            stg[q].w = hi.y;
+                        }
+                    }
+                }
             }
         }
         if (sl == 0 && tid < 32) {
@@ -740,8 +764,9 @@ __global__ __launch_bounds__(256) void score_topk_slab_kernel(
             }
         } else {
             for (int c = tid; c < 32 * SW; c += NT_) {
-                const int item = c / SW, e = sl * SW + c % SW, col = t * 32 + item;
-                dst[item * KP + c % SW] = (e < k && col < n_cols) ? Vt[(size_t)col * k + e] : 0.f;
+                const int item = c / SW, p = c % SW, col = t * 32 + item;
+                const int j = sl * KHP + p % KHP, e = (p / KHP) * KH + j;
+                dst[item * KP + p] = (j < KH && e < k && col < n_cols) ? Vt[(size_t)col * k + e] : 0.f;
             }
         }
         if (sl == 0 && tid < 32) sm.tbias[(t & 1) * 32 + tid] = stg_bias;
