@@ -386,10 +386,13 @@ int tkr_count_hits(const int32_t* ids, int32_t n_rows, int32_t K, const int64_t*
  * j = t // step) -- and sums reciprocal ranks 1/(t+1).  With ids = K4's first K unrated columns of each row,
  *   raw_rank[r][p] = p + #{rated columns of row r ranked before ids[r][p]}   (-1 where ids is -1)
  * under the canonical order (descending score, ties -> higher column first); kept and rated columns are scored
- * by the same fp32 dot routine inside the kernel.  rated_ptr/rated_cols: the CSR given to tkr_build_rated_mask.
+ * by the fp32 chain of tkr_score_topk's modes 1 and 2 (fl(acc + bias), -0.0 -> +0.0): the bits the kept list was
+ * ordered by, so the count agrees with K4, K8 and K12 down to the last ulp.  rated_ptr/rated_cols: the CSR given to
+ * tkr_build_rated_mask (columns in [0, n_cols) of Vt; they are not checked).
  * tkr_count_hits_rr: hit_first[r][j] += 1 and rr_first[r][j] += 1/(t+1) (fp64) for every kept liked column with
  * j = t / step < interval, sequentially per row (reproducible); the caller zeroes both arrays, sums over rows and
- * accumulates buckets <= k (utils.py:115-117).  K <= 256, k <= 256. */
+ * accumulates buckets <= k (utils.py:115-117).  K <= 256 per launch (TKR_E_UNSUPPORTED above; utils.evaluate
+ * chunks a longer list), any factor width k. */
 int tkr_raw_ranks(const float* U, const int32_t* user_idx, int32_t n_rows, const float* Vt, const float* bias, int32_t k,
                   const int64_t* rated_ptr, const int32_t* rated_cols, const int32_t* ids, int32_t K, int32_t* raw_rank,
                   void* stream);

@@ -158,3 +158,58 @@ def case(k, shape=None):
         idx[-1] = idx[0]
         rated = rated[:n_rows]
     return dict(U=U, V=V, b=b, rated=rated, user_idx=idx, rows=U if idx is None else U[idx])
+
+
+# ---- near-ties by construction: the inputs of the K6 tests (tests/test_gpu_utils_eval.py) and of the mirror case of the chain file -----
+# widths of tkr_raw_ranks: one factor; an odd width below a wave; 50 (the first width the near-ties show at); 64 / 65, 128 / 129 and
+# 256 / 257 -- one more 64-wide pass of the reduction K6 had; 200; 300, 387, 513 -- above the 256 K6 stopped at, K4's slab kernel; 769,
+# 1032 -- K4's generic kernel
+MIRROR_WIDTHS = [1, 7, 50, 64, 65, 128, 129, 200, 256, 257, 300, 387, 513, 769, 1032]
+MIRROR_ROWS, MIRROR_M = 62, 600              # 15 blocks of 4 waves and a tail of 2; 1,200 columns, rated rows of ~600: ten waves long
+MIRROR_SEED = 9100
+
+
+def mirror_case(k, n_rows=MIRROR_ROWS, m=MIRROR_M, seed=None):
+    """-> dict(U, V, b, rated, user_idx, rows) as case(): a catalogue of m mirror pairs.  The user rows are palindromes (U[r, j] ==
+    U[r, k-1-j]; at odd k the middle factor is free), column c + m is column c read backwards with the same bias: the two scores of a
+    pair are equal in real arithmetic and only the order of summation separates them in fp32.  Values are N(0, 0.01^2) rounded like
+    '%f'.  Every column is rated with probability 1/2 on its own, so half the pairs have exactly one column rated; row 0 has no rated
+    column, row 1 all but 3 (its kept list is shorter than any K > 3), row 2 every column.  At k = IDX_WIDTH user_idx is a permutation
+    of a larger table with one user twice."""
+    seed = MIRROR_SEED + k if seed is None else seed
+    rng = np.random.Generator(np.random.PCG64(seed))
+    with_idx = k == IDX_WIDTH
+    n_all = n_rows + 20 if with_idx else n_rows
+    half = (k + 1) // 2
+    A = np.round(rng.standard_normal((n_all, half)) * 0.01, 6).astype(F32)
+    U = np.empty((n_all, k), dtype=F32)
+    U[:, :half] = A
+    U[:, k - half:] = A[:, ::-1]
+    V0 = np.round(rng.standard_normal((m, k)) * 0.01, 6).astype(F32)
+    b0 = np.round(rng.standard_normal(m) * 0.01, 6).astype(F32)
+    V = np.ascontiguousarray(np.concatenate([V0, V0[:, ::-1]]))
+    b = np.concatenate([b0, b0])
+    rated = [np.flatnonzero(rng.random(2 * m) < 0.5).astype(np.int32) for _ in range(n_rows)]
+    if n_rows > 0:
+        rated[0] = np.zeros(0, dtype=np.int32)
+    if n_rows > 1:
+        rated[1] = np.delete(np.arange(2 * m, dtype=np.int32), np.sort(rng.choice(2 * m, 3, replace=False)))
+    if n_rows > 2:
+        rated[2] = np.arange(2 * m, dtype=np.int32)
+    idx = None
+    if with_idx:
+        idx = rng.permutation(n_all)[:n_rows].astype(np.int32)
+        idx[-1] = idx[3]                     # (rows 0 to 2 keep their special rated lists to themselves)
+    return dict(U=U, V=V, b=b, rated=rated, user_idx=idx, rows=U if idx is None else U[idx])
+
+
+def left_to_right_scores(U, V, bias=None):
+    """the same products added in plain index order, one fp32 rounding per step (the double rounding of mfma_chain_scores, unmarked):
+    a second summation order, to show that an input set tells orders apart.  Not an oracle of any kernel."""
+    u64, v64 = np.asarray(U, dtype=np.float64), np.asarray(V, dtype=np.float64)
+    acc = np.zeros((u64.shape[0], v64.shape[0]), dtype=F32)
+    for j in range(u64.shape[1]):
+        acc = (np.outer(u64[:, j], v64[:, j]) + acc).astype(F32)
+    if bias is not None:
+        acc = (acc + np.asarray(bias, dtype=F32).reshape(1, -1)).astype(F32)
+    return acc + F32(0.0)

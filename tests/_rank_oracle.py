@@ -28,6 +28,20 @@ def like_ranks_np(scores_row, rated, likes):
     return pos[np.sort(np.fromiter(likes, dtype=np.int64, count=len(likes)))]
 
 
+def raw_ranks_np(scores_row, rated_cols, kept_ids):
+    """what K6 (tkr_raw_ranks) returns for one row: for every entry of kept_ids (unrated columns, -1 padded) its position among ALL
+    columns of the row in the canonical order, rated ones counted; a -1 stays -1"""
+    order = np.argsort(np.asarray(scores_row), kind='stable')[::-1]
+    pos = np.empty(len(order), dtype=np.int64)
+    pos[order] = np.arange(len(order))
+    kept = np.asarray(kept_ids, dtype=np.int64)
+    live = kept >= 0
+    assert not np.isin(kept[live], np.asarray(list(rated_cols), dtype=np.int64)).any(), 'a kept column is rated'
+    out = np.full(len(kept), -1, dtype=np.int32)
+    out[live] = pos[kept[live]]
+    return out
+
+
 def load_lines(data_dir, model_dir, fold, scenario, scoring='blas'):
     """the reference's view of one scenario -> (scores [n_users, n_cols], [(user row, rated column set, liked column set)]) for the
     test lines with at least one like.  scoring: 'blas' (np.dot, as evaluate.py:78), 'chain' (the kernels' fma chain), 'f64'"""

@@ -4,33 +4,22 @@
 // RAW rank t (train-rated items included, utils.py:113-117: j = t // step) and reciprocal ranks 1/(t+1) are
 // summed next to the hit counts.  K4 yields the first `total` unrated columns of a user in order; the raw rank of
 // the p-th of them is p + (number of the user's train-rated columns ranked before it).  K6 computes exactly that
-// count: one wave per row scores the kept columns and the rated columns of its user with ONE dot routine (so
-// the comparisons are self-consistent) and counts, for every kept column, the rated ones in front of it under the
-// canonical order (descending score, ties -> higher column first).  K7 turns (kept ids, raw ranks, like lists) into
-// per-row first-bucket hit counts and reciprocal-rank sums; the host sums rows and accumulates buckets
-// (utils.py:115-117: for k in range(j, interval)).
+// count: one wave per row; a lane takes one column, kept or rated, and runs the library's ONE fp32 score chain over it
+// (exact_score, csrc/topk_parts.h: the bits K4 ranked the kept list by, at any factor width), then the wave counts,
+// for every kept column, the rated ones in front of it under the canonical order (descending score, ties -> higher
+// column first).  K7 turns (kept ids, raw ranks, like lists) into per-row first-bucket hit counts and
+// reciprocal-rank sums; the host sums rows and accumulates buckets (utils.py:115-117: for k in range(j, interval)).
 //
-// Integer/byte work bound by the row gathers of Vt: (n_rated + total) rows of k floats per user.
+// Integer/byte work bound by the row gathers of Vt: (n_rated + total) rows of k floats per user, every lane its own.
 #include "tkr_common.h"
+#include "topk_parts.h"
 #include "../../include/tkr.h"
 
 namespace tkr {
 
 constexpr int kRawMaxK = 256;      // kept columns per row a launch handles
+constexpr int kRawSlots = kRawMaxK / 64;      // ... kept in registers: position lane + 64 i belongs to lane
 
-template <int NE>
-__device__ __forceinline__ float row_dot(const float (&u)[NE], const float* __restrict__ row, int k, int lane) {
-    float p = 0.f;
-#pragma unroll
-    for (int q = 0; q < NE; ++q) {
-        const int e = lane * NE + q;
-        const float v = row[min(e, k - 1)];
-        p = fmaf(u[q], (e < k) ? v : 0.f, p);
-    }
-    return wave_sum(p);
-}
-
-template <int NE>
 __global__ __launch_bounds__(256) void raw_rank_kernel(const float* __restrict__ U, const int32_t* __restrict__ uidx,
                                                        int n_rows, const float* __restrict__ Vt,
                                                        const float* __restrict__ bias, int k,
@@ -38,39 +27,44 @@ __global__ __launch_bounds__(256) void raw_rank_kernel(const float* __restrict__
                                                        const int32_t* __restrict__ rated_cols,
                                                        const int32_t* __restrict__ ids, int K,
                                                        int32_t* __restrict__ raw_rank) {
-    __shared__ float s_score[4][kRawMaxK];
-    __shared__ int s_before[4][kRawMaxK];
-    const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
-    const int r = blockIdx.x * 4 + wave;
+    const int lane = threadIdx.x & 63;
+    const int r = blockIdx.x * 4 + (threadIdx.x >> 6);
     if (r >= n_rows) return;
-    const int urow = uidx ? uidx[r] : r;
-    float u[NE];
+    const float* up = U + (size_t)(uidx ? uidx[r] : r) * k;
+    // kept columns: the scores K4 ordered them by
+    int cp[kRawSlots], before[kRawSlots];
+    float sp[kRawSlots];
 #pragma unroll
-    for (int q = 0; q < NE; ++q) {
-        const int e = lane * NE + q;
-        const float v = U[(size_t)urow * k + min(e, k - 1)];
-        u[q] = (e < k) ? v : 0.f;
+    for (int i = 0; i < kRawSlots; ++i) {
+        const int p = lane + 64 * i;
+        cp[i] = p < K ? ids[(size_t)r * K + p] : -1;
+        sp[i] = -INFINITY;
+        before[i] = 0;
+        if (cp[i] >= 0) sp[i] = exact_score(up, Vt + (size_t)cp[i] * k, k, bias, cp[i]);
     }
-    // kept columns: score with the same routine as the rated ones
-    for (int p = 0; p < K; ++p) {
-        const int c = ids[(size_t)r * K + p];                    // wave-uniform
+    // rated columns, 64 at a time: lane j scores one, every lane compares it with its kept columns
+    const int64_t q1 = rated_ptr[r + 1];
+    for (int64_t q0 = rated_ptr[r]; q0 < q1; q0 += 64) {
+        const int n = (int)min((int64_t)64, q1 - q0);
+        int c = -1;
         float s = -INFINITY;
-        if (c >= 0) s = row_dot<NE>(u, Vt + (size_t)c * k, k, lane) + (bias ? bias[c] : 0.f);
-        if (lane == 0) { s_score[wave][p] = s + 0.0f; s_before[wave][p] = 0; }
-    }
-    __builtin_amdgcn_wave_barrier();
-    for (int64_t q = rated_ptr[r]; q < rated_ptr[r + 1]; ++q) {
-        const int c = rated_cols[q];
-        const float s = row_dot<NE>(u, Vt + (size_t)c * k, k, lane) + (bias ? bias[c] : 0.f) + 0.0f;
-        for (int p = lane; p < K; p += 64) {
-            const int cp = ids[(size_t)r * K + p];
-            const float sp = s_score[wave][p];
-            if (cp >= 0 && (s > sp || (s == sp && c > cp))) s_before[wave][p] += 1;
+        if (lane < n) {
+            c = rated_cols[q0 + lane];
+            s = exact_score(up, Vt + (size_t)c * k, k, bias, c);
+        }
+        for (int j = 0; j < n; ++j) {
+            const int cj = __shfl(c, j, 64);
+            const float sj = __shfl(s, j, 64);
+#pragma unroll
+            for (int i = 0; i < kRawSlots; ++i)
+                if (cp[i] >= 0 && (sj > sp[i] || (sj == sp[i] && cj > cp[i]))) before[i] += 1;
         }
     }
-    __builtin_amdgcn_wave_barrier();
-    for (int p = lane; p < K; p += 64)
-        raw_rank[(size_t)r * K + p] = ids[(size_t)r * K + p] >= 0 ? p + s_before[wave][p] : -1;
+#pragma unroll
+    for (int i = 0; i < kRawSlots; ++i) {
+        const int p = lane + 64 * i;
+        if (p < K) raw_rank[(size_t)r * K + p] = cp[i] >= 0 ? p + before[i] : -1;
+    }
 }
 
 // one thread per row: sequential over the kept positions, so the reciprocal-rank sums are reproducible
@@ -105,15 +99,9 @@ extern "C" int tkr_raw_ranks(const float* U, const int32_t* user_idx, int32_t n_
                              int32_t k, const int64_t* rated_ptr, const int32_t* rated_cols, const int32_t* ids, int32_t K,
                              int32_t* raw_rank, void* stream) {
     if (!U || !Vt || !rated_ptr || !ids || !raw_rank || n_rows <= 0 || k <= 0 || K <= 0) return TKR_EINVAL;
-    if (K > tkr::kRawMaxK || k > 256) return TKR_EUNSUPPORTED;
-    const dim3 grid((n_rows + 3) / 4), block(256);
-    hipStream_t s = (hipStream_t)stream;
-    switch ((k + 63) / 64) {
-        case 1: hipLaunchKernelGGL(tkr::raw_rank_kernel<1>, grid, block, 0, s, U, user_idx, n_rows, Vt, bias, k, rated_ptr, rated_cols, ids, K, raw_rank); break;
-        case 2: hipLaunchKernelGGL(tkr::raw_rank_kernel<2>, grid, block, 0, s, U, user_idx, n_rows, Vt, bias, k, rated_ptr, rated_cols, ids, K, raw_rank); break;
-        case 3: hipLaunchKernelGGL(tkr::raw_rank_kernel<3>, grid, block, 0, s, U, user_idx, n_rows, Vt, bias, k, rated_ptr, rated_cols, ids, K, raw_rank); break;
-        default: hipLaunchKernelGGL(tkr::raw_rank_kernel<4>, grid, block, 0, s, U, user_idx, n_rows, Vt, bias, k, rated_ptr, rated_cols, ids, K, raw_rank); break;
-    }
+    if (K > tkr::kRawMaxK) return TKR_EUNSUPPORTED;
+    hipLaunchKernelGGL(tkr::raw_rank_kernel, dim3((n_rows + 3) / 4), dim3(256), 0, (hipStream_t)stream, U, user_idx, n_rows, Vt, bias, k,
+                       rated_ptr, rated_cols, ids, K, raw_rank);
     TKR_LAUNCH_CHECK();
     return TKR_OK;
 }
