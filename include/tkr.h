@@ -427,7 +427,7 @@ int tkr_like_ranks(const float* U, const int32_t* user_idx, int32_t n_rows, cons
  * candidate columns of every row as CSR, STRICTLY ASCENDING inside a row and in [0, n_cols) (no duplicates; the caller's contract --
  * top-k-rec_amd/tkr_hip.py rank_candidates checks the pointer, evaluate._group builds such rows).  For entry e of row r, c = cand_cols[e]:
  *   score_out[e] = s(r, c), masked entries included: the mode-1 score of K4 (the fma chain with the two k-halves interleaved, fl(acc +
- *                  bias), -0.0 -> +0.0; csrc/topk_parts.h exact_score, restated by oracle/ref_np.py mfma_chain_scores), at every k
+ *                  bias), -0.0 -> +0.0; csrc/score_chain.h exact_score, restated by oracle/ref_np.py mfma_chain_scores), at every k
  *   rank_out[e]  = -1 when c is masked for the row, otherwise
  *                  #{e' in row r, unmasked, e' != e : s(r, c_e') > s(r, c_e) or (s equal and c_e' > c_e)}
  * -- K4's canonical order restricted to the list.  Integer and bit-exact; no atomics; two runs give the same bits, and a block of rows
@@ -727,7 +727,7 @@ int tkr_compact_rows_emit_dev(const int64_t* ptr, const int64_t* pos, int64_t n_
  * needs no entry point: top-k-rec_amd/fusion.py concatenates the tables.)  The models arrive in one struct: n_models <= 16 table pairs
  * over the same n_users and n_items, each with its own width k (= its row pitch) and an optional bias [n_items].  All pointers inside
  * are device pointers; the struct itself is read on the host.
- * The per-model score s_m(u, c) is the score of tkr_rank_candidates / tkr_score_topk bit for bit (csrc/topk_parts.h exact_score: the
+ * The per-model score s_m(u, c) is the score of tkr_rank_candidates / tkr_score_topk bit for bit (csrc/score_chain.h exact_score: the
  * fma chain with the two k-halves interleaved, fl(acc + bias), -0.0 -> +0.0; oracle/ref_np.py mfma_chain_scores), one lane per score.
  *
  *   tkr_fusion_features      triplet g = first_triplet + t, t < count, is K1's draw (tkr_sample_plan's stream under `seed`:
@@ -774,7 +774,7 @@ int tkr_fusion_user_weights(const tkr_fusion_models* models, const int64_t* like
  * New design: the reference sorts every list by score alone.  Both entry points are built on the similarity of two entries of a row,
  *   sim(a, b) = chain(S[id_a], S[id_b]),   S fp32 [n_items, k]: whatever the caller measures similarity in (row-normalised item factors
  * for cosine, the factors themselves for dot; top-k-rec_amd/diversity.py prepare), chain = the mode-1 score of K4 / K12 without a bias
- * (csrc/topk_parts.h exact_score; oracle/ref_np.py mfma_chain_scores): symmetric bit for bit.
+ * (csrc/score_chain.h exact_score; oracle/ref_np.py mfma_chain_scores): symmetric bit for bit.
  *
  *   tkr_mmr_select      ids int32 [n_rows, N]: a pool per row, valid up to the first negative id (the -1 padding of tkr_score_topk);
  *                       rel fp32 [n_rows, N]: the relevance of every entry.  sel_pos int32 [n_rows, t]: pool POSITIONS in pick order,
@@ -851,7 +851,7 @@ int tkr_bootstrap_sums(const double* X, int64_t n, int32_t C, int64_t pitch, int
  * whose factors are closest to it; "is the list more of the same?" -- 1 - the similarity of an entry to the nearest item of the
  * history (unexpectedness).  Both are one operation: for every entry of a row's list, the e most similar items of a second, per-row
  * set, the ANCHORS.  sim(a, b) = chain(S[a], S[b]) is K17's similarity exactly: S fp32 [n_items, k] is whatever the caller measures
- * similarity in (top-k-rec_amd/diversity.py similarity_table), chain = the mode-1 score of K4 / K12 without a bias (csrc/topk_parts.h
+ * similarity in (top-k-rec_amd/diversity.py similarity_table), chain = the mode-1 score of K4 / K12 without a bias (csrc/score_chain.h
  * exact_score; oracle/ref_np.py mfma_chain_scores), -0.0 mapped to +0.0, symmetric bit for bit; any k.
  *
  *   tkr_nearest_anchors  ids int32 [n_rows, t]: a list per row, valid up to the first id that is negative or >= n_items (K17's prefix

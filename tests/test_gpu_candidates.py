@@ -41,7 +41,7 @@ def _run(U, V, cands, bias=None, user_idx=None, rated=None):
     return s.cpu().numpy(), r.cpu().numpy(), ptr, cols
 
 
-@pytest.mark.parametrize('k', [1, 7, 8, 50, 128, 130, 264, 1000])
+@pytest.mark.parametrize('k', [1, 7, 8, 17, 50, 128, 130, 136, 264, 1000])
 def test_exact_arithmetic_with_ties_matches_oracle(k):
     """factors m * 2^-6 with small integer m, biases m * 2^-12: every order of summation gives the same bits and equal scores are
     everywhere; two columns planted to tie for every user sit in every list that is long enough.  1, 3, 5 and 70 rows (70: not a

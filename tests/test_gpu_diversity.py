@@ -48,7 +48,7 @@ def _pool(rng, rows, N, t):
     return ids
 
 
-@pytest.mark.parametrize('k', [1, 7, 50, 128, 130, 264, 1000])
+@pytest.mark.parametrize('k', [1, 7, 17, 50, 128, 130, 136, 264, 1000])
 def test_exact_arithmetic_with_ties_matches_oracle(k):
     """S entries m / 8 with integer |m| <= 2, rel entries q / 64, lambda a multiple of 1/4: every product and sum is exact in fp32 in any
     order and equal objectives are everywhere, so the tie rule decides most picks.  sel_pos equals the oracle's for EVERY row, and the

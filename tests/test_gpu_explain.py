@@ -58,7 +58,7 @@ def _case(rng, rows, t, e):
     return ids, ptr, np.concatenate(anchors).astype(np.int32)
 
 
-@pytest.mark.parametrize('k', [1, 7, 50, 128, 130, 264, 1000])
+@pytest.mark.parametrize('k', [1, 7, 17, 50, 128, 130, 136, 264, 1000])
 def test_exact_arithmetic_with_ties_matches_oracle(k):
     """S entries m / 8 with integer |m| <= 2: every product and sum is exact in fp32 in any order and equal similarities are everywhere,
     so the tie rule decides most results.  best_pos and the bits of best_sim equal the oracle's for EVERY row, among them an empty list,

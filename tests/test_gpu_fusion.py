@@ -21,6 +21,7 @@ pytestmark = pytest.mark.gpu
 N_USERS, N_ITEMS = 300, 200
 FIRST = 2 ** 32 - 1000                       # the counter carries into its high word inside the call
 KS16 = (8, 50, 128, 3, 24, 1, 64, 17, 8, 50, 2, 40, 128, 5, 16, 33)
+GENERIC_KS = (8, 50, 128, 136, 17)           # test_features_generic_inputs_equal_the_difference_of_k12_scores
 
 
 def _dev(a, dtype=None):
@@ -65,12 +66,12 @@ def _exact_models(ks, biased, n_users=N_USERS, n_items=N_ITEMS, seed=1):
 
 
 @functools.lru_cache(maxsize=None)
-def _generic_models(M=3, n_users=N_USERS, n_items=N_ITEMS, seed=2):
+def _generic_models(M=3, n_users=N_USERS, n_items=N_ITEMS, seed=2, ks=KS16):
     """N(0, 0.1^2) tables rounded like '%f'; k = (8, 50, 128, ...), model 1 with a bias"""
     rng = np.random.Generator(np.random.PCG64(seed))
     return tuple((np.round(rng.standard_normal((n_users, k)) * 0.1, 6).astype(np.float32),
                   np.round(rng.standard_normal((n_items, k)) * 0.1, 6).astype(np.float32),
-                  np.round(rng.standard_normal(n_items) * 0.1, 6).astype(np.float32) if q % 3 == 1 else None) for q, k in enumerate(KS16[:M]))
+                  np.round(rng.standard_normal(n_items) * 0.1, 6).astype(np.float32) if q % 3 == 1 else None) for q, k in enumerate(ks[:M]))
 
 
 @functools.lru_cache(maxsize=None)
@@ -113,9 +114,11 @@ def test_features_one_and_sixteen_models(M):
 
 
 def test_features_generic_inputs_equal_the_difference_of_k12_scores():
-    """K12 (tkr_hip.rank_candidates, the parent's kernel) scores the two-column rows {i, j}: D is fl(a - b) of ITS bits"""
+    """K12 (tkr_hip.rank_candidates, the parent's kernel) scores the two-column rows {i, j}: D is fl(a - b) of ITS bits.  Widths 8, 50
+    and 128 as everywhere here, then 136 (aligned: 17 float4 steps, a remainder behind every unroll factor of the chain) and 17 (odd:
+    one block of 8 paired steps, then the odd factor)"""
     import tkr_hip
-    models = _generic_models(3)
+    models = _generic_models(5, ks=GENERIC_KS)
     md = _models_dev(models)
     count = 4133
     D, trip = tkr_hip.fusion_features(md, _csr(), N_ITEMS, 21, FIRST, count, want_triplets=True)

@@ -1,5 +1,5 @@
 """K4 (tkr_score_topk) at EVERY factor width on generic inputs, held to the one fma chain of the library -- oracle/ref_np.mfma_chain_scores,
-exact_score in csrc/topk_parts.h -- bit for bit, and K12 / K8 / evaluate.py -M held to K4.  The other K4 tests reach widths above 256
+exact_score in csrc/score_chain.h -- bit for bit, and K12 / K8 / evaluate.py -M held to K4.  The other K4 tests reach widths above 256
 only with exact arithmetic, where any order of summation gives the same bits; here the factors are N(0, 0.01^2) rounded like '%f', on
 which the order shows in most score bits (tests/test_chain_oracle_cpu.py).  The oracle's double rounding is marked entry by entry
 (tests/_chain_oracle.chain_scores_checked), so no share of mismatches is allowed anywhere.

@@ -4,7 +4,7 @@ Index work (raw ranks, hit counts): bit-exact.  Reciprocal-rank sums: fp64, |d| 
 the same terms in a different order).
 
 From test_raw_ranks_are_the_oracles_on_the_chain on: K6 (tkr_raw_ranks) held to the library's one fp32 score chain
-(oracle/ref_np.mfma_chain_scores, exact_score in csrc/topk_parts.h) at any factor width, on generic inputs and on
+(oracle/ref_np.mfma_chain_scores, exact_score in csrc/score_chain.h) at any factor width, on generic inputs and on
 mirror pairs (tests/_chain_oracle.mirror_case: every column has a twin whose score is equal in real arithmetic, so
 only the order of summation separates the two), and K7 alone on raw ranks made up by the test.
 

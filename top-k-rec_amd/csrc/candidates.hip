@@ -1,7 +1,7 @@
 // K12 -- score and rank per-user candidate lists: many rows, a short list of candidate columns each (re-ranking a first-stage
 // shortlist; evaluation against sampled negatives).  For entry e of row r with column c = cand_cols[e]:
 //
-//   score_out[e] = s(r, c)                       the one fp32 score of K4 / K8: exact_score (csrc/topk_parts.h), masked entries too
+//   score_out[e] = s(r, c)                       the one fp32 score of K4 / K8: exact_score (csrc/score_chain.h), masked entries too
 //   rank_out[e]  = -1                            when c is masked for the row, else
 //                  #{e' of the row, unmasked, e' != e : s(r, c_e') > s(r, c_e) or (equal and c_e' > c_e)}
 //
@@ -43,7 +43,7 @@ __device__ __forceinline__ CandEntry cand_entry(const float* __restrict__ up, co
     CandEntry r;
     if ((uint32_t)c >= (uint32_t)n_cols) { r.score = -INFINITY; r.key = 0u; return r; }
     r.score = exact_score(up, Vt + (size_t)c * k, k, bias, c);
-    const bool masked = mask && ((mask[(size_t)(c >> 5) * pitch + row] >> (c & 31)) & 1u);
+    const bool masked = mask && col_masked(mask, pitch, row, c);
     r.key = masked ? 0u : ordered_bits(r.score);
     return r;
 }
@@ -61,10 +61,8 @@ __device__ __forceinline__ int count4_rule(uint4 o, int j, uint32_t mine, int i)
 // A slab is kStageS factors of each k-half of every row: 8 consecutive lanes bring one row's slab (2 x 64 B) with one float4 load
 // each, 8 loads per lane and slab, held in registers while the previous slab is consumed (the double buffer: registers + one LDS
 // image), then written to the wave's image [64][2 kStageS + 4] (pitch 36 floats: conflict-free b128 reads); every lane runs the chain
-// of exact_score (csrc/topk_parts.h) over its own row out of LDS -- the same fused multiply-adds on the same operands in the same
-// order, acc <- fma(v[j], u[j], acc); acc <- fma(v[KH+j], u[KH+j], acc), then fl(acc + bias) and + 0.0: the same bits (the tests hold
-// it to the oracle, to K4's score bits and to K8's ranks; measured against the form in which every lane gathers its own row with
-// exact_score, bitwise equal on 120 M scores and 7-8 % faster: DESIGN.md section 4 K12).
+// (csrc/score_chain.h chain_step4, chain_finish) over its own row out of LDS (measured against the form in which every lane gathers
+// its own row with exact_score, bitwise equal on 120 M scores and 7-8 % faster: DESIGN.md section 4 K12).
 constexpr int kStageS = 16, kStagePitch = 2 * kStageS + 4;
 
 __device__ __forceinline__ float staged_score(const float* __restrict__ up, const float* __restrict__ Vt, const float* __restrict__ bias,
@@ -96,14 +94,10 @@ __device__ __forceinline__ float staged_score(const float* __restrict__ up, cons
         for (int kk = 0; kk < n; kk += 4) {
             const float4 a0 = *reinterpret_cast<const float4*>(mine + kk), a1 = *reinterpret_cast<const float4*>(mine + kStageS + kk);
             const float4 b0 = *reinterpret_cast<const float4*>(up + s0 + kk), b1 = *reinterpret_cast<const float4*>(up + KH + s0 + kk);
-            acc = fmaf(a0.x, b0.x, acc); acc = fmaf(a1.x, b1.x, acc);
-            acc = fmaf(a0.y, b0.y, acc); acc = fmaf(a1.y, b1.y, acc);
-            acc = fmaf(a0.z, b0.z, acc); acc = fmaf(a1.z, b1.z, acc);
-            acc = fmaf(a0.w, b0.w, acc); acc = fmaf(a1.w, b1.w, acc);
+            chain_step4(acc, a0, a1, b0, b1);
         }
     }
-    acc = acc + ((bias && live) ? bias[c_own] : 0.f);
-    return acc + 0.0f;
+    return chain_finish(acc, live ? bias : nullptr, c_own);
 }
 
 __global__ __launch_bounds__(kCandWaves * TKR_WAVE) void cand_rows_kernel(
@@ -129,7 +123,7 @@ __global__ __launch_bounds__(kCandWaves * TKR_WAVE) void cand_rows_kernel(
             if (i < L) {
                 if (!live) sc = -INFINITY;
                 score_out[e0 + i] = sc;
-                const bool masked = !live || (mask && ((mask[(size_t)(c >> 5) * pitch + row] >> (c & 31)) & 1u));
+                const bool masked = !live || (mask && col_masked(mask, pitch, row, c));
                 key = masked ? 0u : ordered_bits(sc);
             }
             keys[i] = key;
@@ -178,7 +172,7 @@ __global__ __launch_bounds__(256) void cand_long_kernel(
         auto key_of = [&](int i) -> uint32_t {
             const int c = cand_cols[e0 + i];
             if ((uint32_t)c >= (uint32_t)n_cols) return 0u;
-            const bool masked = mask && ((mask[(size_t)(c >> 5) * pitch + row] >> (c & 31)) & 1u);
+            const bool masked = mask && col_masked(mask, pitch, row, c);
             return masked ? 0u : ordered_bits(score_out[e0 + i]);
         };
         for (int b0 = 0; b0 < L; b0 += 256) {

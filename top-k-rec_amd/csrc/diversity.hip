@@ -4,7 +4,7 @@
 //
 //   sim(a, b) = chain(S[id_a], S[id_b])          S: dense fp32 [n_items, k], whatever the caller measures similarity in
 //
-// with chain = exact_score (csrc/topk_parts.h) without bias: the fma chain of K4 / K8 / K12 with the two k-halves interleaved, the one
+// with chain = exact_score (csrc/score_chain.h) without bias: the fma chain of K4 / K8 / K12 with the two k-halves interleaved, the one
 // fp32 order of the library (oracle/ref_np.py mfma_chain_scores).  Products commute and the order is fixed: sim(a, b) == sim(b, a) bit
 // for bit.
 //

@@ -3,7 +3,7 @@
 //
 //   sim(a, b) = chain(S[a], S[b])          S: dense fp32 [n_items, k], whatever the caller measures similarity in
 //
-// with chain = exact_score (csrc/topk_parts.h) without bias: one fma chain per (entry, anchor) pair, kept in ONE lane from the first
+// with chain = exact_score (csrc/score_chain.h) without bias: one fma chain per (entry, anchor) pair, kept in ONE lane from the first
 // product to the last -- a chain is never reduced across lanes, which would change its bits.
 //
 //   nearest_anchors_kernel<STAGED, E, BLOCK>
@@ -65,34 +65,13 @@ __device__ __forceinline__ void keep_best(uint64_t (&keys)[E], uint64_t x) {
     }
 }
 
-// N chains of one entry at once: exact_score(other[j], mine) for every j, each chain in exact_score's order (the same fma sequence, so
-// the same bits), with the entry's row read ONCE per N chains -- the kernel is bound by its LDS reads, and this takes them from 2 to
-// 1 + 1 / N rows per chain
+// N chains of one entry at once: exact_score(other[j], mine) for every j with the entry's row read ONCE per N chains -- the kernel is
+// bound by its LDS reads, and this takes them from 2 to 1 + 1 / N rows per chain
 template <int N>
 __device__ __forceinline__ void chains(const float* __restrict__ mine, const float* const (&other)[N], int k, float (&out)[N]) {
-    if ((k & 7) == 0) {
-        const int KH = k >> 1;
-        float acc[N];
+    chain_rows<N, 2, 1, false>(mine, other, k, out);
 #pragma unroll
-        for (int j = 0; j < N; ++j) acc[j] = 0.f;
-#pragma unroll 2
-        for (int kk = 0; kk < KH; kk += 4) {
-            const float4 a0 = *reinterpret_cast<const float4*>(mine + kk), a1 = *reinterpret_cast<const float4*>(mine + KH + kk);
-#pragma unroll
-            for (int j = 0; j < N; ++j) {
-                const float4 b0 = *reinterpret_cast<const float4*>(other[j] + kk), b1 = *reinterpret_cast<const float4*>(other[j] + KH + kk);
-                acc[j] = fmaf(a0.x, b0.x, acc[j]); acc[j] = fmaf(a1.x, b1.x, acc[j]);
-                acc[j] = fmaf(a0.y, b0.y, acc[j]); acc[j] = fmaf(a1.y, b1.y, acc[j]);
-                acc[j] = fmaf(a0.z, b0.z, acc[j]); acc[j] = fmaf(a1.z, b1.z, acc[j]);
-                acc[j] = fmaf(a0.w, b0.w, acc[j]); acc[j] = fmaf(a1.w, b1.w, acc[j]);
-            }
-        }
-#pragma unroll
-        for (int j = 0; j < N; ++j) out[j] = acc[j] + 0.0f;          // -0.0 -> +0.0, as exact_score
-    } else {
-#pragma unroll
-        for (int j = 0; j < N; ++j) out[j] = exact_score(other[j], mine, k, nullptr, 0);
-    }
+    for (int j = 0; j < N; ++j) out[j] = chain_pos_zero(out[j]);     // no bias
 }
 
 // rows cols[0 .. n) of S -> dst[a][pitch], all threads together, coalesced over k; a row whose column is negative is left out.  With

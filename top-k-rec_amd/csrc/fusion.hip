@@ -1,7 +1,7 @@
 // K16 -- learn the weights of a linear fusion of several trained models (the reference's old/methods/bfusion.py + ranking_fusion.py and
 // efusion.py).  Serving a fused model needs no kernel: sum_m w_m (<U_m[u], V_m[i]> + b_m[i]) is the inner product of two concatenated
 // tables (top-k-rec_amd/fusion.py fuse).  Learning the weights needs the per-model scores of sampled triplets or of every training
-// like: gathers over M table pairs.  Every score here is exact_score (csrc/topk_parts.h) as it stands -- the bits of K4 and K12 --
+// like: gathers over M table pairs.  Every score here is exact_score (csrc/score_chain.h) as it stands -- the bits of K4 and K12 --
 // sequential in one lane, never reduced across lanes (chain_scores below: exact_score's chain with more loads in flight).
 //
 //   fusion_features_kernel       a lane per triplet g = first_triplet + t: draw_triplet (csrc/sampler_draw.h, K1's stream) then, model
@@ -15,7 +15,7 @@
 //   fusion_user_weights_kernel   a wave per user: lanes take likes l, l + 64, ..., the user's rows are uniform over the wave; the
 //                                squared errors go through wave_sum.
 #include "tkr_common.h"
-#include "topk_parts.h"
+#include "score_chain.h"
 #include "sampler_draw.h"
 #include "../../include/tkr.h"
 
@@ -27,67 +27,12 @@ constexpr int kFusionMax = TKR_FUSION_MAX_MODELS;
 constexpr int kSgdThreads = 1024, kSgdWaves = kSgdThreads / TKR_WAVE;
 constexpr int kUwWaves = 4;
 
-// The chain of exact_score (csrc/topk_parts.h) for N item rows against one user row, side by side: per row the same fused multiply-adds
-// on the same operands in the same order -- acc <- fma(v[kk], u[kk], acc); acc <- fma(v[KH + kk], u[KH + kk], acc), kk = 0 .. KH-1 (the
-// second only while KH + kk < k) -- so the same bits (the tests hold D to K12's own scores and to the oracle).  What differs is the
-// loads: the user's factors are loaded once for the positive and the negative of a triplet, and at a width that is no multiple of 8
-// (k = 50, the reference's default) eight steps of both halves are in flight at a time instead of one (measured: DESIGN.md section 4 K16).
+// exact_score's chain (csrc/score_chain.h chain_rows) for N item rows against one user row, with other loads: the user's factors are
+// loaded once for the positive and the negative of a triplet, and at a width that is no multiple of 8 (k = 50, the reference's
+// default) eight steps of both halves are in flight at a time instead of one (measured: DESIGN.md section 4 K16).
 template <int N>
 __device__ __forceinline__ void chain_scores(const float* __restrict__ up, const float* const (&vp)[N], int k, float (&acc)[N]) {
-    const int KH = (k + 1) >> 1;
-#pragma unroll
-    for (int n = 0; n < N; ++n) acc[n] = 0.f;
-    if ((k & 7) == 0) {                                          // both halves 16-byte aligned
-#pragma unroll 4
-        for (int kk = 0; kk < KH; kk += 4) {
-            const float4 b0 = *reinterpret_cast<const float4*>(up + kk), b1 = *reinterpret_cast<const float4*>(up + KH + kk);
-            float4 a0[N], a1[N];
-#pragma unroll
-            for (int n = 0; n < N; ++n) {
-                a0[n] = *reinterpret_cast<const float4*>(vp[n] + kk);
-                a1[n] = *reinterpret_cast<const float4*>(vp[n] + KH + kk);
-            }
-#pragma unroll
-            for (int n = 0; n < N; ++n) {
-                acc[n] = fmaf(a0[n].x, b0.x, acc[n]); acc[n] = fmaf(a1[n].x, b1.x, acc[n]);
-                acc[n] = fmaf(a0[n].y, b0.y, acc[n]); acc[n] = fmaf(a1[n].y, b1.y, acc[n]);
-                acc[n] = fmaf(a0[n].z, b0.z, acc[n]); acc[n] = fmaf(a1[n].z, b1.z, acc[n]);
-                acc[n] = fmaf(a0[n].w, b0.w, acc[n]); acc[n] = fmaf(a1[n].w, b1.w, acc[n]);
-            }
-        }
-        return;
-    }
-    const int both = k - KH;                                     // steps that have a factor in each half: KH, or KH - 1 at an odd k
-    int kk = 0;
-    for (; kk + 8 <= both; kk += 8) {
-        float b0[8], b1[8], a0[N][8], a1[N][8];
-#pragma unroll
-        for (int q = 0; q < 8; ++q) {
-            b0[q] = up[kk + q];
-            b1[q] = up[KH + kk + q];
-#pragma unroll
-            for (int n = 0; n < N; ++n) { a0[n][q] = vp[n][kk + q]; a1[n][q] = vp[n][KH + kk + q]; }
-        }
-#pragma unroll
-        for (int q = 0; q < 8; ++q)
-#pragma unroll
-            for (int n = 0; n < N; ++n) { acc[n] = fmaf(a0[n][q], b0[q], acc[n]); acc[n] = fmaf(a1[n][q], b1[q], acc[n]); }
-    }
-    for (; kk < both; ++kk) {
-        const float b0 = up[kk], b1 = up[KH + kk];
-#pragma unroll
-        for (int n = 0; n < N; ++n) { acc[n] = fmaf(vp[n][kk], b0, acc[n]); acc[n] = fmaf(vp[n][KH + kk], b1, acc[n]); }
-    }
-    if (k & 1) {
-        const float b0 = up[KH - 1];
-#pragma unroll
-        for (int n = 0; n < N; ++n) acc[n] = fmaf(vp[n][KH - 1], b0, acc[n]);
-    }
-}
-// fl(acc + bias), then -0.0 -> +0.0: the tail of exact_score
-__device__ __forceinline__ float with_bias(float acc, const float* bias, int col) {
-    acc = acc + (bias ? bias[col] : 0.f);
-    return acc + 0.0f;
+    chain_rows<N, 4, 8, false>(up, vp, k, acc);
 }
 
 __global__ __launch_bounds__(256) void fusion_features_kernel(
@@ -114,7 +59,7 @@ __global__ __launch_bounds__(256) void fusion_features_kernel(
             const float* const vp[2] = {md.m[m].V + (size_t)i * k, md.m[m].V + (size_t)j * k};
             float acc[2];
             chain_scores<2>(md.m[m].U + (size_t)u * k, vp, k, acc);
-            d = with_bias(acc[0], md.m[m].bias, i) - with_bias(acc[1], md.m[m].bias, j);
+            d = chain_finish(acc[0], md.m[m].bias, i) - chain_finish(acc[1], md.m[m].bias, j);
         }
         D_out[t * M + m] = d;
     }
@@ -219,7 +164,7 @@ __global__ __launch_bounds__(kUwWaves * TKR_WAVE) void fusion_user_weights_kerne
                 const float* const vp[1] = {md.m[m].V + (size_t)c * k};
                 float one[1];
                 chain_scores<1>(up, vp, k, one);
-                s = with_bias(one[0], md.m[m].bias, c);
+                s = chain_finish(one[0], md.m[m].bias, c);
             }
             const float err = s - 1.0f;
             acc = fmaf(err, err, acc);

@@ -70,7 +70,7 @@ __global__ __launch_bounds__(256) void like_keys_kernel(const float* __restrict_
     for (int64_t e = e0 + lane; e < e1; e += 64) {
         const int c = like_cols[e];
         bool ranked = c >= 0 && c < n_cols;
-        if (ranked && mask) ranked = ((mask[(size_t)(c >> 5) * pitch + row] >> (c & 31)) & 1u) == 0u;
+        if (ranked && mask) ranked = !col_masked(mask, pitch, row, c);
         ws.ukey[e] = ranked ? like_key(exact_score(up, Vt + (size_t)c * k, k, bias, c), c) : (((uint64_t)kNoRank << 32) | (uint32_t)c);
         rank_out[e] = ranked ? 0 : -1;
     }
@@ -103,8 +103,9 @@ __global__ __launch_bounds__((like_waves<KHP>() * TKR_WAVE)) void like_ranks_ker
     const int64_t* __restrict__ like_ptr, int32_t* __restrict__ rank_out, LikeWs ws, int tiles_per_split) {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem_raw[];
     constexpr int WAVES = like_waves<KHP>();
-    constexpr int KP = 2 * KHP + 4;                              // padded LDS row (floats): conflict-free b128 reads
     constexpr int users = WAVES * 32, NT_ = WAVES * 64;
+    using Tile = ScoreTile<KHP, NT_>;
+    constexpr int KP = Tile::KP;
     float* tile = reinterpret_cast<float*>(smem_raw);            // [2][32][KP]
     float* tbias = tile + 2 * 32 * KP;                           // [2][32]
     uint64_t* keys = reinterpret_cast<uint64_t*>(tbias + 64);    // [kLikeCap]
@@ -116,77 +117,19 @@ __global__ __launch_bounds__((like_waves<KHP>() * TKR_WAVE)) void like_ranks_ker
     const int block = blockIdx.x;
     const int row = block * users + wave * 32 + ul;
     const bool user_ok = row < n_rows;
-    const int KH = (k + 1) >> 1;
     const int64_t seg0 = like_ptr[block * users], seg1 = like_ptr[min(n_rows, (block + 1) * users)];
     if (seg1 <= seg0) return;                                    // no likes in this user block (workgroup-uniform)
     const int64_t my0 = user_ok ? like_ptr[row] : seg1, my1 = user_ok ? like_ptr[row + 1] : seg1;
 
-    // ---- B operand: this lane's user, half h of its factor row, resident for the whole kernel
     float breg[KHP];
-    {
-        const int urow = user_ok ? (uidx ? uidx[row] : row) : 0;
-        const float* up = U + (size_t)urow * k + h * KH;
-#pragma unroll
-        for (int kk = 0; kk < KHP; ++kk) {
-            const int e = h * KH + kk;
-            breg[kk] = (user_ok && kk < KH && e < k) ? up[kk] : 0.f;
-        }
-    }
+    Tile::load_user(breg, U, uidx, row, user_ok, k, h);
     const int n_tiles_all = (n_cols + 31) >> 5;
     const int t_begin = blockIdx.y * tiles_per_split;
     const int n_tiles = min(n_tiles_all, t_begin + tiles_per_split);
     if (t_begin >= n_tiles) return;
 
-    // ---- tile staging: global -> registers (issued early) -> LDS (written after the MFMA chain), as score_topk_kernel
-    constexpr int NC = (32 * 2 * KHP / 4 + NT_ - 1) / NT_;        // float4 chunks per thread
-    const bool vec = (k & 7) == 0;                                // then KH % 4 == 0: no chunk straddles the halves
-    const int k4 = k >> 2;
-    int src_off[NC], dst_off[NC], item_of[NC];
-#pragma unroll
-    for (int q = 0; q < NC; ++q) {
-        const int c = tid + q * NT_;
-        const int item = vec ? c / k4 : 0, e = vec ? (c % k4) * 4 : 0;
-        const bool live = vec && c < 32 * k4;
-        src_off[q] = live ? item * k + e : -1;
-        dst_off[q] = item * KP + (e / KH) * KHP + (e % KH);
-        item_of[q] = item;
-    }
-    float4 stg[NC];
-    float stg_bias = 0.f;
-    auto stage_load = [&](int t) {
-        if (vec) {
-#pragma unroll
-            for (int q = 0; q < NC; ++q) {
-                stg[q] = make_float4(0.f, 0.f, 0.f, 0.f);
-                if (src_off[q] >= 0 && t * 32 + item_of[q] < n_cols)
-                    stg[q] = *reinterpret_cast<const float4*>(Vt + (size_t)t * 32 * k + src_off[q]);
-            }
-        }
-        if (tid < 32) {
-            const int col = t * 32 + tid;
-            stg_bias = (bias && col < n_cols) ? bias[col] : 0.f;
-        }
-    };
-    auto stage_store = [&](int t, int buf) {
-        float* dst = tile + buf * 32 * KP;
-        if (vec) {
-#pragma unroll
-            for (int q = 0; q < NC; ++q)
-                if (src_off[q] >= 0) *reinterpret_cast<float4*>(dst + dst_off[q]) = stg[q];
-        } else {
-            for (int c = tid; c < 32 * 2 * KHP; c += NT_) {
-                const int item = c / (2 * KHP), p = c % (2 * KHP);
-                const int hh = p / KHP, kk = p % KHP;
-                const int e = hh * KH + kk, col = t * 32 + item;
-                float v = 0.f;
-                if (kk < KH && e < k && col < n_cols) v = Vt[(size_t)col * k + e];
-                dst[item * KP + p] = v;
-            }
-        }
-        if (tid < 32) tbias[buf * 32 + tid] = stg_bias;
-    };
-    if (vec)                                                     // zero the LDS padding the vector path never writes
-        for (int c = tid; c < 2 * 32 * KP; c += NT_) tile[c] = 0.f;
+    Tile tl(tile, tbias, Vt, bias, n_cols, k, NT_);
+    if (tl.vec) tl.zero_padding();
     const uint32_t tail_mask = (n_cols & 31) ? (0xffffffffu << (n_cols & 31)) : 0u;
 
     for (int64_t cs = seg0; cs < seg1; cs += kLikeCap) {         // chunks of the block's sorted keys (one, as a rule)
@@ -201,11 +144,11 @@ __global__ __launch_bounds__((like_waves<KHP>() * TKR_WAVE)) void like_ranks_ker
         for (int o = 1; o < 64; o <<= 1) pmax = max(pmax, __shfl_xor(pmax, o, 64));
         const bool wave_counts = pmax > 0;                       // wave-uniform: no like of these 32 users in this chunk
         const int top = __builtin_amdgcn_readfirstlane(wave_counts ? 1 << (31 - __clz(pmax)) : 0);
-        stage_load(t_begin);
-        stage_store(t_begin, t_begin & 1);
+        tl.stage_load(t_begin);
+        tl.stage_store(t_begin, t_begin & 1);
         __syncthreads();
         const uint64_t lowest = P > 0 ? keys[base] : ~0ull;
-        if (t_begin + 1 < n_tiles) stage_load(t_begin + 1);
+        if (t_begin + 1 < n_tiles) tl.stage_load(t_begin + 1);
 
         for (int t = t_begin; t < n_tiles; ++t) {
             const int buf = t & 1;
@@ -213,19 +156,10 @@ __global__ __launch_bounds__((like_waves<KHP>() * TKR_WAVE)) void like_ranks_ker
             f32x16 acc = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
             if (wave_counts) {
                 // ---- 32 items x 32 users x k: exact fp32 MFMA
-                const float* arow = tile + buf * 32 * KP + ul * KP + h * KHP;
-#pragma unroll
-                for (int kk = 0; kk < KHP; kk += 4) {
-                    const float4 a = *reinterpret_cast<const float4*>(arow + kk);
-                    acc = __builtin_amdgcn_mfma_f32_32x32x2f32(a.x, breg[kk + 0], acc, 0, 0, 0);
-                    acc = __builtin_amdgcn_mfma_f32_32x32x2f32(a.y, breg[kk + 1], acc, 0, 0, 0);
-                    acc = __builtin_amdgcn_mfma_f32_32x32x2f32(a.z, breg[kk + 2], acc, 0, 0, 0);
-                    acc = __builtin_amdgcn_mfma_f32_32x32x2f32(a.w, breg[kk + 3], acc, 0, 0, 0);
-                }
-                mfma_result_guard(acc);
+                mfma_f32_group<KHP>(acc, tl.arow(buf, ul, h), breg);
             }
-            if (t + 1 < n_tiles) stage_store(t + 1, buf ^ 1);
-            if (t + 2 < n_tiles) stage_load(t + 2);
+            if (t + 1 < n_tiles) tl.stage_store(t + 1, buf ^ 1);
+            if (t + 2 < n_tiles) tl.stage_load(t + 2);
             if (wave_counts) {
                 // ---- epilogue: register r of lane (ul, h) = item (r&3) + 8*(r>>2) + 4h of the tile, user ul of the wave
                 if (!user_ok) maskw = 0xffffffffu;
@@ -241,7 +175,7 @@ __global__ __launch_bounds__((like_waves<KHP>() * TKR_WAVE)) void like_ranks_ker
 #pragma unroll
                     for (int j = 0; j < 4; ++j) {
                         const int r = 4 * g + j;
-                        const float s = (acc[r] + bb[j]) + 0.0f;     // fl(fl(dot) + b); -0.0 -> +0.0
+                        const float s = chain_finish(acc[r], bb[j]);
                         const uint64_t x = like_key(s, t * 32 + 8 * g + 4 * h + j);
                         key[r] = ((mh >> (8 * g + j)) & 1u) ? 0ull : x;      // 0: below every like
                         any |= key[r] > lowest;
@@ -297,7 +231,7 @@ __global__ __launch_bounds__(256) void like_ranks_wide_kernel(const float* __res
     for (int c0 = 0; c0 < n_cols; c0 += 64) {
         const int c = c0 + lane;
         uint64_t x = 0;                                          // 0: below every like
-        if (c < n_cols && !(mask && ((mask[(size_t)(c >> 5) * pitch + row] >> (c & 31)) & 1u)))
+        if (c < n_cols && !(mask && col_masked(mask, pitch, row, c)))
             x = like_key(exact_score(up, Vt + (size_t)c * k, k, bias, c), c);
         for (int64_t e = e0; e < e1; ++e) {
             const uint64_t tq = ws.ukey[e];

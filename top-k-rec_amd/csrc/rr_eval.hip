@@ -5,7 +5,7 @@
 // summed next to the hit counts.  K4 yields the first `total` unrated columns of a user in order; the raw rank of
 // the p-th of them is p + (number of the user's train-rated columns ranked before it).  K6 computes exactly that
 // count: one wave per row; a lane takes one column, kept or rated, and runs the library's ONE fp32 score chain over it
-// (exact_score, csrc/topk_parts.h: the bits K4 ranked the kept list by, at any factor width), then the wave counts,
+// (exact_score, csrc/score_chain.h: the bits K4 ranked the kept list by, at any factor width), then the wave counts,
 // for every kept column, the rated ones in front of it under the canonical order (descending score, ties -> higher
 // column first).  K7 turns (kept ids, raw ranks, like lists) into per-row first-bucket hit counts and
 // reciprocal-rank sums; the host sums rows and accumulates buckets (utils.py:115-117: for k in range(j, interval)).

@@ -186,7 +186,7 @@ struct FastVisit {
             asm volatile("" ::: "memory");                       // keeps the scalar branch
             uint64_t m = hr[R];
             if constexpr (MASKED) m = __ballot((hits & (1u << R)) != 0u);
-            const float val = REFINE ? sc[R] : sc[R] + 0.0f;     // -0.0 -> +0.0: ties with 0.0 like numpy (refine: rescored exactly later)
+            const float val = REFINE ? sc[R] : chain_pos_zero(sc[R]);     // (refine: rescored exactly later)
             uint64_t saved;
             uint32_t id;
             if constexpr (sizeof(IdT) == 2)
@@ -286,7 +286,7 @@ __device__ __forceinline__ void filter_tile(const TopkSmem<IdT>& sm, const f32x1
             asm volatile("" ::: "memory");                       // (keeps the branch: the body must not be if-converted)
             if (hits & (1u << r)) {
                 if (pos < kCap) {
-                    sm.cs[pos * users + uw] = sc[r] + 0.0f;      // -0.0 -> +0.0: ties with 0.0 like numpy
+                    sm.cs[pos * users + uw] = chain_pos_zero(sc[r]);
                     sm.ci[pos * users + uw] = (IdT)(t * 32 + (r & 3) + 8 * (r >> 2) + 4 * h);
                 } else {
                     unplaced |= 1u << r;                         // list full: trimmed below, then appended
@@ -309,7 +309,7 @@ __device__ __forceinline__ void filter_tile(const TopkSmem<IdT>& sm, const f32x1
                 if ((unplaced & (1u << r)) && sc[r] >= thr) {
                     const int p2 = atomicAdd(&sm.cnt[uw], 1);
                     if (!REFINE || p2 < kCap) {
-                        sm.cs[p2 * users + uw] = sc[r] + 0.0f;
+                        sm.cs[p2 * users + uw] = chain_pos_zero(sc[r]);
                         sm.ci[p2 * users + uw] = (IdT)(t * 32 + (r & 3) + 8 * (r >> 2) + 4 * h);
                     } else {
                         *lost = true;
@@ -330,15 +330,6 @@ __device__ __forceinline__ void add_bias_inplace(f32x16& acc, const float* tbias
     for (int g = 0; g < 4; ++g) {
         const float4 bq = *reinterpret_cast<const float4*>(tbias + 8 * g + 4 * h);
         acc[4 * g + 0] += bq.x; acc[4 * g + 1] += bq.y; acc[4 * g + 2] += bq.z; acc[4 * g + 3] += bq.w;
-    }
-}
-
-__device__ __forceinline__ void add_scaled_bias_inplace(f32x16& acc, const float* tbias, int h, float bscale) {
-#pragma unroll
-    for (int g = 0; g < 4; ++g) {
-        const float4 bq = *reinterpret_cast<const float4*>(tbias + 8 * g + 4 * h);
-        acc[4 * g + 0] = fmaf(bq.x, bscale, acc[4 * g + 0]); acc[4 * g + 1] = fmaf(bq.y, bscale, acc[4 * g + 1]);
-        acc[4 * g + 2] = fmaf(bq.z, bscale, acc[4 * g + 2]); acc[4 * g + 3] = fmaf(bq.w, bscale, acc[4 * g + 3]);
     }
 }
 
@@ -449,8 +440,8 @@ __device__ __forceinline__ void write_rows_refine(const TopkSmem<IdT>& sm, const
             // exact_score runs four dependent memory round trips per candidate (32 of its 64 row loads fit the registers at a time)
             // and the final stage is bound by exactly that chain (68 round trips per wave: 16 % of the Netflix pass, 30 % of the
             // ML-10M pass).  Here ALL the loads of the candidate's item row go out first (128 registers), the few user rows of the
-            // pass follow through LDS (every lane of a user reads the same addresses: broadcasts), and the fma chain -- the same
-            // chain, element for element -- starts after ONE round trip.
+            // pass follow through LDS (every lane of a user reads the same addresses: broadcasts), and the fma chain starts after ONE
+            // round trip.
             const bool live = f < total;
             const int e = f - offs[u], uq = wave * 32 + u;
             const int col = live ? (int)sm.ci[e * sm.users + uq] : 0;
@@ -480,19 +471,15 @@ __device__ __forceinline__ void write_rows_refine(const TopkSmem<IdT>& sm, const
             for (int j0 = 0; j0 < q4; j0 += NF) {
 #pragma unroll
                 for (int j = 0; j < NF; ++j) {
-                    const float4 b0 = urow[j0 + j], b1 = urow[q4 + j0 + j];
-                    acc = fmaf(va[j].x, b0.x, acc); acc = fmaf(vb[j].x, b1.x, acc);
-                    acc = fmaf(va[j].y, b0.y, acc); acc = fmaf(vb[j].y, b1.y, acc);
-                    acc = fmaf(va[j].z, b0.z, acc); acc = fmaf(vb[j].z, b1.z, acc);
-                    acc = fmaf(va[j].w, b0.w, acc); acc = fmaf(vb[j].w, b1.w, acc);
+                    chain_step4(acc, va[j], vb[j], urow[j0 + j], urow[q4 + j0 + j]);
                 }
                 if (j0 + NF < q4) {
 #pragma unroll
                     for (int j = 0; j < NF; ++j) { va[j] = vrow[j0 + NF + j]; vb[j] = vrow[q4 + j0 + NF + j]; }
                 }
             }
-            acc = acc + (bias ? bias[col] : 0.f);
-            if (live) sm.cs[e * sm.users + uq] = acc + 0.0f;
+            const float sc = chain_finish(acc, bias, col);
+            if (live) sm.cs[e * sm.users + uq] = sc;
             __builtin_amdgcn_wave_barrier();                     // the next pass overwrites the staged rows
         } else if (f < total) {
             const int e = f - offs[u], uq = wave * 32 + u, r = ws.block * sm.users + uq;
@@ -522,7 +509,8 @@ __global__ __launch_bounds__((WAVES * TKR_WAVE)) void score_topk_kernel(
     const uint32_t* __restrict__ only_flagged /*per user block, or null: rank every block.  Set by the bound-and-refine kernel
                                                 for blocks it could not finish*/) {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem_raw[];
-    constexpr int KP = 2 * KHP + 4;                              // padded LDS row (floats): conflict-free b128 reads
+    using Tile = ScoreTile<KHP, WAVES * 64>;
+    constexpr int KP = Tile::KP;
     const int W = blockDim.x >> 6;
     const int users = W * 32;
     TopkSmem<IdT> sm;
@@ -542,84 +530,24 @@ __global__ __launch_bounds__((WAVES * TKR_WAVE)) void score_topk_kernel(
     const TopkSlot ws = {it.x, it.w & 0xffff, it.w >> 16};
     const int row = ws.block * users + uw;                       // row of the output / index into uidx
     const bool user_ok = row < n_rows;
-    const int KH = (k + 1) >> 1;                                 // k-range of half h: [h*KH, min(k, (h+1)*KH))
 
-    // ---- B operand: this lane's user, half h of its factor row, resident for the whole kernel
     float breg[KHP];
-    {
-        const int urow = user_ok ? (uidx ? uidx[row] : row) : 0;
-        const float* up = U + (size_t)urow * k + h * KH;
-#pragma unroll
-        for (int kk = 0; kk < KHP; ++kk) {
-            const int e = h * KH + kk;
-            breg[kk] = (user_ok && kk < KH && e < k) ? up[kk] : 0.f;
-        }
-    }
+    Tile::load_user(breg, U, uidx, row, user_ok, k, h);
     for (int s = tid; s < users; s += blockDim.x) sm.cnt[s] = 0;
     float thr = (thr_shared && user_ok) ? unordered_bits(thr_shared[row]) : -INFINITY;   // what other item ranges found so far
     const int n_tiles_all = (n_cols + 31) >> 5;
     const int t_begin = it.y;                                    // this workgroup ranks items of tiles [t_begin, n_tiles)
     const int n_tiles = items ? it.z : min(n_tiles_all, t_begin + tiles_per_split);
 
-    // ---- tile staging: global -> registers (issued early) -> LDS (written after the MFMA chain) ------
-    // float4 path when every k-half starts 16-B aligned (k % 8 == 0); scalar path otherwise.
-    constexpr int NT_ = WAVES * 64;
-    constexpr int NC = (32 * 2 * KHP / 4 + NT_ - 1) / NT_;         // float4 chunks per thread
-    const bool vec = (k & 7) == 0;                                // then KH % 4 == 0: no chunk straddles the halves
-    const int nthreads = blockDim.x;
-    const int k4 = k >> 2;
-    int src_off[NC], dst_off[NC], item_of[NC];                    // per-chunk offsets, fixed for the whole kernel
-#pragma unroll
-    for (int q = 0; q < NC; ++q) {
-        const int c = tid + q * nthreads;
-        const int item = vec ? c / k4 : 0, e = vec ? (c % k4) * 4 : 0;
-        const bool live = vec && c < 32 * k4;
-        src_off[q] = live ? item * k + e : -1;
-        dst_off[q] = item * KP + (e / KH) * KHP + (e % KH);
-        item_of[q] = item;
-    }
-    float4 stg[NC];
-    float stg_bias = 0.f;
-    auto stage_load = [&](int t) {                                // tile t -> registers
-        if (vec) {
-#pragma unroll
-            for (int q = 0; q < NC; ++q) {
-                stg[q] = make_float4(0.f, 0.f, 0.f, 0.f);
-                if (src_off[q] >= 0 && t * 32 + item_of[q] < n_cols)
-                    stg[q] = *reinterpret_cast<const float4*>(Vt + (size_t)t * 32 * k + src_off[q]);
-            }
-        }
-        if (tid < 32) {
-            const int col = t * 32 + tid;
-            stg_bias = (bias && col < n_cols) ? bias[col] : 0.f;
-        }
-    };
-    auto stage_store = [&](int t, int buf) {                      // registers (or, scalar path, global) -> LDS
-        float* dst = sm.tile + buf * 32 * KP;
-        if (vec) {
-#pragma unroll
-            for (int q = 0; q < NC; ++q)
-                if (src_off[q] >= 0) *reinterpret_cast<float4*>(dst + dst_off[q]) = stg[q];
-        } else {
-            for (int c = tid; c < 32 * 2 * KHP; c += nthreads) {
-                const int item = c / (2 * KHP), p = c % (2 * KHP);
-                const int hh = p / KHP, kk = p % KHP;
-                const int e = hh * KH + kk, col = t * 32 + item;
-                float v = 0.f;
-                if (kk < KH && e < k && col < n_cols) v = Vt[(size_t)col * k + e];
-                dst[item * KP + p] = v;
-            }
-        }
-        if (tid < 32) sm.tbias[buf * 32 + tid] = stg_bias;
-    };
-    if (vec) {                                                    // zero the LDS padding the vector path never writes
-        for (int c = tid; c < 2 * 32 * KP; c += nthreads) sm.tile[c] = 0.f;
+    Tile tl(sm.tile, sm.tbias, Vt, bias, n_cols, k, blockDim.x);
+    if (tl.vec) {
+        tl.zero_padding();
         __syncthreads();
     }
-    stage_load(t_begin);
-    stage_store(t_begin, t_begin & 1);
+    tl.stage_load(t_begin);
+    tl.stage_store(t_begin, t_begin & 1);
     __syncthreads();
-    if (t_begin + 1 < n_tiles) stage_load(t_begin + 1);
+    if (t_begin + 1 < n_tiles) tl.stage_load(t_begin + 1);
 
     const uint32_t tail_mask = (n_cols & 31) ? (0xffffffffu << (n_cols & 31)) : 0u;
     int next_sched = t_begin + 2;                                // scheduled trims after 2, 3, 5, 8, 12, ... tiles (x1.5)
@@ -629,19 +557,10 @@ __global__ __launch_bounds__((WAVES * TKR_WAVE)) void score_topk_kernel(
         uint32_t maskw = (mask && user_ok) ? mask[(size_t)t * mask_pitch + row] : 0u;
         // ---- 32 items x 32 users x k: exact fp32 MFMA ------------------------------------------
         f32x16 acc = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
-        const float* arow = sm.tile + buf * 32 * KP + ul * KP + h * KHP;
-#pragma unroll
-        for (int kk = 0; kk < KHP; kk += 4) {
-            const float4 a = *reinterpret_cast<const float4*>(arow + kk);
-            acc = __builtin_amdgcn_mfma_f32_32x32x2f32(a.x, breg[kk + 0], acc, 0, 0, 0);
-            acc = __builtin_amdgcn_mfma_f32_32x32x2f32(a.y, breg[kk + 1], acc, 0, 0, 0);
-            acc = __builtin_amdgcn_mfma_f32_32x32x2f32(a.z, breg[kk + 2], acc, 0, 0, 0);
-            acc = __builtin_amdgcn_mfma_f32_32x32x2f32(a.w, breg[kk + 3], acc, 0, 0, 0);
-        }
-        mfma_result_guard(acc);
+        mfma_f32_group<KHP>(acc, tl.arow(buf, ul, h), breg);
         // tile t+1: registers -> the other LDS buffer (free since the barrier of tile t-1); tile t+2 -> registers
-        if (t + 1 < n_tiles) stage_store(t + 1, buf ^ 1);
-        if (t + 2 < n_tiles) stage_load(t + 2);
+        if (t + 1 < n_tiles) tl.stage_store(t + 1, buf ^ 1);
+        if (t + 2 < n_tiles) tl.stage_load(t + 2);
         // ---- epilogue: bias, mask, threshold filter ----------------------------------------------
         if (!user_ok) maskw = 0xffffffffu;
         if (t == n_tiles_all - 1) maskw |= tail_mask;
@@ -665,7 +584,7 @@ __global__ __launch_bounds__((WAVES * TKR_WAVE)) void score_topk_kernel(
 // user operand of EVERY slab stays in registers (SLABS x 128: the 512-register file of a one-wave-per-SIMD workgroup holds two or
 // three slabs) and the item tiles go through the same two LDS buffers one slab at a time -- unit (tile, slab) is staged while unit
 // (tile, slab - 1) is multiplied; the accumulator runs over a tile's slabs and the filter sees it after the last.  Same lists, trims
-// and merge as score_topk_kernel, and the same fma chain as exact_score (topk_parts.h): the two k-halves are the halves of the WHOLE
+// and merge as score_topk_kernel, and the same fma chain as exact_score (score_chain.h): the two k-halves are the halves of the WHOLE
 // width, KH = ceil(k / 2) -- half-wave h, slab s, element kk holds factor h KH + 128 s + kk, zero beyond its half -- so the chain is
 // (j, KH + j) for j = 0 .. KH-1, what K8, K12, K16, K17, K19 and the wave-per-row form below run.  A slab of 256 CONSECUTIVE
 // factors, 128 per half-wave, would be simpler to stage but interleaves the halves per slab: a few ulp away from every other kernel
@@ -792,15 +711,7 @@ __global__ __launch_bounds__(256) void score_topk_slab_kernel(
         for (int sl = 0; sl < SLABS; ++sl, ++unit) {
             const int buf = unit & 1;
             const float* arow = sm.tile + buf * 32 * KP + ul * KP + h * KHP;
-#pragma unroll
-            for (int kk = 0; kk < KHP; kk += 4) {
-                const float4 a = *reinterpret_cast<const float4*>(arow + kk);
-                acc = __builtin_amdgcn_mfma_f32_32x32x2f32(a.x, breg[sl * KHP + kk + 0], acc, 0, 0, 0);
-                acc = __builtin_amdgcn_mfma_f32_32x32x2f32(a.y, breg[sl * KHP + kk + 1], acc, 0, 0, 0);
-                acc = __builtin_amdgcn_mfma_f32_32x32x2f32(a.z, breg[sl * KHP + kk + 2], acc, 0, 0, 0);
-                acc = __builtin_amdgcn_mfma_f32_32x32x2f32(a.w, breg[sl * KHP + kk + 3], acc, 0, 0, 0);
-            }
-            if (sl + 1 == SLABS) mfma_result_guard(acc);
+            mfma_f32_group<KHP>(acc, arow, breg + sl * KHP, sl + 1 == SLABS);
             // the next unit: registers -> the other buffer (free since the barrier before this unit); the one after it -> registers
             int t1 = t, s1 = sl;
             next_unit(t1, s1);
@@ -909,53 +820,8 @@ __global__ __launch_bounds__((topk_waves_bf16<KS, IdT>() * TKR_WAVE), 2) void sc
 
     // ---- B operand: lane (user ul, k-group h) holds elements 16s + 8h .. +7 of its user's row, scaled to fp16
     f16x8 hreg[KS];
-    float margin = 0.f, bscale = 1.f, inv_bscale = 1.f, sv = 1.f;
-    {
-        const int urow = user_ok ? (uidx ? uidx[row] : row) : 0;
-        const float* up = U + (size_t)urow * k;
-        float uv[KS][8];
-        if ((k & 3) == 0) {                                      // two 16-byte loads per 16-wide k step, all issued before use
-#pragma unroll
-            for (int s = 0; s < KS; ++s)
-#pragma unroll
-                for (int q = 0; q < 2; ++q) {
-                    const int e = 16 * s + 8 * h + 4 * q;
-                    float4 v = make_float4(0.f, 0.f, 0.f, 0.f);
-                    if (user_ok && e < k) v = *reinterpret_cast<const float4*>(up + e);
-                    uv[s][4 * q + 0] = v.x; uv[s][4 * q + 1] = v.y; uv[s][4 * q + 2] = v.z; uv[s][4 * q + 3] = v.w;
-                }
-        } else {
-#pragma unroll
-            for (int s = 0; s < KS; ++s)
-#pragma unroll
-                for (int i = 0; i < 8; ++i) {
-                    const int e = 16 * s + 8 * h + i;
-                    const float v = up[min(e, k - 1)];
-                    uv[s][i] = (user_ok && e < k) ? v : 0.f;
-                }
-        }
-        float nu = 0.f, amax = 0.f;
-#pragma unroll
-        for (int s = 0; s < KS; ++s)
-#pragma unroll
-            for (int i = 0; i < 8; ++i) {
-                nu = fmaf(uv[s][i], uv[s][i], nu);
-                amax = fmaxf(amax, fabsf(uv[s][i]));
-            }
-        nu += __shfl_xor(nu, 32, 64);                          // the other k-group of the same user
-        amax = fmaxf(amax, __shfl_xor(amax, 32, 64));
-        const float su = pow2_scale(amax);
-        sv = pow2_scale(__uint_as_float(extra[2]));
-        bscale = su * sv;
-        inv_bscale = __uint_as_float((254u - ((__float_as_uint(bscale) >> 23) & 0xffu)) << 23);
-#pragma unroll
-        for (int s = 0; s < KS; ++s)
-#pragma unroll
-            for (int i = 0; i < 8; ++i) hreg[s][i] = (_Float16)(uv[s][i] * su);
-        const float reach = sqrtf(nu) * 1.001f * __uint_as_float(extra[0]);      // >= |u| * max |v_i|
-        margin = (fmaf(1.05f * 0.0009765625f, reach, 3.8146973e-6f * (reach + __uint_as_float(extra[1]))) + 7.7e-34f) * bscale +
-                 2.01f * (float)KPAD;
-    }
+    float margin, bscale, sv;
+    refine_prologue<KS>(U + (size_t)(user_ok ? (uidx ? uidx[row] : row) : 0) * k, k, user_ok, h, extra, hreg, margin, bscale, sv);
     const float m2 = 2.f * margin;
     bool lost = false;
     for (int s = tid; s < users; s += blockDim.x) sm.cnt[s] = 0;

@@ -1,7 +1,9 @@
-// Device helpers shared by the K4 translation units (csrc/topk.hip, csrc/topk_refine.hip): ordered keys, the wave-wide bitonic
-// sorts, the bounds the item ranges of a user block tell each other, the exact fp32 score of one (user, item) pair.
+// Device helpers of K4 and K8 (csrc/topk.hip, csrc/topk_refine.hip, csrc/like_ranks.hip): ordered keys, the wave-wide bitonic sorts,
+// the bounds the item ranges of a user block tell each other, the fp32 MFMA tile, the prologue of the fp16 bound-and-refine kernels.
+// The fp32 score of one (user, item) pair is csrc/score_chain.h, included here for every file that scores pairs.
 #pragma once
 #include "tkr_common.h"
+#include "score_chain.h"
 
 namespace tkr {
 
@@ -128,35 +130,6 @@ __device__ __forceinline__ u16x2 count_ge2(uint32_t xo, uint32_t cand2, u16x2 ac
 }
 
 
-// ---- bound-and-refine: the exact score of one candidate ------------------------------------------------------------------
-// The fp32 dot product of the fp32-MFMA kernel, bit for bit: v_mfma_f32_32x32x2_f32 adds the product of k-half 0, then the
-// product of k-half 1, one fused multiply-add each (measured: scripts/probe_mfma_order.py, 100 % of 7,680 scores at k = 50,
-// 64, 100, 128) -- so acc <- fma(v[kk], u[kk], acc); acc <- fma(v[KH+kk], u[KH+kk], acc) for kk = 0 .. KH-1, then fl(acc + bias)
-// and -0.0 -> +0.0 as the filter of that kernel does.
-__device__ __forceinline__ float exact_score(const float* __restrict__ up, const float* __restrict__ vp, int k, const float* bias, int col) {
-    const int KH = (k + 1) >> 1;
-    float acc = 0.f;
-    if ((k & 7) == 0) {                                         // both halves 16-byte aligned
-#pragma unroll 8                                                // 32 loads in flight: two memory round trips per 128 factors
-        for (int kk = 0; kk < KH; kk += 4) {
-            const float4 a0 = *reinterpret_cast<const float4*>(vp + kk), a1 = *reinterpret_cast<const float4*>(vp + KH + kk);
-            const float4 b0 = *reinterpret_cast<const float4*>(up + kk), b1 = *reinterpret_cast<const float4*>(up + KH + kk);
-            acc = fmaf(a0.x, b0.x, acc); acc = fmaf(a1.x, b1.x, acc);
-            acc = fmaf(a0.y, b0.y, acc); acc = fmaf(a1.y, b1.y, acc);
-            acc = fmaf(a0.z, b0.z, acc); acc = fmaf(a1.z, b1.z, acc);
-            acc = fmaf(a0.w, b0.w, acc); acc = fmaf(a1.w, b1.w, acc);
-        }
-    } else {
-        for (int kk = 0; kk < KH; ++kk) {
-            acc = fmaf(vp[kk], up[kk], acc);
-            if (KH + kk < k) acc = fmaf(vp[KH + kk], up[KH + kk], acc);
-        }
-    }
-    acc = acc + (bias ? bias[col] : 0.f);
-    return acc + 0.0f;
-}
-
-
 // A compiler hole, ROCm 7.2 / gfx950 (found in round 5; tests/test_gpu_topk.py test_exact_arithmetic_lists caught it): the wait states
 // between a 16-pass MFMA and the first VALU read of its result (19 on this chip; the hardware does NOT interlock them) are counted by
 // hipcc along the LAYOUT of the code, not along the control flow.  On a workgroup's LAST tile the staging code between the chain and
@@ -173,9 +146,175 @@ __device__ __forceinline__ void mfma_result_guard_8pass(f32x16& acc) {      // b
     asm volatile("s_nop 10" : "+v"(acc));
 }
 
+// ---- the fp32 MFMA tile of K4 and K8: 32 items x 32 users x k -----------------------------------------------------------------------
+// KHP MFMAs on top of `acc`: arow = the lane's half of its item's LDS row (ScoreTile: [h * KHP + kk]), breg = the lane's half of its
+// user's row.  The guard comes with the chain; a caller whose accumulator runs over several groups (the slabs of a wide row) asks for it
+// behind the last one only.
+template <int KHP>
+__device__ __forceinline__ void mfma_f32_group(f32x16& acc, const float* arow, const float* breg, bool guard = true) {
+#pragma unroll
+    for (int kk = 0; kk < KHP; kk += 4) {
+        const float4 a = *reinterpret_cast<const float4*>(arow + kk);
+        acc = __builtin_amdgcn_mfma_f32_32x32x2f32(a.x, breg[kk + 0], acc, 0, 0, 0);
+        acc = __builtin_amdgcn_mfma_f32_32x32x2f32(a.y, breg[kk + 1], acc, 0, 0, 0);
+        acc = __builtin_amdgcn_mfma_f32_32x32x2f32(a.z, breg[kk + 2], acc, 0, 0, 0);
+        acc = __builtin_amdgcn_mfma_f32_32x32x2f32(a.w, breg[kk + 3], acc, 0, 0, 0);
+    }
+    if (guard) mfma_result_guard(acc);
+}
+
+// The item tiles of a workgroup of at most NT threads (`nthreads` of them at run time), double-buffered in LDS: tile [2][32][KP] with
+// half hh of an item's factors at [hh * KHP + kk], zero beyond the half, and the tile's biases tbias [2][32].  Tile t goes global ->
+// registers (stage_load, issued early) -> LDS (stage_store, written after the MFMA chain).  float4 path when every k-half starts
+// 16-byte aligned (k % 8 == 0); scalar path otherwise.
+template <int KHP, int NT>
+struct ScoreTile {
+    static constexpr int KP = 2 * KHP + 4;                       // padded LDS row (floats): conflict-free b128 reads
+    static constexpr int NC = (32 * 2 * KHP / 4 + NT - 1) / NT;  // float4 chunks per thread
+    float* tile;
+    float* tbias;
+    const float* Vt;
+    const float* bias;
+    int n_cols, k, KH, tid, nthreads;
+    bool vec;                                                    // then KH % 4 == 0: no chunk straddles the halves
+    int src_off[NC], dst_off[NC], item_of[NC];                   // per-chunk offsets, fixed for the whole kernel
+    float4 stg[NC];
+    float stg_bias;
+
+    __device__ __forceinline__ ScoreTile(float* tile_, float* tbias_, const float* Vt_, const float* bias_, int n_cols_, int k_, int nthreads_)
+        : tile(tile_), tbias(tbias_), Vt(Vt_), bias(bias_), n_cols(n_cols_), k(k_), KH((k_ + 1) >> 1), tid(threadIdx.x),
+          nthreads(nthreads_), vec((k_ & 7) == 0), stg_bias(0.f) {
+        const int k4 = k >> 2;
+#pragma unroll
+        for (int q = 0; q < NC; ++q) {
+            const int c = tid + q * nthreads;
+            const int item = vec ? c / k4 : 0, e = vec ? (c % k4) * 4 : 0;
+            const bool live = vec && c < 32 * k4;
+            src_off[q] = live ? item * k + e : -1;
+            dst_off[q] = item * KP + (e / KH) * KHP + (e % KH);
+            item_of[q] = item;
+        }
+    }
+
+    // B operand: half h of the factor row of this lane's user (k-range [h * KH, min(k, (h + 1) * KH))), resident for the whole kernel
+    static __device__ __forceinline__ void load_user(float (&breg)[KHP], const float* U, const int32_t* uidx,
+                                                     int row, bool user_ok, int k, int h) {
+        const int KH = (k + 1) >> 1;
+        const int urow = user_ok ? (uidx ? uidx[row] : row) : 0;
+        const float* up = U + (size_t)urow * k + h * KH;
+#pragma unroll
+        for (int kk = 0; kk < KHP; ++kk) {
+            const int e = h * KH + kk;
+            breg[kk] = (user_ok && kk < KH && e < k) ? up[kk] : 0.f;
+        }
+    }
+
+    __device__ __forceinline__ void stage_load(int t) {          // tile t -> registers
+        if (vec) {
+#pragma unroll
+            for (int q = 0; q < NC; ++q) {
+                stg[q] = make_float4(0.f, 0.f, 0.f, 0.f);
+                if (src_off[q] >= 0 && t * 32 + item_of[q] < n_cols)
+                    stg[q] = *reinterpret_cast<const float4*>(Vt + (size_t)t * 32 * k + src_off[q]);
+            }
+        }
+        if (tid < 32) {
+            const int col = t * 32 + tid;
+            stg_bias = (bias && col < n_cols) ? bias[col] : 0.f;
+        }
+    }
+
+    __device__ __forceinline__ void stage_store(int t, int buf) {   // registers (or, scalar path, global) -> LDS
+        float* dst = tile + buf * 32 * KP;
+        if (vec) {
+#pragma unroll
+            for (int q = 0; q < NC; ++q)
+                if (src_off[q] >= 0) *reinterpret_cast<float4*>(dst + dst_off[q]) = stg[q];
+        } else {
+            for (int c = tid; c < 32 * 2 * KHP; c += nthreads) {
+                const int item = c / (2 * KHP), p = c % (2 * KHP);
+                const int hh = p / KHP, kk = p % KHP;
+                const int e = hh * KH + kk, col = t * 32 + item;
+                float v = 0.f;
+                if (kk < KH && e < k && col < n_cols) v = Vt[(size_t)col * k + e];
+                dst[item * KP + p] = v;
+            }
+        }
+        if (tid < 32) tbias[buf * 32 + tid] = stg_bias;
+    }
+
+    __device__ __forceinline__ void zero_padding() {             // what the vector path never writes
+        for (int c = tid; c < 2 * 32 * KP; c += nthreads) tile[c] = 0.f;
+    }
+
+    __device__ __forceinline__ const float* arow(int buf, int ul, int h) const { return tile + buf * 32 * KP + ul * KP + h * KHP; }
+};
+
 
 typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
 typedef _Float16 f16x4 __attribute__((ext_vector_type(4)));
+
+// ---- the fp16 bound-and-refine kernels (csrc/topk.hip score_topk_bf16_kernel, csrc/topk_refine.hip): what a lane sets up once ---------
+// B operand: lane (user ul, k-group h) holds elements 16s + 8h .. +7 of its user's row, scaled by the user's own power of two su to
+// fp16 (hreg); the item factors are scaled by sv, scores live in units of bscale = su * sv.  `margin`: how far the approximate score
+// may be from the exact fp32 score in those units -- what makes the filter's lists supersets of the exact top K; derived in
+// csrc/topk.hip above score_topk_bf16_kernel.  extra: bits of [0] max |v_i|, [1] max |bias|, [2] max |V element|.
+template <int KS>
+__device__ __forceinline__ void refine_prologue(const float* up, int k, bool user_ok, int h, const uint32_t* extra,
+                                                f16x8 (&hreg)[KS], float& margin, float& bscale, float& sv) {
+    constexpr int KPAD = KS * 16;
+    float uv[KS][8];
+    if ((k & 3) == 0) {                                          // two 16-byte loads per 16-wide k step, all issued before use
+#pragma unroll
+        for (int s = 0; s < KS; ++s)
+#pragma unroll
+            for (int q = 0; q < 2; ++q) {
+                const int e = 16 * s + 8 * h + 4 * q;
+                float4 v = make_float4(0.f, 0.f, 0.f, 0.f);
+                if (user_ok && e < k) v = *reinterpret_cast<const float4*>(up + e);
+                uv[s][4 * q + 0] = v.x; uv[s][4 * q + 1] = v.y; uv[s][4 * q + 2] = v.z; uv[s][4 * q + 3] = v.w;
+            }
+    } else {
+#pragma unroll
+        for (int s = 0; s < KS; ++s)
+#pragma unroll
+            for (int i = 0; i < 8; ++i) {
+                const int e = 16 * s + 8 * h + i;
+                const float v = up[min(e, k - 1)];
+                uv[s][i] = (user_ok && e < k) ? v : 0.f;
+            }
+    }
+    float nu = 0.f, amax = 0.f;
+#pragma unroll
+    for (int s = 0; s < KS; ++s)
+#pragma unroll
+        for (int i = 0; i < 8; ++i) {
+            nu = fmaf(uv[s][i], uv[s][i], nu);
+            amax = fmaxf(amax, fabsf(uv[s][i]));
+        }
+    nu += __shfl_xor(nu, 32, 64);                                // the other k-group of the same user
+    amax = fmaxf(amax, __shfl_xor(amax, 32, 64));
+    const float su = pow2_scale(amax);
+    sv = pow2_scale(__uint_as_float(extra[2]));
+    bscale = su * sv;
+#pragma unroll
+    for (int s = 0; s < KS; ++s)
+#pragma unroll
+        for (int i = 0; i < 8; ++i) hreg[s][i] = (_Float16)(uv[s][i] * su);
+    const float reach = sqrtf(nu) * 1.001f * __uint_as_float(extra[0]);      // >= |u| * max |v_i|
+    margin = (fmaf(1.05f * 0.0009765625f, reach, 3.8146973e-6f * (reach + __uint_as_float(extra[1]))) + 7.7e-34f) * bscale +
+             2.01f * (float)KPAD;
+}
+
+// acc <- fma(bias, bscale, acc) in the accumulator's own registers: the biases of a tile in the user's scaled units
+__device__ __forceinline__ void add_scaled_bias_inplace(f32x16& acc, const float* tbias, int h, float bscale) {
+#pragma unroll
+    for (int g = 0; g < 4; ++g) {
+        const float4 bq = *reinterpret_cast<const float4*>(tbias + 8 * g + 4 * h);
+        acc[4 * g + 0] = fmaf(bq.x, bscale, acc[4 * g + 0]); acc[4 * g + 1] = fmaf(bq.y, bscale, acc[4 * g + 1]);
+        acc[4 * g + 2] = fmaf(bq.z, bscale, acc[4 * g + 2]); acc[4 * g + 3] = fmaf(bq.w, bscale, acc[4 * g + 3]);
+    }
+}
 
 
 template <int KS>

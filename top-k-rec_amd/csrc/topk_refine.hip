@@ -16,7 +16,7 @@
 //    entries in a register: no LDS atomic, no length word in LDS, an append is one ds_write_b32.
 //  * the kernel ends by DUMPING its lists; topk_finish2_kernel ranks every row ONCE over the union of its pieces: item rows are
 //    staged through LDS by direct-to-LDS loads, eight lanes per 128-byte line (8 cache lines per instruction instead of 64), the
-//    user's row comes through the scalar cache, the fp32 fma chain is the fp32-MFMA kernel's own (exact_score, topk_parts.h):
+//    user's row comes through the scalar cache, the fp32 fma chain is the fp32-MFMA kernel's own (exact_score, score_chain.h):
 //    ids and score bits are those of tkr_topk_set_math(fp32).
 // User blocks whose lists cannot hold their margin are flagged and redone by the fp32 kernel, as before (csrc/topk.hip).
 #include "topk_refine.h"
@@ -304,7 +304,6 @@ __global__ __launch_bounds__(256, 3) void score_topk_refine2_kernel(const Refine
     extern __shared__ __attribute__((aligned(16))) unsigned char smem_raw[];
     constexpr int ROWB = KS * 32;                                // bytes of an item row of the image (KS * 16 fp16)
     constexpr int TILEB = 32 * ROWB;
-    constexpr int KPAD = KS * 16;
     constexpr int NT_ = 256;
     constexpr int NG = (TILEB / 16 + NT_ - 1) / NT_;             // 16-byte direct-to-LDS loads per thread and tile
     float* tbias = reinterpret_cast<float*>(smem_raw + 2 * TILEB);   // [2][32]
@@ -326,51 +325,7 @@ __global__ __launch_bounds__(256, 3) void score_topk_refine2_kernel(const Refine
     // ---- B operand: lane (user ul, k-group h) holds elements 16s + 8h .. +7 of its user's row, scaled to fp16
     f16x8 hreg[KS];
     float margin, bscale, sv;
-    {
-        const int urow = user_ok ? (a.uidx ? a.uidx[row] : row) : 0;
-        const float* up = a.U + (size_t)urow * k;
-        float uv[KS][8];
-        if ((k & 3) == 0) {
-#pragma unroll
-            for (int s = 0; s < KS; ++s)
-#pragma unroll
-                for (int q = 0; q < 2; ++q) {
-                    const int e = 16 * s + 8 * h + 4 * q;
-                    float4 v = make_float4(0.f, 0.f, 0.f, 0.f);
-                    if (user_ok && e < k) v = *reinterpret_cast<const float4*>(up + e);
-                    uv[s][4 * q + 0] = v.x; uv[s][4 * q + 1] = v.y; uv[s][4 * q + 2] = v.z; uv[s][4 * q + 3] = v.w;
-                }
-        } else {
-#pragma unroll
-            for (int s = 0; s < KS; ++s)
-#pragma unroll
-                for (int i = 0; i < 8; ++i) {
-                    const int e = 16 * s + 8 * h + i;
-                    const float v = up[min(e, k - 1)];
-                    uv[s][i] = (user_ok && e < k) ? v : 0.f;
-                }
-        }
-        float nu = 0.f, amax = 0.f;
-#pragma unroll
-        for (int s = 0; s < KS; ++s)
-#pragma unroll
-            for (int i = 0; i < 8; ++i) {
-                nu = fmaf(uv[s][i], uv[s][i], nu);
-                amax = fmaxf(amax, fabsf(uv[s][i]));
-            }
-        nu += __shfl_xor(nu, 32, 64);                            // the other k-group of the same user
-        amax = fmaxf(amax, __shfl_xor(amax, 32, 64));
-        const float su = pow2_scale(amax);
-        sv = pow2_scale(__uint_as_float(a.extra[2]));
-        bscale = su * sv;
-#pragma unroll
-        for (int s = 0; s < KS; ++s)
-#pragma unroll
-            for (int i = 0; i < 8; ++i) hreg[s][i] = (_Float16)(uv[s][i] * su);
-        const float reach = sqrtf(nu) * 1.001f * __uint_as_float(a.extra[0]);        // >= |u| * max |v_i|
-        margin = (fmaf(1.05f * 0.0009765625f, reach, 3.8146973e-6f * (reach + __uint_as_float(a.extra[1]))) + 7.7e-34f) * bscale +
-                 2.01f * (float)KPAD;
-    }
+    refine_prologue<KS>(a.U + (size_t)(user_ok ? (a.uidx ? a.uidx[row] : row) : 0) * k, k, user_ok, h, a.extra, hreg, margin, bscale, sv);
     const float m2 = 2.f * margin;
     bool lost = false;
     const uint32_t seg0 = (uint32_t)(uintptr_t)(ent + (h * kSeg) * kR2Users + uw);      // LDS byte address of this lane's segment
@@ -427,15 +382,7 @@ __global__ __launch_bounds__(256, 3) void score_topk_refine2_kernel(const Refine
         __builtin_amdgcn_sched_group_barrier(0x100, KS, 0);       // all the fragment reads first, then the chain
         __builtin_amdgcn_sched_group_barrier(0x008, KS, 0);
         mfma_result_guard_8pass(acc);
-        if (a.bias) {                                            // scores in the user's scaled units: fma(bias, scale, acc)
-            const float* tb = tbias + buf * 32;
-#pragma unroll
-            for (int g = 0; g < 4; ++g) {
-                const float4 bq = *reinterpret_cast<const float4*>(tb + 8 * g + 4 * h);
-                acc[4 * g + 0] = fmaf(bq.x, bscale, acc[4 * g + 0]); acc[4 * g + 1] = fmaf(bq.y, bscale, acc[4 * g + 1]);
-                acc[4 * g + 2] = fmaf(bq.z, bscale, acc[4 * g + 2]); acc[4 * g + 3] = fmaf(bq.w, bscale, acc[4 * g + 3]);
-            }
-        }
+        if (a.bias) add_scaled_bias_inplace(acc, tbias + buf * 32, h, bscale);
 #ifdef TKR_R2_PROF
         asm volatile("" : "+v"(acc));
         R2_MARK(0)
@@ -632,18 +579,12 @@ __global__ __launch_bounds__(kF2Waves * 64) void topk_finish2_kernel(const Finis
                 const float4* u0 = reinterpret_cast<const float4*>(s_u[wave] + 16 * step);       // every lane the same address: broadcasts
                 const float4* u1 = reinterpret_cast<const float4*>(s_u[wave] + KH + 16 * step);
 #pragma unroll
-                for (int c = 0; c < 4; ++c) {                    // chunk c of half 0 and chunk c of half 1: k ascending, halves interleaved
-                    const float4 b0 = u0[c], b1 = u1[c];
-                    acc = fmaf(v[c].x, b0.x, acc); acc = fmaf(v[4 + c].x, b1.x, acc);
-                    acc = fmaf(v[c].y, b0.y, acc); acc = fmaf(v[4 + c].y, b1.y, acc);
-                    acc = fmaf(v[c].z, b0.z, acc); acc = fmaf(v[4 + c].z, b1.z, acc);
-                    acc = fmaf(v[c].w, b0.w, acc); acc = fmaf(v[4 + c].w, b1.w, acc);
-                }
+                for (int c = 0; c < 4; ++c)                      // chunk c of half 0 and chunk c of half 1: k ascending, halves interleaved
+                    chain_step4(acc, v[c], v[4 + c], u0[c], u1[c]);
                 asm volatile("" : "+v"(acc) : : "memory");       // the reads of this buffer are done before it is filled again
                 if (step + 2 < NSTEP) issue(step + 2, step & 1);
             }
-            acc = acc + (a.bias ? a.bias[col] : 0.f);
-            sc = acc + 0.0f;
+            sc = chain_finish(acc, a.bias, col);
         } else {
             sc = live ? exact_score(up, a.Vt + (size_t)col * k, k, a.bias, col) : 0.f;
         }
