@@ -567,14 +567,19 @@ def test_a_timed_out_spin_steps_down_k2o_k2f_k2():
     eng.run_batches(csr, 5, 256, want_loss=False)
     eng.check()
     assert eng.layout == 'flow' and eng.plan.owners > 0
+    assert eng._plan_owners(256) == eng.plan.owners and eng.wants_flow(256) and eng._last_step_kind == 'own'
     inject()
+    assert eng._plan_owners(256) == 0 and eng.wants_flow(256)           # the choice, before the kernel it names runs ...
     eng.run_batches(csr, 5, 256, want_loss=False)
     eng.check()
     assert eng.layout == 'flow' and eng.plan.owners == 0                 # K2f
+    assert eng._plan_owners(256) == 0 and eng.wants_flow(256) and eng._last_step_kind == 'flow'          # ... and after
     inject()
+    assert eng._plan_owners(256) == 0 and not eng.wants_flow(256)
     eng.run_batches(csr, 5, 256, want_loss=False)
     eng.check()
     assert eng.layout == 'bulk'                                          # K2
+    assert eng._plan_owners(256) == 0 and not eng.wants_flow(256)
     # ... and what it trains from the restored tables is the model: against the oracle on the stream the engine drew last
     ref = dict(U=keep['U'][0].cpu().numpy().copy(), V=keep['V'][0].cpu().numpy().copy(), b=keep['b'][0].cpu().numpy().copy(),
                msU=keep['U'][1].cpu().numpy().copy(), msV=keep['V'][1].cpu().numpy().copy(), msb=keep['b'][1].cpu().numpy().copy())

@@ -112,6 +112,8 @@ class ItemSync:
     own fused kernels (tkr_sync_flow_*: 464 -> ~60 us per exchange at the ML-10M shape, against a 1.25 ms epoch at 8 GPUs)."""
 
     def __init__(self, engine, names=None):
+        # ``engine``: a BprEngine / VbprEngine, or any object with get(name) and set_replicated(new) alone (the stand-ins of the gloo
+        # tests).  The getattr(self.eng, ...) below are for those: replicated_names, layout_epoch, flow_sync_tables, replicated_tables, settle
         self.eng = engine
         self.names = tuple(names or getattr(engine, 'replicated_names', ('V', 'b')))
         self.start = None
@@ -160,17 +162,14 @@ class ItemSync:
         on a shadow until after_exchange(); afterwards they describe exactly the freshly re-assigned tables)."""
         settle = getattr(self.eng, 'settle', None)
         if settle is not None:
-            if keep_epoch_ahead:
-                settle(check=False, keep_epoch_ahead=True)
-            else:
-                settle(check=False)
-            self.eng.check_async()       # a failed persistent step surfaces at the next exchange (or at the final get): no host wait here
+            settle(check=False, keep_epoch_ahead=keep_epoch_ahead)
+            self.eng.check_async()      # a failed persistent step surfaces at the next exchange (or at the final get): no host wait here
 
     def begin(self):
         # no snapshot launch is needed when the unpack of the exchange before left this epoch's start in start_flat: then nothing here
         # reads the item counters, and a chunk planned ahead of that exchange may stay
-        fresh = (self.flow is not None and self._bound == getattr(self.eng, 'layout_epoch', 0) and
-                 self._start_valid == (self._bound, getattr(self.eng, 'item_mutations', 0)))
+        fresh = (self.flow is not None and self._bound == self.eng.layout_epoch and
+                 self._start_valid == (self._bound, self.eng.item_mutations))
         self._settle(keep_epoch_ahead=fresh)
         self._bind()
         if self.flow is not None:
@@ -178,7 +177,7 @@ class ItemSync:
             V, msV, tail, rd, icnt, n, k, bufs = self.flow
             # the unpack of the exchange before left the new values in start_flat: they ARE this epoch's start, unless somebody wrote
             # the item tables since (set_items, a layout change: the engine counts those)
-            if self._start_valid != (self._bound, getattr(self.eng, 'item_mutations', 0)):
+            if self._start_valid != (self._bound, self.eng.item_mutations):
                 tkr_hip.sync_flow_snapshot(V, tail, icnt, self.start_flat, n, k, bufs)
             self._start_valid = None
             self.start = True
@@ -205,8 +204,8 @@ class ItemSync:
     def _flag_status(self, total):
         """the last word of the exchanged vector: did a persistent step of THIS rank give up during the epoch (the engine's device
         status word)?  Summed by the same all-reduce, so that every rank learns it without a collective of its own."""
-        ctl = getattr(self.eng, 'ctl', None)
-        if ctl is not None and getattr(self.eng, 'layout', None) == 'flow':
+        ctl = self.eng.ctl
+        if ctl is not None and self.eng.layout == 'flow':
             import tkr_hip
             self.flat[2 * total:] = (ctl[tkr_hip.FLOW_CTL_STATUS:tkr_hip.FLOW_CTL_STATUS + 1] != 0).float()
         else:
@@ -275,10 +274,8 @@ class ItemSync:
             V, msV, tail, rd, icnt, n, k, bufs = self.flow
             total = n * (k + 1)
             tkr_hip.sync_flow_unpack(V, msV, tail, rd, icnt, self.start_flat, flat[:total], flat[total:2 * total], n, k, bufs)
-            self._start_valid = (self._bound, getattr(self.eng, 'item_mutations', 0))
-            after = getattr(self.eng, 'after_exchange', None)
-            if after is not None:
-                after()                  # a chunk planned ahead of this exchange becomes runnable
+            self._start_valid = (self._bound, self.eng.item_mutations)
+            self.eng.after_exchange()    # a chunk planned ahead of this exchange becomes runnable
             return
         if self.tabs is None:
             new, off = {}, 0

@@ -4,6 +4,8 @@ HIP kernels reached through the C ABI (tkr_hip).  Nothing here computes on the C
 """
 from __future__ import annotations
 
+import warnings
+
 import numpy as np
 import torch
 
@@ -66,6 +68,7 @@ class TrainingCSR:
         self.cols_sorted = torch.from_numpy(srt).to(device)
         self.tr_users = torch.from_numpy(tr_users).to(device)
         self.nnz = int(row_ptr[-1])
+        self.local = False               # rows in a shard's own numbering (shard())
 
 
 class PlanBuffers:
@@ -104,6 +107,7 @@ class PlanBuffers:
         self.loss = torch.zeros(cap, dtype=torch.float32, device=device)
         need = tkr_hip.plan_workspace_bytes(B, cap)                       # B > 8192: scratch of the grid-wide planner
         self.ws = torch.empty(need, dtype=torch.uint8, device=device) if need else None
+        self._callers = {}               # K1's C call structs / closures into this buffer, by data and counters (PlanMixin._caller)
 
 
 class UpdateCounters:
@@ -132,6 +136,7 @@ class PlanPipeline:
         self._side = None                # taken on first overlapped use: an idle second queue is not free
         self.bufs = [None, None]
         self.planned = [None, None]      # event: plan in bufs[i] complete (side stream)
+        self._side_dirty = False         # something runs on the side stream that the main stream has not waited for
 
     @property
     def side(self):
@@ -166,7 +171,7 @@ class PlanPipeline:
             ev = torch.cuda.Event()
             ev.record(self.side)
             self.planned[i] = ev
-        self._side_dirty = True                       # something runs on the side stream that the main stream has not waited for
+        self._side_dirty = True
 
     def acquire(self, i):
         if self.planned[i] is not None:
@@ -177,7 +182,7 @@ class PlanPipeline:
     def drain(self):
         # only when a side-stream plan was queued since the last drain: an event create + record + wait + destroy is ~15 us of host
         # time in front of the first launch of a short call (the driver's 20-step run)
-        if self._side is not None and getattr(self, '_side_dirty', False):
+        if self._side is not None and self._side_dirty:
             torch.cuda.current_stream(self.device).wait_stream(self._side)
             self._side_dirty = False
 
@@ -240,9 +245,12 @@ class PlanMixin:
     advances the update counters for every PLANNED batch.  The stream is counter-based, so re-planning from the same
     position reproduces the same triplets."""
 
+    layout = 'bulk'                      # engines with one table layout: the plain one ...
+    ctl = None                           # ... and no persistent step, so no control words (BPR.train and dist.ItemSync read both)
+
     def _plan_flow(self):
         """does the step of this engine read the dataflow form of the plan?"""
-        return False
+        return self.layout == 'flow'
 
     def _plan_owners(self, B):
         """owners of item rows when the step is K2o (the owner-ordered dataflow form), else 0"""
@@ -264,7 +272,7 @@ class PlanMixin:
 
     def _plan_overlap(self, B):
         """plan the chunk after the running one on the side stream?"""
-        if getattr(self, 'plan_in_order', False):      # one of several shards on one GPU: no planner stream (see BPR._stream_shards)
+        if self.plan_in_order:                         # one of several shards on one GPU: no planner stream (see BPR._stream_shards)
             return False
         return B >= self.cfg.overlap_min_batch or self._plan_flow()
 
@@ -286,8 +294,17 @@ class PlanMixin:
         self.step_events = None         # list of (start, end, n_launches) when a bench wants kernel time
         self._event_pool = []           # event pairs that already exist on the device (reserve_events)
         self._fused_calls = {}          # plan buffer index -> (the C struct of its fused K1 + step call, the csr it names)
-        self._again_key = None          # what the last call was, when the same call again can skip the planning decisions (BprEngine)
-        self._again_buf = 0             # ... and the plan buffer it used
+        self._step_key = None           # what self._step was built for: the batch size (VbprEngine), a _Built (BprEngine)
+        self._step = None               # step_fn(B) of the last call: the C struct and the closure are built once, not per call
+        self._warned_wide = False       # the warning about rows wider than the register forms hold went out
+        self._shadow_icnt = None        # zeroed item counters that a chunk planned ahead of an exchange counts on (_next_chunk)
+        self.ranks_on_device = 1        # ranks that share this engine's GPU (dist.ranks_sharing_device): K2o splits the CUs between them
+        self.own_min_owners = 0         # K2f below that many owners (shards of one process: BPR._stream_shards)
+        self.private_side_stream = False        # a planner stream of this engine's own (PlanPipeline)
+        self.plan_in_order = False      # never plan on a side stream (shards of one GPU whose streams would share hardware queues)
+        self.tables_invalid = False     # a persistent step gave up in mid-launch: until somebody puts tables back (restore)
+        self._last_step_kind = None     # 'own' / 'flow': the persistent kernel that stepped last (what a step-down takes out of the choice)
+        self._flow_ran = False          # a persistent launch ran since the status word was last looked at
 
     @property
     def cnt(self):
@@ -342,19 +359,24 @@ class PlanMixin:
         self._cnt.icnt.copy_(ah.shadow)
         ah.shadow = None
 
+    def _caller(self, buf, make, csr, cnt, B):
+        """K1 into plan buffer `buf` for this data and these counters, bound once: make = tkr_hip.plan_call (the C struct that rides in
+        the step's call) or tkr_hip.plan_caller (the closure that launches it)"""
+        key = (make, id(csr), id(cnt.ucnt), id(cnt.icnt), self.seed)        # the call holds csr and the counters: their ids stay theirs
+        call = buf._callers.get(key)
+        if call is None:
+            if len(buf._callers) > 4:
+                buf._callers.clear()
+            call = buf._callers[key] = make(csr, self.n_users, self.n_items, self.seed, B, cnt, buf)
+        return call
+
     def _plan_chunk(self, idx, csr, B, first, overlap, want, shadow=None, fuse=False):
         nb = max(1, min(self._cap(B), want))
         cnt = self._cnt if shadow is None else _ShadowCounters(self._cnt, shadow)
         if fuse:            # K1 rides in the step's C call (tkr_bpr_own_plan_run): nothing is launched here
             self.pipe.drain()
             buf = self.pipe.bufs[idx]
-            key = ('fused', id(csr), id(cnt.ucnt), id(cnt.icnt), self.seed)
-            callers = buf.__dict__.setdefault('_callers', {})
-            call = callers.get(key)
-            if call is None:
-                if len(callers) > 4:
-                    callers.clear()
-                call = callers[key] = tkr_hip.plan_call(csr, self.n_users, self.n_items, self.seed, B, cnt, buf)
+            call = self._caller(buf, tkr_hip.plan_call, csr, cnt, B)
             call.first_triplet, call.n_batches = first, nb
             self.pipe.planned[idx] = None
             ch = _Chunk(idx, nb, B, first, csr, shadow)
@@ -365,14 +387,7 @@ class PlanMixin:
         def fn(buf):
             if shadow is not None:
                 shadow.zero_()
-            key = (id(csr), id(cnt.ucnt), id(cnt.icnt), self.seed)          # the closure holds csr and cnt: their ids stay theirs
-            callers = buf.__dict__.setdefault('_callers', {})
-            call = callers.get(key)
-            if call is None:
-                if len(callers) > 4:
-                    callers.clear()
-                call = callers[key] = tkr_hip.plan_caller(csr, self.n_users, self.n_items, self.seed, B, cnt, buf)
-            call(first, nb)
+            self._caller(buf, tkr_hip.plan_caller, csr, cnt, B)(first, nb)
             self._plan_extra(buf, nb, B)
             buf.loss[:nb].zero_()                     # where K1 runs (the side stream when it is planned ahead): the step starts without a fill in front of it
         self.pipe.plan(idx, fn, overlap)
@@ -384,7 +399,7 @@ class PlanMixin:
         """may the first chunk of the epoch AFTER an exchange be planned before it?  Only where the exchange leaves the tables in
         a state K1 can name in advance without touching them (the granule layout: every item at version 0, dist.ItemSync's
         fused unpack) and takes no snapshot at the next begin()."""
-        return self._plan_flow() and self.cfg.epoch_ahead and not getattr(self, 'plan_in_order', False)
+        return self._plan_flow() and self.cfg.epoch_ahead and not self.plan_in_order
 
     def _next_chunk(self, csr, B, want, then_exchange=0):
         """the chunk that holds the batch at the current stream position; `want` = batches the running call still has to run;
@@ -399,7 +414,7 @@ class PlanMixin:
             self.settle(check=False)
             cur = None
         if self.pipe is None:
-            self.pipe = PlanPipeline(self.device, getattr(self, 'private_side_stream', False))
+            self.pipe = PlanPipeline(self.device, self.private_side_stream)
         self.pipe.ensure(self._cap(B), B, self._plan_flow(), self._plan_cols(B), self._plan_owners(B))
         # K1 of the chunk after this one on the side stream: behind the per-batch launches of a large batch, or behind the ONE
         # persistent launch of a dataflow chunk (100 us of planner per 512 batches that otherwise sit in front of every 1.4 ms launch)
@@ -411,7 +426,7 @@ class PlanMixin:
         else:
             # a short call (this chunk holds all that is left of it, nothing is planned beside it): K1 goes out in the step's call
             fuse = (self.cfg.fuse_short and then_exchange == 0 and want <= self._cap(B) and
-                    getattr(getattr(self, '_step', None), 'plan_and_run', None) is not None and self._plan_owners(B) > 0)
+                    getattr(self._step, 'plan_and_run', None) is not None and self._plan_owners(B) > 0)
             nxt = self._plan_chunk(0 if cur is None else cur.idx ^ 1, csr, B, self._drawn, False, want, fuse=fuse)
         if overlap and want > nxt.nb:                 # the chunk after it, behind the steps of this one
             self._ahead = self._plan_chunk(nxt.idx ^ 1, csr, B, nxt.first + nxt.nb * B, True, want - nxt.nb)
@@ -425,7 +440,7 @@ class PlanMixin:
             # the LAST chunk of an epoch: after the exchange every item row is at version 0 again and the users go on where this
             # chunk leaves them -- everything K1 needs to plan the first chunk of the next epoch, so it runs now, on the side stream
             # behind this chunk's steps and the exchange, instead of ~120 us in front of the next epoch's first step
-            if getattr(self, '_shadow_icnt', None) is None:
+            if self._shadow_icnt is None:
                 self._shadow_icnt = torch.zeros_like(self._cnt.icnt)
             self.pipe.side
             self._ahead = self._plan_chunk(nxt.idx ^ 1, csr, B, nxt.first + nxt.nb * B, True, then_exchange, shadow=self._shadow_icnt)
@@ -477,6 +492,7 @@ class DoubleTable:
         shape = (2, n, k) if k else (2, n)
         self.p = torch.zeros(shape, dtype=torch.float32, device=device)
         self.ms = torch.ones(shape, dtype=torch.float32, device=device)
+        self.mutations = 0               # assign() calls: writes from outside the step kernels (BprEngine.item_mutations)
         if init is not None:
             self.p[0].normal_(0.0, init, generator=gen)
 
@@ -487,7 +503,7 @@ class DoubleTable:
 
     def assign(self, values, ms=None):
         """write values into buffer 0 (the caller zeroes the update counters so that buffer 0 is current)"""
-        self.mutations = getattr(self, 'mutations', 0) + 1
+        self.mutations += 1
         self.p[0].copy_(values)
         if ms is not None:
             self.ms[0].copy_(ms)
@@ -521,6 +537,7 @@ class FlowTable:
         self.n, self.k, self.kp, self.bufs = n, k, tkr_hip.flow_row_granules(k), bufs
         self.p = torch.zeros((bufs, n, self.kp, 2), dtype=torch.float32, device=device)
         self.ms = torch.zeros((bufs, n, self.kp, 2), dtype=torch.float32, device=device)
+        self.mutations = 0
 
     def current(self, cnt):
         sel = (cnt & (self.bufs - 1)).long()
@@ -529,7 +546,7 @@ class FlowTable:
 
     def assign(self, values, ms):
         """version 0 of every row in buffer 0 (the caller zeroes the update counters); the other buffers hold no version"""
-        self.mutations = getattr(self, 'mutations', 0) + 1
+        self.mutations += 1
         for t, v, pad in ((self.p, values, 0.0), (self.ms, ms, 1.0)):
             t.zero_()
             t[0, :, :, 0] = pad
@@ -546,6 +563,7 @@ class FlowTail:
         self.n, self.bufs = n, bufs
         self.t = torch.zeros((bufs, n, 2 * bufs, 2), dtype=torch.float32, device=device)
         self.rd = torch.zeros(bufs * n, dtype=torch.int32, device=device)
+        self.mutations = 0
         _tags(self.t)[1:] = -1
 
     def current(self, cnt):
@@ -554,7 +572,7 @@ class FlowTail:
         return self.t[sel, idx, 0, 0], self.t[sel, idx, 1, 0]
 
     def assign(self, b=None, msb=None):
-        self.mutations = getattr(self, 'mutations', 0) + 1
+        self.mutations += 1
         self.t.zero_()
         if b is not None:
             self.t[0, :, 0, 0] = b
@@ -563,13 +581,51 @@ class FlowTail:
         self.rd.zero_()
 
 
+def layout_for(B, k, cfg, fits, flow_disabled):
+    """the table layout batch size B trains on: 'flow' (granule tables, a persistent step) or 'bulk'.  ``fits``: the granule tables
+    fit the device (decided once per engine); ``flow_disabled``: a persistent step gave up on them earlier"""
+    if cfg.flow and B <= cfg.flow_max_batch and k <= tkr_hip.FLOW_MAX_K and not flow_disabled and fits:
+        return 'flow'
+    return 'bulk'
+
+
+def step_kind(layout, B, cfg, owners, min_owners, own_failed):
+    """the kernel that steps batch size B on tables in ``layout``: 'own' (K2o), 'flow' (K2f) or 'bulk' (K2).  ``owners``: workgroups
+    that can hold the item rows in their LDS on this engine's share of the CUs, 0 = they do not fit"""
+    if layout != 'flow':
+        return 'bulk'
+    if B <= min(cfg.own_max_batch, 1024) and cfg.own != '0' and not own_failed and owners > 0 and owners >= min_owners:
+        return 'own'
+    return 'flow'
+
+
+def stepped_down(last_kind, own_failed, flow_disabled):
+    """(own_failed, flow_disabled) once the kernel that ran last has gone out of the choice: K2o -> K2f -> K2.  By the kernel that
+    RAN, not the one configured; an engine that ran neither persistent kernel gives up the granule layout"""
+    return (True, flow_disabled) if last_kind == 'own' else (own_failed, True)
+
+
+class _Built:
+    """what BprEngine.run_batches built its step for: a copy of EVERY switch (cfg's fields as a dict, compared as a whole in 0.2 us: one
+    added to Tuning later is covered) and the inputs of the choice that are no switches (BprEngine._inputs).  ``data`` / ``buf``: the
+    training data and the plan buffer of a short call that left in one C call -- the same call again may take _run_again -- else None"""
+
+    def __init__(self, cfg, inputs, step):
+        self.cfg, self.inputs, self.step, self.data, self.buf = dict(vars(cfg)), inputs, step, None, None
+
+    def same(self, cfg, inputs):
+        return self.inputs == inputs and self.cfg == vars(cfg)
+
+
 class BprEngine(PlanMixin):
     """Tables + sampler + step loop of one BPR model on one GPU.
 
-    Two layouts of the same model.  ``bulk``: plain double-buffered tables, one launch of K2 per batch (large batches:
-    bandwidth-bound).  ``flow``: granule tables with in-band versions, ONE persistent launch of K2f per chunk (batch sizes
-    up to cfg.flow_max_batch, where a launch per batch is latency-bound).  run_batches picks by batch size and converts the
-    tables when it changes; get / set work on either."""
+    Two layouts of the same model, three step kernels.  ``bulk``: plain double-buffered tables, one launch of K2 (csrc/bpr_step.hip)
+    per batch (large batches: bandwidth-bound).  ``flow``: granule tables with in-band versions, ONE persistent launch per chunk (batch
+    sizes up to cfg.flow_max_batch, where a launch per batch is latency-bound): K2o (csrc/bpr_own.hip) up to cfg.own_max_batch where the
+    item rows fit their owners' LDS, else K2f (csrc/bpr_flow.hip).  The rule is layout_for() and step_kind() above, stepped_down() after
+    a persistent step gave up; the methods here fetch the device facts those take.  run_batches converts the tables when the layout
+    changes; get / set work on either."""
 
     def __init__(self, n_users, n_items, k, hp, device=None, seed=None, user_seed=None, tuning=None):
         """``user_seed``: this engine holds ONE SHARD of the users (multi-GPU: n_users = rows owned by the rank): the user
@@ -588,63 +644,58 @@ class BprEngine(PlanMixin):
         self.b = DoubleTable(n_items, 0, self.device)
         self.tailU = self.tailV = self.ctl = None
         self._item_mutations = 0        # writes to the item tables from outside the step kernels (dist.ItemSync: is its snapshot still the truth?)
-        self._flow_ran = False          # a persistent launch ran since the status word was last looked at
         self._status_host = self._status_event = None
+        self._own_failed = False        # K2o gave up in this process: K2f from here on (stepped_down)
+        self._flow_disabled = False     # ... K2f did, or a persistent step that was not K2o: the plain layout and K2 from here on
+        self._flow_fits = None          # do the granule tables fit the device?  Asked once, when the answer first hangs on it (wants_flow)
+        self._owners_by_share = {}      # ranks sharing the GPU -> owners of item rows K2o has on this engine's share of it (_step_kind)
         self._init_plans(tuning)
 
     @property
     def item_mutations(self):
         """every write to the item tables from outside the step kernels: the engine's own (set_items, prepare) AND direct
         assign() calls on the table objects (those left dist.ItemSync's cached epoch start stale, silently)"""
-        return self._item_mutations + sum(getattr(t, 'mutations', 0) for t in (self.V, self.b, self.tailV) if t is not None)
+        return self._item_mutations + sum(t.mutations for t in (self.V, self.b, self.tailV) if t is not None)
 
     @item_mutations.setter
     def item_mutations(self, value):
-        self._item_mutations = value - sum(getattr(t, 'mutations', 0) for t in (self.V, self.b, self.tailV) if t is not None)
+        self._item_mutations = value - sum(t.mutations for t in (self.V, self.b, self.tailV) if t is not None)
 
     # ---- layout ----------------------------------------------------------------------------------
-    def _plan_flow(self):
-        return self.layout == 'flow'
+    # The two decisions everything below reads.  A device fact is fetched only where the answer hangs on it -- the rule is first asked
+    # with the fact granted: the memory probe is sticky and the owners query warns, neither is for a batch size that never needs it
+    def wants_flow(self, B):
+        """the granule layout + persistent step for this batch size (layout_for)?  Not when the granule tables would not fit: a granule
+        row is k rounded up to 128 elements of 8 bytes, in two buffers, parameter + slot = 4 KB per row WHATEVER k is (k = 16: 16x the
+        plain layout), and prepare() holds a copy of the old tables while it builds the new ones."""
+        cfg, off = self.cfg, self._flow_disabled
+        fits = self.layout == 'flow' or self._flow_fits
+        # decided ONCE per engine (ADVICE r3: asked on every call, the answer -- and with it the summation order of the step --
+        # followed whatever memory happened to be free, could differ between ranks and flip in mid-training)
+        if fits is None and layout_for(B, self.k, cfg, True, off) == 'flow':
+            rows = self.n_users + self.n_items
+            need = (rows + (cfg.flow_item_bufs // 2 - 1) * self.n_items) * (tkr_hip.flow_row_granules(self.k) * 32 + 96 + 8 * self.k)
+            free = torch.cuda.mem_get_info(self.device)[0] if self.device.type == 'cuda' else need
+            fits = self._flow_fits = need <= 0.7 * free
+        return layout_for(B, self.k, cfg, bool(fits), off) == 'flow'
 
-    def _plan_owners(self, B):
-        """workgroups that own item rows when batch size B steps with K2o, else 0.  K2o wants its workgroups -- 12 waves each, one
-        per CU -- all resident at once; ranks that share a GPU (the multi-rank tests of a one-GPU box, a launcher that packs ranks)
-        split the CUs: `ranks_on_device` (dist.ranks_sharing_device, set by whoever initialises the process group) ranks run
-        CUs // ranks owners each, as long as the rows of an owner still fit its LDS."""
-        if self.layout != 'flow' or B > min(self.cfg.own_max_batch, 1024) or self.cfg.own == '0' or getattr(self, '_own_failed', False):
-            return 0
-        share = max(1, int(getattr(self, 'ranks_on_device', 1)))
-        cache = self.__dict__.setdefault('_owners_by_share', {})
-        if share not in cache:                         # a property of the device, the table shape and the ranks beside us
-            cache[share] = tkr_hip.bpr_own_owners(self.n_items, self.k, self.device, share)
+    def _step_kind(self, B):
+        """(step_kind() on the tables AS THEY ARE: a layout forced through prepare(B, layout=...) counts; the owners of item rows when
+        that is K2o, else 0).  K2o wants its workgroups -- 12 waves each, one per CU -- all resident at once; ranks that share a GPU (the
+        multi-rank tests of a one-GPU box, a launcher that packs ranks) split the CUs: `ranks_on_device` ranks run CUs // ranks owners
+        each, as long as the rows of an owner still fit its LDS."""
+        cfg, failed, cache, share = self.cfg, self._own_failed, self._owners_by_share, max(1, int(self.ranks_on_device))
+        if share not in cache and step_kind(self.layout, B, cfg, 1, 0, failed) == 'own':
+            cache[share] = tkr_hip.bpr_own_owners(self.n_items, self.k, self.device, share)     # a property of the device, the table shape and the ranks beside us
             if cache[share] == 0 and share > 1:
-                import warnings
                 cus = torch.cuda.get_device_properties(self.device).multi_processor_count if self.device.type == 'cuda' else 0
                 warnings.warn('K2o is off: %d ranks share this GPU and %d item rows of width %d do not fit %d owners\' LDS; the persistent '
                               'step without owned rows (K2f) runs instead' % (share, self.n_items, self.k, cus // share))
-        if cache[share] < getattr(self, 'own_min_owners', 0):          # shards of one process (BPR._stream_shards): K2f below that many owners
-            return 0
-        return cache[share]
+        kind = step_kind(self.layout, B, cfg, cache.get(share, 0), self.own_min_owners, failed)
+        return kind, cache[share] if kind == 'own' else 0
 
-    def wants_flow(self, B):
-        """the granule layout + persistent step for this batch size?  Not when the granule tables would not fit: a granule row
-        is k rounded up to 128 elements of 8 bytes, in two buffers, parameter + slot = 4 KB per row WHATEVER k is (k = 16: 16x
-        the plain layout), and prepare() holds a copy of the old tables while it builds the new ones."""
-        if B > self.cfg.flow_max_batch or not self.cfg.flow or self.k > tkr_hip.FLOW_MAX_K:
-            return False
-        if getattr(self, '_flow_disabled', False):     # a bounded spin of the persistent kernel ran out in this process: K2 from here on
-            return False
-        if self.layout == 'flow':
-            return True
-        # decided ONCE per engine (ADVICE r3: asked on every call, the answer -- and with it the summation order of the step --
-        # followed whatever memory happened to be free, could differ between ranks and flip in mid-training)
-        fits = getattr(self, '_flow_fits', None)
-        if fits is None:
-            rows = self.n_users + self.n_items
-            need = (rows + (self.cfg.flow_item_bufs // 2 - 1) * self.n_items) * (tkr_hip.flow_row_granules(self.k) * 32 + 96 + 8 * self.k)
-            free = torch.cuda.mem_get_info(self.device)[0] if self.device.type == 'cuda' else need
-            fits = self._flow_fits = need <= 0.7 * free
-        return fits
+    def _plan_owners(self, B):
+        return self._step_kind(B)[1]
 
     def prepare(self, B, layout=None):
         """put the tables into the layout that batch size B runs on (or the one named)"""
@@ -675,40 +726,29 @@ class BprEngine(PlanMixin):
         self._cnt.ucnt.zero_()
         self._cnt.icnt.zero_()
 
+    def _step_down(self):
+        """stepped_down(): the kernel that ran last goes out of the choice, the built step and the short-call shortcut with it"""
+        self._own_failed, self._flow_disabled = stepped_down(self._last_step_kind, self._own_failed, self._flow_disabled)
+        self._step_key = None
+        return 'the persistent step without owned rows (K2f)' if self._last_step_kind == 'own' else 'the per-batch step (K2)'
+
     def _failed(self, code):
         post = self.ctl[tkr_hip.FLOW_CTL_DEBUG:tkr_hip.FLOW_CTL_DEBUG + 16].cpu().tolist()      # what the first wave that gave up waited for
         self.ctl.zero_()
         self._flow_ran = False
-        # The persistent kernel needs one resident wave per ticket queue; where that cannot be had (a GPU shared with a kernel that
-        # never ends) every later launch would time out the same way.  The tables of THIS run are lost -- a launch is not
-        # transactional -- but the engine stays usable: from here on it steps with K2 (one launch per batch, no co-residency
-        # assumption), e.g. after the caller re-imports a checkpoint.
-        # K2o asks for more than K2f -- a 12-wave workgroup resident on EVERY CU: where THAT is what failed (the GPU is shared), the
-        # next thing to try is K2f (4 waves per CU); a K2f launch that gives up goes straight to the per-batch step (the
-        # step-down used to follow whether K2o was configured, not which kernel had run: a K2f failure at batch 512 of an engine
-        # that had run K2o at batch 256 "stepped down" to K2f again).
-        if getattr(self, '_last_step_kind', None) == 'own':
-            self._own_failed = True
-            nxt = 'the persistent step without owned rows (K2f)'
-        else:
-            self._flow_disabled = True
-            nxt = 'the per-batch step (K2)'
+        # A persistent kernel needs its waves resident (K2o a 12-wave workgroup on EVERY CU, K2f 4 waves per CU); where that cannot be
+        # had (a GPU shared with a kernel that never ends) every later launch would time out the same way.  The tables of THIS run are
+        # lost -- a launch is not transactional -- but the engine stays usable one kernel down, once the caller has put tables back
+        nxt = self._step_down()
         self.tables_invalid = True       # until somebody puts tables back (set_users + set_items: BPR.train's retry does)
-        self._step_key = None
         raise tkr_hip.StepGaveUp('persistent BPR step gave up waiting for a row version (status %d): tables are invalid; this engine uses %s '
                                'from now on; post-mortem words (csrc/bpr_flow.hip kCtlDebug) %r' % (code, nxt, post))
 
     def step_down(self):
         """what _failed() does to the choice of kernel, without a failure of this engine's own: a sharded run restarts every rank
-        together when ANY rank's persistent step gave up, and the ranks that did not fail themselves step down with it -- otherwise
-        they retry the same kernel while the failed rank is one form further, every rank burns an attempt per try, and ranks on
-        different layouts would meet in one all-reduce"""
-        if getattr(self, '_last_step_kind', None) == 'own':
-            self._own_failed = True
-        else:
-            self._flow_disabled = True
-        self._step_key = None
-        self._again_key = None
+        together when ANY rank's step gave up, and the others step down with it -- else they retry the same kernel while the failed
+        rank is one form further, and ranks on different layouts would meet in one all-reduce"""
+        self._step_down()
 
     def _raise_pending(self):
         ev, self._status_event = self._status_event, None
@@ -847,33 +887,35 @@ class BprEngine(PlanMixin):
         """sample + plan + step for n_batches consecutive batches; returns the per-batch
         losses of the LAST chunk as a device tensor (or None).  ``then_exchange`` = m > 0: the caller runs dist.ItemSync.end()
         right after this call and then goes on with an epoch of m batches -- its first chunk is planned ahead (PlanMixin)."""
-        if (self.k > 512 or (self.k > 256 and B > 1024)) and not getattr(self, '_warned_wide', False):
-            self._warned_wide = True
-            import warnings
-            warnings.warn('BPR: k = %d at batch_size = %d is wider than a wave can hold a row in registers beside its partners (k <= 512, '
-                          '<= 256 above batch 1024): the generic row form steps (csrc/bpr_step.hip bpr_wide_kernel: every occurrence in two '
-                          'passes over k, the gradient sum through memory)' % (self.k, B))
-        cfg = self.cfg
-        again = (id(csr), 0, B, self.layout_epoch, cfg.own, cfg.own_waves, cfg.fuse_short, cfg.fuse_plan, cfg.own_max_batch, cfg.flow, cfg.flow_max_batch, getattr(self, '_flow_disabled', False),
-                 getattr(self, '_own_failed', False), getattr(self, 'ranks_on_device', 1), self.seed)
-        if again == getattr(self, '_again_key', None) and then_exchange == 0 and self.step_events is None:
+        built = self._step_key
+        if (built is not None and built.buf is not None and built.data is csr and then_exchange == 0 and self.step_events is None
+                and built.same(self.cfg, self._inputs(B))):
             loss = self._run_again(csr, n_batches, B, want_loss)
             if loss is not False:
                 return loss
+        if (self.k > 512 or (self.k > 256 and B > 1024)) and not self._warned_wide:
+            self._warned_wide = True
+            warnings.warn('BPR: k = %d at batch_size = %d is wider than a wave can hold a row in registers beside its partners (k <= 512, '
+                          '<= 256 above batch 1024): the generic row form steps (csrc/bpr_step.hip bpr_wide_kernel: every occurrence in two '
+                          'passes over k, the gradient sum through memory)' % (self.k, B))
         self.prepare(B)
-        again = again[:3] + (self.layout_epoch,) + again[4:]
-        key = (self.layout_epoch, B, self.cfg.flow_waves_per_cu, self._plan_owners(B), self.cfg.own_waves, self.cfg.fuse_plan)
-        if getattr(self, '_step_key', None) != key:       # the C struct and the closure are built once per layout, not per call
-            self._step_key, self._step = key, self.step_fn(B)
-        self._flow_ran = self._flow_ran or self.layout == 'flow'
-        if self.layout == 'flow':
-            self._last_step_kind = 'own' if self._plan_owners(B) else 'flow'
+        inputs = self._inputs(B)
+        if built is None or not built.same(self.cfg, inputs):      # the C struct and the closure are built once per choice, not per call
+            built = self._step_key = _Built(self.cfg, inputs, self.step_fn(B))
+            self._step = built.step
+        kind = self._step_kind(B)[0]
+        if kind != 'bulk':
+            self._flow_ran, self._last_step_kind = True, kind
         loss = self._run(csr, n_batches, B, want_loss, self._step, then_exchange)
         # a short call that left in one C call (K1 in the step's launch): the same call again needs none of the decisions above
         cur = self._cur
         fused = cur is not None and cur.fused and cur.used == cur.nb and self._ahead is None
-        self._again_key, self._again_buf = (again, cur.idx) if fused else (None, 0)
+        built.data, built.buf = (csr, cur.idx) if fused else (None, None)
         return loss
+
+    def _inputs(self, B):
+        """what the choice of step for batch size B hangs on beside the switches (_Built)"""
+        return (B, self.layout_epoch, self.seed, self.ranks_on_device, self.own_min_owners, self._own_failed, self._flow_disabled)
 
     def _run_again(self, csr, n_batches, B, want_loss):
         """another short call like the last one (same training data, batch size, layout and switches; a driver's timed 20-batch call
@@ -881,14 +923,13 @@ class BprEngine(PlanMixin):
         one C call and the bookkeeping -- 12 us less Python in front of the one launch (scripts/probe_short_host.py: 124 -> 111 us
         per 20-batch call).  False: take the long way."""
         cur, pipe = self._cur, self.pipe
-        if ((cur is not None and cur.used != cur.nb) or self._ahead is not None or getattr(pipe, '_side_dirty', False)       # (a settle() in between leaves no chunk)
-                or getattr(self, 'tables_invalid', False)):
-            return False
+        if (cur is not None and cur.used != cur.nb) or self._ahead is not None or pipe._side_dirty or self.tables_invalid:
+            return False                              # (a settle() in between leaves no chunk)
         if n_batches > self._cap(B):                  # more than one chunk: K1 of the second belongs on the side stream
             return False
         if n_batches <= 0 or (want_loss and not getattr(self._step, 'assigns_loss', False)):
             return False                              # nothing to run / a step form that ADDS to the loss words: _run zeroes them (ADVICE r5)
-        idx = self._again_buf ^ 1                     # the other plan buffer, as _next_chunk alternates them
+        idx = self._step_key.buf ^ 1                  # the other plan buffer, as _next_chunk alternates them
         call = self._fused_calls.get(idx)
         if call is None or call[1] is not csr or call[2] is not pipe.bufs[idx]:       # planned for other data / a replaced buffer
             return False
@@ -899,16 +940,16 @@ class BprEngine(PlanMixin):
         ch.fused = True
         self._step.plan_and_run(buf, call, 0, n_batches, buf.loss if want_loss else None, None)
         ch.used = n_batches
-        self._cur, self.plan, self._again_buf = ch, buf, idx
+        self._cur, self.plan, self._step_key.buf = ch, buf, idx
         self._drawn += n_batches * B
         self._flow_ran, self._last_step_kind = True, 'own'
         return buf.loss[:n_batches] if want_loss else None
 
     def step_fn(self, B):
-        state = self.state()
-        if self.layout == 'flow':
-            if self._plan_owners(B):
-                return tkr_hip.own_stepper(state, B, self.ctl, self.cfg.own_waves | (0 if self.cfg.fuse_plan else 0x1000))
+        state, kind = self.state(), self._step_kind(B)[0]
+        if kind == 'own':
+            return tkr_hip.own_stepper(state, B, self.ctl, self.cfg.own_waves | (0 if self.cfg.fuse_plan else 0x1000))
+        if kind == 'flow':
             return tkr_hip.flow_stepper(state, B, self.ctl, self.cfg.flow_waves_per_cu)
         return lambda plan, lo, nb, loss: tkr_hip.bpr_run(state, plan, B, nb, loss, first=lo)
 
@@ -943,6 +984,7 @@ class VbprEngine(PlanMixin):
         self.feat = self.feat.to(self.device).contiguous()
         assert self.feat.shape == (n_items, d)
         self._init_plans(tuning)
+        self._warned_big = False        # the warning about the O(B^2) pair sums of a huge batch went out
         self.ws = None
         self.sparse = None
         nnz = int(torch.count_nonzero(self.feat))
@@ -1064,18 +1106,16 @@ class VbprEngine(PlanMixin):
         if self.kh > 128 and self.sparse is None:
             raise ValueError('VBPR: k // 2 = %d takes the CSR view of feat (sparse=True or None): the dense fp32-MFMA view holds at most '
                              '128 factors' % self.kh)
-        if B > 65536 and not getattr(self, '_warned_big', False):
+        if B > 65536 and not self._warned_big:
             self._warned_big = True
-            import warnings
             warnings.warn('VBPR: batch_size = %d: the objective sums over all B^2 = %.3g pairs of a batch (vbpr.py:61,64 broadcast to [B, B]), '
                           'so the pair sums of every batch are O(B^2) work' % (B, float(B) * B))
-        if self.kh > 128 and not getattr(self, '_warned_wide', False):
+        if self.kh > 128 and not self._warned_wide:
             self._warned_wide = True
-            import warnings
             warnings.warn('VBPR: k // 2 = %d is wider than the step\'s kernels hold a row in registers (128): the generic form steps '
                           '(csrc/vbpr_wide.hip: every kernel walks the factors in passes of its threads; the column plan where it applies, '
                           'the five-launch sparse view elsewhere)' % self.kh)
-        if getattr(self, '_step_key', None) != B:           # the C struct and the closure are built once per batch size, not per call
+        if self._step_key != B:           # the C struct and the closure are built once per batch size, not per call
             self._step_key, self._step = B, self.step_fn(B)
         return self._run(csr, n_batches, B, want_loss, self._step)
 

@@ -127,7 +127,7 @@ class BPR(REC):
         self._owned = None if owned is None else np.asarray(owned, dtype=np.int64)
         if self._owned is None:
             self._eng = self._make_engine(device, seed)
-            if self._csr is None or self._csr.row_ptr.device != self._eng.device or getattr(self._csr, 'local', False):
+            if self._csr is None or self._csr.row_ptr.device != self._eng.device or self._csr.local:
                 self._csr = self._make_csr(self.tr_users, self._eng.device)
             return self._eng
         import dist as tdist
@@ -256,7 +256,7 @@ class BPR(REC):
         # (VBPR steps one launch at a time: nothing to give up; TKR_RESTART=0: no copy of the tables, a step that gives up raises)
         # Shards of one GPU all start from the lead's model: its snapshot restores every one of them.
         lead = self._eng
-        start = lead.snapshot() if (getattr(lead, 'layout', None) == 'flow' and lead.cfg.restart) else None
+        start = lead.snapshot() if (lead.layout == 'flow' and lead.cfg.restart) else None
         if len(shards) > 1:                                # where the user rows of the shards are merged from after training
             users_start = start['U'] if start is not None else tuple(t.clone() for t in lead.get('U'))
         for attempt in range(3):
@@ -273,7 +273,7 @@ class BPR(REC):
                     e.check()
                 except tkr_hip.StepGaveUp as x:
                     warnings.warn('BPR.train restarts from its initial state: %s' % x)
-                if not getattr(e, 'tables_invalid', False):
+                if not e.tables_invalid:
                     e.step_down()
             if start is None or attempt == 2:
                 raise tkr_hip.StepGaveUp('BPR.train: the step gave up on every kernel form')
