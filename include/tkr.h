@@ -31,7 +31,7 @@
 extern "C" {
 #endif
 
-#define TKR_VERSION 120 /* (additions that change no existing entry point keep the number: K10 tkr_bpr_foldin_items, K11 tkr_ratings_*_dev, K12 tkr_rank_candidates, K13 tkr_lists_format_* / tkr_matrix_format_*, K15 tkr_group_*_dev / tkr_last_line_of_user_dev / tkr_compact_rows_*_dev, K16 tkr_fusion_*, K17 tkr_mmr_select / tkr_list_pair_sums.) 0.1.20: K9 tkr_bpr_foldin (user vectors for new histories against frozen item factors; csrc/foldin.hip). 0.1.19: K8 tkr_like_ranks + tkr_like_ranks_workspace_bytes (filtered rank of every liked test column; csrc/like_ranks.hip). 0.1.18: K4 second form of bound-and-refine (csrc/topk_refine.hip; tkr_topk_workspace_bytes_for grows by the pieces' packed lists), any k (bpr_wide_kernel, score_topk_wide_kernel), tkr_lab_build; tkr_topk_set_finish is gone, tkr_topk_set_math(0) and tkr_vbpr_set_pairs(1 | 2) need the lab library. 0.1.17: tkr_vbpr_set_pairs (tkr_vbpr_workspace_floats + 64). 0.1.16: tkr_topk_set_finish (larger tkr_topk_workspace_bytes), tkr_bpr_own_plan_run plans inside the step's launch. 0.1.15: tkr_bpr_own_owners_shared; tkr_bpr_run takes `rec` non-const. 0.1.14: per-task loss sums instead of atomics on loss_out (larger tkr_vbpr_workspace_floats; K2 writes word 15 of its records). 0.1.13: tkr_bpr_own_plan_run, K4 to k = 768. 0.1.12: tkr_bpr_own_run_between. 0.1.11: K2o (tkr_sample_plan_owned, tkr_bpr_own_run: item rows owned by one workgroup each, resident in its LDS); prec[5] = last batch of the call that updated the row. 0.1.10: tkr_topk_workspace_bytes_for (K4 stages pre-converted fp16 tiles). 0.1.9: tkr_vbpr_colplan + tkr_vbpr_run_cols (VBPR in three launches per batch). 0.1.8: tkr_sync_flow_* (exchange of the granule tables). 0.1.7: K4 bound-and-refine arithmetic (tkr_topk_set_math(2), the default; larger tkr_topk_workspace_bytes); K2f leaves its ticket words zero. 0.1.6: K2f persistent dataflow step, tkr_plan_rollback, batches above 8192 */
+#define TKR_VERSION 120 /* (additions that change no existing entry point keep the number: K10 tkr_bpr_foldin_items, K11 tkr_ratings_*_dev, K12 tkr_rank_candidates, K13 tkr_lists_format_* / tkr_matrix_format_*, K15 tkr_group_*_dev / tkr_last_line_of_user_dev / tkr_compact_rows_*_dev, K16 tkr_fusion_*, K17 tkr_mmr_select / tkr_list_pair_sums, K21 tkr_als_solve_rows_prior / tkr_als_prior_workspace_bytes.) 0.1.20: K9 tkr_bpr_foldin (user vectors for new histories against frozen item factors; csrc/foldin.hip). 0.1.19: K8 tkr_like_ranks + tkr_like_ranks_workspace_bytes (filtered rank of every liked test column; csrc/like_ranks.hip). 0.1.18: K4 second form of bound-and-refine (csrc/topk_refine.hip; tkr_topk_workspace_bytes_for grows by the pieces' packed lists), any k (bpr_wide_kernel, score_topk_wide_kernel), tkr_lab_build; tkr_topk_set_finish is gone, tkr_topk_set_math(0) and tkr_vbpr_set_pairs(1 | 2) need the lab library. 0.1.17: tkr_vbpr_set_pairs (tkr_vbpr_workspace_floats + 64). 0.1.16: tkr_topk_set_finish (larger tkr_topk_workspace_bytes), tkr_bpr_own_plan_run plans inside the step's launch. 0.1.15: tkr_bpr_own_owners_shared; tkr_bpr_run takes `rec` non-const. 0.1.14: per-task loss sums instead of atomics on loss_out (larger tkr_vbpr_workspace_floats; K2 writes word 15 of its records). 0.1.13: tkr_bpr_own_plan_run, K4 to k = 768. 0.1.12: tkr_bpr_own_run_between. 0.1.11: K2o (tkr_sample_plan_owned, tkr_bpr_own_run: item rows owned by one workgroup each, resident in its LDS); prec[5] = last batch of the call that updated the row. 0.1.10: tkr_topk_workspace_bytes_for (K4 stages pre-converted fp16 tiles). 0.1.9: tkr_vbpr_colplan + tkr_vbpr_run_cols (VBPR in three launches per batch). 0.1.8: tkr_sync_flow_* (exchange of the granule tables). 0.1.7: K4 bound-and-refine arithmetic (tkr_topk_set_math(2), the default; larger tkr_topk_workspace_bytes); K2f leaves its ticket words zero. 0.1.6: K2f persistent dataflow step, tkr_plan_rollback, batches above 8192 */
 #define TKR_OK 0
 #define TKR_E_INVAL (-1)
 #define TKR_E_UNSUPPORTED (-2)
@@ -918,7 +918,28 @@ int tkr_nearest_anchors(const float* S, int32_t n_items, int32_t k, const int32_
  * The input is not trusted: nothing refused is ever used as an index.  Arguments are checked before any device access and before any
  * launch (TKR_E_INVAL): a null Y / G / X / like_ptr / status, a null like_cols with n_likes > 0, a misaligned status / row_loss /
  * workspace, k / n / n_y / n_x < 1, n_x >= 2^31, n_listed / n_likes < 0, heavy_from < 1, ridge < 0 (solve), a weight that is not finite,
- * a workspace too small.  Deterministic: two calls give the same bits; no float atomics, the only atomic is the status word's minimum. */
+ * a workspace too small.  Deterministic: two calls give the same bits; no float atomics, the only atomic is the status word's minimum.
+ *
+ * K21 (CER, the reference's single/cer.py:49-63): the same half-step with a prior on every row, and EVERY row solved.
+ *   tkr_als_solve_rows_prior  the arguments of tkr_als_solve_rows, and prior fp32 [n_x, k], w_prior >= 0; p = prior[r].
+ *                       Rows with likes (m_r > 0 of them inside [0, n_y)):  A = G + w_like * sum y y^T as above,
+ *                         rhs = fp32(w_rhs * sum y + w_prior * p)   (both terms in fp64, rounded once),  X[r] = (A + ridge I)^-1 rhs
+ *                         row_loss[r] = tkr_als_solve_rows' expression + 1/2 w_prior * sum_j (x_j - p_j)^2   (differences and sum in fp64)
+ *                       With w_prior = 0 and a prior of zeros such a row has the bits of tkr_als_solve_rows, X and row_loss, on the own-sum
+ *                       and on the heavy path: the prior is one more term of the right-hand side and of the loss and nothing else.
+ *                       Rows without likes (like_ptr[r] == like_ptr[r + 1]):  X[r] = (G + ridge I)^-1 fp32(w_prior * p),
+ *                         row_loss[r] = 1/2 w_prior * sum_j (x_j - p_j)^2 only (cer.py:61-63 adds no quadratic term for them).
+ *                       They all have ONE matrix: fp32(G + ridge I) is factorised once per call, by one workgroup with the Cholesky of
+ *                       the per-row kernel, into the workspace; a second launch substitutes forwards and backwards, a lane per row, 256
+ *                       rows per workgroup, the factor in LDS and read wave-uniformly, the row's z and x in registers.  The bits of such a
+ *                       row depend on G, ridge, w_prior and its own prior only: not on n_x, on which other rows are cold or on its lane.
+ *                       A row whose likes were ALL refused (kind 1) is reported, left as it is, row_loss 0: it is not a cold row.
+ *                       status as above; kind 2 on the shared factor refuses every cold row (4 * (the smallest cold row) + 2, none of
+ *                       them touched); kind 2 on one row's own solution (a prior holding inf or NaN) refuses that row only.  No NaN is
+ *                       ever written to X.  workspace: never NULL, 16-byte aligned, tkr_als_prior_workspace_bytes(n_x, k, n_slabs) =
+ *                       tkr_als_workspace_bytes(n_x, k, n_slabs) + room for the factor (k * k + 4 floats, rounded up to 16 bytes).
+ *                       TKR_E_INVAL before any device access: prior NULL (the caller wants tkr_als_solve_rows) or not 4-byte aligned,
+ *                       w_prior negative or not finite, and everything tkr_als_solve_rows refuses. */
 #define TKR_ALS_MAX_K 128
 #define TKR_ALS_GRAM_SLAB 1024
 int64_t tkr_als_workspace_bytes(int64_t n_x, int32_t k, int64_t n_slabs);
@@ -927,6 +948,11 @@ int tkr_als_gram(const float* Y, int32_t n, int32_t k, const int32_t* rows, int6
 int tkr_als_solve_rows(const float* Y, int32_t n_y, int32_t k, const float* G, const int64_t* like_ptr, const int32_t* like_cols,
                        int64_t n_likes, int64_t n_x, double w_like, double w_rhs, double ridge, int64_t heavy_from, float* X,
                        double* row_loss, void* workspace, int64_t workspace_bytes, int64_t* status, void* stream);
+int64_t tkr_als_prior_workspace_bytes(int64_t n_x, int32_t k, int64_t n_slabs);
+int tkr_als_solve_rows_prior(const float* Y, int32_t n_y, int32_t k, const float* G, const int64_t* like_ptr, const int32_t* like_cols,
+                             int64_t n_likes, int64_t n_x, double w_like, double w_rhs, double ridge, int64_t heavy_from, float* X,
+                             double* row_loss, const float* prior, double w_prior, void* workspace, int64_t workspace_bytes, int64_t* status,
+                             void* stream);
 
 #ifdef __cplusplus
 }

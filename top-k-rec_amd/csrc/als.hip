@@ -1,4 +1,4 @@
-// K20 -- the two kernels of implicit-feedback ALS (WMF; top-k-rec_amd/als.py).  One half-step of the alternation is
+// K20 -- the two kernels of implicit-feedback ALS (WMF; top-k-rec_amd/als.py); K21, their content-aware form (CER), below.  One half-step of the alternation is
 //
 //   G = scale * sum over the rated rows y of  y y^T  (+ ridge I)                               tkr_als_gram
 //   for every row r with likes:  (G + w_like * sum_{y in L_r} y y^T + ridge I) x_r = w_rhs * sum_{y in L_r} y      tkr_als_solve_rows
@@ -26,6 +26,14 @@
 //                           ridge is kept apart: the row's loss needs them after the factorisation.  Every barrier is in
 //                           workgroup-uniform control flow: the loop bounds are k, the row's (checked) length and flags every
 //                           thread reads from the same LDS word.
+//
+// K21 -- the same half-step with a prior on every row, every row solved (CER; tkr_als_solve_rows_prior):
+//   als_solve_kernel<KT, kAlsPrior>   the per-row kernel with w_prior * prior[r] added to the right-hand side and 1/2 w_prior |x - prior[r]|^2
+//                           to the loss; rows without likes are not its business.
+//   als_solve_kernel<KT, kAlsFactor>  one workgroup: fp32(G + ridge I), the matrix every row without likes has, factorised ONCE per call
+//                           by the per-row kernel's own Cholesky (a mode of the same template, not a copy); L goes to the workspace.
+//   als_cold_kernel<KT>     a lane per row without likes: L in LDS, read wave-uniformly, z and x in registers, two triangular
+//                           substitutions by dot products over contiguous rows (of L, then of L^T).
 // No float atomics; the only atomic is the status word's minimum.  Nothing refused is used as an index.
 #include "tkr_common.h"
 #include "../../include/tkr.h"
@@ -262,13 +270,26 @@ struct AlsSolveLds {
     }
 };
 
-template <int KT>
+// The one per-row solve, and the ONE factorisation of this file, in three modes (the factor of K21's cold rows is this code, not a copy:
+// a wrapper around a shared device function gave K20 other register numbers and 0.9 % at k = 128, one template does not); everything that differs is behind `if constexpr`, so
+// kAlsK20 is K20's kernel as it was:
+//   kAlsK20     tkr_als_solve_rows
+//   kAlsPrior   K21, tkr_als_solve_rows_prior: the right-hand side adds w_prior * prior[r] and the loss 1/2 w_prior |x - prior[r]|^2; a
+//               row without likes is the cold kernel's
+//   kAlsFactor  K21, one workgroup: the "row" has no likes and no right-hand side, A = fp32(G + ridge I) as a row's diagonal is
+//               rounded; after the factorisation L goes to `factor` (als_factor_floats) in place of a back substitution
+enum { kAlsK20 = 0, kAlsPrior = 1, kAlsFactor = 2 };
+__host__ __device__ inline int64_t als_factor_floats(int k) { return (int64_t)k * k + 4; }      // L row-major [k][k], one int: 1 = factorised
+
+template <int KT, int MODE>
 __global__ __launch_bounds__(kAlsBlock) void als_solve_kernel(const float* __restrict__ Y, int n_y, int k, const float* __restrict__ G,
                                                               const int64_t* __restrict__ like_ptr, const int32_t* __restrict__ like_cols,
                                                               long long n_likes, double w_like, double w_rhs, double ridge,
                                                               const int32_t* __restrict__ heavy_base, const float* __restrict__ partial,
                                                               float* __restrict__ X, double* __restrict__ row_loss,
-                                                              unsigned long long* __restrict__ status) {
+                                                              unsigned long long* __restrict__ status, const float* __restrict__ prior,
+                                                              double w_prior, float* __restrict__ factor) {
+    constexpr bool PRIOR = MODE == kAlsPrior;
     extern __shared__ __attribute__((aligned(16))) float als_lds[];
     const AlsSolveLds at(k, KT);
     const int AP = als_a_pitch(k);
@@ -289,7 +310,7 @@ __global__ __launch_bounds__(kAlsBlock) void als_solve_kernel(const float* __res
     const unsigned long long word = (unsigned long long)r * 4ull;
 
     // the row's likes: the same two words in every thread, so every exit below is taken by the whole workgroup
-    const long long lo = like_ptr[r], hi = like_ptr[r + 1];
+    const long long lo = MODE == kAlsFactor ? 0 : like_ptr[r], hi = MODE == kAlsFactor ? 0 : like_ptr[r + 1];
     if (!als_ptr_ok(lo, hi, n_likes, r)) {
         if (tid == 0) {
             atomicMin(status, word + 3ull);                       // kind 3: the row is left as it is
@@ -298,9 +319,12 @@ __global__ __launch_bounds__(kAlsBlock) void als_solve_kernel(const float* __res
         return;
     }
     const int m = (int)(hi - lo);
-    if (m == 0) {
-        if (tid == 0 && row_loss) row_loss[r] = 0.0;
-        return;
+    if constexpr (MODE != kAlsFactor) {
+        if (m == 0) {
+            if constexpr (!PRIOR)
+                if (tid == 0 && row_loss) row_loss[r] = 0.0;
+            return;
+        }
     }
     const int hb = heavy_base ? heavy_base[r] : -1;
     double col_sum = 0.0;
@@ -314,7 +338,12 @@ __global__ __launch_bounds__(kAlsBlock) void als_solve_kernel(const float* __res
             A[p * AP + q] = (float)v;
         }
     };
-    if (hb < 0) {                                                 // (uniform) the row sums its own likes
+    if constexpr (MODE == kAlsFactor) {
+        for (int idx = tid; idx < k * k; idx += kAlsBlock) {
+            const int p = idx / k;
+            put(p, idx - p * k, 0.0);
+        }
+    } else if (hb < 0) {                                          // (uniform) the row sums its own likes
         als_f32x16 acc[als_tiles_per_wave(KT)];
         als_zero<KT>(acc);
         slab_sum<KT>(Y, n_y, k, like_cols, lo, m, stage, cols_s, acc, col_sum, n_valid, r, status);
@@ -336,16 +365,22 @@ __global__ __launch_bounds__(kAlsBlock) void als_solve_kernel(const float* __res
             }
         }
     }
+    float pv = 0.f;                                               // (PRIOR) the prior's element tid, kept for the loss
     if (tid < k) {
         cs[tid] = col_sum;
-        A[k * AP + tid] = (float)(w_rhs * col_sum);
+        if constexpr (PRIOR) {
+            pv = prior[(size_t)r * k + tid];
+            A[k * AP + tid] = (float)(w_rhs * col_sum + w_prior * (double)pv);      // both terms in fp64, rounded once
+        } else {
+            A[k * AP + tid] = (float)(w_rhs * col_sum);
+        }
     }
     if (tid == 0) {
         *n_valid_s = n_valid;
         *fail_s = 0;
     }
     __syncthreads();
-    const int nv = *n_valid_s;
+    const int nv = MODE == kAlsFactor ? 1 : *n_valid_s;
     if (nv == 0) {                                                // (uniform) every like was refused: as a row without likes
         if (tid == 0 && row_loss) row_loss[r] = 0.0;
         return;
@@ -418,6 +453,17 @@ __global__ __launch_bounds__(kAlsBlock) void als_solve_kernel(const float* __res
         }
     }
     __syncthreads();
+    if constexpr (MODE == kAlsFactor) {
+        int* flag = reinterpret_cast<int*>(factor + (size_t)k * k);
+        if (ok) {                                                 // (uniform)
+            for (int idx = tid; idx < k * k; idx += kAlsBlock) {
+                const int p = idx / k, q = idx - p * k;
+                factor[idx] = q < p ? A[p * AP + q] : (q == p ? ldiag[p] : 0.f);
+            }
+        }
+        if (tid == 0) *flag = ok ? 1 : 0;
+        return;
+    }
     if (ok && tid < TKR_WAVE) {                                   // wave 0: L^T x = z, z and x in registers (element i in lane i & 63)
         const int lane = tid;
         float z0 = lane < k ? zf[lane] : 0.f, z1 = lane + 64 < k ? zf[lane + 64] : 0.f;
@@ -458,11 +504,23 @@ __global__ __launch_bounds__(kAlsBlock) void als_solve_kernel(const float* __res
         t *= 0.5;
         if (tid < k) t -= w_rhs * (cs[tid] * (double)xs[tid]);
         red[tid] = t;
+        if constexpr (PRIOR) {
+            if (tid < k) {                                        // (cs[tid] is this thread's own word: read above, free now)
+                const double d = (double)xs[tid] - (double)pv;
+                cs[tid] = d * d;
+            }
+        }
         __syncthreads();
         if (tid == 0) {
             double s = 0.0;
             for (int i = 0; i < kAlsBlock; ++i) s += red[i];
-            row_loss[r] = s + 0.5 * w_rhs * (double)nv;
+            if constexpr (PRIOR) {
+                double q = 0.0;
+                for (int j = 0; j < k; ++j) q += cs[j];
+                row_loss[r] = (s + 0.5 * w_rhs * (double)nv) + 0.5 * w_prior * q;
+            } else {
+                row_loss[r] = s + 0.5 * w_rhs * (double)nv;
+            }
         }
     }
 }
@@ -493,17 +551,223 @@ static int launch_slabs_kt(int KT, hipStream_t stream, long long n_slabs, const 
     }
 }
 
-template <int KT>
+template <int KT, bool PRIOR>
 static int launch_solve(hipStream_t stream, long long n_x, const float* Y, int n_y, int k, const float* G, const int64_t* like_ptr,
                         const int32_t* like_cols, long long n_likes, double w_like, double w_rhs, double ridge, const int32_t* heavy_base,
-                        const float* partial, float* X, double* row_loss, unsigned long long* st) {
+                        const float* partial, float* X, double* row_loss, unsigned long long* st, const float* prior, double w_prior) {
     const size_t lds = (size_t)AlsSolveLds(k, KT).floats * 4;
-    auto kern = als_solve_kernel<KT>;
+    auto kern = als_solve_kernel<KT, PRIOR ? kAlsPrior : kAlsK20>;
     if (lds > 64 * 1024) TKR_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
     hipLaunchKernelGGL(kern, dim3((unsigned)n_x), dim3(kAlsBlock), lds, stream, Y, n_y, k, G, like_ptr, like_cols, n_likes, w_like, w_rhs, ridge,
-                       heavy_base, partial, X, row_loss, st);
+                       heavy_base, partial, X, row_loss, st, prior, w_prior, (float*)nullptr);
     TKR_LAUNCH_CHECK();
     return TKR_OK;
+}
+
+// ---- K21: the rows without likes of tkr_als_solve_rows_prior ------------------------------------------------------------------------------
+// Every such row has the same matrix, fp32(G + ridge I): it is factorised ONCE per call (one workgroup runs
+// als_solve_kernel in its factor mode) and the rows are two triangular substitutions each (als_cold_kernel).
+// A lane per row, 256 rows per workgroup; a workgroup without a cold row leaves at once.  The factor sits in LDS at a pitch of 32 KT
+// floats: every lane of a wave reads the same entry at the same time (a broadcast), at an address the compiler knows, so a row
+// comes four entries per LDS instruction.  z, then x in its place, stays in registers (the loops are unrolled over 32 KT; the guards
+// on k are wave-uniform).  Both substitutions are DOT products over a contiguous row in LDS, summed apart from the element they are
+// taken from -- four fp32 fma chains from +0.0 over the terms i = 0, 1, 2, 3 mod 4, added as (s0 + s1) + (s2 + s3) -- and then ONE
+// subtraction and ONE division: z_j = (b_j - sum_{i<j} L_ji z_i) / l_jj over row j of L, and, after the workgroup has put L^T where L
+// was, x_j = (z_j - sum_{i>j} L_ij x_i) / l_jj over row j of L^T.  (Updating z_i in place, term by term, rounds every term at the size
+// of z_i: measured 6 x 2^-23 of the solution against 0.8 for fp32 LAPACK where the sums are small beside z.)  Every lane runs the same
+// chain on its own row: a row's bits depend on the factor, w_prior and its prior, not on n_x, its neighbours or its lane.  Priors come
+// in and rows go out through a [64][33] LDS tile per wave, 32 columns at a time, so that global memory sees 32 consecutive floats of
+// a row per half-wave.
+constexpr int kAlsColdPitch = 33;
+__host__ __device__ constexpr int als_cold_lds_floats(int KT) { return KT * 32 * KT * 32 + kAlsWaves * TKR_WAVE * kAlsColdPitch; }
+
+template <int KT>
+__global__ __launch_bounds__(kAlsBlock) void als_cold_kernel(const float* __restrict__ factor, int k, const int64_t* __restrict__ like_ptr,
+                                                             long long n_likes, long long n_x, const float* __restrict__ prior, double w_prior,
+                                                             float* __restrict__ X, double* __restrict__ row_loss,
+                                                             unsigned long long* __restrict__ status) {
+    constexpr int LP = KT * 32;
+    extern __shared__ __attribute__((aligned(16))) float als_lds[];
+    float* L = als_lds;                                            // [k][LP]: L, the lower triangle with the diagonal; later L^T
+    const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63, l31 = lane & 31;
+    float* st = L + LP * LP + wave * (TKR_WAVE * kAlsColdPitch);      // this wave's tile
+    const long long r = (long long)blockIdx.x * kAlsBlock + tid;
+    bool cold = false;
+    if (r < n_x) {
+        const long long lo = like_ptr[r], hi = like_ptr[r + 1];
+        cold = lo == hi && als_ptr_ok(lo, hi, n_likes, r);         // (a row like_ptr is wrong at: kind 3, the per-row kernel's)
+    }
+    if (*reinterpret_cast<const int*>(factor + (size_t)k * k) == 0) {      // (the same word in every thread of the grid)
+        if (cold) {                                               // kind 2 on the shared factor: every cold row refused, none touched
+            atomicMin(status, (unsigned long long)r * 4ull + 2ull);
+            if (row_loss) row_loss[r] = 0.0;
+        }
+        return;
+    }
+    if (!__syncthreads_or(cold)) return;                          // (uniform)
+    for (int idx = tid; idx < k * k; idx += kAlsBlock) {
+        const int p = idx / k, q = idx - p * k;
+        L[p * LP + q] = factor[idx];
+    }
+    const unsigned long long mask = __ballot(cold);               // the wave's rows r0 + rr, rr = the lane that holds the row
+    const long long r0 = r - lane;
+    auto stage_prior = [&](int c) {                               // the wave's 64 rows, columns 32 c .. 32 c + 31 (zeros beyond k, in rows not cold)
+        const int col = c * 32 + l31;
+        for (int rr = lane >> 5; rr < TKR_WAVE; rr += 2)
+            st[rr * kAlsColdPitch + l31] = ((mask >> rr) & 1ull) && col < k ? prior[(size_t)(r0 + rr) * k + col] : 0.f;
+    };
+    float z[LP];
+#pragma unroll
+    for (int c = 0; c < KT; ++c) {
+        stage_prior(c);
+        __syncthreads();                                          // (also: the factor is in LDS)
+#pragma unroll
+        for (int i = 0; i < 32; ++i) z[c * 32 + i] = (float)(w_prior * (double)st[lane * kAlsColdPitch + i]);
+        __syncthreads();
+    }
+    // (the empty asm keeps the scheduler from fetching rows far ahead of their use: the registers are z's)
+    if (mask != 0ull) {                                           // (wave-uniform; no barrier inside)
+#pragma unroll
+        for (int j = 0; j < LP; ++j) {
+            if (j < k) {
+                float s[4] = {0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+                for (int i = 0; i < j; ++i) s[i & 3] = fmaf(L[j * LP + i], z[i], s[i & 3]);
+                z[j] = (z[j] - ((s[0] + s[1]) + (s[2] + s[3]))) / L[j * LP + j];
+                asm volatile("" ::: "memory");
+            }
+        }
+    }
+    __syncthreads();                                              // every wave is done with L: L^T takes its place
+    for (int idx = tid; idx < k * LP; idx += kAlsBlock) {         // row p of L^T = column p of L, zeros from column k on
+        const int p = idx / LP, q = idx - p * LP;
+        L[idx] = q < k ? factor[q * k + p] : 0.f;
+    }
+    __syncthreads();
+    if (mask != 0ull) {
+#pragma unroll
+        for (int j = LP - 1; j >= 0; --j) {
+            if (j < k) {                                          // (x_i = z_i = 0 at i >= k, and L^T is zero-filled there: the sum runs to LP)
+                float s[4] = {0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+                for (int i = j + 1; i < LP; ++i) s[i & 3] = fmaf(L[j * LP + i], z[i], s[i & 3]);
+                z[j] = (z[j] - ((s[0] + s[1]) + (s[2] + s[3]))) / L[j * LP + j];
+                asm volatile("" ::: "memory");
+            }
+        }
+    }
+    bool finite = true;
+    double q = 0.0;                                               // sum (x_j - p_j)^2, j ascending, in fp64
+#pragma unroll
+    for (int c = 0; c < KT; ++c) {
+        stage_prior(c);
+        __syncthreads();
+#pragma unroll
+        for (int i = 0; i < 32; ++i) {
+            if (c * 32 + i < k) {
+                finite = finite && fabsf(z[c * 32 + i]) < INFINITY;            // (false for a NaN)
+                const double d = (double)z[c * 32 + i] - (double)st[lane * kAlsColdPitch + i];
+                q += d * d;
+            }
+        }
+        __syncthreads();
+    }
+    const bool write = cold && finite;
+    if (cold) {
+        if (!finite) atomicMin(status, (unsigned long long)r * 4ull + 2ull);   // kind 2 on this row's own solution: left as it is
+        if (row_loss) row_loss[r] = finite ? 0.5 * w_prior * q : 0.0;
+    }
+    const unsigned long long wmask = __ballot(write);
+#pragma unroll
+    for (int c = 0; c < KT; ++c) {
+#pragma unroll
+        for (int i = 0; i < 32; ++i) st[lane * kAlsColdPitch + i] = z[c * 32 + i];
+        __syncthreads();
+        const int col = c * 32 + l31;
+        for (int rr = lane >> 5; rr < TKR_WAVE; rr += 2)
+            if (((wmask >> rr) & 1ull) && col < k) X[(size_t)(r0 + rr) * k + col] = st[rr * kAlsColdPitch + l31];
+        __syncthreads();
+    }
+}
+
+template <int KT>
+static int launch_cold(hipStream_t stream, long long n_x, int k, const float* G, double ridge, float* factor, const int64_t* like_ptr,
+                       long long n_likes, const float* prior, double w_prior, float* X, double* row_loss, unsigned long long* st) {
+    const size_t lds_f = (size_t)AlsSolveLds(k, KT).floats * 4, lds_c = (size_t)als_cold_lds_floats(KT) * 4;
+    auto fk = als_solve_kernel<KT, kAlsFactor>;
+    auto ck = als_cold_kernel<KT>;
+    if (lds_f > 64 * 1024) TKR_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(fk), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_f));
+    if (lds_c > 64 * 1024) TKR_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(ck), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_c));
+    hipLaunchKernelGGL(fk, dim3(1), dim3(kAlsBlock), lds_f, stream, (const float*)nullptr, 0, k, G, (const int64_t*)nullptr, (const int32_t*)nullptr, 0ll,
+                       0.0, 0.0, ridge, (const int32_t*)nullptr, (const float*)nullptr, (float*)nullptr, (double*)nullptr,
+                       (unsigned long long*)nullptr, (const float*)nullptr, 0.0, factor);
+    TKR_LAUNCH_CHECK();
+    hipLaunchKernelGGL(ck, dim3((unsigned)((n_x + kAlsBlock - 1) / kAlsBlock)), dim3(kAlsBlock), lds_c, stream, factor, k, like_ptr, n_likes, n_x, prior,
+                       w_prior, X, row_loss, st);
+    TKR_LAUNCH_CHECK();
+    return TKR_OK;
+}
+
+// what tkr_als_solve_rows and tkr_als_solve_rows_prior share: the checks, the plan of the heavy rows, the per-row launch.  prior ==
+// nullptr is K20: its kernel instantiation, its launches.
+static int als_solve(const float* Y, int32_t n_y, int32_t k, const float* G, const int64_t* like_ptr, const int32_t* like_cols, int64_t n_likes,
+                     int64_t n_x, double w_like, double w_rhs, double ridge, int64_t heavy_from, float* X, double* row_loss, void* workspace,
+                     int64_t workspace_bytes, int64_t* status, void* stream_, const float* prior, double w_prior) {
+    if (!Y || !G || !like_ptr || !X || !status || ((uintptr_t)status & 7) || ((uintptr_t)workspace & 15) || ((uintptr_t)row_loss & 7))
+        return TKR_EINVAL;
+    if (n_likes < 0 || (n_likes > 0 && !like_cols) || n_y < 1 || n_x < 1 || n_x > (int64_t)INT_MAX || heavy_from < 1 || workspace_bytes < 0)
+        return TKR_EINVAL;
+    if (!std::isfinite(w_like) || !std::isfinite(w_rhs) || !std::isfinite(ridge) || ridge < 0.0) return TKR_EINVAL;
+    TKR_CHECK_RC(als_check_k(k));
+    float* factor = nullptr;
+    if (prior) {                                                  // the factor takes the front of the workspace, K20's part follows
+        const int64_t front = als_align(als_factor_floats(k) * 4);
+        if (!workspace || workspace_bytes < front) return TKR_EINVAL;
+        factor = reinterpret_cast<float*>(workspace);
+        workspace = reinterpret_cast<unsigned char*>(workspace) + front;
+        workspace_bytes -= front;
+    }
+    // the heavy rows' part of the workspace: heavy_base [n_x], slab_row [cap], the partials [cap]
+    const int64_t stride = als_partial_stride(k);
+    int64_t cap = 0;
+    if (heavy_from <= n_likes) {                                  // otherwise no row can be heavy
+        if (!workspace || workspace_bytes < als_align(n_x * 4)) return TKR_EINVAL;
+        const int64_t most = n_likes / kAlsSlab + n_likes / heavy_from + 1;       // slabs the heavy rows can have together
+        const int64_t room = workspace_bytes - als_align(n_x * 4);
+        cap = std::min<int64_t>(std::min<int64_t>(most, kAlsMaxSlabs), room / (stride * 4 + 4));
+        while (cap > 0 && als_align(cap * 4) + als_align(cap * stride * 4) > room) --cap;
+    }
+    hipStream_t stream = (hipStream_t)stream_;
+    unsigned long long* st = reinterpret_cast<unsigned long long*>(status);
+    TKR_CHECK(hipMemsetAsync(st, 0xff, sizeof(unsigned long long), stream));          // -1: nothing refused
+    const int KT = (k + 31) / 32;
+    int32_t* heavy_base = nullptr;
+    float* partial = nullptr;
+    if (cap > 0) {
+        unsigned char* ws = reinterpret_cast<unsigned char*>(workspace);
+        heavy_base = reinterpret_cast<int32_t*>(ws);
+        int32_t* slab_row = reinterpret_cast<int32_t*>(ws + als_align(n_x * 4));
+        partial = reinterpret_cast<float*>(ws + als_align(n_x * 4) + als_align(cap * 4));
+        TKR_CHECK(hipMemsetAsync(slab_row, 0xff, (size_t)cap * 4, stream));           // -1: a slab nobody has
+        hipLaunchKernelGGL(als_plan_kernel, dim3(1), dim3(kAlsPlanBlock), 0, stream, like_ptr, (long long)n_likes, (long long)n_x,
+                           (long long)heavy_from, (int)cap, heavy_base, slab_row);
+        TKR_LAUNCH_CHECK();
+        TKR_CHECK_RC(launch_slabs_kt(KT, stream, cap, Y, n_y, k, like_cols, n_likes, like_ptr, slab_row, heavy_base, partial, st));
+    }
+#define TKR_ALS_SOLVE(KTT)                                                                                                                      \
+    if (!prior)                                                                                                                                 \
+        return launch_solve<KTT, false>(stream, n_x, Y, n_y, k, G, like_ptr, like_cols, (long long)n_likes, w_like, w_rhs, ridge, heavy_base,   \
+                                        partial, X, row_loss, st, nullptr, 0.0);                                                               \
+    TKR_CHECK_RC((launch_solve<KTT, true>(stream, n_x, Y, n_y, k, G, like_ptr, like_cols, (long long)n_likes, w_like, w_rhs, ridge, heavy_base, \
+                                          partial, X, row_loss, st, prior, w_prior)));                                                         \
+    return launch_cold<KTT>(stream, n_x, k, G, ridge, factor, like_ptr, (long long)n_likes, prior, w_prior, X, row_loss, st)
+    switch (KT) {
+        case 1: TKR_ALS_SOLVE(1);
+        case 2: TKR_ALS_SOLVE(2);
+        case 3: TKR_ALS_SOLVE(3);
+        default: TKR_ALS_SOLVE(4);
+    }
+#undef TKR_ALS_SOLVE
 }
 
 }  // namespace tkr
@@ -537,47 +801,20 @@ extern "C" int tkr_als_gram(const float* Y, int32_t n, int32_t k, const int32_t*
 extern "C" int tkr_als_solve_rows(const float* Y, int32_t n_y, int32_t k, const float* G, const int64_t* like_ptr, const int32_t* like_cols,
                                   int64_t n_likes, int64_t n_x, double w_like, double w_rhs, double ridge, int64_t heavy_from, float* X,
                                   double* row_loss, void* workspace, int64_t workspace_bytes, int64_t* status, void* stream_) {
-    if (!Y || !G || !like_ptr || !X || !status || ((uintptr_t)status & 7) || ((uintptr_t)workspace & 15) || ((uintptr_t)row_loss & 7))
-        return TKR_EINVAL;
-    if (n_likes < 0 || (n_likes > 0 && !like_cols) || n_y < 1 || n_x < 1 || n_x > (int64_t)INT_MAX || heavy_from < 1 || workspace_bytes < 0)
-        return TKR_EINVAL;
-    if (!std::isfinite(w_like) || !std::isfinite(w_rhs) || !std::isfinite(ridge) || ridge < 0.0) return TKR_EINVAL;
-    TKR_CHECK_RC(tkr::als_check_k(k));
-    // the heavy rows' part of the workspace: heavy_base [n_x], slab_row [cap], the partials [cap]
-    const int64_t stride = tkr::als_partial_stride(k);
-    int64_t cap = 0;
-    if (heavy_from <= n_likes) {                                  // otherwise no row can be heavy
-        if (!workspace || workspace_bytes < tkr::als_align(n_x * 4)) return TKR_EINVAL;
-        const int64_t most = n_likes / tkr::kAlsSlab + n_likes / heavy_from + 1;       // slabs the heavy rows can have together
-        const int64_t room = workspace_bytes - tkr::als_align(n_x * 4);
-        cap = std::min<int64_t>(std::min<int64_t>(most, tkr::kAlsMaxSlabs), room / (stride * 4 + 4));
-        while (cap > 0 && tkr::als_align(cap * 4) + tkr::als_align(cap * stride * 4) > room) --cap;
-    }
-    hipStream_t stream = (hipStream_t)stream_;
-    unsigned long long* st = reinterpret_cast<unsigned long long*>(status);
-    TKR_CHECK(hipMemsetAsync(st, 0xff, sizeof(unsigned long long), stream));          // -1: nothing refused
-    const int KT = (k + 31) / 32;
-    int32_t* heavy_base = nullptr;
-    float* partial = nullptr;
-    if (cap > 0) {
-        unsigned char* ws = reinterpret_cast<unsigned char*>(workspace);
-        heavy_base = reinterpret_cast<int32_t*>(ws);
-        int32_t* slab_row = reinterpret_cast<int32_t*>(ws + tkr::als_align(n_x * 4));
-        partial = reinterpret_cast<float*>(ws + tkr::als_align(n_x * 4) + tkr::als_align(cap * 4));
-        TKR_CHECK(hipMemsetAsync(slab_row, 0xff, (size_t)cap * 4, stream));           // -1: a slab nobody has
-        hipLaunchKernelGGL(tkr::als_plan_kernel, dim3(1), dim3(tkr::kAlsPlanBlock), 0, stream, like_ptr, (long long)n_likes, (long long)n_x,
-                           (long long)heavy_from, (int)cap, heavy_base, slab_row);
-        TKR_LAUNCH_CHECK();
-        TKR_CHECK_RC(tkr::launch_slabs_kt(KT, stream, cap, Y, n_y, k, like_cols, n_likes, like_ptr, slab_row, heavy_base, partial, st));
-    }
-#define TKR_ALS_SOLVE(KTT)                                                                                                               \
-    return tkr::launch_solve<KTT>(stream, n_x, Y, n_y, k, G, like_ptr, like_cols, (long long)n_likes, w_like, w_rhs, ridge, heavy_base, partial, \
-                                  X, row_loss, st)
-    switch (KT) {
-        case 1: TKR_ALS_SOLVE(1);
-        case 2: TKR_ALS_SOLVE(2);
-        case 3: TKR_ALS_SOLVE(3);
-        default: TKR_ALS_SOLVE(4);
-    }
-#undef TKR_ALS_SOLVE
+    return tkr::als_solve(Y, n_y, k, G, like_ptr, like_cols, n_likes, n_x, w_like, w_rhs, ridge, heavy_from, X, row_loss, workspace, workspace_bytes,
+                          status, stream_, nullptr, 0.0);
+}
+
+extern "C" int64_t tkr_als_prior_workspace_bytes(int64_t n_x, int32_t k, int64_t n_slabs) {
+    const int64_t base = tkr_als_workspace_bytes(n_x, k, n_slabs);
+    return base < 0 ? base : base + tkr::als_align(tkr::als_factor_floats(k) * 4);
+}
+
+extern "C" int tkr_als_solve_rows_prior(const float* Y, int32_t n_y, int32_t k, const float* G, const int64_t* like_ptr, const int32_t* like_cols,
+                                        int64_t n_likes, int64_t n_x, double w_like, double w_rhs, double ridge, int64_t heavy_from, float* X,
+                                        double* row_loss, const float* prior, double w_prior, void* workspace, int64_t workspace_bytes,
+                                        int64_t* status, void* stream_) {
+    if (!prior || ((uintptr_t)prior & 3) || !std::isfinite(w_prior) || w_prior < 0.0) return TKR_EINVAL;
+    return tkr::als_solve(Y, n_y, k, G, like_ptr, like_cols, n_likes, n_x, w_like, w_rhs, ridge, heavy_from, X, row_loss, workspace, workspace_bytes,
+                          status, stream_, prior, w_prior);
 }

@@ -90,9 +90,10 @@ EXPORTS = ('tkr_version', 'tkr_plan_team', 'tkr_plan_max_blocks', 'tkr_sample_pl
            'tkr_matrix_tokens_host', 'tkr_group_count_dev', 'tkr_group_emit_dev', 'tkr_last_line_of_user_dev', 'tkr_compact_rows_count_dev',
            'tkr_compact_rows_emit_dev', 'tkr_fusion_features', 'tkr_fusion_sgd', 'tkr_fusion_user_weights',
            'tkr_mmr_select', 'tkr_list_pair_sums', 'tkr_line_metrics', 'tkr_bootstrap_sums', 'tkr_nearest_anchors', 'tkr_als_gram',
-           'tkr_als_solve_rows')
+           'tkr_als_solve_rows', 'tkr_als_solve_rows_prior')
 EXPORTS_I64 = ('tkr_vbpr_workspace_floats', 'tkr_vbpr_colplan_lds_bytes', 'tkr_topk_workspace_bytes_for', 'tkr_topk_workspace_bytes', 'tkr_plan_workspace_bytes', 'tkr_like_ranks_workspace_bytes',
-               'tkr_parse_dev_workspace_bytes', 'tkr_idtable_slots', 'tkr_scan_dev_workspace_bytes', 'tkr_als_workspace_bytes')
+               'tkr_parse_dev_workspace_bytes', 'tkr_idtable_slots', 'tkr_scan_dev_workspace_bytes', 'tkr_als_workspace_bytes',
+               'tkr_als_prior_workspace_bytes')
 
 
 def lib():
@@ -1350,6 +1351,50 @@ def als_solve_rows(Y, G, like_ptr, like_cols, X, *, w_like, w_rhs, ridge, heavy_
     _call('tkr_als_solve_rows', Y, _p(Y), C.c_int32(n_y), C.c_int32(k), _p(G), _p(like_ptr), _p(like_cols) if n_likes else C.c_void_p(0),
           C.c_int64(n_likes), C.c_int64(n_x), C.c_double(w_like), C.c_double(w_rhs), C.c_double(ridge), C.c_int64(heavy_from), _p(X), _p(loss),
           _p(workspace), C.c_int64(workspace.numel() * workspace.element_size()), _p(status))
+    if not check:
+        return loss, status
+    word = int(status.item())
+    if word != -1:
+        raise AlsRefused(what, word)
+    return loss
+
+
+def als_prior_workspace_bytes(n_x, k, n_slabs):
+    need = int(lib().tkr_als_prior_workspace_bytes(C.c_int64(n_x), C.c_int32(k), C.c_int64(n_slabs)))
+    if need < 0:
+        raise TkrError('tkr_als_prior_workspace_bytes(%d, %d, %d) failed: tkr error %d' % (n_x, k, n_slabs, need))
+    return need
+
+
+def als_solve_rows_prior(Y, G, like_ptr, like_cols, X, prior, *, w_like, w_rhs, w_prior, ridge, heavy_from=None, want_loss=False, workspace=None,
+                         heavy_slabs=None, check=True):
+    """K21, in place on X fp32 [n_x, k]: als_solve_rows with w_prior * prior[r] added to row r's right-hand side and 1/2 w_prior
+    |x - prior[r]|^2 to its loss, and the rows WITHOUT likes solved too: X[r] = (G + ridge I)^-1 (w_prior prior[r]), against one factor
+    computed once per call (include/tkr.h tkr_als_solve_rows_prior).  prior: fp32 [n_x, k] on X's device.  The other arguments, the
+    result, AlsRefused and check=False as als_solve_rows"""
+    what = 'als_solve_rows_prior'
+    n_y, k = _als_table(what, 'Y', Y)
+    n_x, _ = _als_table(what, 'X', X, k)
+    _als_table(what, 'G', G, k)
+    _als_table(what, 'prior', prior, k)
+    if G.shape[0] != k or X.device != Y.device or G.device != Y.device or prior.device != Y.device or prior.shape[0] != n_x:
+        raise TkrError('%s: G must be [k, k], prior [n_x, k], and Y, G, X and prior on one GPU' % what)
+    _group_tensor(what, 'like_ptr', like_ptr, torch.int64, Y.device)
+    _group_tensor(what, 'like_cols', like_cols, torch.int32, Y.device)
+    if like_ptr.numel() != n_x + 1:
+        raise ValueError('%s: like_ptr must hold n_x + 1 = %d entries, not %d' % (what, n_x + 1, like_ptr.numel()))
+    heavy_from = ALS_HEAVY_FROM if heavy_from is None else int(heavy_from)
+    n_likes = int(like_cols.numel())
+    slabs = 0
+    if heavy_from <= n_likes:
+        slabs = als_heavy_slabs(like_ptr, heavy_from) if heavy_slabs is None else heavy_slabs
+    need = als_prior_workspace_bytes(n_x if heavy_from <= n_likes else 0, k, slabs)
+    workspace = _als_workspace(workspace, need, Y.device)
+    loss = torch.empty(n_x, dtype=torch.float64, device=Y.device) if want_loss else None
+    status = torch.empty(1, dtype=torch.int64, device=Y.device)
+    _call('tkr_als_solve_rows_prior', Y, _p(Y), C.c_int32(n_y), C.c_int32(k), _p(G), _p(like_ptr), _p(like_cols) if n_likes else C.c_void_p(0),
+          C.c_int64(n_likes), C.c_int64(n_x), C.c_double(w_like), C.c_double(w_rhs), C.c_double(ridge), C.c_int64(heavy_from), _p(X), _p(loss),
+          _p(prior), C.c_double(w_prior), _p(workspace), C.c_int64(workspace.numel() * workspace.element_size()), _p(status))
     if not check:
         return loss, status
     word = int(status.item())
