@@ -31,7 +31,7 @@
 extern "C" {
 #endif
 
-#define TKR_VERSION 120 /* (additions that change no existing entry point keep the number: K10 tkr_bpr_foldin_items, K11 tkr_ratings_*_dev, K12 tkr_rank_candidates, K13 tkr_lists_format_* / tkr_matrix_format_*, K15 tkr_group_*_dev / tkr_last_line_of_user_dev / tkr_compact_rows_*_dev, K16 tkr_fusion_*, K17 tkr_mmr_select / tkr_list_pair_sums, K21 tkr_als_solve_rows_prior / tkr_als_prior_workspace_bytes.) 0.1.20: K9 tkr_bpr_foldin (user vectors for new histories against frozen item factors; csrc/foldin.hip). 0.1.19: K8 tkr_like_ranks + tkr_like_ranks_workspace_bytes (filtered rank of every liked test column; csrc/like_ranks.hip). 0.1.18: K4 second form of bound-and-refine (csrc/topk_refine.hip; tkr_topk_workspace_bytes_for grows by the pieces' packed lists), any k (bpr_wide_kernel, score_topk_wide_kernel), tkr_lab_build; tkr_topk_set_finish is gone, tkr_topk_set_math(0) and tkr_vbpr_set_pairs(1 | 2) need the lab library. 0.1.17: tkr_vbpr_set_pairs (tkr_vbpr_workspace_floats + 64). 0.1.16: tkr_topk_set_finish (larger tkr_topk_workspace_bytes), tkr_bpr_own_plan_run plans inside the step's launch. 0.1.15: tkr_bpr_own_owners_shared; tkr_bpr_run takes `rec` non-const. 0.1.14: per-task loss sums instead of atomics on loss_out (larger tkr_vbpr_workspace_floats; K2 writes word 15 of its records). 0.1.13: tkr_bpr_own_plan_run, K4 to k = 768. 0.1.12: tkr_bpr_own_run_between. 0.1.11: K2o (tkr_sample_plan_owned, tkr_bpr_own_run: item rows owned by one workgroup each, resident in its LDS); prec[5] = last batch of the call that updated the row. 0.1.10: tkr_topk_workspace_bytes_for (K4 stages pre-converted fp16 tiles). 0.1.9: tkr_vbpr_colplan + tkr_vbpr_run_cols (VBPR in three launches per batch). 0.1.8: tkr_sync_flow_* (exchange of the granule tables). 0.1.7: K4 bound-and-refine arithmetic (tkr_topk_set_math(2), the default; larger tkr_topk_workspace_bytes); K2f leaves its ticket words zero. 0.1.6: K2f persistent dataflow step, tkr_plan_rollback, batches above 8192 */
+#define TKR_VERSION 120 /* (additions that change no existing entry point keep the number: K10 tkr_bpr_foldin_items, K11 tkr_ratings_*_dev, K12 tkr_rank_candidates, K13 tkr_lists_format_* / tkr_matrix_format_*, K15 tkr_group_*_dev / tkr_last_line_of_user_dev / tkr_compact_rows_*_dev, K16 tkr_fusion_*, K17 tkr_mmr_select / tkr_list_pair_sums, K21 tkr_als_solve_rows_prior / tkr_als_prior_workspace_bytes, K22 tkr_mlp_forward / tkr_mlp_fit / tkr_mlp_workspace_bytes.) 0.1.20: K9 tkr_bpr_foldin (user vectors for new histories against frozen item factors; csrc/foldin.hip). 0.1.19: K8 tkr_like_ranks + tkr_like_ranks_workspace_bytes (filtered rank of every liked test column; csrc/like_ranks.hip). 0.1.18: K4 second form of bound-and-refine (csrc/topk_refine.hip; tkr_topk_workspace_bytes_for grows by the pieces' packed lists), any k (bpr_wide_kernel, score_topk_wide_kernel), tkr_lab_build; tkr_topk_set_finish is gone, tkr_topk_set_math(0) and tkr_vbpr_set_pairs(1 | 2) need the lab library. 0.1.17: tkr_vbpr_set_pairs (tkr_vbpr_workspace_floats + 64). 0.1.16: tkr_topk_set_finish (larger tkr_topk_workspace_bytes), tkr_bpr_own_plan_run plans inside the step's launch. 0.1.15: tkr_bpr_own_owners_shared; tkr_bpr_run takes `rec` non-const. 0.1.14: per-task loss sums instead of atomics on loss_out (larger tkr_vbpr_workspace_floats; K2 writes word 15 of its records). 0.1.13: tkr_bpr_own_plan_run, K4 to k = 768. 0.1.12: tkr_bpr_own_run_between. 0.1.11: K2o (tkr_sample_plan_owned, tkr_bpr_own_run: item rows owned by one workgroup each, resident in its LDS); prec[5] = last batch of the call that updated the row. 0.1.10: tkr_topk_workspace_bytes_for (K4 stages pre-converted fp16 tiles). 0.1.9: tkr_vbpr_colplan + tkr_vbpr_run_cols (VBPR in three launches per batch). 0.1.8: tkr_sync_flow_* (exchange of the granule tables). 0.1.7: K4 bound-and-refine arithmetic (tkr_topk_set_math(2), the default; larger tkr_topk_workspace_bytes); K2f leaves its ticket words zero. 0.1.6: K2f persistent dataflow step, tkr_plan_rollback, batches above 8192 */
 #define TKR_OK 0
 #define TKR_E_INVAL (-1)
 #define TKR_E_UNSUPPORTED (-2)
@@ -953,6 +953,61 @@ int tkr_als_solve_rows_prior(const float* Y, int32_t n_y, int32_t k, const float
                              int64_t n_likes, int64_t n_x, double w_like, double w_rhs, double ridge, int64_t heavy_from, float* X,
                              double* row_loss, const float* prior, double w_prior, void* workspace, int64_t workspace_bytes, int64_t* status,
                              void* stream);
+
+/* ---- K22: a dense MLP content encoder, applied and trained (csrc/mlp.hip) ----------------------------------------------------------------
+ * Replaces the TensorFlow graph of the reference's single/mlp.py:14-40 (tf.layers.dense, RMSPropOptimizer.minimize, the sess.run of out
+ * and fit), the encoder of single/dpm.py (top-k-rec_amd/als.py MLP and DPM).
+ *
+ *   tkr_mlp_net         n_layers dense layers, 1 <= n_layers <= TKR_MLP_MAX_LAYERS; width[0] = d .. width[n_layers] = k, every width >= 1
+ *                       (no tile-multiple requirement; above 2^21: TKR_E_UNSUPPORTED).  Layer l: W[l] fp32 [width[l], width[l + 1]] row-major
+ *                       (the layout of a TF dense kernel), bias[l] [width[l + 1]], msW[l] and msb[l] the RMSProp slots of the same shapes
+ *                       (tkr_mlp_forward does not look at the slots: they may be NULL there).  Every layer but the last has the sigmoid
+ *                       s = 1 / (1 + expf(-x)), the last is linear.
+ *   tkr_mlp_forward     out fp32 [m, k] = the network applied to X[rows[t]], t < m; X fp32 [n, d]; rows int32 [m], or NULL: the rows
+ *                       0 .. m - 1 (m <= n).  Per layer two launches: the products on the exact-fp32 MFMA (v_mfma_f32_32x32x2_f32: per
+ *                       element one fp32 fma chain in input order from +0.0), the contraction cut into slabs of TKR_MLP_SLAB inputs, one
+ *                       workgroup per 64 x 64 tile of the output and slab, each slab's sum an fp32 partial in the workspace; then the
+ *                       partials are added in ascending slab order in fp64 and rounded once, the bias is added in fp32 and the activation
+ *                       applied.  Rows are taken TKR_MLP_FORWARD_CHUNK at a time; a row's bits do not depend on m or on its place.
+ *   tkr_mlp_fit         one epoch of mlp.py:32-40: batch t takes the rows order[t * batch .. min((t + 1) * batch, m)) of X [n, d] and
+ *                       Y fp32 [n, k] (the last batch may be short), 1 <= batch <= TKR_MLP_MAX_BATCH.  Per batch, every gradient from the
+ *                       parameters as they were before the batch (as TF computes them):
+ *                         forward through every layer as above, the activations kept;
+ *                         batch_loss[t] (float64) = 1/2 sum (y - F)^2, differences and sum in fp64;
+ *                         delta_L = F - Y, delta_{l-1} = (delta_l W_l^T) * (h (1 - h)) (the product slabbed over the layer's outputs, as
+ *                         above); no delta for the input;
+ *                         per layer ONE launch: a workgroup owns a 64 x 64 tile of W_l, forms g[i, j] = sum_b A[b, i] delta[b, j] on the
+ *                         MFMA (one fma chain per element in batch order from +0.0; A = the layer's input) and applies dense RMSProp in
+ *                         registers -- rho = 0.9, eps = 1e-10 inside the root, momentum 0, every operation rounded on its own in fp32:
+ *                           q = g * g;  ms' = ms + (q - ms) * fl(1 - rho);  w' = w - (lr * g) / sqrt(ms' + eps)
+ *                         -- W and its slot are read once and stored once, the gradient never exists in memory.  The bias gradient is
+ *                         the same chain with A = 1.
+ *                       Everything is enqueued on `stream`; nothing synchronises.  lr is rounded to fp32 by the caller.
+ *   tkr_mlp_workspace_bytes   what both need for a net of this shape (only n_layers and width are looked at): m rows forwarded, batches
+ *                       of `batch` fitted (batch = 0: forward only); a multiple of 16, or TKR_E_INVAL.
+ * The input is not trusted: a pre-pass checks rows / order.  status: -1, or 4 * t + 1 for the smallest t whose index lies outside [0, n);
+ * then NO parameter, slot, output or batch_loss is written by the call (every kernel reads the status word first).  m = 0 writes status -1
+ * and nothing else.  Arguments are checked before any device access and before any launch (TKR_E_INVAL): a null net / X / Y / out / status
+ * (order, batch_loss, workspace: with m > 0), a pointer off its alignment (floats 4, status and batch_loss 8, workspace 16), n_layers or a
+ * width out of range, a null parameter (fit: or slot), n < 1, m < 0, rows NULL with m > n, batch < 1, lr negative or not finite, a workspace
+ * too small; batch > TKR_MLP_MAX_BATCH: TKR_E_UNSUPPORTED.  Deterministic: two calls give the same bits; no float atomics. */
+#define TKR_MLP_MAX_LAYERS 5
+#define TKR_MLP_MAX_BATCH 256
+#define TKR_MLP_SLAB 512          /* inputs of a layer one workgroup sums */
+#define TKR_MLP_FORWARD_CHUNK 256 /* rows tkr_mlp_forward takes at a time */
+typedef struct tkr_mlp_net {
+    int32_t n_layers;
+    int32_t width[TKR_MLP_MAX_LAYERS + 1];
+    float* W[TKR_MLP_MAX_LAYERS];
+    float* bias[TKR_MLP_MAX_LAYERS];
+    float* msW[TKR_MLP_MAX_LAYERS];
+    float* msb[TKR_MLP_MAX_LAYERS];
+} tkr_mlp_net;
+int64_t tkr_mlp_workspace_bytes(const tkr_mlp_net* net, int64_t m, int32_t batch);
+int tkr_mlp_forward(const tkr_mlp_net* net, const float* X, int32_t n, const int32_t* rows, int64_t m, float* out, void* workspace,
+                    int64_t workspace_bytes, int64_t* status, void* stream);
+int tkr_mlp_fit(const tkr_mlp_net* net, const float* X, int32_t n, const float* Y, const int32_t* order, int64_t m, int32_t batch, float lr,
+                double* batch_loss, void* workspace, int64_t workspace_bytes, int64_t* status, void* stream);
 
 #ifdef __cplusplus
 }

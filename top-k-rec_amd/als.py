@@ -1,5 +1,6 @@
-"""WMF and CER -- weighted matrix factorisation for implicit feedback by alternating least squares, and its content-aware form
-(collaborative embedding regression), trained on MI355X (K20 and K21, csrc/als.hip).
+"""WMF, CER and DPM -- weighted matrix factorisation for implicit feedback by alternating least squares, and its two content-aware
+forms (collaborative embedding regression: a linear map of the item's features; DPM: an MLP on them), trained on MI355X (K20 and K21,
+csrc/als.hip; K22, csrc/mlp.hip).
 
     from als import WMF
     model = WMF(k=50)
@@ -30,6 +31,17 @@ regression for E behind it:
 
     every item j:  (G_U + (a - b) sum_{u in L_j} u u^T + lv I) v = a sum_{u in L_j} u + lv Fe_j,  Fe = F E;  an item without likes too
     E = (lv F^T F + le I)^-1 (lv F^T V)
+
+``DPM`` (single/dpm.py:10-76) puts ``MLP`` (single/mlp.py), a dense network d -> 2000 -> 1000 -> k with sigmoid hidden layers, where CER
+has E: the prior of item j is encoder(f_j), and after every alternation the encoder takes one epoch of mini-batch RMSProp towards the
+item table:
+
+    model = DPM(k=50, d=20000)
+    model.load_training_data('data/uid', 'data/vid', 'data/f0tr.txt')
+    model.load_content_data('data/meta.pkl', 'data/vid')
+    model.train(MLP, max_iter=200)
+    model.export_embeddings('embed/dpm')                     # final-U.dat, final-V.dat, mlp.npz (the encoder, exact fp32)
+    rows = model.embed_items(new_features)
 """
 from __future__ import annotations
 
@@ -337,3 +349,295 @@ class CER(WMF):
                 raise ValueError('CER.import_model: %s holds a matrix of shape %s, the model needs (d, k) = (%d, %d)'
                                  % (source, np.shape(E), self.d, self.k))
             self.E = E
+
+
+# ---- MLP and DPM (K22) ----------------------------------------------------------------------------------------------------------------------
+MLP_MAX_HIDDEN = tkr_hip.MLP_MAX_LAYERS - 1
+MLP_MAX_BATCH = tkr_hip.MLP_MAX_BATCH
+_MLP_PARTS = ('W', 'bias', 'msW', 'msb')
+
+
+def _check_batch(who, batch_size):
+    if not isinstance(batch_size, (int, np.integer)) or not 1 <= batch_size <= MLP_MAX_BATCH:
+        raise ValueError('%s: batch_size = %r, 1 <= batch_size <= %d is supported (TKR_MLP_MAX_BATCH)' % (who, batch_size, MLP_MAX_BATCH))
+
+
+def _cuda(device, who):
+    device = torch.device(foldin._device(device, who))
+    return torch.device('cuda', torch.cuda.current_device()) if device.index is None else device
+
+
+def epoch_order(seed, epoch, n):
+    """the row order of MLP.fit's epoch `epoch` (counted from 0 over the life of the encoder, saved with it)"""
+    return np.random.Generator(np.random.PCG64(np.random.SeedSequence([int(seed), int(epoch)]))).permutation(int(n)).astype(np.int32)
+
+
+class MLP:
+    """the content encoder of single/mlp.py:7-43 (d -> hidden layers with a sigmoid -> k, linear), trained by dense RMSProp in
+    mini-batches; forward, gradients and the fused update are K22 (csrc/mlp.hip).  The reference's class cannot be instantiated
+    (encoder.py:23 names the abstract method `pertrain`, mlp.py:42 defines `pretrain`: both names work here) and sizes the buffer of
+    out() by the columns of X (mlp.py:26: by its rows here); `lbd` is accepted and unused, as there.
+
+    The start is tf.layers.dense's: W Glorot-uniform, (2 r - 1) * fp32(sqrt(6 / (in + out))) in fp32 with r = Generator(PCG64(seed))
+    .random(fp32) drawn layer by layer, biases 0; RMSProp slots 1.  fit() draws the order of epoch e as epoch_order(seed, e, n): a
+    saved encoder resumes on the same stream.  Parameters and slots live on the device between calls."""
+
+    def __init__(self, k: int, d: int, lr: float = 1e-4, lbd: float = 1e-4, hidden_layers=(2000, 1000), seed=None) -> None:
+        hidden = list(hidden_layers)
+        if not isinstance(k, (int, np.integer)) or not 1 <= k <= MAX_K:
+            raise ValueError('MLP: k = %r, 1 <= k <= %d is supported (the ALS half-steps the encoder feeds)' % (k, MAX_K))
+        if not isinstance(d, (int, np.integer)) or d < 1:
+            raise ValueError('MLP: d = %r, the width of the content features, must be a positive integer' % (d,))
+        if len(hidden) > MLP_MAX_HIDDEN:
+            raise ValueError('MLP: %d hidden layers, at most %d are supported (TKR_MLP_MAX_LAYERS)' % (len(hidden), MLP_MAX_HIDDEN))
+        if any(not isinstance(h, (int, np.integer)) or h < 1 for h in hidden):
+            raise ValueError('MLP: hidden_layers = %r, every width must be a positive integer' % (hidden,))
+        if not (np.isfinite(lr) and lr >= 0):
+            raise ValueError('MLP: lr = %r must be finite and not negative' % (lr,))
+        if seed is not None and not 0 <= int(seed) < 2 ** 63:
+            raise ValueError('MLP: seed = %r, 0 <= seed < 2^63' % (seed,))
+        self.k, self.d, self.lr, self.lbd = int(k), int(d), float(lr), float(lbd)
+        self.hidden_layers = tuple(int(h) for h in hidden)
+        self.seed = int(np.random.SeedSequence().generate_state(1, np.uint64)[0] >> 1) if seed is None else int(seed)
+        self.epochs_done = 0
+        rng = np.random.Generator(np.random.PCG64(self.seed))
+        self._host, self._dev, self._net, self._ws = [], None, None, None
+        for fan_in, fan_out in zip(self.widths, self.widths[1:]):
+            limit = np.float32(np.sqrt(6.0 / (fan_in + fan_out)))
+            W = (np.float32(2) * rng.random((fan_in, fan_out), dtype=np.float32) - np.float32(1)) * limit
+            self._host.append(dict(W=W.astype(np.float32), bias=np.zeros(fan_out, np.float32), msW=np.ones((fan_in, fan_out), np.float32),
+                                   msb=np.ones(fan_out, np.float32)))
+
+    @property
+    def widths(self):
+        return (self.d,) + self.hidden_layers + (self.k,)
+
+    # ------------------------------------------------------------------ state
+    def _layers_host(self):
+        if self._dev is None:
+            return self._host
+        return [{name: t.cpu().numpy() for name, t in layer.items()} for layer in self._dev]
+
+    def state(self):
+        """-> a dict of NumPy arrays: the parameters and slots (exact fp32), the widths, lr, seed and epochs_done"""
+        out = dict(widths=np.asarray(self.widths, dtype=np.int64), lr=np.float64(self.lr), lbd=np.float64(self.lbd), seed=np.int64(self.seed),
+                   epochs_done=np.int64(self.epochs_done))
+        for l, layer in enumerate(self._layers_host()):
+            for name in _MLP_PARTS:
+                out['%s%d' % (name, l)] = np.array(layer[name], dtype=np.float32)
+        return out
+
+    def load_state(self, state):
+        widths = [int(w) for w in np.asarray(state['widths']).reshape(-1)]
+        if len(widths) < 2 or widths[0] != self.d or widths[-1] != self.k:
+            raise ValueError('MLP.load_state: the state is a net of widths %s, this encoder maps d = %d to k = %d' % (widths, self.d, self.k))
+        if len(widths) - 2 > MLP_MAX_HIDDEN or min(widths) < 1:
+            raise ValueError('MLP.load_state: widths %s' % (widths,))
+        host = []
+        for l, (fan_in, fan_out) in enumerate(zip(widths, widths[1:])):
+            layer = {}
+            for name, shape in (('W', (fan_in, fan_out)), ('bias', (fan_out,)), ('msW', (fan_in, fan_out)), ('msb', (fan_out,))):
+                a = np.asarray(state['%s%d' % (name, l)])
+                if a.shape != shape or a.dtype != np.float32:
+                    raise ValueError('MLP.load_state: %s%d is %s %s, the net needs float32 %s' % (name, l, a.dtype, a.shape, shape))
+                layer[name] = np.array(a)
+            host.append(layer)
+        self.hidden_layers = tuple(widths[1:-1])
+        self.lr, self.lbd = float(state['lr']), float(state['lbd'])
+        self.seed, self.epochs_done = int(state['seed']), int(state['epochs_done'])
+        self._host, self._dev, self._net, self._ws = host, None, None, None
+
+    def _on(self, device):
+        if self._dev is None or self._dev[0]['W'].device != device:
+            host = self._layers_host()
+            self._dev = [{name: foldin._upload(np.ascontiguousarray(layer[name], dtype=np.float32), device) for name in _MLP_PARTS} for layer in host]
+            self._host, self._ws = None, None
+            self._net = tkr_hip.mlp_net(self._dev)
+        return self._net
+
+    def _room(self, need, device):
+        if self._ws is None or self._ws.device != device or self._ws.numel() * 8 < need:
+            self._ws = torch.empty(max(need, 16) // 8 + 1, dtype=torch.int64, device=device)
+        return self._ws
+
+    @staticmethod
+    def _table(who, name, X, width):
+        """a host array or a device tensor, checked -> a float32 [n, width] array, or the tensor made contiguous"""
+        if isinstance(X, torch.Tensor):
+            if X.dtype != torch.float32 or X.dim() != 2 or X.shape[1] != width or not X.is_cuda:
+                raise ValueError('%s: %s is a %s tensor of shape %s on %s, the encoder needs float32 (n, %d) on the GPU'
+                                 % (who, name, X.dtype, tuple(X.shape), X.device, width))
+            return X.contiguous()
+        X = np.ascontiguousarray(X, dtype=np.float32)
+        if X.ndim != 2 or X.shape[1] != width:
+            raise ValueError('%s: %s has shape %s, the encoder needs (n, %d)' % (who, name, X.shape, width))
+        return X
+
+    # ------------------------------------------------------------------ mlp.py:24-43
+    def out(self, X, device=None):
+        """fp32 [rows of X, k] = the network applied to every row of X (fp32 [n, d]): a NumPy array for a host array, a tensor on X's
+        device for a device tensor"""
+        X = self._table('MLP.out', 'X', X, self.d)
+        from_host = not isinstance(X, torch.Tensor)
+        if from_host:
+            X = foldin._upload(X, _cuda(device, 'MLP.out'))
+        if X.shape[0] == 0:
+            F = torch.zeros((0, self.k), dtype=torch.float32, device=X.device)
+        else:
+            net = self._on(X.device)
+            F = tkr_hip.mlp_forward(net, X, workspace=self._room(tkr_hip.mlp_workspace_bytes(net, int(X.shape[0])), X.device))
+        return F.cpu().numpy() if from_host else F
+
+    def _fit_device(self, X, Y, batch_size, order=None):
+        """one epoch on device tensors -> (batch_loss float64 [batches], status int64 [1]) on the device; nothing is read back"""
+        n = int(X.shape[0])
+        if order is None:
+            order = epoch_order(self.seed, self.epochs_done, n)
+        if not isinstance(order, torch.Tensor):
+            order = foldin._upload(np.ascontiguousarray(np.asarray(order).reshape(-1), dtype=np.int32), X.device)
+        net = self._on(X.device)
+        ws = self._room(tkr_hip.mlp_workspace_bytes(net, 0, int(batch_size)), X.device)
+        self.epochs_done += 1
+        return tkr_hip.mlp_fit(net, X, Y, order, int(batch_size), np.float32(self.lr), workspace=ws, check=False)
+
+    def fit(self, X, Y, batch_size: int = 64, order=None, device=None) -> float:
+        """one epoch of mlp.py:32-40 over the rows of X (fp32 [n, d]) and Y (fp32 [n, k]), host arrays or device tensors, in the order
+        `order` (None: epoch_order(seed, epochs_done, n)) -> the sum of the batch objectives 1/2 sum (y - F)^2, each taken before its
+        batch's step"""
+        _check_batch('MLP.fit', batch_size)
+        X, Y = self._table('MLP.fit', 'X', X, self.d), self._table('MLP.fit', 'Y', Y, self.k)
+        if Y.shape[0] != X.shape[0] or X.shape[0] < 1:
+            raise ValueError('MLP.fit: X has %d rows and Y %d; both need the same number, at least one' % (X.shape[0], Y.shape[0]))
+        on = [t.device for t in (X, Y) if isinstance(t, torch.Tensor)]
+        device = on[0] if on else _cuda(device, 'MLP.fit')
+        X, Y = (t.to(device) if isinstance(t, torch.Tensor) else foldin._upload(t, device) for t in (X, Y))
+        loss, status = self._fit_device(X, Y, batch_size, order)
+        down = torch.cat([loss.sum().reshape(1), status.double()]).cpu().numpy()
+        if int(down[1]) != -1:
+            self.epochs_done -= 1                                  # (nothing was written: the epoch did not happen)
+            raise tkr_hip.MlpRefused('MLP.fit', int(down[1]))
+        if not np.isfinite(down[0]):
+            raise FloatingPointError('MLP.fit: the objective of epoch %d is %r' % (self.epochs_done - 1, float(down[0])))
+        return float(down[0])
+
+    def pretrain(self, X=None, Y=None) -> None:
+        tprint('MLP encoder does not implement pretrain method')
+
+    pertrain = pretrain                                            # encoder.py:23 spells the abstract method this way
+
+
+def dpm_train_bytes(n_users, n_items, k, d, widths, batch_size):
+    """device bytes DPM.train allocates for a model of this shape -> (features, tables, encoder): features = 4 n_items d; tables =
+    4 k (n_users + 2 n_items), U, V and Fe; encoder = 16 bytes per parameter (W, bias and their slots) and the workspace of K22"""
+    net = tkr_hip.MlpNet()
+    net.n_layers = len(widths) - 1
+    for l, w in enumerate(widths):
+        net.width[l] = int(w)
+    params = sum(a * b + b for a, b in zip(widths, widths[1:]))
+    return 4 * int(n_items) * int(d), 4 * int(k) * (int(n_users) + 2 * int(n_items)), 16 * params + tkr_hip.mlp_workspace_bytes(net, int(n_items), int(batch_size))
+
+
+class DPM(WMF):
+    """single/dpm.py:10-76: WMF whose item rows have the prior v_j ~ encoder(f_j), the encoder an MLP on the item's content features
+    trained on the item table after every alternation.  `le` is accepted and unused, as in the reference."""
+
+    def __init__(self, k: int, d: int, lu: float = 0.01, lv: float = 10, le: float = 10e3, a: float = 1, b: float = 0.01) -> None:
+        super().__init__(k, lu, lv, a, b)
+        if not isinstance(d, (int, np.integer)) or d < 1:
+            raise ValueError('DPM: d = %r, the width of the content features, must be a positive integer' % (d,))
+        if not lv > 0:
+            raise ValueError('DPM: lv = %r must be positive (the weight of the prior v ~ encoder(f))' % (lv,))
+        self.__sn = 'dpm'
+        self.d, self.le = int(d), float(le)
+        self.encoder = None
+        self.feat = None
+
+    def _check_encoder(self, where):
+        if not isinstance(self.encoder, MLP):
+            raise ValueError('%s: the encoder is %r; als.MLP (the class, or an instance) is the one there is' % (where, self.encoder))
+        if (self.encoder.d, self.encoder.k) != (self.d, self.k):
+            raise ValueError('%s: the encoder maps d = %d to k = %d, the model needs (d, k) = (%d, %d)'
+                             % (where, self.encoder.d, self.encoder.k, self.d, self.k))
+
+    # ------------------------------------------------------------------ train (dpm.py:20-64)
+    def train(self, encoder=MLP, max_iter: int = 200, model_path: str = None, verbose: bool = True, device=None, heavy_from=None,
+              batch_size: int = 64) -> None:
+        if self._csr is None:
+            raise ValueError('DPM.train: load_training_data() first')
+        if self.feat is None:
+            raise ValueError('DPM.train: load_content_data() first')
+        if np.shape(self.feat) != (self.n_items, self.d):
+            raise ValueError('DPM.train: feat has shape %s, the model needs (%d, %d)' % (np.shape(self.feat), self.n_items, self.d))
+        _check_batch('DPM.train', batch_size)
+        self.encoder = encoder(self.k, self.d) if isinstance(encoder, type) else encoder
+        self._check_encoder('DPM.train')
+        if model_path is not None and os.path.isdir(model_path):
+            self.import_embeddings(model_path)
+        for name, table, rows in (('fue', self.fue, self.n_users), ('fie', self.fie, self.n_items)):
+            if np.shape(table) != (rows, self.k):
+                raise ValueError('DPM.train: %s has shape %s, the model needs (%d, %d)' % (name, np.shape(table), rows, self.k))
+        device = _cuda(device, 'DPM.train')
+        features, tables, enc = dpm_train_bytes(self.n_users, self.n_items, self.k, self.d, self.encoder.widths, batch_size)
+        free = torch.cuda.mem_get_info(device)[0]
+        if features + tables + enc > free:
+            raise ValueError('DPM.train: the features need %d bytes (4 n_items d, d = %d, n_items = %d), the tables %d and the encoder with its '
+                             'workspace %d; %d are free on %s' % (features, self.d, self.n_items, tables, enc, free, device))
+        up, uc, ip, ic = (foldin._upload(x, device) for x in self._csr)
+        u_rated = foldin._upload(np.asarray(self.u_rated, dtype=np.int32), device)
+        i_rated = foldin._upload(np.asarray(self.i_rated, dtype=np.int32), device)
+        U, V = foldin._upload(self.fue, device, np.float32), foldin._upload(self.fie, device, np.float32)
+        F = foldin._upload(np.ascontiguousarray(self.feat, dtype=np.float32), device, np.float32)
+        w = Work(heavy_from)
+        hyper = dict(a=self.a, b=self.b, w=w)
+        self.losses = []
+        for it in range(max_iter):                                 # no stopping test: dpm.py:31-60 runs every iteration
+            t1 = time.time()
+            Fe = self.encoder.out(F)
+            V.copy_(Fe)                                            # dpm.py:33: the item table IS the encoder's output when the users are solved
+            _, su = half_step(U, V, up, uc, i_rated, ridge_in_G=self.lu, ridge=0.0, **hyper)
+            rows, sv = half_step(V, U, ip, ic, u_rated, ridge_in_G=0.0, ridge=self.lv, want_loss=True, prior=Fe, w_prior=self.lv, **hyper)
+            fit, se = self.encoder._fit_device(F, V, batch_size)
+            total = rows.sum() + 0.5 * self.lu * U.double().square().sum() + fit.sum()
+            down = torch.cat([total.reshape(1), su.double(), sv.double(), se.double()]).cpu().numpy()      # one copy: the loss, the five status words behind it
+            check_status(down[1:5], ('the user step of iteration %d' % it, 'the item step of iteration %d' % it))
+            if int(down[5]) != -1:
+                raise tkr_hip.MlpRefused('the encoder step of iteration %d' % it, int(down[5]))
+            loss = float(down[0])
+            if not np.isfinite(loss):
+                raise FloatingPointError('DPM.train: the loss of iteration %d is %r' % (it, loss))
+            self.losses.append(loss)
+            if verbose:
+                tprint('Iter %3d, loss %.6f, time %.2fs' % (it, loss, time.time() - t1))
+        Fe = self.encoder.out(F)                                   # dpm.py:61-64: an item without a training like gets its content's row
+        cold = np.setdiff1d(np.arange(self.n_items), np.asarray(self.i_rated, dtype=np.int64))
+        if len(cold):
+            at = foldin._upload(cold.astype(np.int64), device)
+            V[at] = Fe[at]
+        self.fue, self.fie = U.cpu().numpy(), V.cpu().numpy()
+
+    def embed_items(self, feat):
+        """fp32 [m, d] content features -> fp32 [m, k] = encoder.out(feat): the row of an item that was no line of vid, by the rule
+        train() gives an item without a training like"""
+        if self.encoder is None:
+            raise ValueError('DPM.embed_items: train() or import_embeddings() first')
+        feat = np.asarray(feat, dtype=np.float32)
+        if feat.ndim != 2 or feat.shape[1] != self.d:
+            raise ValueError('DPM.embed_items: feat has shape %s, the model needs (m, %d)' % (feat.shape, self.d))
+        return self.encoder.out(feat)
+
+    def export_model(self, model_path: str) -> None:
+        if os.path.isdir(model_path) and self.encoder is not None:
+            target = os.path.join(model_path, 'mlp.npz')
+            tprint('Saving the encoder to %s' % target)
+            np.savez(target, **self.encoder.state())
+
+    def import_model(self, model_path: str) -> None:
+        source = os.path.join(model_path, 'mlp.npz')
+        if os.path.exists(source):
+            tprint('Loading the encoder from %s' % source)
+            with np.load(source) as fh:
+                state = {name: fh[name] for name in fh.files}
+            if self.encoder is None:
+                self.encoder = MLP(self.k, self.d, hidden_layers=())
+            self._check_encoder('DPM.import_model')
+            self.encoder.load_state(state)

@@ -90,10 +90,10 @@ EXPORTS = ('tkr_version', 'tkr_plan_team', 'tkr_plan_max_blocks', 'tkr_sample_pl
            'tkr_matrix_tokens_host', 'tkr_group_count_dev', 'tkr_group_emit_dev', 'tkr_last_line_of_user_dev', 'tkr_compact_rows_count_dev',
            'tkr_compact_rows_emit_dev', 'tkr_fusion_features', 'tkr_fusion_sgd', 'tkr_fusion_user_weights',
            'tkr_mmr_select', 'tkr_list_pair_sums', 'tkr_line_metrics', 'tkr_bootstrap_sums', 'tkr_nearest_anchors', 'tkr_als_gram',
-           'tkr_als_solve_rows', 'tkr_als_solve_rows_prior')
+           'tkr_als_solve_rows', 'tkr_als_solve_rows_prior', 'tkr_mlp_forward', 'tkr_mlp_fit')
 EXPORTS_I64 = ('tkr_vbpr_workspace_floats', 'tkr_vbpr_colplan_lds_bytes', 'tkr_topk_workspace_bytes_for', 'tkr_topk_workspace_bytes', 'tkr_plan_workspace_bytes', 'tkr_like_ranks_workspace_bytes',
                'tkr_parse_dev_workspace_bytes', 'tkr_idtable_slots', 'tkr_scan_dev_workspace_bytes', 'tkr_als_workspace_bytes',
-               'tkr_als_prior_workspace_bytes')
+               'tkr_als_prior_workspace_bytes', 'tkr_mlp_workspace_bytes')
 
 
 def lib():
@@ -1404,6 +1404,125 @@ def als_solve_rows_prior(Y, G, like_ptr, like_cols, X, prior, *, w_like, w_rhs, 
 
 
 ALS_HEAVY_FROM = 4 * ALS_GRAM_SLAB       # a row with this many likes is shared by several workgroups (scripts/time_als.py)
+
+
+# ---- K22: a dense MLP content encoder, applied and trained (csrc/mlp.hip) ------------------------------------------------------------------
+MLP_MAX_LAYERS = 5           # TKR_MLP_MAX_LAYERS of include/tkr.h
+MLP_MAX_BATCH = 256          # TKR_MLP_MAX_BATCH
+MLP_SLAB = 512               # TKR_MLP_SLAB: the inputs of a layer one workgroup sums
+MLP_FORWARD_CHUNK = 256      # TKR_MLP_FORWARD_CHUNK
+
+
+class MlpNet(C.Structure):
+    """mirror of tkr_mlp_net (include/tkr.h)"""
+    _fields_ = [('n_layers', C.c_int32), ('width', C.c_int32 * (MLP_MAX_LAYERS + 1))] + \
+               [(n, C.c_void_p * MLP_MAX_LAYERS) for n in ('W', 'bias', 'msW', 'msb')]
+
+
+class MlpRefused(TkrError):
+    """a status word of K22 that is not -1: .position is the entry of rows / order that lies outside [0, n)"""
+
+    def __init__(self, what, word):
+        self.word, self.position = word, word >> 2
+        super().__init__('%s: entry %d of the row list lies outside [0, n)' % (what, self.position))
+
+
+def mlp_net(layers):
+    """layers: per dense layer a dict of device tensors W fp32 [in, out], bias [out] and (for mlp_fit) msW, msb -> MlpNet; the tensors
+    live as long as the struct"""
+    what = 'mlp_net'
+    if not 1 <= len(layers) <= MLP_MAX_LAYERS:
+        raise ValueError('%s: %d layers, 1 <= layers <= %d is supported' % (what, len(layers), MLP_MAX_LAYERS))
+    net = MlpNet()
+    net.n_layers = len(layers)
+    device = layers[0]['W'].device
+    for l, layer in enumerate(layers):
+        W = layer['W']
+        if not isinstance(W, torch.Tensor) or W.dtype != torch.float32 or W.dim() != 2 or W.shape[0] < 1 or W.shape[1] < 1:
+            raise TkrError('%s: W of layer %d must be a two-dimensional float32 tensor' % (what, l))
+        if l and W.shape[0] != layers[l - 1]['W'].shape[1]:
+            raise ValueError('%s: layer %d takes %d inputs, layer %d gives %d' % (what, l, W.shape[0], l - 1, layers[l - 1]['W'].shape[1]))
+        net.width[l], net.width[l + 1] = int(W.shape[0]), int(W.shape[1])
+        for name, shape in (('W', W.shape), ('bias', W.shape[1:]), ('msW', W.shape), ('msb', W.shape[1:])):
+            t = layer.get(name)
+            if t is None and name in ('msW', 'msb'):
+                continue
+            if not isinstance(t, torch.Tensor) or t.dtype != torch.float32 or t.shape != shape or not t.is_contiguous() or t.device != device or not t.is_cuda:
+                raise TkrError('%s: %s of layer %d must be a contiguous float32 tensor of shape %s on the GPU of layer 0' % (what, name, l, tuple(shape)))
+            getattr(net, name)[l] = t.data_ptr()
+    net.keep = layers
+    net.device = device
+    return net
+
+
+def mlp_workspace_bytes(net, m, batch=0):
+    need = int(lib().tkr_mlp_workspace_bytes(C.byref(net), C.c_int64(m), C.c_int32(batch)))
+    if need < 0:
+        raise TkrError('tkr_mlp_workspace_bytes(m = %d, batch = %d) failed: tkr error %d' % (m, batch, need))
+    return need
+
+
+def _mlp_rows(what, name, t, device):
+    if not isinstance(t, torch.Tensor) or t.dtype != torch.int32 or t.dim() != 1 or not t.is_contiguous() or t.device != device:
+        raise TkrError('%s: %s must be a contiguous one-dimensional int32 tensor on the GPU of the parameters' % (what, name))
+
+
+def mlp_forward(net, X, rows=None, workspace=None, out=None, check=True):
+    """K22 -> fp32 [m, k] on the device: the network applied to X[rows] (int32 tensor; None: every row of X), include/tkr.h
+    tkr_mlp_forward.  A row outside [0, n) raises MlpRefused and nothing is written; check=False returns (out, status tensor) and
+    reads nothing back"""
+    what = 'mlp_forward'
+    if not isinstance(X, torch.Tensor) or X.dtype != torch.float32 or X.dim() != 2 or not X.is_contiguous() or X.device != net.device or \
+            X.shape[1] != net.width[0] or X.shape[0] < 1:
+        raise TkrError('%s: X must be a contiguous float32 [n, %d] tensor on the GPU of the parameters' % (what, net.width[0]))
+    n = int(X.shape[0])
+    if rows is not None:
+        _mlp_rows(what, 'rows', rows, X.device)
+    m = n if rows is None else int(rows.numel())
+    k = net.width[net.n_layers]
+    workspace = _als_workspace(workspace, mlp_workspace_bytes(net, m), X.device)
+    if out is None:
+        out = torch.empty((m, k), dtype=torch.float32, device=X.device)
+    elif not isinstance(out, torch.Tensor) or out.dtype != torch.float32 or tuple(out.shape) != (m, k) or not out.is_contiguous() or out.device != X.device:
+        raise TkrError('%s: out must be a contiguous float32 [%d, %d] tensor on the GPU of X' % (what, m, k))
+    status = torch.empty(1, dtype=torch.int64, device=X.device)
+    _call('tkr_mlp_forward', X, C.byref(net), _p(X), C.c_int32(n), C.c_void_p(0) if rows is None else _p(rows if m else X), C.c_int64(m),
+          _p(out if m else X), _p(workspace), C.c_int64(workspace.numel() * workspace.element_size()), _p(status))
+    if not check:
+        return out, status
+    word = int(status.item())
+    if word != -1:
+        raise MlpRefused(what, word)
+    return out
+
+
+def mlp_fit(net, X, Y, order, batch, lr, workspace=None, check=True):
+    """K22: one epoch of mini-batch RMSProp over the rows `order` (int32 tensor) of X fp32 [n, d] and Y fp32 [n, k], in place on the
+    parameters and slots of `net` (include/tkr.h tkr_mlp_fit) -> batch_loss float64 [ceil(m / batch)] on the device.  An entry of
+    order outside [0, n) raises MlpRefused and nothing is written; check=False returns (batch_loss, status tensor) and reads nothing
+    back"""
+    what = 'mlp_fit'
+    k = net.width[net.n_layers]
+    for name, t, width in (('X', X, net.width[0]), ('Y', Y, k)):
+        if not isinstance(t, torch.Tensor) or t.dtype != torch.float32 or t.dim() != 2 or not t.is_contiguous() or t.device != net.device or \
+                t.shape[1] != width or t.shape[0] != X.shape[0] or t.shape[0] < 1:
+            raise TkrError('%s: %s must be a contiguous float32 [n, %d] tensor on the GPU of the parameters' % (what, name, width))
+    _mlp_rows(what, 'order', order, X.device)
+    batch = int(batch)
+    if not 1 <= batch <= MLP_MAX_BATCH:
+        raise ValueError('%s: batch = %d, 1 <= batch <= %d is supported' % (what, batch, MLP_MAX_BATCH))
+    m = int(order.numel())
+    workspace = _als_workspace(workspace, mlp_workspace_bytes(net, 0, batch), X.device)
+    loss = torch.zeros((m + batch - 1) // batch, dtype=torch.float64, device=X.device)
+    status = torch.empty(1, dtype=torch.int64, device=X.device)
+    _call('tkr_mlp_fit', X, C.byref(net), _p(X), C.c_int32(int(X.shape[0])), _p(Y), _p(order if m else X), C.c_int64(m), C.c_int32(batch),
+          C.c_float(lr), _p(loss if m else X), _p(workspace), C.c_int64(workspace.numel() * workspace.element_size()), _p(status))
+    if not check:
+        return loss, status
+    word = int(status.item())
+    if word != -1:
+        raise MlpRefused(what, word)
+    return loss
 
 
 # ---- K18: the metric values of every test line, their sums over resampled lines (csrc/line_metrics.hip) -------------------------------

@@ -1,8 +1,7 @@
 """Training driver -- the BPR/VBPR part of the reference's train.py (train.py:1-16): the same
 hard-coded data/ and embed/ locations, k = 50, five epochs of batch 256 from scratch, export, then
-five more epochs warm-started from the exported model.  The reference's lines 18-29 (WMF, CER:
-the ALS models) are train_als.py's, on als.WMF and als.CER; lines 30-36 (DPM) are outside the
-path this build accelerates.
+five more epochs warm-started from the exported model.  The reference's lines 18-36 (WMF, CER,
+DPM: the ALS models) are train_als.py's, on als.WMF, als.CER and als.DPM with its als.MLP encoder.
 
     cd top-k-rec_amd && python train.py            # expects data/uid, data/vid, data/f0tr.txt (+ data/meta.pkl)
 
