@@ -770,6 +770,39 @@ int tkr_fusion_sgd(const float* D, int64_t n_rows, int32_t n_models, int32_t bat
 int tkr_fusion_user_weights(const tkr_fusion_models* models, const int64_t* like_ptr, const int32_t* like_cols, int32_t n_users,
                             float* rmse_out, float* w_out, void* stream);
 
+/* ---- K23: the sums of one Newton pass of the SVM fusion (csrc/fusion_svm.hip) -------------------------------------------------------
+ * The reference's old/methods/sfusion.py fits LinearSVC(C) to the score differences of sampled triplets, row t as +d_t with label +1
+ * (t even) or as -d_t with label -1 (t odd): squared hinge, L2 penalty, the intercept regularised as one more feature of value 1, i.e.
+ *   f(w, b) = (|w|^2 + b^2) / 2 + C sum_t max(0, 1 - z_t)^2,   z_t = w . d_t + y_t b,   y_t = +1 (t even), -1 (t odd).
+ * top-k-rec_amd/svmfusion.py minimises f by Newton's method on the host; every pass is one reduction over all rows, done here.
+ *
+ *   tkr_fusion_svm_sums      D fp32 [n_rows, n_models] as tkr_fusion_features writes it; row t is row g = first_row + t of the run, of
+ *                            parity g & 1, x~ = (d, y).  W device fp64 [n_models + 1]: the weights, then the intercept.
+ *                            z = sum_m W[m] d[m] + y W[M] in fp64, ONE fma chain, m ascending.  A row is active iff 1 - z > 0 (strictly:
+ *                            a row exactly on the hinge adds nothing).  Over the active rows, every term one fp64 fma:
+ *                              S      the upper triangle of sum x~ x~^T, row by row: (M + 1)(M + 2) / 2 values
+ *                              r      sum (1 - z) x~, M + 1 values
+ *                              q      sum (1 - z)^2
+ *                              count  the number of active rows
+ *                            One workgroup per slab of TKR_FUSION_SVM_SLAB rows, slabs cut at multiples of the slab IN g; lanes and
+ *                            waves are combined through one fixed tree, and a slab's sums (S | r | q | count, all fp64) go to
+ *                            partial[slab_offset + s], s = 0, 1, ... over the slabs that [first_row, first_row + n_rows) touches.
+ *                            With out != NULL a second launch adds partial[0 .. slab_offset + this call's slabs) in ascending order into
+ *                            out: fp64 S | r | q, then the count as int64 -- (M + 1)(M + 2) / 2 + M + 3 eight-byte words.  The result
+ *                            depends on g alone: two calls give the same bits, and so does a run cut into calls of whole slabs
+ *                            (first_row a multiple of the slab, slab_offset carried, out passed to the last call only).
+ *                            No float atomics.  A row with an entry that is not finite (tkr_fusion_features writes NaN for an id
+ *                            outside the tables) is never summed: *status (device int64, set to -1 by the call with slab_offset 0)
+ *                            takes the smallest such g by atomic min, and the second launch then leaves out as it is.
+ *   tkr_fusion_svm_partial_bytes   the bytes of partial for the rows [first_row, first_row + n_rows), or TKR_E_INVAL.
+ * Arguments are checked before any device access and before any launch (TKR_E_INVAL): a null D / W / partial / status, n_models outside
+ * [1, 16], n_rows < 1, first_row < 0 (either above 2^42), slab_offset < 0, a misaligned D / W / partial / out / status, partial_bytes too
+ * small for slab_offset + this call's slabs. */
+#define TKR_FUSION_SVM_SLAB 4096
+int tkr_fusion_svm_sums(const float* D, int64_t n_rows, int32_t n_models, int64_t first_row, const double* W, double* partial,
+                        int64_t partial_bytes, int64_t slab_offset, double* out, int64_t* status, void* stream);
+int64_t tkr_fusion_svm_partial_bytes(int64_t n_rows, int32_t n_models, int64_t first_row);
+
 /* ---- K17: diversify a pool into a list (greedy MMR) and the pair sums of list diversity (csrc/diversity.hip) ----------------------
  * New design: the reference sorts every list by score alone.  Both entry points are built on the similarity of two entries of a row,
  *   sim(a, b) = chain(S[id_a], S[id_b]),   S fp32 [n_items, k]: whatever the caller measures similarity in (row-normalised item factors

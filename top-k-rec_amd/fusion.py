@@ -18,7 +18,8 @@ What differs from the reference, on purpose:
     2.0 (efusion.py:72).
   * a user whose mean RMSE is exactly 0 (no training likes) gets the weights 1.0, the continuous value of exp(-(r - mean)); the
     reference leaves them 0 (efusion.py:79), which erases that user's ranking.
-  * sfusion.py (an SVM from scikit-learn on the score vectors) is not built.
+  * sfusion.py (an SVM from scikit-learn on the score differences of sampled triplets) lives in svmfusion.py (K23): the same
+    objective minimised by Newton's method on sums formed on the GPU, no library; ``fuse.py --method s``.
 """
 from __future__ import annotations
 

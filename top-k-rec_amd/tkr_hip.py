@@ -88,12 +88,12 @@ EXPORTS = ('tkr_version', 'tkr_plan_team', 'tkr_plan_max_blocks', 'tkr_sample_pl
            'tkr_ratings_emit_dev', 'tkr_rank_candidates', 'tkr_lists_format_sizes_dev', 'tkr_lists_format_emit_dev',
            'tkr_matrix_format_sizes_dev', 'tkr_matrix_format_emit_dev', 'tkr_matrix_count_dev', 'tkr_matrix_emit_dev', 'tkr_matrix_token_host',
            'tkr_matrix_tokens_host', 'tkr_group_count_dev', 'tkr_group_emit_dev', 'tkr_last_line_of_user_dev', 'tkr_compact_rows_count_dev',
-           'tkr_compact_rows_emit_dev', 'tkr_fusion_features', 'tkr_fusion_sgd', 'tkr_fusion_user_weights',
+           'tkr_compact_rows_emit_dev', 'tkr_fusion_features', 'tkr_fusion_sgd', 'tkr_fusion_user_weights', 'tkr_fusion_svm_sums',
            'tkr_mmr_select', 'tkr_list_pair_sums', 'tkr_line_metrics', 'tkr_bootstrap_sums', 'tkr_nearest_anchors', 'tkr_als_gram',
            'tkr_als_solve_rows', 'tkr_als_solve_rows_prior', 'tkr_mlp_forward', 'tkr_mlp_fit')
 EXPORTS_I64 = ('tkr_vbpr_workspace_floats', 'tkr_vbpr_colplan_lds_bytes', 'tkr_topk_workspace_bytes_for', 'tkr_topk_workspace_bytes', 'tkr_plan_workspace_bytes', 'tkr_like_ranks_workspace_bytes',
                'tkr_parse_dev_workspace_bytes', 'tkr_idtable_slots', 'tkr_scan_dev_workspace_bytes', 'tkr_als_workspace_bytes',
-               'tkr_als_prior_workspace_bytes', 'tkr_mlp_workspace_bytes')
+               'tkr_als_prior_workspace_bytes', 'tkr_mlp_workspace_bytes', 'tkr_fusion_svm_partial_bytes')
 
 
 def lib():
@@ -1144,6 +1144,102 @@ def fusion_user_weights(models, like_ptr, like_cols):
     w = torch.empty((n_users, M), dtype=torch.float32, device=device)
     _call('tkr_fusion_user_weights', rmse, C.byref(st), _p(like_ptr), _p(like_cols), C.c_int32(n_users), _p(rmse), _p(w))
     return rmse, w
+
+
+# ---- K23: the sums of one Newton pass of the SVM fusion (csrc/fusion_svm.hip) ------------------------------------------------------
+FUSION_SVM_SLAB = 4096       # TKR_FUSION_SVM_SLAB of include/tkr.h
+
+
+def fusion_svm_words(M):
+    """the eight-byte words of one slab's partial and of the result: S (upper triangle) | r | q | count"""
+    return (M + 1) * (M + 2) // 2 + M + 3
+
+
+def fusion_svm_slabs(n_rows, first_row=0):
+    """the slabs that the rows [first_row, first_row + n_rows) touch: slabs are cut at multiples of FUSION_SVM_SLAB"""
+    return (first_row + n_rows - 1) // FUSION_SVM_SLAB - first_row // FUSION_SVM_SLAB + 1
+
+
+def fusion_svm_partial_bytes(n_rows, M, first_row=0):
+    need = int(lib().tkr_fusion_svm_partial_bytes(C.c_int64(n_rows), C.c_int32(M), C.c_int64(first_row)))
+    if need < 0:
+        raise TkrError('tkr_fusion_svm_partial_bytes(%d, %d, %d) failed: tkr error %d' % (n_rows, M, first_row, need))
+    return need
+
+
+def _fusion_svm_f64(what, name, t, numel, device, at_least=False):
+    if not isinstance(t, torch.Tensor):
+        raise TkrError('%s: %s must be a tensor' % (what, name))
+    if t.dtype != torch.float64:
+        raise TkrError('%s: %s must be torch.float64, not %s' % (what, name, t.dtype))
+    if not t.is_contiguous():
+        raise TkrError('%s: %s must be contiguous' % (what, name))
+    if t.numel() < numel if at_least else t.numel() != numel:
+        raise TkrError('%s: %s must hold %s%d values, not %d' % (what, name, 'at least ' if at_least else '', numel, t.numel()))
+    if t.device != device:
+        raise TkrError('%s: D and %s must live on one GPU' % (what, name))
+
+
+def fusion_svm_unpack(out, M):
+    """the result of fusion_svm_sums on the host (numpy fp64 [fusion_svm_words(M)]) -> (S fp64 [M + 1, M + 1] symmetric, r fp64 [M + 1],
+    q, count)"""
+    import numpy as np
+    out = np.ascontiguousarray(out, dtype=np.float64)
+    X = M + 1
+    nS = X * (X + 1) // 2
+    S = np.zeros((X, X), dtype=np.float64)
+    S[np.triu_indices(X)] = out[:nS]
+    S = S + np.triu(S, 1).T
+    return S, out[nS:nS + X].copy(), float(out[nS + X]), int(out[nS + X + 1:nS + X + 2].view(np.int64)[0])
+
+
+def fusion_svm_sums(D, W, first_row=0, *, partial=None, slab_offset=0, reduce=True, out=None, status=None, check=True):
+    """K23 -> out, device fp64 [fusion_svm_words(M)] (fusion_svm_unpack reads it): over the active rows of D fp32 [n_rows, M] under
+    W fp64 [M + 1] (weights, then intercept) the sums S, r, q and the count of include/tkr.h tkr_fusion_svm_sums; row t of D is row
+    first_row + t of the run.  A run cut into calls of whole slabs shares ``partial`` (fusion_svm_partial_bytes of the whole run),
+    carries ``slab_offset`` and reduces in its last call only (reduce=False before it: None is returned); the status word is set by the
+    call with slab_offset 0.  A row that is not finite raises TkrError naming it and leaves ``out`` as it is; check=False reads
+    nothing back (the caller reads ``status``: -1 or the row)."""
+    what = 'fusion_svm_sums'
+    _fusion_table(what, 'D', D, 2)
+    n_rows, M = int(D.shape[0]), int(D.shape[1])
+    first_row, slab_offset = int(first_row), int(slab_offset)
+    if not 1 <= M <= FUSION_MAX_MODELS:
+        raise TkrError('%s: 1 .. %d models required, D has %d columns' % (what, FUSION_MAX_MODELS, M))
+    if n_rows < 1:
+        raise TkrError('%s: D must hold at least one row' % what)
+    if first_row < 0 or slab_offset < 0:
+        raise TkrError('%s: first_row and slab_offset must not be negative (%d, %d)' % (what, first_row, slab_offset))
+    if not D.is_cuda:
+        raise TkrError('%s: D must live on the GPU, not on %s' % (what, D.device))
+    words = fusion_svm_words(M)
+    _fusion_svm_f64(what, 'W', W, M + 1, D.device)
+    need = (slab_offset + fusion_svm_slabs(n_rows, first_row)) * words
+    if partial is None:
+        partial = torch.empty(need, dtype=torch.float64, device=D.device)
+    _fusion_svm_f64(what, 'partial', partial, need, D.device, at_least=True)
+    if reduce:
+        if out is None:
+            out = torch.empty(words, dtype=torch.float64, device=D.device)
+        _fusion_svm_f64(what, 'out', out, words, D.device)
+    else:
+        out = None
+    if status is None:
+        status = torch.empty(1, dtype=torch.int64, device=D.device)
+    if status.dtype != torch.int64 or status.numel() != 1 or not status.is_contiguous() or status.device != D.device:
+        raise TkrError('%s: status must be one torch.int64 word on the GPU that holds D' % what)
+    _call('tkr_fusion_svm_sums', D, _p(D), C.c_int64(n_rows), C.c_int32(M), C.c_int64(first_row), _p(W), _p(partial),
+          C.c_int64(partial.numel() * 8), C.c_int64(slab_offset), _p(out), _p(status))
+    if check and reduce:
+        fusion_svm_check(int(status.item()))
+    return out
+
+
+def fusion_svm_check(word):
+    """the status word of a run of fusion_svm_sums, read on the host"""
+    if word != -1:
+        raise TkrError('fusion_svm_sums: row %d of the features holds a value that is not finite (fusion_features writes NaN for an id '
+                       'outside the tables); nothing was summed' % word)
 
 
 # ---- K17: diversify a pool into a list, the pair sums of list diversity (csrc/diversity.hip) -------------------------------------------
