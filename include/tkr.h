@@ -987,6 +987,48 @@ int tkr_als_solve_rows_prior(const float* Y, int32_t n_y, int32_t k, const float
                              double* row_loss, const float* prior, double w_prior, void* workspace, int64_t workspace_bytes, int64_t* status,
                              void* stream);
 
+/* ---- K24: the ALS half-step by conjugate gradients, and the Gram at any width up to 512 (csrc/als_cg.hip) --------------------------------
+ * A second, opt-in solver beside K20 / K21; 1 <= k <= TKR_ALS_CG_MAX_K (wider: TKR_E_UNSUPPORTED).  The
+ * notation is tkr_als_solve_rows' and tkr_als_solve_rows_prior's.
+ *
+ *   tkr_als_cg_rows     For row r with likes y in L_r (m_r of them inside [0, n_y)) and, where prior != NULL, p_r = prior[r]:
+ *                         A_r v = G v + w_like * sum_y (y . v) y + ridge * v                  (never stored as a matrix)
+ *                         b_r   = fp32(w_rhs * sum_y y + w_prior * p_r)                       (both terms in fp64, rounded once)
+ *                         x <- X[r];  r <- b - A x;  p <- r;  rho <- r . r
+ *                         `steps` times, unless rho < 1e-20 (the row is done):
+ *                           q <- A p;  alpha <- rho / (p . q);  x <- fma(alpha, p, x);  r <- fma(-alpha, q, r);  rho' <- r . r;
+ *                           p <- fma(rho' / rho, p, r);  rho <- rho'
+ *                         X[r] <- x                                                           (steps = 0 stores nothing)
+ *                         row_loss[r] = 1/2 x . q' - w_rhs * sum_y (y . x) + 1/2 w_rhs m_r (+ 1/2 w_prior sum_j (x_j - p_j)^2),
+ *                                       q' = fp32(G x + w_like * sum_y (y . x) y) from ONE fresh product with the final x; fp64 sums;
+ *                                       only when row_loss != NULL
+ *                       A v is fp32(G v + w_like * s + ridge * v) with the three terms in fp64; G v is one fp32 fma chain over the
+ *                       columns in ascending order from +0.0 (the exact-fp32 MFMA), s = sum_y t_y y one fma chain per component over the
+ *                       likes in stored order, t_y = y . v.  Every dot product is one fixed tree: lane l of 64 chains its elements l,
+ *                       l + 64, .. by fma from +0.0, then s += s(lane ^ 32), ^ 16, .. ^ 1.  Divisions are IEEE fp32 divisions.
+ *                       prior == NULL: rows with m_r = 0 are left untouched, row_loss 0.  prior != NULL: EVERY row is solved; a row
+ *                       without likes is the same recurrence with an empty list and its loss is the prior term alone; a row whose likes
+ *                       were ALL refused is reported, left as it is, row_loss 0.
+ *                       status: -1, or the smallest 4 * r + kind: 1 -- a like column outside [0, n_y) was skipped; 2 -- p . q is not
+ *                       positive and finite, or x is not finite: X[r] is left as it came in, row_loss[r] = 0, no NaN is written; 3 --
+ *                       like_ptr is broken at this row (as tkr_als_solve_rows): left as it is, row_loss[r] = 0.
+ *                       The bits of row r depend on G, the weights, its likes in stored order, its X[r] and prior, and steps: not on
+ *                       n_x or on the other rows of the call.  workspace: not used (tkr_als_cg_workspace_bytes gives 0; NULL is fine).
+ *                       TKR_E_INVAL before any device access: a null or misaligned pointer, n_y / n_x < 1, n_x >= 2^31, n_likes < 0,
+ *                       steps < 0, ridge < 0, w_prior < 0, a weight that is not finite.
+ *   tkr_als_gram_wide   tkr_als_gram's definition, arguments, status word and skipped-row rule for 1 <= k <= TKR_ALS_CG_MAX_K: slabs of
+ *                       TKR_ALS_GRAM_SLAB rows, fp32 partials on the exact MFMA, added in ascending slab order in fp64, rounded once.
+ *                       For k <= TKR_ALS_MAX_K its output has tkr_als_gram's bits.  workspace: at least
+ *                       tkr_als_gram_wide_workspace_bytes(k, ceil(n_listed / TKR_ALS_GRAM_SLAB)) bytes (k * k floats per slab). */
+#define TKR_ALS_CG_MAX_K 512
+int64_t tkr_als_cg_workspace_bytes(int64_t n_x, int32_t k);
+int tkr_als_cg_rows(const float* Y, int32_t n_y, int32_t k, const float* G, const int64_t* like_ptr, const int32_t* like_cols,
+                    int64_t n_likes, int64_t n_x, double w_like, double w_rhs, double ridge, int32_t steps, float* X, double* row_loss,
+                    const float* prior, double w_prior, void* workspace, int64_t workspace_bytes, int64_t* status, void* stream);
+int64_t tkr_als_gram_wide_workspace_bytes(int32_t k, int64_t n_slabs);
+int tkr_als_gram_wide(const float* Y, int32_t n, int32_t k, const int32_t* rows, int64_t n_listed, double scale, double ridge, float* G,
+                      void* workspace, int64_t workspace_bytes, int64_t* status, void* stream);
+
 /* ---- K22: a dense MLP content encoder, applied and trained (csrc/mlp.hip) ----------------------------------------------------------------
  * Replaces the TensorFlow graph of the reference's single/mlp.py:14-40 (tf.layers.dense, RMSPropOptimizer.minimize, the sess.run of out
  * and fit), the encoder of single/dpm.py (top-k-rec_amd/als.py MLP and DPM).

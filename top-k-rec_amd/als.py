@@ -19,6 +19,10 @@ whole loop, and one scalar (the loss, with the kernels' status words behind it) 
 the reference's package surface is pinned as it is, this class lives here.  What it writes (final-U.dat, final-V.dat, no final-B.dat)
 is a model directory like any other to evaluate.py, recommend.py and fuse.py.
 
+``WMF(k, ..., solver='cg', cg_steps=3)`` (K24, csrc/als_cg.hip; the same keywords on CER and DPM) takes cg_steps steps of conjugate
+gradients per row and half-step from the row's previous value in place of the per-row Gram + Cholesky: no k x k matrix per row, so
+k <= 512 for WMF and CER.  The default, 'cholesky', is the path above with its bits and its bound k <= 128.
+
 ``CER`` (single/cer.py:16-85) is WMF with a prior on every item row, v_j ~ E^T f_j from the item's content features f_j, and a ridge
 regression for E behind it:
 
@@ -82,16 +86,29 @@ class Work:
         return self.workspace
 
 
-def half_step(X, Y, like_ptr, like_cols, rated_y, *, w=None, ridge_in_G, ridge, a, b, want_loss=False, prior=None, w_prior=0.0):
+def half_step(X, Y, like_ptr, like_cols, rated_y, *, w=None, ridge_in_G, ridge, a, b, want_loss=False, prior=None, w_prior=0.0,
+              solver='cholesky', cg_steps=tkr_hip.ALS_CG_STEPS):
     """one gram plus one solve, in place on X: G = b sum over the rows rated_y of Y of y y^T + ridge_in_G I, then for every row r of X
     with likes (G + (a - b) sum y y^T + ridge I) x = a sum y.  All arguments device tensors (rated_y int32, or None: every row of Y);
     w: a Work to reuse between calls.  -> (row_loss float64 [n_x] or None, status int64 [2]: the words of the two launches, -1 = nothing
     refused).  Nothing is read back here: the caller looks at the status when it next synchronises (check_status).
     prior (fp32 [n_x, k]) and w_prior: K21 -- the right-hand side of row r adds w_prior prior[r], its loss 1/2 w_prior |x - prior[r]|^2, and
-    the rows WITHOUT likes are solved too (tkr_hip.als_solve_rows_prior).  None: the calls above and no others."""
+    the rows WITHOUT likes are solved too (tkr_hip.als_solve_rows_prior).  None: the calls above and no others.
+    solver 'cg' (K24): the same system by cg_steps steps of conjugate gradients from the value X holds, k up to tkr_hip.ALS_CG_MAX_K
+    (tkr_hip.als_gram_wide + tkr_hip.als_cg_rows); the default takes the calls above and no others."""
     w = Work() if w is None else w
     n_x, k = int(X.shape[0]), int(Y.shape[1])
     n_listed = int(Y.shape[0]) if rated_y is None else int(rated_y.numel())
+    if solver == 'cg':
+        ws = w.room(tkr_hip.als_gram_wide_workspace_bytes(k, (n_listed + tkr_hip.ALS_GRAM_SLAB - 1) // tkr_hip.ALS_GRAM_SLAB), Y.device)
+        if w.G is None or w.G.shape != (k, k) or w.G.device != Y.device:
+            w.G = torch.empty((k, k), dtype=torch.float32, device=Y.device)
+        _, s0 = tkr_hip.als_gram_wide(Y, rated_y, scale=b, ridge=ridge_in_G, workspace=ws, out=w.G, check=False)
+        loss, s1 = tkr_hip.als_cg_rows(Y, w.G, like_ptr, like_cols, X, w_like=a - b, w_rhs=a, ridge=ridge, steps=int(cg_steps), prior=prior,
+                                       w_prior=w_prior, want_loss=want_loss, check=False)
+        return loss, torch.cat([s0, s1])
+    if solver != 'cholesky':
+        raise ValueError("half_step: solver = %r, 'cholesky' and 'cg' are the ones there are" % (solver,))
     n_likes = int(like_cols.numel())
     need = tkr_hip.als_workspace_bytes(0, k, (n_listed + tkr_hip.ALS_GRAM_SLAB - 1) // tkr_hip.ALS_GRAM_SLAB)
     slabs = None
@@ -121,8 +138,21 @@ def check_status(words, what):
             raise tkr_hip.AlsRefused('%s, %s' % (what[i // 2], 'als_solve_rows' if i & 1 else 'als_gram (row = position in the rated list)'), word)
 
 
-def _check_hyper(k, lu, lv, a, b):
-    if not isinstance(k, (int, np.integer)) or not 1 <= k <= MAX_K:
+SOLVERS = ('cholesky', 'cg')
+CG_MAX_K = tkr_hip.ALS_CG_MAX_K
+
+
+def _check_hyper(k, lu, lv, a, b, solver='cholesky', cg_steps=tkr_hip.ALS_CG_STEPS):
+    if solver not in SOLVERS:
+        raise ValueError("WMF: solver = %r, 'cholesky' (per-row Gram + Cholesky, K20) and 'cg' (conjugate gradients, K24) are the ones "
+                         'there are' % (solver,))
+    if not isinstance(cg_steps, (int, np.integer)) or isinstance(cg_steps, bool) or cg_steps < 1:
+        raise ValueError('WMF: cg_steps = %r must be an integer, at least 1' % (cg_steps,))
+    if solver == 'cg':
+        if not isinstance(k, (int, np.integer)) or not 1 <= k <= CG_MAX_K:
+            raise ValueError("WMF: k = %r, 1 <= k <= %d is supported under solver='cg' (TKR_ALS_CG_MAX_K: a row's x and r are 8 registers "
+                             'per lane each)' % (k, CG_MAX_K))
+    elif not isinstance(k, (int, np.integer)) or not 1 <= k <= MAX_K:
         raise ValueError('WMF: k = %r, 1 <= k <= %d is supported (TKR_ALS_MAX_K: the k x k system of a row lives in the LDS of one '
                          'workgroup)' % (k, MAX_K))
     if not b > 0:
@@ -134,10 +164,12 @@ def _check_hyper(k, lu, lv, a, b):
 
 
 class WMF(REC):
-    def __init__(self, k: int, lu: float = 0.01, lv: float = 0.01, a: float = 1, b: float = 0.01) -> None:
-        _check_hyper(k, lu, lv, a, b)
+    def __init__(self, k: int, lu: float = 0.01, lv: float = 0.01, a: float = 1, b: float = 0.01, *, solver: str = 'cholesky',
+                 cg_steps: int = tkr_hip.ALS_CG_STEPS) -> None:
+        _check_hyper(k, lu, lv, a, b, solver, cg_steps)
         self.__sn = 'wmf'
         self.k = int(k)
+        self.solver, self.cg_steps = solver, int(cg_steps)
         self.lu, self.lv, self.a, self.b = float(lu), float(lv), float(a), float(b)
         self.uids = self.iids = None
         self.n_users = self.n_items = self.n_ratings = None
@@ -184,7 +216,7 @@ class WMF(REC):
         i_rated = foldin._upload(np.asarray(self.i_rated, dtype=np.int32), device)
         U, V = foldin._upload(self.fue, device, np.float32), foldin._upload(self.fie, device, np.float32)
         w = Work(heavy_from)
-        hyper = dict(a=self.a, b=self.b, w=w)
+        hyper = dict(a=self.a, b=self.b, w=w, solver=self.solver, cg_steps=self.cg_steps)
         loss, self.losses = np.exp(50), []
         for it in range(max_iter):
             t1 = time.time()
@@ -204,10 +236,14 @@ class WMF(REC):
         self.fue, self.fie = U.cpu().numpy(), V.cpu().numpy()
 
     # ------------------------------------------------------------------ fold-in (new: the reference can only retrain)
-    def fold_in(self, histories, device=None, heavy_from=None):
+    def fold_in(self, histories, device=None, heavy_from=None, steps=None):
         """rows for users who were not in the training file, from the items they like: one user half-step against the trained item
         table (the kernel of train()).  histories: a list of item-index sequences, one per user, or the (ptr, cols) pair of
-        foldin.group_history.  -> fp32 [n_new, k]; a user without likes gets a row of zeros"""
+        foldin.group_history.  -> fp32 [n_new, k]; a user without likes gets a row of zeros.  steps (solver='cg' only): the rows start
+        from zero, not from a trained value, so the default is k steps, the bound at which conjugate gradients end in exact arithmetic;
+        a row whose residual is gone (rho < 1e-20) stops sooner"""
+        if steps is not None and (self.solver != 'cg' or not isinstance(steps, (int, np.integer)) or steps < 1):
+            raise ValueError("WMF.fold_in: steps = %r is the step count of solver='cg', an integer of at least 1" % (steps,))
         if self.fie is None or self._csr is None:
             raise ValueError('WMF.fold_in: load_training_data() and train() first')
         device = foldin._device(device, 'WMF.fold_in')
@@ -217,7 +253,7 @@ class WMF(REC):
             return X.cpu().numpy()
         _, status = half_step(X, foldin._upload(self.fie, device, np.float32), foldin._upload(ptr, device), foldin._upload(cols, device),
                               foldin._upload(np.asarray(self.i_rated, dtype=np.int32), device), w=Work(heavy_from), ridge_in_G=self.lu, ridge=0.0,
-                              a=self.a, b=self.b)
+                              a=self.a, b=self.b, solver=self.solver, cg_steps=self.k if steps is None else int(steps))
         check_status(status.cpu().numpy(), ('fold_in',))
         return X.cpu().numpy()
 
@@ -240,8 +276,9 @@ class CER(WMF):
     """single/cer.py:16-85.  The start: load_training_data(seed=) draws fue and fie as WMF does, and the SAME generator, carried on,
     draws E standard normal fp32 [d, k] in train() when no final-E.dat was imported -- one seed fixes all three."""
 
-    def __init__(self, k: int, d: int, lu: float = 0.01, lv: float = 10, le: float = 10e3, a: float = 1, b: float = 0.01) -> None:
-        super().__init__(k, lu, lv, a, b)
+    def __init__(self, k: int, d: int, lu: float = 0.01, lv: float = 10, le: float = 10e3, a: float = 1, b: float = 0.01, *,
+                 solver: str = 'cholesky', cg_steps: int = tkr_hip.ALS_CG_STEPS) -> None:
+        super().__init__(k, lu, lv, a, b, solver=solver, cg_steps=cg_steps)
         if not isinstance(d, (int, np.integer)) or d < 1:
             raise ValueError('CER: d = %r, the width of the content features, must be a positive integer' % (d,))
         if not lv > 0:
@@ -296,7 +333,7 @@ class CER(WMF):
         FF = torch.addmm(torch.eye(self.d, dtype=torch.float64, device=device), F.t(), F, beta=self.le, alpha=self.lv)
         FF = torch.linalg.cholesky(FF)
         w = Work(heavy_from)
-        hyper = dict(a=self.a, b=self.b, w=w)
+        hyper = dict(a=self.a, b=self.b, w=w, solver=self.solver, cg_steps=self.cg_steps)
         loss, self.losses = np.exp(50), []
         for it in range(max_iter):
             t1 = time.time()
@@ -541,8 +578,12 @@ class DPM(WMF):
     """single/dpm.py:10-76: WMF whose item rows have the prior v_j ~ encoder(f_j), the encoder an MLP on the item's content features
     trained on the item table after every alternation.  `le` is accepted and unused, as in the reference."""
 
-    def __init__(self, k: int, d: int, lu: float = 0.01, lv: float = 10, le: float = 10e3, a: float = 1, b: float = 0.01) -> None:
-        super().__init__(k, lu, lv, a, b)
+    def __init__(self, k: int, d: int, lu: float = 0.01, lv: float = 10, le: float = 10e3, a: float = 1, b: float = 0.01, *,
+                 solver: str = 'cholesky', cg_steps: int = tkr_hip.ALS_CG_STEPS) -> None:
+        if solver == 'cg' and isinstance(k, (int, np.integer)) and k > MAX_K:
+            raise ValueError("DPM: k = %r, 1 <= k <= %d is supported under either solver: the encoder als.MLP is bounded there "
+                             "(TKR_ALS_MAX_K), whatever solver='cg' allows WMF and CER" % (k, MAX_K))
+        super().__init__(k, lu, lv, a, b, solver=solver, cg_steps=cg_steps)
         if not isinstance(d, (int, np.integer)) or d < 1:
             raise ValueError('DPM: d = %r, the width of the content features, must be a positive integer' % (d,))
         if not lv > 0:
@@ -588,7 +629,7 @@ class DPM(WMF):
         U, V = foldin._upload(self.fue, device, np.float32), foldin._upload(self.fie, device, np.float32)
         F = foldin._upload(np.ascontiguousarray(self.feat, dtype=np.float32), device, np.float32)
         w = Work(heavy_from)
-        hyper = dict(a=self.a, b=self.b, w=w)
+        hyper = dict(a=self.a, b=self.b, w=w, solver=self.solver, cg_steps=self.cg_steps)
         self.losses = []
         for it in range(max_iter):                                 # no stopping test: dpm.py:31-60 runs every iteration
             t1 = time.time()

@@ -90,10 +90,11 @@ EXPORTS = ('tkr_version', 'tkr_plan_team', 'tkr_plan_max_blocks', 'tkr_sample_pl
            'tkr_matrix_tokens_host', 'tkr_group_count_dev', 'tkr_group_emit_dev', 'tkr_last_line_of_user_dev', 'tkr_compact_rows_count_dev',
            'tkr_compact_rows_emit_dev', 'tkr_fusion_features', 'tkr_fusion_sgd', 'tkr_fusion_user_weights', 'tkr_fusion_svm_sums',
            'tkr_mmr_select', 'tkr_list_pair_sums', 'tkr_line_metrics', 'tkr_bootstrap_sums', 'tkr_nearest_anchors', 'tkr_als_gram',
-           'tkr_als_solve_rows', 'tkr_als_solve_rows_prior', 'tkr_mlp_forward', 'tkr_mlp_fit')
+           'tkr_als_solve_rows', 'tkr_als_solve_rows_prior', 'tkr_mlp_forward', 'tkr_mlp_fit', 'tkr_als_cg_rows', 'tkr_als_gram_wide')
 EXPORTS_I64 = ('tkr_vbpr_workspace_floats', 'tkr_vbpr_colplan_lds_bytes', 'tkr_topk_workspace_bytes_for', 'tkr_topk_workspace_bytes', 'tkr_plan_workspace_bytes', 'tkr_like_ranks_workspace_bytes',
                'tkr_parse_dev_workspace_bytes', 'tkr_idtable_slots', 'tkr_scan_dev_workspace_bytes', 'tkr_als_workspace_bytes',
-               'tkr_als_prior_workspace_bytes', 'tkr_mlp_workspace_bytes', 'tkr_fusion_svm_partial_bytes')
+               'tkr_als_prior_workspace_bytes', 'tkr_mlp_workspace_bytes', 'tkr_fusion_svm_partial_bytes', 'tkr_als_cg_workspace_bytes',
+               'tkr_als_gram_wide_workspace_bytes')
 
 
 def lib():
@@ -1500,6 +1501,99 @@ def als_solve_rows_prior(Y, G, like_ptr, like_cols, X, prior, *, w_like, w_rhs, 
 
 
 ALS_HEAVY_FROM = 4 * ALS_GRAM_SLAB       # a row with this many likes is shared by several workgroups (scripts/time_als.py)
+
+
+# ---- K24: the half-step by conjugate gradients, the Gram at any width up to 512 (csrc/als_cg.hip) -------------------------------------------
+ALS_CG_MAX_K = 512           # TKR_ALS_CG_MAX_K of include/tkr.h: a row's x and r are 8 registers per lane each
+ALS_CG_STEPS = 3             # the steps per half-step als.py takes by default
+_ALS_CG_REFUSED = (None, _ALS_REFUSED[1], 'p.q of row %d is not positive and finite, or its solution is not finite', _ALS_REFUSED[3])
+
+
+class AlsCgRefused(AlsRefused):
+    """a status word of K24 that is not -1 (the kinds of K20; kind 2 is conjugate gradients' own)"""
+
+    def __init__(self, what, word):
+        self.word, self.row, self.kind = word, word >> 2, word & 3
+        TkrError.__init__(self, '%s: %s (kind %d)' % (what, _ALS_CG_REFUSED[self.kind] % self.row, self.kind))
+
+
+def _als_cg_table(what, name, t, k=None):
+    if not isinstance(t, torch.Tensor) or t.dtype != torch.float32 or t.dim() != 2 or not t.is_contiguous() or not t.is_cuda:
+        raise TkrError('%s: %s must be a contiguous two-dimensional float32 tensor on the GPU' % (what, name))
+    if t.shape[0] < 1 or (k is not None and t.shape[1] != k):
+        raise TkrError('%s: %s has shape %s' % (what, name, tuple(t.shape)))
+    if not 1 <= t.shape[1] <= ALS_CG_MAX_K:
+        raise ValueError('%s: k = %d, 1 <= k <= %d is supported' % (what, t.shape[1], ALS_CG_MAX_K))
+    return int(t.shape[0]), int(t.shape[1])
+
+
+def als_cg_workspace_bytes(n_x, k):
+    need = int(lib().tkr_als_cg_workspace_bytes(C.c_int64(n_x), C.c_int32(k)))
+    if need < 0:
+        raise TkrError('tkr_als_cg_workspace_bytes(%d, %d) failed: tkr error %d' % (n_x, k, need))
+    return need
+
+
+def als_gram_wide_workspace_bytes(k, n_slabs):
+    need = int(lib().tkr_als_gram_wide_workspace_bytes(C.c_int32(k), C.c_int64(n_slabs)))
+    if need < 0:
+        raise TkrError('tkr_als_gram_wide_workspace_bytes(%d, %d) failed: tkr error %d' % (k, n_slabs, need))
+    return need
+
+
+def als_gram_wide(Y, rows=None, scale=1.0, ridge=0.0, workspace=None, out=None, check=True):
+    """K24 -> G fp32 [k, k]: als_gram's definition, arguments and result for 1 <= k <= ALS_CG_MAX_K (include/tkr.h tkr_als_gram_wide)"""
+    what = 'als_gram_wide'
+    n, k = _als_cg_table(what, 'Y', Y)
+    if rows is not None:
+        _group_tensor(what, 'rows', rows, torch.int32, Y.device)
+    n_listed = n if rows is None else int(rows.numel())
+    need = als_gram_wide_workspace_bytes(k, (n_listed + ALS_GRAM_SLAB - 1) // ALS_GRAM_SLAB)
+    workspace = _als_workspace(workspace, need, Y.device)
+    G = torch.empty((k, k), dtype=torch.float32, device=Y.device) if out is None else out
+    status = torch.empty(1, dtype=torch.int64, device=Y.device)
+    rows_p = C.c_void_p(0) if rows is None else _p(rows if n_listed else Y)
+    _call('tkr_als_gram_wide', Y, _p(Y), C.c_int32(n), C.c_int32(k), rows_p, C.c_int64(n_listed), C.c_double(scale), C.c_double(ridge), _p(G),
+          _p(workspace), C.c_int64(workspace.numel() * workspace.element_size()), _p(status))
+    if not check:
+        return G, status
+    word = int(status.item())
+    if word != -1:
+        raise AlsRefused(what, word)
+    return G
+
+
+def als_cg_rows(Y, G, like_ptr, like_cols, X, *, w_like, w_rhs, ridge, steps=ALS_CG_STEPS, prior=None, w_prior=0.0, want_loss=False, check=True):
+    """K24, in place on X fp32 [n_x, k]: `steps` steps of conjugate gradients on (G + w_like sum y y^T + ridge I) x = w_rhs sum y
+    (+ w_prior prior[r]) from the value X[r] holds; without a prior the rows without likes are left as they are, with one every row is
+    solved (include/tkr.h tkr_als_cg_rows).  -> row_loss float64 [n_x] with want_loss, else None.  A refusal raises AlsCgRefused naming
+    row and kind; check=False returns (row_loss, status tensor) instead and reads nothing back"""
+    what = 'als_cg_rows'
+    n_y, k = _als_cg_table(what, 'Y', Y)
+    n_x, _ = _als_cg_table(what, 'X', X, k)
+    _als_cg_table(what, 'G', G, k)
+    if prior is not None:
+        _als_cg_table(what, 'prior', prior, k)
+    if G.shape[0] != k or X.device != Y.device or G.device != Y.device or (prior is not None and (prior.device != Y.device or prior.shape[0] != n_x)):
+        raise TkrError('%s: G must be [k, k], prior [n_x, k], and Y, G, X and prior on one GPU' % what)
+    _group_tensor(what, 'like_ptr', like_ptr, torch.int64, Y.device)
+    _group_tensor(what, 'like_cols', like_cols, torch.int32, Y.device)
+    if like_ptr.numel() != n_x + 1:
+        raise ValueError('%s: like_ptr must hold n_x + 1 = %d entries, not %d' % (what, n_x + 1, like_ptr.numel()))
+    if not isinstance(steps, (int,)) or isinstance(steps, bool) or steps < 0:
+        raise ValueError('%s: steps = %r must be an integer, at least 0' % (what, steps))
+    n_likes = int(like_cols.numel())
+    loss = torch.empty(n_x, dtype=torch.float64, device=Y.device) if want_loss else None
+    status = torch.empty(1, dtype=torch.int64, device=Y.device)
+    _call('tkr_als_cg_rows', Y, _p(Y), C.c_int32(n_y), C.c_int32(k), _p(G), _p(like_ptr), _p(like_cols) if n_likes else C.c_void_p(0),
+          C.c_int64(n_likes), C.c_int64(n_x), C.c_double(w_like), C.c_double(w_rhs), C.c_double(ridge), C.c_int32(steps), _p(X), _p(loss),
+          _p(prior), C.c_double(w_prior), C.c_void_p(0), C.c_int64(0), _p(status))
+    if not check:
+        return loss, status
+    word = int(status.item())
+    if word != -1:
+        raise AlsCgRefused(what, word)
+    return loss
 
 
 # ---- K22: a dense MLP content encoder, applied and trained (csrc/mlp.hip) ------------------------------------------------------------------

@@ -1,6 +1,7 @@
 """Training driver for WMF, CER and DPM -- the reference's train.py:18-36 with its constants as options:
 
     cd top-k-rec_amd && python train_als.py -d data -o embed/wmf -k 50 --iters 200 --tol 1e-4
+    cd top-k-rec_amd && python train_als.py -d data -o embed/wmf256 -k 256 --solver cg --cg-steps 3
     cd top-k-rec_amd && python train_als.py --model cer --content data/meta.pkl --dim 20000 -d data -o embed/cer -k 50
     cd top-k-rec_amd && python train_als.py --model dpm --content data/meta.pkl --dim 20000 -d data -o embed/dpm -k 50 --hidden 2000 1000
 
@@ -19,7 +20,9 @@ def main(argv=None):
     ap = argparse.ArgumentParser(description=__doc__.split('\n')[0])
     ap.add_argument('-d', '--data', default='data', help='directory with uid, vid and f<FOLD>tr.txt')
     ap.add_argument('-o', '--out', default='embed/wmf', help='model directory to write (read first when it holds a model)')
-    ap.add_argument('-k', type=int, default=50, help='factors, at most 128')
+    ap.add_argument('-k', type=int, default=50, help="factors, at most 128 (512 for wmf and cer under --solver cg)")
+    ap.add_argument('--solver', choices=('cholesky', 'cg'), default='cholesky', help='the half-step: per-row Gram + Cholesky (K20), or conjugate gradients (K24)')
+    ap.add_argument('--cg-steps', type=int, default=3, metavar='N', help='--solver cg: steps of conjugate gradients per half-step')
     ap.add_argument('--iters', type=int, default=200, help='iterations at most (max_iter)')
     ap.add_argument('--tol', type=float, default=1e-4, help='stop when the loss changes by less than this, relatively')
     ap.add_argument('--lu', type=float, default=0.01)
@@ -46,17 +49,18 @@ def main(argv=None):
         ap.error('--hidden, --mlp-lr, --batch and --mlp-seed go with --model dpm')
     lv = args.lv if args.lv is not None else (10.0 if cer or dpm else 0.01)
     encoder, batch = None, 64 if args.batch is None else args.batch
+    how = dict(solver=args.solver, cg_steps=args.cg_steps)
     try:
         if dpm:
             if not 1 <= batch <= 256:
                 raise ValueError('--batch %d: 1 <= batch <= 256 is supported' % batch)
-            model = DPM(k=args.k, d=args.dim, lu=args.lu, lv=lv, le=args.le, a=args.a, b=args.b)
+            model = DPM(k=args.k, d=args.dim, lu=args.lu, lv=lv, le=args.le, a=args.a, b=args.b, **how)
             encoder = MLP(args.k, args.dim, lr=1e-4 if args.mlp_lr is None else args.mlp_lr, hidden_layers=(2000, 1000) if args.hidden is None else args.hidden,
                           seed=args.seed if args.mlp_seed is None else args.mlp_seed)
         elif cer:
-            model = CER(k=args.k, d=args.dim, lu=args.lu, lv=lv, le=args.le, a=args.a, b=args.b)
+            model = CER(k=args.k, d=args.dim, lu=args.lu, lv=lv, le=args.le, a=args.a, b=args.b, **how)
         else:
-            model = WMF(k=args.k, lu=args.lu, lv=lv, a=args.a, b=args.b)
+            model = WMF(k=args.k, lu=args.lu, lv=lv, a=args.a, b=args.b, **how)
     except ValueError as e:
         ap.error(str(e))
     model.load_training_data(os.path.join(args.data, 'uid'), os.path.join(args.data, 'vid'), os.path.join(args.data, 'f%dtr.txt' % args.fold),
