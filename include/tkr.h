@@ -341,6 +341,19 @@ int tkr_vbpr_run_cols(const tkr_vbpr_state* st, const int32_t* tri_i, const int3
  *     train-rated by row's user (evaluate.py:98); built by tkr_build_rated_mask into a zeroed buffer
  *   out_ids [n_rows, K]: the K best unrated columns, descending score, ties -> higher column first;
  *     -1 where fewer than K unrated columns exist.  out_scores (nullable) alike, -inf padded.
+ *   THE CANONICAL ORDER (K4, K6, K8 and K12 rank by it) covers every fp32 value a score can take:
+ *       NaN  >  +inf  >  the finite scores  >  -inf;   ties -> the higher column first.
+ *     All NaNs tie, whatever their sign and payload (the GPU makes positive ones, an x86 host and a "-nan" token of a model
+ *     file negative ones); -0.0 == +0.0.  It is np.argsort(scores, kind='stable') read backwards -- numpy sorts a NaN of either
+ *     sign as the largest value -- that is oracle/ref_np.py filtered_topk(canonical=True), the order evaluate.py:81 gives a model
+ *     that diverged.  An unrated column is listed whatever its score: a NaN column comes first, a true -inf score is an entry
+ *     with its id.  out_scores (and K12's score_out) hold A NaN for a NaN score, the payload is not specified; every other score
+ *     keeps its bits.  -1 / -inf is the padding of a short list and nothing else.
+ *     Under mode 2 a user block is ranked by the mode-1 kernel when its margin means nothing: the user row or the item table or
+ *     the bias holds a NaN or an infinity, |u| * max|v_i| + max|bias| comes near fp32's range, or the largest |element| of the
+ *     row (of the table) is outside [2^-47, 2^60) and not 0 -- the row's sum of squares or the fp16 scaling would overflow or
+ *     underflow --, or max|bias| in the user's scaled units leaves fp32's range.  What the fp16 pass made of such a block is thrown
+ *     away, the thresholds it published included; the lists are mode 1's either way (tests/test_gpu_nonfinite_scores.py).
  *   workspace (nullable, device, workspace_bytes): scratch for per-item-range partial lists; with
  *     tkr_topk_workspace_bytes(n_rows, K) bytes the launch splits the catalogue so that the grid fills
  *     the 256 CUs in whole rounds (results are identical with or without it)
@@ -385,7 +398,8 @@ int tkr_count_hits(const int32_t* ids, int32_t n_rows, int32_t K, const int64_t*
  * utils.evaluate buckets a hit by the item's RAW rank t -- train-rated columns included (utils.py:113-117:
  * j = t // step) -- and sums reciprocal ranks 1/(t+1).  With ids = K4's first K unrated columns of each row,
  *   raw_rank[r][p] = p + #{rated columns of row r ranked before ids[r][p]}   (-1 where ids is -1)
- * under the canonical order (descending score, ties -> higher column first); kept and rated columns are scored
+ * under K4's canonical order over every fp32 value (NaN > +inf > finite > -inf, all NaNs tie, ties -> higher column first: a rated
+ * column whose score is NaN is in front of every kept column that is not); kept and rated columns are scored
  * by the fp32 chain of tkr_score_topk's modes 1 and 2 (fl(acc + bias), -0.0 -> +0.0): the bits the kept list was
  * ordered by, so the count agrees with K4, K8 and K12 down to the last ulp.  rated_ptr/rated_cols: the CSR given to
  * tkr_build_rated_mask (columns in [0, n_cols) of Vt; they are not checked).
@@ -407,7 +421,8 @@ int tkr_count_hits_rr(const int32_t* ids, const int32_t* raw_rank, int32_t n_row
  *   rank_out[e] = -1 when l is masked for the row (a rated like is never reached by the reference walk) or not in [0, n_cols)
  *   rank_out[e] = #{c < n_cols unmasked, c != l : s(r,c) > s(r,l) or (s(r,c) == s(r,l) and c > l)} otherwise
  * -- the number of kept columns in front of l in K4's canonical order, with s the mode-1 score above (the fma chain, fl(acc + bias),
- * -0.0 -> +0.0), bit for bit: a like at position p of tkr_score_topk's list has rank p.  Integer and deterministic.  accuracy@k for
+ * -0.0 -> +0.0), bit for bit, and ">" / "==" those of the canonical order stated there (every NaN one score above +inf, whatever its
+ * sign and payload): a like at position p of tkr_score_topk's list has rank p.  Integer and deterministic.  accuracy@k for
  * any step / total, AUC, NDCG, MRR and MAP all follow from the ranks (top-k-rec_amd/rankmetrics.py).
  * k <= 256: the fp32-MFMA tile loop of K4 with a counting epilogue (the sorted like scores of a user block and one counter each in
  * LDS, a binary search per score; item ranges of a block add up in rank_out by integer atomics); k > 256: one wave per row, a lane
@@ -434,7 +449,8 @@ int tkr_like_ranks(const float* U, const int32_t* user_idx, int32_t n_rows, cons
  * ranked alone gives what it gives inside a larger call.  When a row lists every column 0 .. n_cols-1, the entry with rank p < K is
  * position p of tkr_score_topk's list with the same score bits (every k; tests/test_gpu_score_chain.py),
  * and the rank of every liked column is tkr_like_ranks's rank (every k).  A column outside [0, n_cols) is never dereferenced: score
- * -inf, rank -1.  A score that is NaN has no defined rank.
+ * -inf, rank -1.  ">" and "equal" are those of K4's canonical order over every fp32 value: a NaN score (any sign, any payload) is
+ * above +inf and ties with every other NaN; score_out holds a NaN for it.
  * Shapes: any k, empty rows, any n_rows, a row of any length up to n_cols.  A row of at most TKR_CANDIDATES_RESIDENT entries belongs to
  * one wave from first score to last rank (a lane per candidate on the chain; the item rows of 64 candidates at a time come through LDS
  * in slabs of k when k % 8 == 0, otherwise every lane gathers its own; the list's 32-bit ordered keys stay in LDS and lane e counts

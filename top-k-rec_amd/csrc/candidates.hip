@@ -6,7 +6,7 @@
 //                  #{e' of the row, unmasked, e' != e : s(r, c_e') > s(r, c_e) or (equal and c_e' > c_e)}
 //
 // -- K4's canonical order restricted to the list.  The columns of a row are strictly ascending, so "c_e' > c_e" is "e' > e": the list
-// is held as one 32-bit key per entry (ordered score bits; 0 = masked, below every score), and with t = key - 1 for the entries behind
+// is held as one 32-bit key per entry (rank_bits of the score: every NaN one key above +inf; 0 = masked, below every score), and with t = key - 1 for the entries behind
 // the own one and t = key for those in front of it the rank is #{e' : key_e' > t_e'}: one compare and one add per pair.
 //
 // Two launches, no atomics, no workspace:
@@ -44,7 +44,7 @@ __device__ __forceinline__ CandEntry cand_entry(const float* __restrict__ up, co
     if ((uint32_t)c >= (uint32_t)n_cols) { r.score = -INFINITY; r.key = 0u; return r; }
     r.score = exact_score(up, Vt + (size_t)c * k, k, bias, c);
     const bool masked = mask && col_masked(mask, pitch, row, c);
-    r.key = masked ? 0u : ordered_bits(r.score);
+    r.key = masked ? 0u : rank_bits(r.score);
     return r;
 }
 
@@ -124,7 +124,7 @@ __global__ __launch_bounds__(kCandWaves * TKR_WAVE) void cand_rows_kernel(
                 if (!live) sc = -INFINITY;
                 score_out[e0 + i] = sc;
                 const bool masked = !live || (mask && col_masked(mask, pitch, row, c));
-                key = masked ? 0u : ordered_bits(sc);
+                key = masked ? 0u : rank_bits(sc);
             }
             keys[i] = key;
         }
@@ -173,7 +173,7 @@ __global__ __launch_bounds__(256) void cand_long_kernel(
             const int c = cand_cols[e0 + i];
             if ((uint32_t)c >= (uint32_t)n_cols) return 0u;
             const bool masked = mask && col_masked(mask, pitch, row, c);
-            return masked ? 0u : ordered_bits(score_out[e0 + i]);
+            return masked ? 0u : rank_bits(score_out[e0 + i]);
         };
         for (int b0 = 0; b0 < L; b0 += 256) {
             const int i = b0 + tid;

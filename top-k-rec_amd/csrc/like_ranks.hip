@@ -2,8 +2,9 @@
 // accuracy@k (evaluate.py:96-112, any step / total) all follow.
 //
 //   rank_out[e] = #{unrated columns c != l ahead of l = like_cols[e] in the canonical order of its row}
-//               = #{c unmasked : key(c) > key(l)},   key = ordered score bits << 32 | column
-// (descending score, ties -> higher column first; -0.0 ties with 0.0), or -1 when l itself is rated: the reference walk never
+//               = #{c unmasked : key(c) > key(l)},   key = rank_bits(score) << 32 | column
+// (K4's canonical order over every fp32 value, include/tkr.h: descending score, every NaN one score above +inf, ties -> higher
+// column first; -0.0 ties with 0.0), or -1 when l itself is rated: the reference walk never
 // reaches a rated like.  The scores are K4's mode-1 bits (fp32 MFMA chain, fl(acc + bias)): exact_score for the likes, the
 // tile loop of score_topk_kernel for the catalogue -- same products, counting in place of selection.
 //
@@ -47,7 +48,7 @@ __device__ __forceinline__ int chunk_pos(int64_t v, int64_t origin, int n) {
     return d < 0 ? 0 : (d > n ? n : (int)d);
 }
 
-__device__ __forceinline__ uint64_t like_key(float s, int col) { return ((uint64_t)ordered_bits(s) << 32) | (uint32_t)col; }
+__device__ __forceinline__ uint64_t like_key(float s, int col) { return ((uint64_t)rank_bits(s) << 32) | (uint32_t)col; }
 
 // the CSR is usable: starts at 0 and fits the workspace (a workspace sized for fewer likes: every rank_out <- -2, nothing else runs)
 __device__ __forceinline__ bool like_csr_ok(const int64_t* __restrict__ like_ptr, int n_rows, int64_t cap) {

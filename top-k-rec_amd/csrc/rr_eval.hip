@@ -33,28 +33,28 @@ __global__ __launch_bounds__(256) void raw_rank_kernel(const float* __restrict__
     const float* up = U + (size_t)(uidx ? uidx[r] : r) * k;
     // kept columns: the scores K4 ordered them by
     int cp[kRawSlots], before[kRawSlots];
-    float sp[kRawSlots];
+    uint32_t sp[kRawSlots];                                      // rank_bits: K4's order over every fp32 value, every NaN one score above +inf
 #pragma unroll
     for (int i = 0; i < kRawSlots; ++i) {
         const int p = lane + 64 * i;
         cp[i] = p < K ? ids[(size_t)r * K + p] : -1;
-        sp[i] = -INFINITY;
+        sp[i] = 0u;
         before[i] = 0;
-        if (cp[i] >= 0) sp[i] = exact_score(up, Vt + (size_t)cp[i] * k, k, bias, cp[i]);
+        if (cp[i] >= 0) sp[i] = rank_bits(exact_score(up, Vt + (size_t)cp[i] * k, k, bias, cp[i]));
     }
     // rated columns, 64 at a time: lane j scores one, every lane compares it with its kept columns
     const int64_t q1 = rated_ptr[r + 1];
     for (int64_t q0 = rated_ptr[r]; q0 < q1; q0 += 64) {
         const int n = (int)min((int64_t)64, q1 - q0);
         int c = -1;
-        float s = -INFINITY;
+        uint32_t s = 0u;
         if (lane < n) {
             c = rated_cols[q0 + lane];
-            s = exact_score(up, Vt + (size_t)c * k, k, bias, c);
+            s = rank_bits(exact_score(up, Vt + (size_t)c * k, k, bias, c));
         }
         for (int j = 0; j < n; ++j) {
             const int cj = __shfl(c, j, 64);
-            const float sj = __shfl(s, j, 64);
+            const uint32_t sj = (uint32_t)__shfl((int)s, j, 64);
 #pragma unroll
             for (int i = 0; i < kRawSlots; ++i)
                 if (cp[i] >= 0 && (sj > sp[i] || (sj == sp[i] && cj > cp[i]))) before[i] += 1;

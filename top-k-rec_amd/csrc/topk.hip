@@ -15,7 +15,12 @@
 //
 // Canonical order: descending score, ties -> higher column first (= a stable
 // ascending argsort read backwards).  -0.0 is canonicalised to +0.0 so it ties with 0.0 like
-// numpy.  Accumulation order of the dot product: k-halves [0,KH) and [KH,2KH) interleaved by
+// numpy, and every NaN to ONE NaN that ranks above +inf, as numpy sorts it (include/tkr.h; topk_parts.h
+// rank_score): "reaches the threshold" is !(score < thr) with thresholds that are never NaN
+// (bound_score), the sorts run on ordered bits, in which that one NaN is above +inf.  Every loop whose
+// trip count hangs on a float ends whatever the scores are: the trims walk bit positions and slots, the
+// overflow loop of filter_tile retires one user's lanes per turn, the wide kernel walks columns.
+// Accumulation order of the dot product: k-halves [0,KH) and [KH,2KH) interleaved by
 // the MFMA, k ascending inside a half (one rounding per product; exact whenever all partial
 // sums are representable, which is what the golden G5/G6 fixtures guarantee).
 //
@@ -75,7 +80,7 @@ __device__ __forceinline__ float trim_user(const TopkSmem<IdT>& sm, int uw, int 
     if constexpr (REFINE) return refined;
     const uint32_t kb = __builtin_amdgcn_readlane((uint32_t)(key >> 32), K - 1);
     const uint32_t kf = (kb & 0x80000000u) ? (kb & 0x7fffffffu) : ~kb;
-    return (n >= K) ? __uint_as_float(kf) : -INFINITY;
+    return (n >= K) ? bound_score(__uint_as_float(kf)) : -INFINITY;     // K NaN scores: the bound is +inf
 }
 
 // Scheduled trim of ALL 32 users of a wave at once, one user per lane pair (half h scans entries
@@ -171,7 +176,7 @@ __device__ __forceinline__ float trim_all_users(const TopkSmem<IdT>& sm, int uw,
     if (active && h == 0) sm.cnt[uw] = mine + other;
     if constexpr (REFINE) return active ? refined : thr;
     const uint32_t f = (ob & 0x80000000u) ? (ob & 0x7fffffffu) : ~ob;
-    return active ? fmaxf(thr, __uint_as_float(f)) : thr;
+    return active ? fmaxf(thr, bound_score(__uint_as_float(f))) : thr;
 }
 
 // One visit of the filter's fast path (filter_tile): the lanes of mask m append register R of the score block to their lists.
@@ -186,7 +191,7 @@ struct FastVisit {
             asm volatile("" ::: "memory");                       // keeps the scalar branch
             uint64_t m = hr[R];
             if constexpr (MASKED) m = __ballot((hits & (1u << R)) != 0u);
-            const float val = REFINE ? sc[R] : chain_pos_zero(sc[R]);     // (refine: rescored exactly later)
+            const float val = REFINE ? sc[R] : rank_score(chain_pos_zero(sc[R]));     // (refine: finite, rescored exactly later)
             uint64_t saved;
             uint32_t id;
             if constexpr (sizeof(IdT) == 2)
@@ -255,11 +260,11 @@ __device__ __forceinline__ void filter_tile(const TopkSmem<IdT>& sm, const f32x1
     }
     uint64_t hr[16], any = 0;
 #pragma unroll
-    for (int r = 0; r < 16; ++r) { hr[r] = __ballot(sc[r] >= thr); any |= hr[r]; }
+    for (int r = 0; r < 16; ++r) { hr[r] = __ballot(!(sc[r] < thr)); any |= hr[r]; }     // "reaches thr": a NaN score always does
     if (!any) return;
     uint32_t hits = 0;                                           // bit r: register r of this lane is a candidate
 #pragma unroll
-    for (int r = 0; r < 16; ++r) hits |= (sc[r] >= thr) ? (1u << r) : 0u;
+    for (int r = 0; r < 16; ++r) hits |= !(sc[r] < thr) ? (1u << r) : 0u;
     // register r <-> mask bit (r&3) + 8*(r>>2): gather the four nibbles at bits 0, 8, 16, 24 of ~mh
     const uint32_t nm = ~mh, raw_hits = hits;
     hits &= (nm & 0xfu) | ((nm >> 4) & 0xf0u) | ((nm >> 8) & 0xf00u) | ((nm >> 12) & 0xf000u);
@@ -286,7 +291,7 @@ __device__ __forceinline__ void filter_tile(const TopkSmem<IdT>& sm, const f32x1
             asm volatile("" ::: "memory");                       // (keeps the branch: the body must not be if-converted)
             if (hits & (1u << r)) {
                 if (pos < kCap) {
-                    sm.cs[pos * users + uw] = chain_pos_zero(sc[r]);
+                    sm.cs[pos * users + uw] = rank_score(chain_pos_zero(sc[r]));
                     sm.ci[pos * users + uw] = (IdT)(t * 32 + (r & 3) + 8 * (r >> 2) + 4 * h);
                 } else {
                     unplaced |= 1u << r;                         // list full: trimmed below, then appended
@@ -306,10 +311,10 @@ __device__ __forceinline__ void filter_tile(const TopkSmem<IdT>& sm, const f32x1
             thr = fmaxf(thr, nt);                                // never below what another item range published
 #pragma unroll
             for (int r = 0; r < 16; ++r)
-                if ((unplaced & (1u << r)) && sc[r] >= thr) {
+                if ((unplaced & (1u << r)) && !(sc[r] < thr)) {
                     const int p2 = atomicAdd(&sm.cnt[uw], 1);
                     if (!REFINE || p2 < kCap) {
-                        sm.cs[p2 * users + uw] = chain_pos_zero(sc[r]);
+                        sm.cs[p2 * users + uw] = rank_score(chain_pos_zero(sc[r]));
                         sm.ci[p2 * users + uw] = (IdT)(t * 32 + (r & 3) + 8 * (r >> 2) + 4 * h);
                     } else {
                         *lost = true;
@@ -821,9 +826,10 @@ __global__ __launch_bounds__((topk_waves_bf16<KS, IdT>() * TKR_WAVE), 2) void sc
     // ---- B operand: lane (user ul, k-group h) holds elements 16s + 8h .. +7 of its user's row, scaled to fp16
     f16x8 hreg[KS];
     float margin, bscale, sv;
-    refine_prologue<KS>(U + (size_t)(user_ok ? (uidx ? uidx[row] : row) : 0) * k, k, user_ok, h, extra, hreg, margin, bscale, sv);
+    bool sane;
+    refine_prologue<KS>(U + (size_t)(user_ok ? (uidx ? uidx[row] : row) : 0) * k, k, user_ok, h, extra, hreg, margin, bscale, sv, sane);
     const float m2 = 2.f * margin;
-    bool lost = false;
+    bool lost = user_ok && !sane;                                // the margin cannot speak for this user: its block goes to the fp32 kernel (refine_prologue)
     for (int s = tid; s < users; s += blockDim.x) sm.cnt[s] = 0;
     float thr = (thr_shared && user_ok) ? unordered_bits(thr_shared[row]) : -INFINITY;   // what other item ranges found so far
     thr = thr * bscale - margin;
@@ -986,7 +992,9 @@ __global__ __launch_bounds__((topk_waves_bf16<KS, IdT>() * TKR_WAVE), 2) void sc
                                                            tile, 2 * TILEB);                                    // the tile buffers are free now
 }
 
-// max_i |v_i| (2-norm, rounded up) and max_i |bias_i| for the margin of the bound-and-refine kernel; bounds[] zeroed before
+// max_i |v_i| (2-norm, rounded up) and max_i |bias_i| for the margin of the bound-and-refine kernel; bounds[] zeroed before.
+// fmaxf leaves a NaN out: a column whose sum of squares is NaN or infinite (a NaN or infinite factor, or squares that overflow) and a
+// bias that is NaN or infinite make max_i |v_i| = +inf instead, which no user's margin survives (refine_prologue, `sane`).
 __global__ __launch_bounds__(256) void topk_bounds_kernel(const float* __restrict__ Vt, const float* __restrict__ bias, int n_cols,
                                                          int k, uint32_t* __restrict__ bounds) {
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
@@ -1009,8 +1017,12 @@ __global__ __launch_bounds__(256) void topk_bounds_kernel(const float* __restric
                 emax = fmaxf(emax, fmaxf(fmaxf(fabsf(v[u].x), fabsf(v[u].y)), fmaxf(fabsf(v[u].z), fabsf(v[u].w))));
 #pragma unroll
                 for (int o = 16; o > 0; o >>= 1) ss += __shfl_xor(ss, o, 64);
-                vmax = fmaxf(vmax, sqrtf(ss) * 1.001f);
-                if (bias && col < n_cols && l == 0) bmax = fmaxf(bmax, fabsf(bias[col]));
+                vmax = (ss <= 3e38f) ? fmaxf(vmax, sqrtf(ss) * 1.001f) : INFINITY;
+                if (bias && col < n_cols && l == 0) {
+                    const float b = fabsf(bias[col]);
+                    bmax = fmaxf(bmax, b);
+                    if (!(b <= 3e38f)) vmax = INFINITY;
+                }
             }
         }
         vmax = fmaxf(vmax, __shfl_xor(vmax, 32, 64));
@@ -1021,8 +1033,12 @@ __global__ __launch_bounds__(256) void topk_bounds_kernel(const float* __restric
             for (int e = lane; e < k; e += 64) { const float v = Vt[(size_t)col * k + e]; ss = fmaf(v, v, ss); emax = fmaxf(emax, fabsf(v)); }
 #pragma unroll
             for (int o = 32; o > 0; o >>= 1) ss += __shfl_xor(ss, o, 64);
-            vmax = fmaxf(vmax, sqrtf(ss) * 1.001f);
-            if (bias) bmax = fmaxf(bmax, fabsf(bias[col]));
+            vmax = (ss <= 3e38f) ? fmaxf(vmax, sqrtf(ss) * 1.001f) : INFINITY;
+            if (bias) {
+                const float b = fabsf(bias[col]);
+                bmax = fmaxf(bmax, b);
+                if (!(b <= 3e38f)) vmax = INFINITY;
+            }
         }
     }
 #pragma unroll
@@ -1342,6 +1358,14 @@ static int launch_fp32_planned(const TopkPlan& p, const float* U, const int32_t*
     return TKR_EUNSUPPORTED;
 }
 
+// The plan of the fp32 kernel that redoes the flagged user blocks of a bound-and-refine launch: the same work items, but the item
+// ranges of a block do not share thresholds.  The words of thr_shared hold what the fp16 pass published, and a user whose margin means
+// nothing (refine_prologue, `sane`) went through that pass with whatever its arithmetic gave: its bounds are not bounds.
+static TopkPlan redo_plan(TopkPlan p) {
+    p.thr_shared = nullptr;
+    return p;
+}
+
 static size_t topk_image_bytes(int n_cols, int k) {               // the fp16 tile image of the bound-and-refine arithmetic (k <= 128)
     const int KS = k <= 16 ? 1 : (k <= 32 ? 2 : (k <= 64 ? 4 : 8));
     return (size_t)((n_cols + 31) / 32) * 32 * KS * 32;
@@ -1400,7 +1424,7 @@ static int launch_topk_bf16(const float* U, const int32_t* uidx, int n_rows, con
             rc = launch_refine2(a, stream);
             if (rc != TKR_OK) return rc;
             // blocks with an overflowed list: the fp32 kernel on the same work items, merged where a block was cut
-            rc = launch_fp32_planned<IdT, topk_waves_bf16<KS, IdT>()>(p, U, uidx, n_rows, Vt, bias, n_cols, k, mask, pitch, K, out_ids, out_scores,
+            rc = launch_fp32_planned<IdT, topk_waves_bf16<KS, IdT>()>(redo_plan(p), U, uidx, n_rows, Vt, bias, n_cols, k, mask, pitch, K, out_ids, out_scores,
                                                                       p.extra + 4, stream);
             if (rc != TKR_OK) return rc;
             return merge_planned(p, users, n_rows, K, out_ids, out_scores, stream, p.extra + 4);
@@ -1416,8 +1440,8 @@ static int launch_topk_bf16(const float* U, const int32_t* uidx, int n_rows, con
     rc = (int)hipGetLastError();
     if (rc != TKR_OK) return rc;
     // blocks with an overflowed list: the fp32 kernel, same work items
-    rc = launch_fp32_planned<IdT, topk_waves_bf16<KS, IdT>()>(p, U, uidx, n_rows, Vt, bias, n_cols, k, mask, pitch, K, out_ids, out_scores, p.extra + 4,
-                                                              stream);
+    rc = launch_fp32_planned<IdT, topk_waves_bf16<KS, IdT>()>(redo_plan(p), U, uidx, n_rows, Vt, bias, n_cols, k, mask, pitch, K, out_ids, out_scores,
+                                                              p.extra + 4, stream);
     if (rc != TKR_OK) return rc;
     return merge_planned(p, users, n_rows, K, out_ids, out_scores, stream);
 }
@@ -1464,7 +1488,7 @@ __global__ __launch_bounds__(256) void score_topk_wide_kernel(const float* __res
         uint64_t key = 0ull;
         if (ok) {
             const float sc = exact_score(up, Vt + (size_t)col * k, k, bias, col);
-            const uint32_t ob = ordered_bits(sc);
+            const uint32_t ob = rank_bits(sc);
             if (ob >= kth) key = ((uint64_t)ob << 32) | ((uint32_t)col + 1u);
         }
         if (__ballot(key != 0ull) == 0) continue;

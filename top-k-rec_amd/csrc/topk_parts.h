@@ -19,6 +19,16 @@ __device__ __forceinline__ uint32_t ordered_bits(float s) {      // monotone flo
     return (f & 0x80000000u) ? ~f : (f | 0x80000000u);
 }
 
+// The canonical order covers every fp32 value (include/tkr.h, K4): NaN > +inf > finite > -inf, and every NaN, whatever its sign and
+// payload, is the same score.  rank_score is that one NaN (the positive quiet one) for a NaN, s itself otherwise; rank_bits its
+// ordered bits, 0xffc00000 for a NaN: above +inf, never 0 and never 0xffffffff (the "absent" and "no rank" words of the keys).
+// bound_score turns a K-th best score into a filter threshold: +inf for a NaN -- thresholds are never NaN, and what reaches a
+// threshold t is !(s < t), which a NaN score always does.
+constexpr uint32_t kNanBits = 0x7fc00000u;
+__device__ __forceinline__ float rank_score(float s) { return (s != s) ? __uint_as_float(kNanBits) : s; }
+__device__ __forceinline__ uint32_t rank_bits(float s) { return (s != s) ? (kNanBits | 0x80000000u) : ordered_bits(s); }
+__device__ __forceinline__ float bound_score(float s) { return fminf(s, INFINITY); }
+
 // value of lane (lane ^ STRIDE).  Strides 1..8 stay in the VALU (DPP), 16 uses the LDS crossbar without
 // an address (ds_swizzle), only 32 needs a bpermute.
 __device__ __forceinline__ float unordered_bits(uint32_t ob) {    // inverse of ordered_bits; 0 -> below every float
@@ -259,9 +269,23 @@ typedef _Float16 f16x4 __attribute__((ext_vector_type(4)));
 // fp16 (hreg); the item factors are scaled by sv, scores live in units of bscale = su * sv.  `margin`: how far the approximate score
 // may be from the exact fp32 score in those units -- what makes the filter's lists supersets of the exact top K; derived in
 // csrc/topk.hip above score_topk_bf16_kernel.  extra: bits of [0] max |v_i|, [1] max |bias|, [2] max |V element|.
+// `sane`: the margin means what it says for this user.  It does not when the row or the item table holds a NaN or an infinity, when
+// |u| * max |v_i| + max |bias| comes near fp32's range (a score, or the bound the item ranges share, could overflow), or when
+// pow2_scale had to clamp (|13 - e| > 60: the scaled factors leave fp16's range, and sum u^2 its own -- it overflows above 2^64 and
+// loses the reach term below 2^-63; kept to largest elements in [2^-47, 2^60)), or when max |bias| in the user's scaled units leaves
+// fp32's range.  A user that is not sane flags its user block, which the fp32 kernel then ranks on its own (the list-overflow path,
+// without the thresholds this pass published: csrc/topk.hip redo_plan), so NaN and infinite scores are ranked by the fp32 kernel alone.
+// The user still goes through the fp16 pass, like its neighbours -- `sane` feeds the block flag and nothing inside the tile loop --
+// and what the pass makes of it (lists of valid columns, thresholds of its own row) is thrown away with the block.
+// topk_bounds_kernel reports a non-finite item table or bias as max |v_i| = +inf: then no user is sane.
+__device__ __forceinline__ bool pow2_scale_exact(float amax) {  // amax = 0, or pow2_scale(amax) is the unclamped power of two
+    const int e = (int)((__float_as_uint(amax) >> 23) & 0xffu) - 127;
+    return amax == 0.f || (e >= -47 && e < 60);
+}
+
 template <int KS>
 __device__ __forceinline__ void refine_prologue(const float* up, int k, bool user_ok, int h, const uint32_t* extra,
-                                                f16x8 (&hreg)[KS], float& margin, float& bscale, float& sv) {
+                                                f16x8 (&hreg)[KS], float& margin, float& bscale, float& sv, bool& sane) {
     constexpr int KPAD = KS * 16;
     float uv[KS][8];
     if ((k & 3) == 0) {                                          // two 16-byte loads per 16-wide k step, all issued before use
@@ -304,6 +328,9 @@ __device__ __forceinline__ void refine_prologue(const float* up, int k, bool use
     const float reach = sqrtf(nu) * 1.001f * __uint_as_float(extra[0]);      // >= |u| * max |v_i|
     margin = (fmaf(1.05f * 0.0009765625f, reach, 3.8146973e-6f * (reach + __uint_as_float(extra[1]))) + 7.7e-34f) * bscale +
              2.01f * (float)KPAD;
+    // (a NaN in the row: nu and the margin are NaN, fmaxf left it out of amax; an infinity: amax)
+    sane = reach + __uint_as_float(extra[1]) < 1e38f && margin < 1e38f && __uint_as_float(extra[1]) * bscale < 1e38f &&
+           pow2_scale_exact(amax) && pow2_scale_exact(__uint_as_float(extra[2]));
 }
 
 // acc <- fma(bias, bscale, acc) in the accumulator's own registers: the biases of a tile in the user's scaled units

@@ -325,9 +325,10 @@ __global__ __launch_bounds__(256, 3) void score_topk_refine2_kernel(const Refine
     // ---- B operand: lane (user ul, k-group h) holds elements 16s + 8h .. +7 of its user's row, scaled to fp16
     f16x8 hreg[KS];
     float margin, bscale, sv;
-    refine_prologue<KS>(a.U + (size_t)(user_ok ? (a.uidx ? a.uidx[row] : row) : 0) * k, k, user_ok, h, a.extra, hreg, margin, bscale, sv);
+    bool sane;
+    refine_prologue<KS>(a.U + (size_t)(user_ok ? (a.uidx ? a.uidx[row] : row) : 0) * k, k, user_ok, h, a.extra, hreg, margin, bscale, sv, sane);
     const float m2 = 2.f * margin;
-    bool lost = false;
+    bool lost = user_ok && !sane;                                // the margin cannot speak for this user: its block goes to the fp32 kernel (refine_prologue)
     const uint32_t seg0 = (uint32_t)(uintptr_t)(ent + (h * kSeg) * kR2Users + uw);      // LDS byte address of this lane's segment
     uint32_t wp = seg0;                                          // ... and of its next free slot: (wp - seg0) >> 9 entries are in
     float thr = (a.thr_shared && user_ok) ? unordered_bits(a.thr_shared[row]) : -INFINITY;   // what other pieces of the block found so far
