@@ -1003,7 +1003,7 @@ int tkr_als_solve_rows_prior(const float* Y, int32_t n_y, int32_t k, const float
                              double* row_loss, const float* prior, double w_prior, void* workspace, int64_t workspace_bytes, int64_t* status,
                              void* stream);
 
-/* ---- K24: the ALS half-step by conjugate gradients, and the Gram at any width up to 512 (csrc/als_cg.hip) --------------------------------
+/* ---- K24: the ALS half-step by conjugate gradients (csrc/als_cg.hip), and the Gram at any width up to 512 (csrc/als.hip) -----------------
  * A second, opt-in solver beside K20 / K21; 1 <= k <= TKR_ALS_CG_MAX_K (wider: TKR_E_UNSUPPORTED).  The
  * notation is tkr_als_solve_rows' and tkr_als_solve_rows_prior's.
  *

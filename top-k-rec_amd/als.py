@@ -19,8 +19,8 @@ whole loop, and one scalar (the loss, with the kernels' status words behind it) 
 the reference's package surface is pinned as it is, this class lives here.  What it writes (final-U.dat, final-V.dat, no final-B.dat)
 is a model directory like any other to evaluate.py, recommend.py and fuse.py.
 
-``WMF(k, ..., solver='cg', cg_steps=3)`` (K24, csrc/als_cg.hip; the same keywords on CER and DPM) takes cg_steps steps of conjugate
-gradients per row and half-step from the row's previous value in place of the per-row Gram + Cholesky: no k x k matrix per row, so
+``WMF(k, ..., solver='cg', cg_steps=3)`` (K24, csrc/als_cg.hip and the wide Gram of csrc/als.hip; the same keywords on CER and DPM)
+takes cg_steps steps of conjugate gradients per row and half-step from the row's previous value in place of the per-row Gram + Cholesky: no k x k matrix per row, so
 k <= 512 for WMF and CER.  The default, 'cholesky', is the path above with its bits and its bound k <= 128.
 
 ``CER`` (single/cer.py:16-85) is WMF with a prior on every item row, v_j ~ E^T f_j from the item's content features f_j, and a ridge
@@ -51,6 +51,7 @@ from __future__ import annotations
 
 import os
 import time
+import types
 
 import numpy as np
 import torch
@@ -81,9 +82,13 @@ class Work:
         return self._slabs[key]
 
     def room(self, need, device):
-        if self.workspace is None or self.workspace.device != device or self.workspace.numel() * 8 < need:
-            self.workspace = torch.empty(max(need, 16) // 8 + 1, dtype=torch.int64, device=device)
+        self.workspace = tkr_hip.workspace_room(self.workspace, need, device)
         return self.workspace
+
+    def gram(self, k, device):
+        if self.G is None or self.G.shape != (k, k) or self.G.device != device:
+            self.G = torch.empty((k, k), dtype=torch.float32, device=device)
+        return self.G
 
 
 def half_step(X, Y, like_ptr, like_cols, rated_y, *, w=None, ridge_in_G, ridge, a, b, want_loss=False, prior=None, w_prior=0.0,
@@ -99,34 +104,26 @@ def half_step(X, Y, like_ptr, like_cols, rated_y, *, w=None, ridge_in_G, ridge, 
     w = Work() if w is None else w
     n_x, k = int(X.shape[0]), int(Y.shape[1])
     n_listed = int(Y.shape[0]) if rated_y is None else int(rated_y.numel())
+    n_slabs = (n_listed + tkr_hip.ALS_GRAM_SLAB - 1) // tkr_hip.ALS_GRAM_SLAB
     if solver == 'cg':
-        ws = w.room(tkr_hip.als_gram_wide_workspace_bytes(k, (n_listed + tkr_hip.ALS_GRAM_SLAB - 1) // tkr_hip.ALS_GRAM_SLAB), Y.device)
-        if w.G is None or w.G.shape != (k, k) or w.G.device != Y.device:
-            w.G = torch.empty((k, k), dtype=torch.float32, device=Y.device)
-        _, s0 = tkr_hip.als_gram_wide(Y, rated_y, scale=b, ridge=ridge_in_G, workspace=ws, out=w.G, check=False)
-        loss, s1 = tkr_hip.als_cg_rows(Y, w.G, like_ptr, like_cols, X, w_like=a - b, w_rhs=a, ridge=ridge, steps=int(cg_steps), prior=prior,
-                                       w_prior=w_prior, want_loss=want_loss, check=False)
-        return loss, torch.cat([s0, s1])
-    if solver != 'cholesky':
+        ws = w.room(tkr_hip.als_gram_wide_workspace_bytes(k, n_slabs), Y.device)
+        gram, solve, more = tkr_hip.als_gram_wide, tkr_hip.als_cg_rows, dict(steps=int(cg_steps), prior=prior, w_prior=w_prior)
+    elif solver == 'cholesky':
+        need = tkr_hip.als_workspace_bytes(0, k, n_slabs)
+        slabs = None
+        if w.heavy_from <= int(like_cols.numel()):
+            slabs = w.heavy_slabs(like_ptr)
+            need = max(need, tkr_hip.als_workspace_bytes(n_x, k, slabs))
+        if prior is not None:
+            need = max(need, tkr_hip.als_prior_workspace_bytes(0 if slabs is None else n_x, k, slabs or 0))
+        ws = w.room(need, Y.device)
+        gram, solve, more = tkr_hip.als_gram, tkr_hip.als_solve_rows, dict(heavy_from=w.heavy_from, workspace=ws, heavy_slabs=slabs)
+        if prior is not None:
+            solve, more = tkr_hip.als_solve_rows_prior, dict(more, prior=prior, w_prior=w_prior)
+    else:
         raise ValueError("half_step: solver = %r, 'cholesky' and 'cg' are the ones there are" % (solver,))
-    n_likes = int(like_cols.numel())
-    need = tkr_hip.als_workspace_bytes(0, k, (n_listed + tkr_hip.ALS_GRAM_SLAB - 1) // tkr_hip.ALS_GRAM_SLAB)
-    slabs = None
-    if w.heavy_from <= n_likes:
-        slabs = w.heavy_slabs(like_ptr)
-        need = max(need, tkr_hip.als_workspace_bytes(n_x, k, slabs))
-    if prior is not None:
-        need = max(need, tkr_hip.als_prior_workspace_bytes(0 if slabs is None else n_x, k, slabs or 0))
-    ws = w.room(need, Y.device)
-    if w.G is None or w.G.shape != (k, k) or w.G.device != Y.device:
-        w.G = torch.empty((k, k), dtype=torch.float32, device=Y.device)
-    _, s0 = tkr_hip.als_gram(Y, rated_y, scale=b, ridge=ridge_in_G, workspace=ws, out=w.G, check=False)
-    if prior is not None:
-        loss, s1 = tkr_hip.als_solve_rows_prior(Y, w.G, like_ptr, like_cols, X, prior, w_like=a - b, w_rhs=a, w_prior=w_prior, ridge=ridge,
-                                                heavy_from=w.heavy_from, want_loss=want_loss, workspace=ws, heavy_slabs=slabs, check=False)
-        return loss, torch.cat([s0, s1])
-    loss, s1 = tkr_hip.als_solve_rows(Y, w.G, like_ptr, like_cols, X, w_like=a - b, w_rhs=a, ridge=ridge, heavy_from=w.heavy_from,
-                                      want_loss=want_loss, workspace=ws, heavy_slabs=slabs, check=False)
+    _, s0 = gram(Y, rated_y, scale=b, ridge=ridge_in_G, workspace=ws, out=w.gram(k, Y.device), check=False)
+    loss, s1 = solve(Y, w.G, like_ptr, like_cols, X, w_like=a - b, w_rhs=a, ridge=ridge, want_loss=want_loss, check=False, **more)
     return loss, torch.cat([s0, s1])
 
 
@@ -203,37 +200,76 @@ class WMF(REC):
 
     # ------------------------------------------------------------------ train (wmf.py:61-101)
     def train(self, max_iter: int = 200, tol: float = 1e-4, model_path: str = None, verbose: bool = True, device=None, heavy_from=None) -> None:
+        self._need_data('WMF.train')
+        self._train('WMF.train', max_iter, tol, model_path, verbose, device, heavy_from)
+
+    def _need_data(self, who):
         if self._csr is None:
-            raise ValueError('WMF.train: load_training_data() first')
+            raise ValueError('%s: load_training_data() first' % who)
+
+    # The one training loop of WMF, CER and DPM.  What the content-aware models add goes through the hooks below; `run` is the device
+    # state of one call: device, U, V and what _prepare puts beside them.
+    def _train(self, who, max_iter, tol, model_path, verbose, device, heavy_from, **options):
         if model_path is not None and os.path.isdir(model_path):
             self.import_embeddings(model_path)
         for name, table, rows in (('fue', self.fue, self.n_users), ('fie', self.fie, self.n_items)):
             if np.shape(table) != (rows, self.k):
-                raise ValueError('WMF.train: %s has shape %s, the model needs (%d, %d)' % (name, np.shape(table), rows, self.k))
-        device = foldin._device(device, 'WMF.train')
+                raise ValueError('%s: %s has shape %s, the model needs (%d, %d)' % (who, name, np.shape(table), rows, self.k))
+        run = self._prepare(who, device, **options)
+        device = run.device
         up, uc, ip, ic = (foldin._upload(x, device) for x in self._csr)
         u_rated = foldin._upload(np.asarray(self.u_rated, dtype=np.int32), device)
         i_rated = foldin._upload(np.asarray(self.i_rated, dtype=np.int32), device)
-        U, V = foldin._upload(self.fue, device, np.float32), foldin._upload(self.fie, device, np.float32)
-        w = Work(heavy_from)
-        hyper = dict(a=self.a, b=self.b, w=w, solver=self.solver, cg_steps=self.cg_steps)
+        U, V = run.U, run.V = foldin._upload(self.fue, device, np.float32), foldin._upload(self.fie, device, np.float32)
+        hyper = dict(a=self.a, b=self.b, w=Work(heavy_from), solver=self.solver, cg_steps=self.cg_steps)
+        steps = ('the user step of iteration %d', 'the item step of iteration %d')
         loss, self.losses = np.exp(50), []
         for it in range(max_iter):
             t1 = time.time()
             loss_old = loss
+            prior = self._prior(run)
             _, su = half_step(U, V, up, uc, i_rated, ridge_in_G=self.lu, ridge=0.0, **hyper)
-            rows, sv = half_step(V, U, ip, ic, u_rated, ridge_in_G=0.0, ridge=self.lv, want_loss=True, **hyper)
-            total = rows.sum() + 0.5 * self.lu * U.double().square().sum() + 0.5 * self.lv * V.double().square().sum()
-            down = torch.cat([total.reshape(1), su.double(), sv.double()]).cpu().numpy()      # one copy: the loss, the four status words behind it
-            check_status(down[1:], ('the user step of iteration %d' % it, 'the item step of iteration %d' % it))
+            rows, sv = half_step(V, U, ip, ic, u_rated, ridge_in_G=0.0, ridge=self.lv, want_loss=True, **prior, **hyper)
+            term, words = self._after_steps(run)
+            total = rows.sum() + 0.5 * self.lu * U.double().square().sum() + term
+            down = torch.cat([total.reshape(1), su.double(), sv.double()] + [x.double() for x in words]).cpu().numpy()      # one copy: the loss, the status words behind it
+            check_status(down[1:5], tuple(x % it for x in steps))
             loss = float(down[0])
+            self._check_iteration(who, it, loss, down[5:])
             self.losses.append(loss)
-            cond = abs(loss_old - loss) / loss_old
+            cond = abs(loss_old - loss) / loss_old if self.STOPS_ON_TOL else None
             if verbose:
-                tprint('Iter %3d, loss %.6f, converge %.6f, time %.2fs' % (it, loss, cond, time.time() - t1))
-            if cond < tol:
+                tprint('Iter %3d, loss %.6f, %stime %.2fs' % (it, loss, 'converge %.6f, ' % cond if self.LOGS_CONVERGE else '', time.time() - t1))
+            if self.STOPS_ON_TOL and cond < tol:
                 break
+        Fe = self._cold_rows(run)
+        if Fe is not None:
+            cold = np.setdiff1d(np.arange(self.n_items), np.asarray(self.i_rated, dtype=np.int64))
+            if len(cold):
+                at = foldin._upload(cold.astype(np.int64), device)
+                V[at] = Fe[at]
         self.fue, self.fie = U.cpu().numpy(), V.cpu().numpy()
+
+    STOPS_ON_TOL = LOGS_CONVERGE = True                            # the stopping test on tol; `converge` in the log line
+
+    def _prepare(self, who, device):
+        """-> the run: its device, and whatever else the model keeps on it for the loop (checked and uploaded here)"""
+        return types.SimpleNamespace(device=foldin._device(device, who))
+
+    def _prior(self, run):
+        """at the head of an iteration -> the keywords of the item half-step: none, or prior and w_prior"""
+        return {}
+
+    def _after_steps(self, run):
+        """behind the two half-steps -> (the model's own term of the loss, a device scalar; its own status words, a list of tensors)"""
+        return 0.5 * self.lv * run.V.double().square().sum(), []
+
+    def _check_iteration(self, who, it, loss, words):
+        """the downloaded loss and the words of _after_steps: raises where they say the iteration failed"""
+
+    def _cold_rows(self, run):
+        """behind the loop -> the table whose rows the items without a training like get, or None: they stay as they are"""
+        return None
 
     # ------------------------------------------------------------------ fold-in (new: the reference can only retrain)
     def fold_in(self, histories, device=None, heavy_from=None, steps=None):
@@ -272,6 +308,13 @@ def cer_train_bytes(n_users, n_items, k, d):
     return 8 * (d * d + n_items * d), 4 * k * (n_users + 2 * n_items + d)
 
 
+def _need_content(model, who):
+    if model.feat is None:
+        raise ValueError('%s: load_content_data() first' % who)
+    if np.shape(model.feat) != (model.n_items, model.d):
+        raise ValueError('%s: feat has shape %s, the model needs (%d, %d)' % (who, np.shape(model.feat), model.n_items, model.d))
+
+
 class CER(WMF):
     """single/cer.py:16-85.  The start: load_training_data(seed=) draws fue and fie as WMF does, and the SAME generator, carried on,
     draws E standard normal fp32 [d, k] in train() when no final-E.dat was imported -- one seed fixes all three."""
@@ -303,62 +346,38 @@ class CER(WMF):
 
     # ------------------------------------------------------------------ train (cer.py:24-73)
     def train(self, max_iter: int = 200, tol: float = 1e-4, model_path: str = None, verbose: bool = True, device=None, heavy_from=None) -> None:
-        if self._csr is None:
-            raise ValueError('CER.train: load_training_data() first')
-        if self.feat is None:
-            raise ValueError('CER.train: load_content_data() first')
-        if np.shape(self.feat) != (self.n_items, self.d):
-            raise ValueError('CER.train: feat has shape %s, the model needs (%d, %d)' % (np.shape(self.feat), self.n_items, self.d))
-        if model_path is not None and os.path.isdir(model_path):
-            self.import_embeddings(model_path)
-        for name, table, rows in (('fue', self.fue, self.n_users), ('fie', self.fie, self.n_items)):
-            if np.shape(table) != (rows, self.k):
-                raise ValueError('CER.train: %s has shape %s, the model needs (%d, %d)' % (name, np.shape(table), rows, self.k))
+        self._need_data('CER.train')
+        _need_content(self, 'CER.train')
+        self._train('CER.train', max_iter, tol, model_path, verbose, device, heavy_from)
+
+    def _prepare(self, who, device):
         if self.E is None:
             self.E = self._rng.standard_normal((self.d, self.k), dtype=np.float32)
-        self._check_E('CER.train')
-        device = foldin._device(device, 'CER.train')
+        self._check_E(who)
+        device = foldin._device(device, who)
         dense, tables = cer_train_bytes(self.n_users, self.n_items, self.k, self.d)
         free = torch.cuda.mem_get_info(device)[0]
         if dense + tables > free:
-            raise ValueError('CER.train: the fp64 features and FF need %d bytes (8 (d^2 + n_items d), d = %d, n_items = %d) and the tables '
-                             '%d; %d are free on %s' % (dense, self.d, self.n_items, tables, free, device))
-        up, uc, ip, ic = (foldin._upload(x, device) for x in self._csr)
-        u_rated = foldin._upload(np.asarray(self.u_rated, dtype=np.int32), device)
-        i_rated = foldin._upload(np.asarray(self.i_rated, dtype=np.int32), device)
-        U, V = foldin._upload(self.fue, device, np.float32), foldin._upload(self.fie, device, np.float32)
+            raise ValueError('%s: the fp64 features and FF need %d bytes (8 (d^2 + n_items d), d = %d, n_items = %d) and the tables '
+                             '%d; %d are free on %s' % (who, dense, self.d, self.n_items, tables, free, device))
         E = foldin._upload(np.ascontiguousarray(self.E, dtype=np.float32), device, np.float32)
         # the dense linear algebra is the library's, in fp64, rounded once: FF = lv F^T F + le I and its Cholesky factor, once per call
         F = foldin._upload(np.ascontiguousarray(self.feat, dtype=np.float32), device, np.float32).double()
         FF = torch.addmm(torch.eye(self.d, dtype=torch.float64, device=device), F.t(), F, beta=self.le, alpha=self.lv)
-        FF = torch.linalg.cholesky(FF)
-        w = Work(heavy_from)
-        hyper = dict(a=self.a, b=self.b, w=w, solver=self.solver, cg_steps=self.cg_steps)
-        loss, self.losses = np.exp(50), []
-        for it in range(max_iter):
-            t1 = time.time()
-            loss_old = loss
-            Fe = (F @ E.double()).float()
-            _, su = half_step(U, V, up, uc, i_rated, ridge_in_G=self.lu, ridge=0.0, **hyper)
-            rows, sv = half_step(V, U, ip, ic, u_rated, ridge_in_G=0.0, ridge=self.lv, want_loss=True, prior=Fe, w_prior=self.lv, **hyper)
-            E = torch.cholesky_solve(self.lv * (F.t() @ V.double()), FF).float()
-            # cer.py:63-65: the new E beside the Fe that entered the solve
-            total = rows.sum() + 0.5 * self.lu * U.double().square().sum() + 0.5 * self.le * E.double().square().sum()
-            down = torch.cat([total.reshape(1), su.double(), sv.double()]).cpu().numpy()      # one copy: the loss, the four status words behind it
-            check_status(down[1:], ('the user step of iteration %d' % it, 'the item step of iteration %d' % it))
-            loss = float(down[0])
-            self.losses.append(loss)
-            cond = abs(loss_old - loss) / loss_old
-            if verbose:
-                tprint('Iter %3d, loss %.6f, time %.2fs' % (it, loss, time.time() - t1))
-            if cond < tol:
-                break
-        Fe = (F @ E.double()).float()                              # cer.py:70-73: an item without a training like gets its content's row
-        cold = np.setdiff1d(np.arange(self.n_items), np.asarray(self.i_rated, dtype=np.int64))
-        if len(cold):
-            at = foldin._upload(cold.astype(np.int64), device)
-            V[at] = Fe[at]
-        self.fue, self.fie, self.E = U.cpu().numpy(), V.cpu().numpy(), E.cpu().numpy()
+        return types.SimpleNamespace(device=device, E=E, F=F, FF=torch.linalg.cholesky(FF))
+
+    def _prior(self, run):
+        return dict(prior=(run.F @ run.E.double()).float(), w_prior=self.lv)
+
+    def _after_steps(self, run):
+        run.E = torch.cholesky_solve(self.lv * (run.F.t() @ run.V.double()), run.FF).float()
+        return 0.5 * self.le * run.E.double().square().sum(), []      # cer.py:63-65: the new E beside the Fe that entered the solve
+
+    LOGS_CONVERGE = False
+
+    def _cold_rows(self, run):                                     # cer.py:70-73: an item without a training like gets its content's row
+        self.E = run.E.cpu().numpy()
+        return (run.F @ run.E.double()).float()
 
     def embed_items(self, feat):
         """fp32 [m, d] content features -> fp32 [m, k] = feat E, the fp64 product rounded once: the row of an item that was no line of
@@ -493,8 +512,7 @@ class MLP:
         return self._net
 
     def _room(self, need, device):
-        if self._ws is None or self._ws.device != device or self._ws.numel() * 8 < need:
-            self._ws = torch.empty(max(need, 16) // 8 + 1, dtype=torch.int64, device=device)
+        self._ws = tkr_hip.workspace_room(self._ws, need, device)
         return self._ws
 
     @staticmethod
@@ -603,58 +621,42 @@ class DPM(WMF):
     # ------------------------------------------------------------------ train (dpm.py:20-64)
     def train(self, encoder=MLP, max_iter: int = 200, model_path: str = None, verbose: bool = True, device=None, heavy_from=None,
               batch_size: int = 64) -> None:
-        if self._csr is None:
-            raise ValueError('DPM.train: load_training_data() first')
-        if self.feat is None:
-            raise ValueError('DPM.train: load_content_data() first')
-        if np.shape(self.feat) != (self.n_items, self.d):
-            raise ValueError('DPM.train: feat has shape %s, the model needs (%d, %d)' % (np.shape(self.feat), self.n_items, self.d))
+        self._need_data('DPM.train')
+        _need_content(self, 'DPM.train')
         _check_batch('DPM.train', batch_size)
         self.encoder = encoder(self.k, self.d) if isinstance(encoder, type) else encoder
         self._check_encoder('DPM.train')
-        if model_path is not None and os.path.isdir(model_path):
-            self.import_embeddings(model_path)
-        for name, table, rows in (('fue', self.fue, self.n_users), ('fie', self.fie, self.n_items)):
-            if np.shape(table) != (rows, self.k):
-                raise ValueError('DPM.train: %s has shape %s, the model needs (%d, %d)' % (name, np.shape(table), rows, self.k))
-        device = _cuda(device, 'DPM.train')
+        self._train('DPM.train', max_iter, None, model_path, verbose, device, heavy_from, batch_size=batch_size)
+
+    STOPS_ON_TOL = LOGS_CONVERGE = False                           # no stopping test: dpm.py:31-60 runs every iteration
+
+    def _prepare(self, who, device, batch_size):
+        device = _cuda(device, who)
         features, tables, enc = dpm_train_bytes(self.n_users, self.n_items, self.k, self.d, self.encoder.widths, batch_size)
         free = torch.cuda.mem_get_info(device)[0]
         if features + tables + enc > free:
-            raise ValueError('DPM.train: the features need %d bytes (4 n_items d, d = %d, n_items = %d), the tables %d and the encoder with its '
-                             'workspace %d; %d are free on %s' % (features, self.d, self.n_items, tables, enc, free, device))
-        up, uc, ip, ic = (foldin._upload(x, device) for x in self._csr)
-        u_rated = foldin._upload(np.asarray(self.u_rated, dtype=np.int32), device)
-        i_rated = foldin._upload(np.asarray(self.i_rated, dtype=np.int32), device)
-        U, V = foldin._upload(self.fue, device, np.float32), foldin._upload(self.fie, device, np.float32)
+            raise ValueError('%s: the features need %d bytes (4 n_items d, d = %d, n_items = %d), the tables %d and the encoder with its '
+                             'workspace %d; %d are free on %s' % (who, features, self.d, self.n_items, tables, enc, free, device))
         F = foldin._upload(np.ascontiguousarray(self.feat, dtype=np.float32), device, np.float32)
-        w = Work(heavy_from)
-        hyper = dict(a=self.a, b=self.b, w=w, solver=self.solver, cg_steps=self.cg_steps)
-        self.losses = []
-        for it in range(max_iter):                                 # no stopping test: dpm.py:31-60 runs every iteration
-            t1 = time.time()
-            Fe = self.encoder.out(F)
-            V.copy_(Fe)                                            # dpm.py:33: the item table IS the encoder's output when the users are solved
-            _, su = half_step(U, V, up, uc, i_rated, ridge_in_G=self.lu, ridge=0.0, **hyper)
-            rows, sv = half_step(V, U, ip, ic, u_rated, ridge_in_G=0.0, ridge=self.lv, want_loss=True, prior=Fe, w_prior=self.lv, **hyper)
-            fit, se = self.encoder._fit_device(F, V, batch_size)
-            total = rows.sum() + 0.5 * self.lu * U.double().square().sum() + fit.sum()
-            down = torch.cat([total.reshape(1), su.double(), sv.double(), se.double()]).cpu().numpy()      # one copy: the loss, the five status words behind it
-            check_status(down[1:5], ('the user step of iteration %d' % it, 'the item step of iteration %d' % it))
-            if int(down[5]) != -1:
-                raise tkr_hip.MlpRefused('the encoder step of iteration %d' % it, int(down[5]))
-            loss = float(down[0])
-            if not np.isfinite(loss):
-                raise FloatingPointError('DPM.train: the loss of iteration %d is %r' % (it, loss))
-            self.losses.append(loss)
-            if verbose:
-                tprint('Iter %3d, loss %.6f, time %.2fs' % (it, loss, time.time() - t1))
-        Fe = self.encoder.out(F)                                   # dpm.py:61-64: an item without a training like gets its content's row
-        cold = np.setdiff1d(np.arange(self.n_items), np.asarray(self.i_rated, dtype=np.int64))
-        if len(cold):
-            at = foldin._upload(cold.astype(np.int64), device)
-            V[at] = Fe[at]
-        self.fue, self.fie = U.cpu().numpy(), V.cpu().numpy()
+        return types.SimpleNamespace(device=device, F=F, batch_size=batch_size)
+
+    def _prior(self, run):
+        Fe = self.encoder.out(run.F)
+        run.V.copy_(Fe)                                            # dpm.py:33: the item table IS the encoder's output when the users are solved
+        return dict(prior=Fe, w_prior=self.lv)
+
+    def _after_steps(self, run):
+        fit, se = self.encoder._fit_device(run.F, run.V, run.batch_size)
+        return fit.sum(), [se]
+
+    def _check_iteration(self, who, it, loss, words):
+        if int(words[0]) != -1:
+            raise tkr_hip.MlpRefused('the encoder step of iteration %d' % it, int(words[0]))
+        if not np.isfinite(loss):
+            raise FloatingPointError('%s: the loss of iteration %d is %r' % (who, it, loss))
+
+    def _cold_rows(self, run):                                     # dpm.py:61-64: an item without a training like gets its content's row
+        return self.encoder.out(run.F)
 
     def embed_items(self, feat):
         """fp32 [m, d] content features -> fp32 [m, k] = encoder.out(feat): the row of an item that was no line of vid, by the rule

@@ -3,7 +3,7 @@
 //   G = scale * sum over the rated rows y of  y y^T  (+ ridge I)                               tkr_als_gram
 //   for every row r with likes:  (G + w_like * sum_{y in L_r} y y^T + ridge I) x_r = w_rhs * sum_{y in L_r} y      tkr_als_solve_rows
 //
-// Both are built on ONE piece of code, slab_sum: a workgroup of 256 threads sums y y^T over a list of rows of Y.  The rows are
+// Both are built on ONE piece of code, slab_sum (csrc/als_parts.h): a workgroup of 256 threads sums y y^T over a list of rows of Y.  The rows are
 // gathered 32 at a time into LDS (columns padded with zeros to whole 32-blocks, a refused row staged as zeros), and the four waves
 // multiply the tile with itself on the exact-fp32 MFMA (v_mfma_f32_32x32x2_f32): the contraction runs over the staged rows, two per
 // instruction, so every element of the sum is one fp32 fma chain in list order -- the same bits run to run.  Only the 32 x 32 blocks
@@ -13,7 +13,12 @@
 //   als_slab_kernel<KT>     one workgroup per slab of TKR_ALS_GRAM_SLAB listed rows -> an fp32 partial [k * k | k column sums | count]
 //                           in the workspace.  Two uses: the slabs of tkr_als_gram's row list, and the slabs of the HEAVY rows of a
 //                           solve (a row with heavy_from likes or more: several workgroups share it).
-//   als_gram_reduce_kernel  adds the partials in ascending slab order in fp64, applies scale and ridge, rounds once.
+//   als_wide_slab_kernel    K24, tkr_als_gram_wide: the slab sum for k <= 512, the slab's rows staged as slab_sum stages them, the
+//                           32 x 32 blocks on and above the diagonal dealt to passes of 12 (blockIdx.y), 3 per wave:
+//                           the accumulators als_slab_kernel<4> holds.  An element is the same fp32 fma chain in list order whichever
+//                           pass and wave has its block, so for k <= 128 the partials are K20's.  No column sums, no count.
+//   als_gram_reduce_kernel  the one reduce of both Grams: adds the partials in ascending slab order in fp64, applies scale and ridge,
+//                           rounds once (s * scale + ridge in this file's contraction mode, the default: that fixes its bits).
 //   als_plan_kernel         (solve, only when a row can be heavy) one workgroup walks like_ptr, gives every heavy row its slabs of the
 //                           workspace in row order (a block-wide scan) and writes heavy_base[row] (-1: the row sums its own likes)
 //                           and slab_row[slab]; a row whose slabs do not fit the workspace sums its own likes.
@@ -35,128 +40,19 @@
 //   als_cold_kernel<KT>     a lane per row without likes: L in LDS, read wave-uniformly, z and x in registers, two triangular
 //                           substitutions by dot products over contiguous rows (of L, then of L^T).
 // No float atomics; the only atomic is the status word's minimum.  Nothing refused is used as an index.
-#include "tkr_common.h"
-#include "../../include/tkr.h"
+#include "als_parts.h"
 
-#include <limits.h>
 #include <math.h>
 
 #include <algorithm>
 
 namespace tkr {
 
-typedef float als_f32x16 __attribute__((ext_vector_type(16)));
-
-constexpr int kAlsBlock = 256;
-constexpr int kAlsWaves = kAlsBlock / TKR_WAVE;
-constexpr int kAlsTile = 32;                                      // rows of Y staged at a time = the MFMA's block edge
-constexpr int kAlsSlab = TKR_ALS_GRAM_SLAB;
 constexpr int kAlsMaxSlabs = 1 << 20;                             // heavy slabs of one solve, at most (the plan kernel scans ints)
-static_assert(kAlsSlab % kAlsTile == 0 && kAlsSlab < (1 << 24), "whole tiles; a slab's count is exact in fp32");
 
-__host__ __device__ constexpr int als_tiles(int KT) { return KT * (KT + 1) / 2; }
-__host__ __device__ constexpr int als_tiles_per_wave(int KT) { return (als_tiles(KT) + kAlsWaves - 1) / kAlsWaves; }
-// floats between two staged rows: the two rows an MFMA reads at once (lanes 0-31, lanes 32-63) start 32 banks apart
-__host__ __device__ constexpr int als_stage_pitch(int KT) { return (KT & 1) ? KT * 32 : KT * 32 + 32; }
 // floats between two rows of A: the smallest pitch >= k that is 16 mod 64
 __host__ __device__ inline int als_a_pitch(int k) { return (k + 47) / 64 * 64 + 16; }
 __host__ __device__ inline int64_t als_partial_stride(int k) { return (int64_t)k * k + k + 1; }
-
-// block `idx` of the upper triangle, row-major: (0,0) (0,1) .. (0,KT-1) (1,1) ..
-__device__ __forceinline__ void als_tile_of(int KT, int idx, int& bi, int& bj) {
-    bi = 0;
-    for (int len = KT; idx >= len; --len) {
-        idx -= len;
-        ++bi;
-    }
-    bj = bi + idx;
-}
-
-// acc += sum over list[first .. first + count) of y y^T (this wave's blocks); col_sum += the column sums (thread j < k: column j, in
-// fp64) and n_valid += the rows that were summed (threads < k).  list == nullptr: the rows first .. first + count themselves.  A row
-// outside [0, n) is skipped and reported: 4 * word_row + 1, or 4 * (its position in the list) + 1 where word_row < 0.
-// Called by all threads of the workgroup with the same arguments; stage [32][SP] floats, cols_s [32] ints.
-template <int KT>
-__device__ __forceinline__ void slab_sum(const float* __restrict__ Y, int n, int k, const int32_t* __restrict__ list, long long first, int count,
-                                         float* stage, int* cols_s, als_f32x16 (&acc)[als_tiles_per_wave(KT)], double& col_sum, int& n_valid,
-                                         long long word_row, unsigned long long* status) {
-    constexpr int SP = als_stage_pitch(KT), NT = als_tiles(KT), TPW = als_tiles_per_wave(KT);
-    const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63, l31 = lane & 31, h = lane >> 5;
-    for (int base = 0; base < count; base += kAlsTile) {          // workgroup-uniform
-        const int n_here = min(kAlsTile, count - base);
-        if (tid < kAlsTile) {
-            int c = -1;
-            if (tid < n_here) {
-                const long long t = first + base + tid;
-                c = list ? list[t] : (int)t;
-                if ((uint32_t)c >= (uint32_t)n) {
-                    atomicMin(status, (unsigned long long)(word_row < 0 ? t : word_row) * 4ull + 1ull);      // kind 1: skipped
-                    c = -1;
-                }
-            }
-            cols_s[tid] = c;
-        }
-        __syncthreads();
-        for (int q = tid >> 5; q < kAlsTile * KT; q += kAlsBlock / 32) {       // 32 lanes bring 32 consecutive floats of a row
-            const int rr = q / KT, col = (q - rr * KT) * 32 + l31;
-            const int c = cols_s[rr];
-            stage[rr * SP + col] = (c >= 0 && col < k) ? Y[(size_t)c * k + col] : 0.f;
-        }
-        __syncthreads();
-        if (tid < k) {
-            for (int i = 0; i < kAlsTile; ++i) {
-                col_sum += (double)stage[i * SP + tid];
-                n_valid += cols_s[i] >= 0;
-            }
-        }
-#pragma unroll
-        for (int s = 0; s < TPW; ++s) {
-            const int idx = wave + kAlsWaves * s;
-            if (idx < NT) {                                       // wave-uniform
-                int bi, bj;
-                als_tile_of(KT, idx, bi, bj);
-                const float* ap = stage + h * SP + bi * 32 + l31;
-                const float* bp = stage + h * SP + bj * 32 + l31;
-#pragma unroll 4
-                for (int t = 0; t < kAlsTile; t += 2)
-                    acc[s] = __builtin_amdgcn_mfma_f32_32x32x2f32(ap[t * SP], bp[t * SP], acc[s], 0, 0, 0);
-            }
-        }
-        __syncthreads();                                          // the tile is done with (after the last one the caller may reuse stage)
-    }
-}
-
-// this wave's blocks, element by element: f(p, q, value) for p, q < k, both triangles
-template <int KT, typename F>
-__device__ __forceinline__ void als_emit(const als_f32x16 (&acc)[als_tiles_per_wave(KT)], int k, F f) {
-    constexpr int NT = als_tiles(KT), TPW = als_tiles_per_wave(KT);
-    const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63, l31 = lane & 31, h = lane >> 5;
-#pragma unroll
-    for (int s = 0; s < TPW; ++s) {
-        const int idx = wave + kAlsWaves * s;
-        if (idx < NT) {
-            int bi, bj;
-            als_tile_of(KT, idx, bi, bj);
-            const int q = bj * 32 + l31;
-#pragma unroll
-            for (int reg = 0; reg < 16; ++reg) {
-                const int p = bi * 32 + (reg & 3) + 8 * (reg >> 2) + 4 * h;
-                if (p < k && q < k) {
-                    f(p, q, acc[s][reg]);
-                    if (bi != bj) f(q, p, acc[s][reg]);
-                }
-            }
-        }
-    }
-}
-
-template <int KT>
-__device__ __forceinline__ void als_zero(als_f32x16 (&acc)[als_tiles_per_wave(KT)]) {
-#pragma unroll
-    for (int s = 0; s < als_tiles_per_wave(KT); ++s)
-#pragma unroll
-        for (int reg = 0; reg < 16; ++reg) acc[s][reg] = 0.f;
-}
 
 // like_ptr == nullptr: slab b of the list (rows, n_listed).  Otherwise slab b of the plan: row slab_row[b] (< 0: nothing to do), its
 // likes first + s * SLAB .., s = b - heavy_base[row].
@@ -183,7 +79,7 @@ __global__ __launch_bounds__(kAlsBlock) void als_slab_kernel(const float* __rest
         count = (int)min((long long)kAlsSlab, n_listed - first);
     }
     als_f32x16 acc[als_tiles_per_wave(KT)];
-    als_zero<KT>(acc);
+    als_zero(acc);
     double col_sum = 0.0;
     int n_valid = 0;
     slab_sum<KT>(Y, n, k, list, first, count, stage, cols_s, acc, col_sum, n_valid, word_row, status);
@@ -193,19 +89,95 @@ __global__ __launch_bounds__(kAlsBlock) void als_slab_kernel(const float* __rest
     if (tid == 0) out[k * k + k] = (float)n_valid;
 }
 
-__global__ __launch_bounds__(kAlsBlock) void als_gram_reduce_kernel(const float* __restrict__ partial, long long n_slabs, int k, double scale,
-                                                                    double ridge, float* __restrict__ G) {
+// K24: the slab sum at any width up to 512: slab_sum's staging, product and emit with the blocks of the triangle dealt to passes, the
+// stage in dynamic LDS (above 64 KB from k = 481), no column sums and no count.  It restates those three steps and does not call
+// pieces of slab_sum: slab_sum and als_emit written over shared pieces are the same arithmetic, but the compiler gave als_slab_kernel
+// and als_solve_kernel other instructions (other scalar registers at KT = 1 and 3, 6 waves per SIMD for 7 in als_solve_kernel<1>, and
+// 1.3 % on the K20 iteration at k = 128).  A change to the staging is a change in both places; test_gram_wide_has_the_bits_of_gram
+// holds them to the same bits.
+constexpr int kWideTpw = als_tiles_per_wave(4);                   // blocks per wave and pass: als_slab_kernel<4>'s accumulators
+constexpr int kWidePass = kWideTpw * kAlsWaves;
+
+// grid (slabs, passes): the blocks 12 blockIdx.y .. of slab blockIdx.x -> partial [slab][k * k], both triangles
+__global__ __launch_bounds__(kAlsBlock) void als_wide_slab_kernel(const float* __restrict__ Y, int n, int k, const int32_t* __restrict__ list,
+                                                                 long long n_listed, float* __restrict__ partial,
+                                                                 unsigned long long* __restrict__ status) {
+    extern __shared__ __attribute__((aligned(16))) float als_lds[];
+    const int KT = (k + 31) / 32, SP = als_stage_pitch(KT), NT = als_tiles(KT);
+    float* stage = als_lds;                                         // [32][SP]
+    int* cols_s = reinterpret_cast<int*>(als_lds + kAlsTile * SP);
+    const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63, l31 = lane & 31, h = lane >> 5;
+    const long long first = (long long)blockIdx.x * kAlsSlab;
+    const int count = (int)(n_listed - first < (long long)kAlsSlab ? n_listed - first : (long long)kAlsSlab);
+    const int idx0 = blockIdx.y * kWidePass + wave;
+    int bi[kWideTpw], bj[kWideTpw];
+    als_f32x16 acc[kWideTpw];
+#pragma unroll
+    for (int s = 0; s < kWideTpw; ++s) {
+        bi[s] = bj[s] = 0;
+        if (idx0 + kAlsWaves * s < NT) als_tile_of(KT, idx0 + kAlsWaves * s, bi[s], bj[s]);
+#pragma unroll
+        for (int reg = 0; reg < 16; ++reg) acc[s][reg] = 0.f;
+    }
+    for (int base = 0; base < count; base += kAlsTile) {           // workgroup-uniform
+        const int n_here = count - base < kAlsTile ? count - base : kAlsTile;
+        if (tid < kAlsTile) {
+            int c = -1;
+            if (tid < n_here) {
+                const long long t = first + base + tid;
+                c = list ? list[t] : (int)t;
+                if ((uint32_t)c >= (uint32_t)n) {
+                    atomicMin(status, (unsigned long long)t * 4ull + 1ull);    // kind 1: skipped
+                    c = -1;
+                }
+            }
+            cols_s[tid] = c;
+        }
+        __syncthreads();
+        for (int q = tid >> 5; q < kAlsTile * KT; q += kAlsBlock / 32) {         // 32 lanes bring 32 consecutive floats of a row
+            const int rr = q / KT, col = (q - rr * KT) * 32 + l31;
+            const int c = cols_s[rr];
+            stage[rr * SP + col] = (c >= 0 && col < k) ? Y[(size_t)c * k + col] : 0.f;
+        }
+        __syncthreads();
+#pragma unroll
+        for (int s = 0; s < kWideTpw; ++s) {
+            if (idx0 + kAlsWaves * s < NT) {                       // wave-uniform
+                const float* ap = stage + h * SP + bi[s] * 32 + l31;
+                const float* bp = stage + h * SP + bj[s] * 32 + l31;
+#pragma unroll 4
+                for (int t = 0; t < kAlsTile; t += 2)
+                    acc[s] = __builtin_amdgcn_mfma_f32_32x32x2f32(ap[t * SP], bp[t * SP], acc[s], 0, 0, 0);
+            }
+        }
+        __syncthreads();
+    }
+    float* out = partial + (size_t)blockIdx.x * (size_t)k * (size_t)k;
+#pragma unroll
+    for (int s = 0; s < kWideTpw; ++s) {
+        if (idx0 + kAlsWaves * s < NT) {
+            const int q = bj[s] * 32 + l31;
+#pragma unroll
+            for (int reg = 0; reg < 16; ++reg) {
+                const int p = bi[s] * 32 + (reg & 3) + 8 * (reg >> 2) + 4 * h;
+                if (p < k && q < k) {
+                    out[(size_t)p * k + q] = acc[s][reg];
+                    if (bi[s] != bj[s]) out[(size_t)q * k + p] = acc[s][reg];
+                }
+            }
+        }
+    }
+}
+
+// partial: [n_slabs][stride] floats, the k * k sums in front (stride: als_partial_stride(k), or k * k for the wide slabs)
+__global__ __launch_bounds__(kAlsBlock) void als_gram_reduce_kernel(const float* __restrict__ partial, long long n_slabs, size_t stride, int k,
+                                                                    double scale, double ridge, float* __restrict__ G) {
     const int idx = blockIdx.x * kAlsBlock + threadIdx.x;
     if (idx >= k * k) return;
-    const size_t stride = (size_t)als_partial_stride(k);
     double s = 0.0;
     for (long long b = 0; b < n_slabs; ++b) s += (double)partial[(size_t)b * stride + idx];
     const int p = idx / k, q = idx - p * k;
     G[idx] = (float)(s * scale + (p == q ? ridge : 0.0));
-}
-
-__device__ __forceinline__ bool als_ptr_ok(long long lo, long long hi, long long n_likes, long long row) {
-    return lo >= 0 && lo <= hi && hi <= n_likes && (row != 0 || lo == 0) && hi - lo <= (long long)INT_MAX;
 }
 
 constexpr int kAlsPlanBlock = 1024;
@@ -345,7 +317,7 @@ __global__ __launch_bounds__(kAlsBlock) void als_solve_kernel(const float* __res
         }
     } else if (hb < 0) {                                          // (uniform) the row sums its own likes
         als_f32x16 acc[als_tiles_per_wave(KT)];
-        als_zero<KT>(acc);
+        als_zero(acc);
         slab_sum<KT>(Y, n_y, k, like_cols, lo, m, stage, cols_s, acc, col_sum, n_valid, r, status);
         als_emit<KT>(acc, k, [&](int p, int q, float v) { put(p, q, (double)v); });
     } else {                                                      // its slabs were summed by the launch before this one
@@ -523,11 +495,6 @@ __global__ __launch_bounds__(kAlsBlock) void als_solve_kernel(const float* __res
             }
         }
     }
-}
-
-static int als_check_k(int32_t k) {
-    if (k < 1) return TKR_EINVAL;
-    return k > TKR_ALS_MAX_K ? TKR_EUNSUPPORTED : TKR_OK;
 }
 
 static int64_t als_align(int64_t bytes) { return (bytes + 15) / 16 * 16; }
@@ -718,7 +685,7 @@ static int als_solve(const float* Y, int32_t n_y, int32_t k, const float* G, con
     if (n_likes < 0 || (n_likes > 0 && !like_cols) || n_y < 1 || n_x < 1 || n_x > (int64_t)INT_MAX || heavy_from < 1 || workspace_bytes < 0)
         return TKR_EINVAL;
     if (!std::isfinite(w_like) || !std::isfinite(w_rhs) || !std::isfinite(ridge) || ridge < 0.0) return TKR_EINVAL;
-    TKR_CHECK_RC(als_check_k(k));
+    TKR_CHECK_RC(als_check_k(k, TKR_ALS_MAX_K));
     float* factor = nullptr;
     if (prior) {                                                  // the factor takes the front of the workspace, K20's part follows
         const int64_t front = als_align(als_factor_floats(k) * 4);
@@ -770,32 +737,66 @@ static int als_solve(const float* Y, int32_t n_y, int32_t k, const float* G, con
 #undef TKR_ALS_SOLVE
 }
 
+// what tkr_als_gram and tkr_als_gram_wide share: the checks, the status word, the slab sums -- launch_slabs(stream, n_slabs, n_listed,
+// partial, st), the one thing that differs, with the bound on k and the floats between two partials -- and the reduce.
+template <typename Launch>
+static int als_gram(const float* Y, int32_t n, int32_t k, int32_t k_max, int64_t stride, const int32_t* rows, int64_t n_listed, double scale,
+                    double ridge, float* G, void* workspace, int64_t workspace_bytes, int64_t* status, void* stream_, Launch launch_slabs) {
+    if (!Y || !G || !status || ((uintptr_t)status & 7) || ((uintptr_t)workspace & 7)) return TKR_EINVAL;
+    if (n < 1 || n_listed < 0 || workspace_bytes < 0 || !std::isfinite(scale) || !std::isfinite(ridge)) return TKR_EINVAL;
+    TKR_CHECK_RC(als_check_k(k, k_max));
+    if (!rows) n_listed = n;
+    const long long n_slabs = (n_listed + kAlsSlab - 1) / kAlsSlab;
+    if (n_slabs > (long long)INT_MAX) return TKR_EUNSUPPORTED;
+    if (n_slabs > 0 && (!workspace || workspace_bytes < n_slabs * stride * 4)) return TKR_EINVAL;
+    hipStream_t stream = (hipStream_t)stream_;
+    unsigned long long* st = reinterpret_cast<unsigned long long*>(status);
+    TKR_CHECK(hipMemsetAsync(st, 0xff, sizeof(unsigned long long), stream));          // -1: nothing refused
+    float* partial = reinterpret_cast<float*>(workspace);
+    if (n_slabs > 0) TKR_CHECK_RC(launch_slabs(stream, n_slabs, (long long)n_listed, partial, st));
+    hipLaunchKernelGGL(als_gram_reduce_kernel, dim3((k * k + kAlsBlock - 1) / kAlsBlock), dim3(kAlsBlock), 0, stream, partial, n_slabs,
+                       (size_t)stride, k, scale, ridge, G);
+    TKR_LAUNCH_CHECK();
+    return TKR_OK;
+}
+
 }  // namespace tkr
 
 extern "C" int64_t tkr_als_workspace_bytes(int64_t n_x, int32_t k, int64_t n_slabs) {
-    if (n_x < 0 || n_slabs < 0 || tkr::als_check_k(k) != TKR_OK) return TKR_EINVAL;
+    if (n_x < 0 || n_slabs < 0 || tkr::als_check_k(k, TKR_ALS_MAX_K) != TKR_OK) return TKR_EINVAL;
     return tkr::als_align(n_x * 4) + tkr::als_align(n_slabs * 4) + tkr::als_align(n_slabs * tkr::als_partial_stride(k) * 4);
 }
 
 extern "C" int tkr_als_gram(const float* Y, int32_t n, int32_t k, const int32_t* rows, int64_t n_listed, double scale, double ridge, float* G,
                             void* workspace, int64_t workspace_bytes, int64_t* status, void* stream_) {
-    if (!Y || !G || !status || ((uintptr_t)status & 7) || ((uintptr_t)workspace & 7)) return TKR_EINVAL;
-    if (n < 1 || n_listed < 0 || workspace_bytes < 0 || !std::isfinite(scale) || !std::isfinite(ridge)) return TKR_EINVAL;
-    TKR_CHECK_RC(tkr::als_check_k(k));
-    if (!rows) n_listed = n;
-    const long long n_slabs = (n_listed + tkr::kAlsSlab - 1) / tkr::kAlsSlab;
-    if (n_slabs > (long long)INT_MAX) return TKR_EUNSUPPORTED;
-    if (n_slabs > 0 && (!workspace || workspace_bytes < n_slabs * tkr::als_partial_stride(k) * 4)) return TKR_EINVAL;
-    hipStream_t stream = (hipStream_t)stream_;
-    unsigned long long* st = reinterpret_cast<unsigned long long*>(status);
-    TKR_CHECK(hipMemsetAsync(st, 0xff, sizeof(unsigned long long), stream));          // -1: nothing refused
-    float* partial = reinterpret_cast<float*>(workspace);
-    if (n_slabs > 0)
-        TKR_CHECK_RC(tkr::launch_slabs_kt((k + 31) / 32, stream, n_slabs, Y, n, k, rows, n_listed, nullptr, nullptr, nullptr, partial, st));
-    hipLaunchKernelGGL(tkr::als_gram_reduce_kernel, dim3((k * k + tkr::kAlsBlock - 1) / tkr::kAlsBlock), dim3(tkr::kAlsBlock), 0, stream, partial,
-                       n_slabs, k, scale, ridge, G);
-    TKR_LAUNCH_CHECK();
-    return TKR_OK;
+    return tkr::als_gram(Y, n, k, TKR_ALS_MAX_K, tkr::als_partial_stride(k), rows, n_listed, scale, ridge, G, workspace, workspace_bytes, status, stream_,
+                         [&](hipStream_t stream, long long n_slabs, long long listed, float* partial, unsigned long long* st) {
+                             return tkr::launch_slabs_kt((k + 31) / 32, stream, n_slabs, Y, n, k, rows, listed, nullptr, nullptr, nullptr, partial, st);
+                         });
+}
+
+extern "C" int64_t tkr_als_gram_wide_workspace_bytes(int32_t k, int64_t n_slabs) {
+    if (n_slabs < 0) return TKR_EINVAL;
+    const int rc = tkr::als_check_k(k, TKR_ALS_CG_MAX_K);
+    if (rc != TKR_OK) return rc;
+    return tkr::als_align(n_slabs * (int64_t)k * k * 4);
+}
+
+extern "C" int tkr_als_gram_wide(const float* Y, int32_t n, int32_t k, const int32_t* rows, int64_t n_listed, double scale, double ridge, float* G,
+                                 void* workspace, int64_t workspace_bytes, int64_t* status, void* stream_) {
+    return tkr::als_gram(Y, n, k, TKR_ALS_CG_MAX_K, (int64_t)k * k, rows, n_listed, scale, ridge, G, workspace, workspace_bytes, status, stream_,
+                         [&](hipStream_t stream, long long n_slabs, long long listed, float* partial, unsigned long long* st) {
+                             const int KT = (k + 31) / 32;
+                             const size_t lds = (size_t)(tkr::kAlsTile * tkr::als_stage_pitch(KT) + tkr::kAlsTile) * 4;
+                             const int passes = (tkr::als_tiles(KT) + tkr::kWidePass - 1) / tkr::kWidePass;
+                             if (lds > 64 * 1024)
+                                 TKR_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(tkr::als_wide_slab_kernel),
+                                                               hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+                             hipLaunchKernelGGL(tkr::als_wide_slab_kernel, dim3((unsigned)n_slabs, (unsigned)passes), dim3(tkr::kAlsBlock), lds, stream, Y,
+                                                n, k, rows, listed, partial, st);
+                             TKR_LAUNCH_CHECK();
+                             return (int)TKR_OK;
+                         });
 }
 
 extern "C" int tkr_als_solve_rows(const float* Y, int32_t n_y, int32_t k, const float* G, const int64_t* like_ptr, const int32_t* like_cols,

@@ -1,5 +1,6 @@
-// K24 -- the ALS half-step by conjugate gradients (tkr_als_cg_rows), and the shared Gram at any width up to 512 (tkr_als_gram_wide).
-// The second, opt-in solver of top-k-rec_amd/als.py; K20 / K21 (csrc/als.hip) stay as they are and this file takes nothing from them.
+// K24 -- the ALS half-step by conjugate gradients (tkr_als_cg_rows): the second, opt-in solver of top-k-rec_amd/als.py.  Conjugate
+// gradients only: the shared Gram at any width up to 512 (tkr_als_gram_wide) is csrc/als.hip's, beside K20's, and what both files use
+// (the MFMA vector type, the stage pitch, als_ptr_ok, the check of k) is csrc/als_parts.h.
 //
 // The per-row matrix A_r = G + w_like * sum_{y in L_r} y y^T + ridge I is never formed.  A row takes `steps` steps of conjugate gradients
 // from the value X[r] holds (Takacs, Pilaszy, Tikk 2011); a step needs q = A_r p, that is  p G  (shared by every row) and
@@ -22,29 +23,18 @@
 //   Every dot product is ONE fixed tree: a lane's partial is an fma chain from +0.0 over its elements in ascending order, then
 //   s += s(lane ^ 32), ^ 16, .. ^ 1.  Divisions are IEEE fp32 divisions.  The file is compiled with `#pragma clang fp contract(off)`:
 //   every fused multiply-add is written as fmaf / the MFMA, everything else rounds on its own, so that tests/_cg_oracle.py can restate
-//   the order operation by operation.  (als_gram_wide_reduce_kernel turns contraction back on for its one expression: it is
-//   tkr_als_gram's, and has to compile as that does.)
+//   the order operation by operation.
 //   Every barrier is in workgroup-uniform control flow: the loops run over k and `steps`; a row that is done (rho < 1e-20), refused or
 //   past n_x is frozen by its state word, which only the branches WITHOUT barriers read.  The bits of a row depend on G, the weights,
 //   its own likes in stored order, its own X[r] and prior, and `steps`: its place in the tile picks a wave and a row of P, not an order.
-//
-//   als_wide_slab_kernel    tkr_als_gram's slab sum for k <= 512: the slab's rows staged 32 at a time (zeros beyond k, a refused row as
-//                           zeros), the 32 x 32 blocks on and above the diagonal dealt to passes of 12 (blockIdx.y), 3 per wave: the
-//                           accumulators K20's kernel holds at k = 128.  An element is the same fp32 fma chain in list order whichever
-//                           pass and wave has its block, so for k <= 128 the partials are K20's.
-//   als_gram_wide_reduce_kernel  the partials added in ascending slab order in fp64, scale and ridge, rounded once.
 // No float atomics; the only atomic is the status word's minimum.  Nothing refused is used as an index.
-#include "tkr_common.h"
-#include "../../include/tkr.h"
+#include "als_parts.h"
 
-#include <limits.h>
 #include <math.h>
 
 #pragma clang fp contract(off)
 
 namespace tkr {
-
-typedef float cg_f32x16 __attribute__((ext_vector_type(16)));
 
 constexpr int kCgBlock = 256;
 constexpr int kCgWaves = kCgBlock / TKR_WAVE;
@@ -58,14 +48,13 @@ enum { kCgFirst = 0, kCgStep = 1, kCgLoss = 2 };
 
 // floats between two rows of P / Q: the smallest pitch >= k that is 2 mod 64
 __host__ __device__ inline int cg_p_pitch(int k) { return (k + 61) / 64 * 64 + 2; }
-// floats between two rows of the panel of G (and of the Gram's stage): the two rows an MFMA reads at once start 32 banks apart
-__host__ __device__ inline int cg_g_pitch(int KT) { return (KT & 1) ? KT * 32 : KT * 32 + 32; }
+// (the panel of G has the Gram's stage pitch, als_stage_pitch)
 
 // dynamic LDS of als_cg_kernel, in floats from the start (every piece an even number of floats)
 struct CgLds {
     int p, q, g, lo, m, c, state, floats;
     __host__ __device__ CgLds(int k) {
-        const int PP = cg_p_pitch(k), GP = cg_g_pitch((k + 31) / 32);
+        const int PP = cg_p_pitch(k), GP = als_stage_pitch((k + 31) / 32);
         p = 0;
         q = p + kCgTile * PP;
         g = q + kCgTile * PP;
@@ -76,10 +65,6 @@ struct CgLds {
         floats = state + kCgTile;
     }
 };
-
-__device__ __forceinline__ bool cg_ptr_ok(long long lo, long long hi, long long n_likes, long long row) {
-    return lo >= 0 && lo <= hi && hi <= n_likes && (row != 0 || lo == 0) && hi - lo <= (long long)INT_MAX;
-}
 
 // the one dot product of this file: every lane returns the same bits
 template <int KC>
@@ -103,7 +88,7 @@ template <int NBW>
 __device__ __forceinline__ void cg_pg(const float* __restrict__ G, int k, int KT, const float* P, float* Q, float* Gs, int PP, int GP) {
     const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63, l31 = lane & 31, h = lane >> 5;
     const int cols = KT * 32;
-    cg_f32x16 acc[NBW];
+    als_f32x16 acc[NBW];
 #pragma unroll
     for (int s = 0; s < NBW; ++s)
 #pragma unroll
@@ -254,7 +239,7 @@ __global__ __launch_bounds__(kCgBlock) void als_cg_kernel(const float* __restric
     constexpr int NBW = KC >= 2 ? KC / 2 : 1;                     // 32-column blocks of Q per wave: ceil(ceil(k / 32) / 4)
     extern __shared__ __attribute__((aligned(16))) float cg_lds[];
     const CgLds at(k);
-    const int KT = (k + 31) / 32, PP = cg_p_pitch(k), GP = cg_g_pitch(KT);
+    const int KT = (k + 31) / 32, PP = cg_p_pitch(k), GP = als_stage_pitch(KT);
     float* P = cg_lds + at.p;
     float* Q = cg_lds + at.q;
     float* Gs = cg_lds + at.g;
@@ -271,7 +256,7 @@ __global__ __launch_bounds__(kCgBlock) void als_cg_kernel(const float* __restric
         int m = 0, state = kCgSkip;
         if (row < n_x) {
             const long long a = like_ptr[row], b = like_ptr[row + 1];
-            if (!cg_ptr_ok(a, b, n_likes, row)) {
+            if (!als_ptr_ok(a, b, n_likes, row)) {
                 atomicMin(status, (unsigned long long)row * 4ull + 3ull);      // kind 3: the row is left as it is
                 state = kCgRefused;
             } else {
@@ -416,117 +401,11 @@ static int launch_cg(hipStream_t stream, const float* Y, int n_y, int k, const f
     return TKR_OK;
 }
 
-static int cg_check_k(int32_t k) {
-    if (k < 1) return TKR_EINVAL;
-    return k > TKR_ALS_CG_MAX_K ? TKR_EUNSUPPORTED : TKR_OK;
-}
-
-// ---- the Gram at any width up to 512 ------------------------------------------------------------------------------------------------------
-constexpr int kWideSlab = TKR_ALS_GRAM_SLAB;
-constexpr int kWideTpw = 3;                                       // blocks per wave and pass: K20's at k = 128
-constexpr int kWidePass = kWideTpw * kCgWaves;
-static_assert(kWideSlab % kCgTile == 0, "whole tiles");
-
-__host__ __device__ inline int wide_tiles(int KT) { return KT * (KT + 1) / 2; }
-
-// block `idx` of the upper triangle, row-major: (0,0) (0,1) .. (0,KT-1) (1,1) ..
-__device__ __forceinline__ void wide_tile_of(int KT, int idx, int& bi, int& bj) {
-    bi = 0;
-    for (int len = KT; idx >= len; --len) {
-        idx -= len;
-        ++bi;
-    }
-    bj = bi + idx;
-}
-
-// grid (slabs, passes): the blocks 12 blockIdx.y .. of slab blockIdx.x -> partial [slab][k * k], both triangles
-__global__ __launch_bounds__(kCgBlock) void als_wide_slab_kernel(const float* __restrict__ Y, int n, int k, const int32_t* __restrict__ list,
-                                                                 long long n_listed, float* __restrict__ partial,
-                                                                 unsigned long long* __restrict__ status) {
-    extern __shared__ __attribute__((aligned(16))) float cg_lds[];
-    const int KT = (k + 31) / 32, SP = cg_g_pitch(KT), NT = wide_tiles(KT);
-    float* stage = cg_lds;                                         // [32][SP]
-    int* cols_s = reinterpret_cast<int*>(cg_lds + kCgTile * SP);
-    const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63, l31 = lane & 31, h = lane >> 5;
-    const long long first = (long long)blockIdx.x * kWideSlab;
-    const int count = (int)(n_listed - first < (long long)kWideSlab ? n_listed - first : (long long)kWideSlab);
-    const int idx0 = blockIdx.y * kWidePass + wave;
-    int bi[kWideTpw], bj[kWideTpw];
-    cg_f32x16 acc[kWideTpw];
-#pragma unroll
-    for (int s = 0; s < kWideTpw; ++s) {
-        bi[s] = bj[s] = 0;
-        if (idx0 + kCgWaves * s < NT) wide_tile_of(KT, idx0 + kCgWaves * s, bi[s], bj[s]);
-#pragma unroll
-        for (int reg = 0; reg < 16; ++reg) acc[s][reg] = 0.f;
-    }
-    for (int base = 0; base < count; base += kCgTile) {           // workgroup-uniform
-        const int n_here = count - base < kCgTile ? count - base : kCgTile;
-        if (tid < kCgTile) {
-            int c = -1;
-            if (tid < n_here) {
-                const long long t = first + base + tid;
-                c = list ? list[t] : (int)t;
-                if ((uint32_t)c >= (uint32_t)n) {
-                    atomicMin(status, (unsigned long long)t * 4ull + 1ull);    // kind 1: skipped
-                    c = -1;
-                }
-            }
-            cols_s[tid] = c;
-        }
-        __syncthreads();
-        for (int q = tid >> 5; q < kCgTile * KT; q += kCgBlock / 32) {         // 32 lanes bring 32 consecutive floats of a row
-            const int rr = q / KT, col = (q - rr * KT) * 32 + l31;
-            const int c = cols_s[rr];
-            stage[rr * SP + col] = (c >= 0 && col < k) ? Y[(size_t)c * k + col] : 0.f;
-        }
-        __syncthreads();
-#pragma unroll
-        for (int s = 0; s < kWideTpw; ++s) {
-            if (idx0 + kCgWaves * s < NT) {                       // wave-uniform
-                const float* ap = stage + h * SP + bi[s] * 32 + l31;
-                const float* bp = stage + h * SP + bj[s] * 32 + l31;
-#pragma unroll 4
-                for (int t = 0; t < kCgTile; t += 2)
-                    acc[s] = __builtin_amdgcn_mfma_f32_32x32x2f32(ap[t * SP], bp[t * SP], acc[s], 0, 0, 0);
-            }
-        }
-        __syncthreads();
-    }
-    float* out = partial + (size_t)blockIdx.x * (size_t)k * (size_t)k;
-#pragma unroll
-    for (int s = 0; s < kWideTpw; ++s) {
-        if (idx0 + kCgWaves * s < NT) {
-            const int q = bj[s] * 32 + l31;
-#pragma unroll
-            for (int reg = 0; reg < 16; ++reg) {
-                const int p = bi[s] * 32 + (reg & 3) + 8 * (reg >> 2) + 4 * h;
-                if (p < k && q < k) {
-                    out[(size_t)p * k + q] = acc[s][reg];
-                    if (bi[s] != bj[s]) out[(size_t)q * k + p] = acc[s][reg];
-                }
-            }
-        }
-    }
-}
-
-__global__ __launch_bounds__(kCgBlock) void als_gram_wide_reduce_kernel(const float* __restrict__ partial, long long n_slabs, int k, double scale,
-                                                                        double ridge, float* __restrict__ G) {
-#pragma clang fp contract(fast)
-    const int idx = blockIdx.x * kCgBlock + threadIdx.x;
-    if (idx >= k * k) return;
-    const size_t stride = (size_t)k * (size_t)k;
-    double s = 0.0;
-    for (long long b = 0; b < n_slabs; ++b) s += (double)partial[(size_t)b * stride + idx];
-    const int p = idx / k, q = idx - p * k;
-    G[idx] = (float)(s * scale + (p == q ? ridge : 0.0));
-}
-
 }  // namespace tkr
 
 extern "C" int64_t tkr_als_cg_workspace_bytes(int64_t n_x, int32_t k) {
     if (n_x < 0) return TKR_EINVAL;
-    const int rc = tkr::cg_check_k(k);
+    const int rc = tkr::als_check_k(k, TKR_ALS_CG_MAX_K);
     return rc != TKR_OK ? rc : 0;                                 // the state of a row is registers and LDS
 }
 
@@ -541,7 +420,7 @@ extern "C" int tkr_als_cg_rows(const float* Y, int32_t n_y, int32_t k, const flo
         return TKR_EINVAL;
     if (!std::isfinite(w_like) || !std::isfinite(w_rhs) || !std::isfinite(ridge) || ridge < 0.0 || !std::isfinite(w_prior) || w_prior < 0.0)
         return TKR_EINVAL;
-    TKR_CHECK_RC(tkr::cg_check_k(k));
+    TKR_CHECK_RC(tkr::als_check_k(k, TKR_ALS_CG_MAX_K));
     hipStream_t stream = (hipStream_t)stream_;
     unsigned long long* st = reinterpret_cast<unsigned long long*>(status);
     TKR_CHECK(hipMemsetAsync(st, 0xff, sizeof(unsigned long long), stream));          // -1: nothing refused
@@ -552,40 +431,4 @@ extern "C" int tkr_als_cg_rows(const float* Y, int32_t n_y, int32_t k, const flo
     if (k <= 256) TKR_CG_LAUNCH(4);
     TKR_CG_LAUNCH(8);
 #undef TKR_CG_LAUNCH
-}
-
-extern "C" int64_t tkr_als_gram_wide_workspace_bytes(int32_t k, int64_t n_slabs) {
-    if (n_slabs < 0) return TKR_EINVAL;
-    const int rc = tkr::cg_check_k(k);
-    if (rc != TKR_OK) return rc;
-    return (n_slabs * (int64_t)k * k * 4 + 15) / 16 * 16;
-}
-
-extern "C" int tkr_als_gram_wide(const float* Y, int32_t n, int32_t k, const int32_t* rows, int64_t n_listed, double scale, double ridge, float* G,
-                                 void* workspace, int64_t workspace_bytes, int64_t* status, void* stream_) {
-    if (!Y || !G || !status || ((uintptr_t)status & 7) || ((uintptr_t)workspace & 7)) return TKR_EINVAL;
-    if (n < 1 || n_listed < 0 || workspace_bytes < 0 || !std::isfinite(scale) || !std::isfinite(ridge)) return TKR_EINVAL;
-    TKR_CHECK_RC(tkr::cg_check_k(k));
-    if (!rows) n_listed = n;
-    const long long n_slabs = (n_listed + tkr::kWideSlab - 1) / tkr::kWideSlab;
-    if (n_slabs > (long long)INT_MAX) return TKR_EUNSUPPORTED;
-    if (n_slabs > 0 && (!workspace || workspace_bytes < n_slabs * (int64_t)k * k * 4)) return TKR_EINVAL;
-    hipStream_t stream = (hipStream_t)stream_;
-    unsigned long long* st = reinterpret_cast<unsigned long long*>(status);
-    TKR_CHECK(hipMemsetAsync(st, 0xff, sizeof(unsigned long long), stream));          // -1: nothing refused
-    float* partial = reinterpret_cast<float*>(workspace);
-    if (n_slabs > 0) {
-        const int KT = (k + 31) / 32;
-        const size_t lds = (size_t)(tkr::kCgTile * tkr::cg_g_pitch(KT) + tkr::kCgTile) * 4;
-        const int passes = (tkr::wide_tiles(KT) + tkr::kWidePass - 1) / tkr::kWidePass;
-        if (lds > 64 * 1024)
-            TKR_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(tkr::als_wide_slab_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-        hipLaunchKernelGGL(tkr::als_wide_slab_kernel, dim3((unsigned)n_slabs, (unsigned)passes), dim3(tkr::kCgBlock), lds, stream, Y, n, k, rows,
-                           (long long)n_listed, partial, st);
-        TKR_LAUNCH_CHECK();
-    }
-    hipLaunchKernelGGL(tkr::als_gram_wide_reduce_kernel, dim3((k * k + tkr::kCgBlock - 1) / tkr::kCgBlock), dim3(tkr::kCgBlock), 0, stream, partial,
-                       n_slabs, k, scale, ridge, G);
-    TKR_LAUNCH_CHECK();
-    return TKR_OK;
 }

@@ -1358,27 +1358,32 @@ _ALS_REFUSED = (None, 'row %d holds a like outside [0, n_y)', 'the system of row
 
 class AlsRefused(TkrError):
     """a status word of K20 that is not -1; .row and .kind say what it holds (include/tkr.h)"""
+    messages = _ALS_REFUSED
 
     def __init__(self, what, word):
         self.word, self.row, self.kind = word, word >> 2, word & 3
-        super().__init__('%s: %s (kind %d)' % (what, _ALS_REFUSED[self.kind] % self.row, self.kind))
+        super().__init__('%s: %s (kind %d)' % (what, self.messages[self.kind] % self.row, self.kind))
 
 
-def _als_table(what, name, t, k=None):
+def _als_table(what, name, t, k_max, k=None):
     if not isinstance(t, torch.Tensor) or t.dtype != torch.float32 or t.dim() != 2 or not t.is_contiguous() or not t.is_cuda:
         raise TkrError('%s: %s must be a contiguous two-dimensional float32 tensor on the GPU' % (what, name))
     if t.shape[0] < 1 or (k is not None and t.shape[1] != k):
         raise TkrError('%s: %s has shape %s' % (what, name, tuple(t.shape)))
-    if not 1 <= t.shape[1] <= ALS_MAX_K:
-        raise ValueError('%s: k = %d, 1 <= k <= %d is supported' % (what, t.shape[1], ALS_MAX_K))
+    if not 1 <= t.shape[1] <= k_max:
+        raise ValueError('%s: k = %d, 1 <= k <= %d is supported' % (what, t.shape[1], k_max))
     return int(t.shape[0]), int(t.shape[1])
 
 
-def als_workspace_bytes(n_x, k, n_slabs):
-    need = int(lib().tkr_als_workspace_bytes(C.c_int64(n_x), C.c_int32(k), C.c_int64(n_slabs)))
+def _als_bytes(entry, types, values):
+    need = int(getattr(lib(), entry)(*(t(v) for t, v in zip(types, values))))
     if need < 0:
-        raise TkrError('tkr_als_workspace_bytes(%d, %d, %d) failed: tkr error %d' % (n_x, k, n_slabs, need))
+        raise TkrError('%s(%s) failed: tkr error %d' % (entry, ', '.join('%d' % v for v in values), need))
     return need
+
+
+def als_workspace_bytes(n_x, k, n_slabs):
+    return _als_bytes('tkr_als_workspace_bytes', (C.c_int64, C.c_int32, C.c_int64), (n_x, k, n_slabs))
 
 
 def als_heavy_slabs(like_ptr, heavy_from):
@@ -1389,36 +1394,62 @@ def als_heavy_slabs(like_ptr, heavy_from):
     return int(((m + ALS_GRAM_SLAB - 1) // ALS_GRAM_SLAB).sum())
 
 
-def _als_workspace(workspace, need, device):
+def workspace_room(workspace, need, device):
+    """-> `workspace` where it holds `need` bytes on `device`, else a new one that does: the one grower of the ALS and MLP workspaces
+    (here, als.Work and als.MLP keep what it returns)"""
     if workspace is not None and workspace.numel() * workspace.element_size() >= need and workspace.device == device:
         return workspace
-    return torch.empty(max(need, 16) // 8, dtype=torch.int64, device=device)
+    return torch.empty((max(need, 16) + 7) // 8, dtype=torch.int64, device=device)
+
+
+def _als_done(what, result, status, check, refused=AlsRefused):
+    """the tail of every ALS wrapper: check=False hands the status word on unread, else it is read and a refusal raised"""
+    if not check:
+        return result, status
+    word = int(status.item())
+    if word != -1:
+        raise refused(what, word)
+    return result
+
+
+def _als_gram(what, entry, k_max, sizer, Y, rows, scale, ridge, workspace, out, check):
+    n, k = _als_table(what, 'Y', Y, k_max)
+    if rows is not None:
+        _group_tensor(what, 'rows', rows, torch.int32, Y.device)
+    n_listed = n if rows is None else int(rows.numel())
+    workspace = workspace_room(workspace, sizer(k, (n_listed + ALS_GRAM_SLAB - 1) // ALS_GRAM_SLAB), Y.device)
+    G = torch.empty((k, k), dtype=torch.float32, device=Y.device) if out is None else out
+    status = torch.empty(1, dtype=torch.int64, device=Y.device)
+    # (an empty list is still a list: its tensor may have no address, so any that is not null stands in for it)
+    rows_p = C.c_void_p(0) if rows is None else _p(rows if n_listed else Y)
+    _call(entry, Y, _p(Y), C.c_int32(n), C.c_int32(k), rows_p, C.c_int64(n_listed), C.c_double(scale), C.c_double(ridge), _p(G), _p(workspace),
+          C.c_int64(workspace.numel() * workspace.element_size()), _p(status))
+    return _als_done(what, G, status, check)
 
 
 def als_gram(Y, rows=None, scale=1.0, ridge=0.0, workspace=None, out=None, check=True):
     """K20 -> G fp32 [k, k] on the device: scale * sum over the listed rows (int32 tensor; None: all) of y y^T + ridge I
     (include/tkr.h tkr_als_gram).  A listed row outside [0, n) raises AlsRefused (after G is written without it); check=False
     returns (G, status tensor) and reads nothing back"""
-    what = 'als_gram'
-    n, k = _als_table(what, 'Y', Y)
-    if rows is not None:
-        _group_tensor(what, 'rows', rows, torch.int32, Y.device)
-    n_listed = n if rows is None else int(rows.numel())
-    n_slabs = (n_listed + ALS_GRAM_SLAB - 1) // ALS_GRAM_SLAB
-    need = als_workspace_bytes(0, k, n_slabs)
-    workspace = _als_workspace(workspace, need, Y.device)
-    G = torch.empty((k, k), dtype=torch.float32, device=Y.device) if out is None else out
-    status = torch.empty(1, dtype=torch.int64, device=Y.device)
-    # (an empty list is still a list: its tensor may have no address, so any that is not null stands in for it)
-    rows_p = C.c_void_p(0) if rows is None else _p(rows if n_listed else Y)
-    _call('tkr_als_gram', Y, _p(Y), C.c_int32(n), C.c_int32(k), rows_p, C.c_int64(n_listed), C.c_double(scale), C.c_double(ridge), _p(G), _p(workspace), C.c_int64(workspace.numel() * workspace.element_size()),
-          _p(status))
-    if not check:
-        return G, status
-    word = int(status.item())
-    if word != -1:
-        raise AlsRefused(what, word)
-    return G
+    return _als_gram('als_gram', 'tkr_als_gram', ALS_MAX_K, lambda k, n_slabs: als_workspace_bytes(0, k, n_slabs), Y, rows, scale, ridge,
+                     workspace, out, check)
+
+
+def _als_rows(what, k_max, Y, G, like_ptr, like_cols, X, priors=None):
+    """what the three row solvers check alike -> (n_y, k, n_x, n_likes).  priors: None where the call takes no prior, else the list of
+    those handed in (none or one)"""
+    n_y, k = _als_table(what, 'Y', Y, k_max)
+    n_x, _ = _als_table(what, 'X', X, k_max, k)
+    _als_table(what, 'G', G, k_max, k)
+    for prior in priors or ():
+        _als_table(what, 'prior', prior, k_max, k)
+    if G.shape[0] != k or X.device != Y.device or G.device != Y.device or any(p.device != Y.device or p.shape[0] != n_x for p in priors or ()):
+        raise TkrError('%s: G must be [k, k], %s on one GPU' % (what, 'and Y, G and X' if priors is None else 'prior [n_x, k], and Y, G, X and prior'))
+    _group_tensor(what, 'like_ptr', like_ptr, torch.int64, Y.device)
+    _group_tensor(what, 'like_cols', like_cols, torch.int32, Y.device)
+    if like_ptr.numel() != n_x + 1:
+        raise ValueError('%s: like_ptr must hold n_x + 1 = %d entries, not %d' % (what, n_x + 1, like_ptr.numel()))
+    return n_y, k, n_x, int(like_cols.numel())
 
 
 def als_solve_rows(Y, G, like_ptr, like_cols, X, *, w_like, w_rhs, ridge, heavy_from=None, want_loss=False, workspace=None, heavy_slabs=None,
@@ -1428,39 +1459,22 @@ def als_solve_rows(Y, G, like_ptr, like_cols, X, *, w_like, w_rhs, ridge, heavy_
     heavy_from: None = ALS_HEAVY_FROM; heavy_slabs: what als_heavy_slabs gives for this CSR (computed when it is not handed in).
     A refusal raises AlsRefused naming row and kind; check=False returns (row_loss, status tensor) instead and reads nothing back"""
     what = 'als_solve_rows'
-    n_y, k = _als_table(what, 'Y', Y)
-    n_x, _ = _als_table(what, 'X', X, k)
-    _als_table(what, 'G', G, k)
-    if G.shape[0] != k or X.device != Y.device or G.device != Y.device:
-        raise TkrError('%s: G must be [k, k], and Y, G and X on one GPU' % what)
-    _group_tensor(what, 'like_ptr', like_ptr, torch.int64, Y.device)
-    _group_tensor(what, 'like_cols', like_cols, torch.int32, Y.device)
-    if like_ptr.numel() != n_x + 1:
-        raise ValueError('%s: like_ptr must hold n_x + 1 = %d entries, not %d' % (what, n_x + 1, like_ptr.numel()))
+    n_y, k, n_x, n_likes = _als_rows(what, ALS_MAX_K, Y, G, like_ptr, like_cols, X)
     heavy_from = ALS_HEAVY_FROM if heavy_from is None else int(heavy_from)
-    n_likes = int(like_cols.numel())
     need = 0
     if heavy_from <= n_likes:
         need = als_workspace_bytes(n_x, k, als_heavy_slabs(like_ptr, heavy_from) if heavy_slabs is None else heavy_slabs)
-    workspace = _als_workspace(workspace, need, Y.device)
+    workspace = workspace_room(workspace, need, Y.device)
     loss = torch.empty(n_x, dtype=torch.float64, device=Y.device) if want_loss else None
     status = torch.empty(1, dtype=torch.int64, device=Y.device)
     _call('tkr_als_solve_rows', Y, _p(Y), C.c_int32(n_y), C.c_int32(k), _p(G), _p(like_ptr), _p(like_cols) if n_likes else C.c_void_p(0),
           C.c_int64(n_likes), C.c_int64(n_x), C.c_double(w_like), C.c_double(w_rhs), C.c_double(ridge), C.c_int64(heavy_from), _p(X), _p(loss),
           _p(workspace), C.c_int64(workspace.numel() * workspace.element_size()), _p(status))
-    if not check:
-        return loss, status
-    word = int(status.item())
-    if word != -1:
-        raise AlsRefused(what, word)
-    return loss
+    return _als_done(what, loss, status, check)
 
 
 def als_prior_workspace_bytes(n_x, k, n_slabs):
-    need = int(lib().tkr_als_prior_workspace_bytes(C.c_int64(n_x), C.c_int32(k), C.c_int64(n_slabs)))
-    if need < 0:
-        raise TkrError('tkr_als_prior_workspace_bytes(%d, %d, %d) failed: tkr error %d' % (n_x, k, n_slabs, need))
-    return need
+    return _als_bytes('tkr_als_prior_workspace_bytes', (C.c_int64, C.c_int32, C.c_int64), (n_x, k, n_slabs))
 
 
 def als_solve_rows_prior(Y, G, like_ptr, like_cols, X, prior, *, w_like, w_rhs, w_prior, ridge, heavy_from=None, want_loss=False, workspace=None,
@@ -1470,97 +1484,45 @@ def als_solve_rows_prior(Y, G, like_ptr, like_cols, X, prior, *, w_like, w_rhs, 
     computed once per call (include/tkr.h tkr_als_solve_rows_prior).  prior: fp32 [n_x, k] on X's device.  The other arguments, the
     result, AlsRefused and check=False as als_solve_rows"""
     what = 'als_solve_rows_prior'
-    n_y, k = _als_table(what, 'Y', Y)
-    n_x, _ = _als_table(what, 'X', X, k)
-    _als_table(what, 'G', G, k)
-    _als_table(what, 'prior', prior, k)
-    if G.shape[0] != k or X.device != Y.device or G.device != Y.device or prior.device != Y.device or prior.shape[0] != n_x:
-        raise TkrError('%s: G must be [k, k], prior [n_x, k], and Y, G, X and prior on one GPU' % what)
-    _group_tensor(what, 'like_ptr', like_ptr, torch.int64, Y.device)
-    _group_tensor(what, 'like_cols', like_cols, torch.int32, Y.device)
-    if like_ptr.numel() != n_x + 1:
-        raise ValueError('%s: like_ptr must hold n_x + 1 = %d entries, not %d' % (what, n_x + 1, like_ptr.numel()))
+    n_y, k, n_x, n_likes = _als_rows(what, ALS_MAX_K, Y, G, like_ptr, like_cols, X, [prior])
     heavy_from = ALS_HEAVY_FROM if heavy_from is None else int(heavy_from)
-    n_likes = int(like_cols.numel())
     slabs = 0
     if heavy_from <= n_likes:
         slabs = als_heavy_slabs(like_ptr, heavy_from) if heavy_slabs is None else heavy_slabs
     need = als_prior_workspace_bytes(n_x if heavy_from <= n_likes else 0, k, slabs)
-    workspace = _als_workspace(workspace, need, Y.device)
+    workspace = workspace_room(workspace, need, Y.device)
     loss = torch.empty(n_x, dtype=torch.float64, device=Y.device) if want_loss else None
     status = torch.empty(1, dtype=torch.int64, device=Y.device)
     _call('tkr_als_solve_rows_prior', Y, _p(Y), C.c_int32(n_y), C.c_int32(k), _p(G), _p(like_ptr), _p(like_cols) if n_likes else C.c_void_p(0),
           C.c_int64(n_likes), C.c_int64(n_x), C.c_double(w_like), C.c_double(w_rhs), C.c_double(ridge), C.c_int64(heavy_from), _p(X), _p(loss),
           _p(prior), C.c_double(w_prior), _p(workspace), C.c_int64(workspace.numel() * workspace.element_size()), _p(status))
-    if not check:
-        return loss, status
-    word = int(status.item())
-    if word != -1:
-        raise AlsRefused(what, word)
-    return loss
+    return _als_done(what, loss, status, check)
 
 
 ALS_HEAVY_FROM = 4 * ALS_GRAM_SLAB       # a row with this many likes is shared by several workgroups (scripts/time_als.py)
 
 
-# ---- K24: the half-step by conjugate gradients, the Gram at any width up to 512 (csrc/als_cg.hip) -------------------------------------------
+# ---- K24: the half-step by conjugate gradients (csrc/als_cg.hip), the Gram at any width up to 512 (csrc/als.hip) ---------------------------
 ALS_CG_MAX_K = 512           # TKR_ALS_CG_MAX_K of include/tkr.h: a row's x and r are 8 registers per lane each
 ALS_CG_STEPS = 3             # the steps per half-step als.py takes by default
-_ALS_CG_REFUSED = (None, _ALS_REFUSED[1], 'p.q of row %d is not positive and finite, or its solution is not finite', _ALS_REFUSED[3])
 
 
 class AlsCgRefused(AlsRefused):
     """a status word of K24 that is not -1 (the kinds of K20; kind 2 is conjugate gradients' own)"""
-
-    def __init__(self, what, word):
-        self.word, self.row, self.kind = word, word >> 2, word & 3
-        TkrError.__init__(self, '%s: %s (kind %d)' % (what, _ALS_CG_REFUSED[self.kind] % self.row, self.kind))
-
-
-def _als_cg_table(what, name, t, k=None):
-    if not isinstance(t, torch.Tensor) or t.dtype != torch.float32 or t.dim() != 2 or not t.is_contiguous() or not t.is_cuda:
-        raise TkrError('%s: %s must be a contiguous two-dimensional float32 tensor on the GPU' % (what, name))
-    if t.shape[0] < 1 or (k is not None and t.shape[1] != k):
-        raise TkrError('%s: %s has shape %s' % (what, name, tuple(t.shape)))
-    if not 1 <= t.shape[1] <= ALS_CG_MAX_K:
-        raise ValueError('%s: k = %d, 1 <= k <= %d is supported' % (what, t.shape[1], ALS_CG_MAX_K))
-    return int(t.shape[0]), int(t.shape[1])
+    messages = (None, _ALS_REFUSED[1], 'p.q of row %d is not positive and finite, or its solution is not finite', _ALS_REFUSED[3])
 
 
 def als_cg_workspace_bytes(n_x, k):
-    need = int(lib().tkr_als_cg_workspace_bytes(C.c_int64(n_x), C.c_int32(k)))
-    if need < 0:
-        raise TkrError('tkr_als_cg_workspace_bytes(%d, %d) failed: tkr error %d' % (n_x, k, need))
-    return need
+    return _als_bytes('tkr_als_cg_workspace_bytes', (C.c_int64, C.c_int32), (n_x, k))
 
 
 def als_gram_wide_workspace_bytes(k, n_slabs):
-    need = int(lib().tkr_als_gram_wide_workspace_bytes(C.c_int32(k), C.c_int64(n_slabs)))
-    if need < 0:
-        raise TkrError('tkr_als_gram_wide_workspace_bytes(%d, %d) failed: tkr error %d' % (k, n_slabs, need))
-    return need
+    return _als_bytes('tkr_als_gram_wide_workspace_bytes', (C.c_int32, C.c_int64), (k, n_slabs))
 
 
 def als_gram_wide(Y, rows=None, scale=1.0, ridge=0.0, workspace=None, out=None, check=True):
     """K24 -> G fp32 [k, k]: als_gram's definition, arguments and result for 1 <= k <= ALS_CG_MAX_K (include/tkr.h tkr_als_gram_wide)"""
-    what = 'als_gram_wide'
-    n, k = _als_cg_table(what, 'Y', Y)
-    if rows is not None:
-        _group_tensor(what, 'rows', rows, torch.int32, Y.device)
-    n_listed = n if rows is None else int(rows.numel())
-    need = als_gram_wide_workspace_bytes(k, (n_listed + ALS_GRAM_SLAB - 1) // ALS_GRAM_SLAB)
-    workspace = _als_workspace(workspace, need, Y.device)
-    G = torch.empty((k, k), dtype=torch.float32, device=Y.device) if out is None else out
-    status = torch.empty(1, dtype=torch.int64, device=Y.device)
-    rows_p = C.c_void_p(0) if rows is None else _p(rows if n_listed else Y)
-    _call('tkr_als_gram_wide', Y, _p(Y), C.c_int32(n), C.c_int32(k), rows_p, C.c_int64(n_listed), C.c_double(scale), C.c_double(ridge), _p(G),
-          _p(workspace), C.c_int64(workspace.numel() * workspace.element_size()), _p(status))
-    if not check:
-        return G, status
-    word = int(status.item())
-    if word != -1:
-        raise AlsRefused(what, word)
-    return G
+    return _als_gram('als_gram_wide', 'tkr_als_gram_wide', ALS_CG_MAX_K, als_gram_wide_workspace_bytes, Y, rows, scale, ridge, workspace, out, check)
 
 
 def als_cg_rows(Y, G, like_ptr, like_cols, X, *, w_like, w_rhs, ridge, steps=ALS_CG_STEPS, prior=None, w_prior=0.0, want_loss=False, check=True):
@@ -1569,31 +1531,15 @@ def als_cg_rows(Y, G, like_ptr, like_cols, X, *, w_like, w_rhs, ridge, steps=ALS
     solved (include/tkr.h tkr_als_cg_rows).  -> row_loss float64 [n_x] with want_loss, else None.  A refusal raises AlsCgRefused naming
     row and kind; check=False returns (row_loss, status tensor) instead and reads nothing back"""
     what = 'als_cg_rows'
-    n_y, k = _als_cg_table(what, 'Y', Y)
-    n_x, _ = _als_cg_table(what, 'X', X, k)
-    _als_cg_table(what, 'G', G, k)
-    if prior is not None:
-        _als_cg_table(what, 'prior', prior, k)
-    if G.shape[0] != k or X.device != Y.device or G.device != Y.device or (prior is not None and (prior.device != Y.device or prior.shape[0] != n_x)):
-        raise TkrError('%s: G must be [k, k], prior [n_x, k], and Y, G, X and prior on one GPU' % what)
-    _group_tensor(what, 'like_ptr', like_ptr, torch.int64, Y.device)
-    _group_tensor(what, 'like_cols', like_cols, torch.int32, Y.device)
-    if like_ptr.numel() != n_x + 1:
-        raise ValueError('%s: like_ptr must hold n_x + 1 = %d entries, not %d' % (what, n_x + 1, like_ptr.numel()))
+    n_y, k, n_x, n_likes = _als_rows(what, ALS_CG_MAX_K, Y, G, like_ptr, like_cols, X, [] if prior is None else [prior])
     if not isinstance(steps, (int,)) or isinstance(steps, bool) or steps < 0:
         raise ValueError('%s: steps = %r must be an integer, at least 0' % (what, steps))
-    n_likes = int(like_cols.numel())
     loss = torch.empty(n_x, dtype=torch.float64, device=Y.device) if want_loss else None
     status = torch.empty(1, dtype=torch.int64, device=Y.device)
     _call('tkr_als_cg_rows', Y, _p(Y), C.c_int32(n_y), C.c_int32(k), _p(G), _p(like_ptr), _p(like_cols) if n_likes else C.c_void_p(0),
           C.c_int64(n_likes), C.c_int64(n_x), C.c_double(w_like), C.c_double(w_rhs), C.c_double(ridge), C.c_int32(steps), _p(X), _p(loss),
           _p(prior), C.c_double(w_prior), C.c_void_p(0), C.c_int64(0), _p(status))
-    if not check:
-        return loss, status
-    word = int(status.item())
-    if word != -1:
-        raise AlsCgRefused(what, word)
-    return loss
+    return _als_done(what, loss, status, check, AlsCgRefused)
 
 
 # ---- K22: a dense MLP content encoder, applied and trained (csrc/mlp.hip) ------------------------------------------------------------------
@@ -1670,7 +1616,7 @@ def mlp_forward(net, X, rows=None, workspace=None, out=None, check=True):
         _mlp_rows(what, 'rows', rows, X.device)
     m = n if rows is None else int(rows.numel())
     k = net.width[net.n_layers]
-    workspace = _als_workspace(workspace, mlp_workspace_bytes(net, m), X.device)
+    workspace = workspace_room(workspace, mlp_workspace_bytes(net, m), X.device)
     if out is None:
         out = torch.empty((m, k), dtype=torch.float32, device=X.device)
     elif not isinstance(out, torch.Tensor) or out.dtype != torch.float32 or tuple(out.shape) != (m, k) or not out.is_contiguous() or out.device != X.device:
@@ -1702,7 +1648,7 @@ def mlp_fit(net, X, Y, order, batch, lr, workspace=None, check=True):
     if not 1 <= batch <= MLP_MAX_BATCH:
         raise ValueError('%s: batch = %d, 1 <= batch <= %d is supported' % (what, batch, MLP_MAX_BATCH))
     m = int(order.numel())
-    workspace = _als_workspace(workspace, mlp_workspace_bytes(net, 0, batch), X.device)
+    workspace = workspace_room(workspace, mlp_workspace_bytes(net, 0, batch), X.device)
     loss = torch.zeros((m + batch - 1) // batch, dtype=torch.float64, device=X.device)
     status = torch.empty(1, dtype=torch.int64, device=X.device)
     _call('tkr_mlp_fit', X, C.byref(net), _p(X), C.c_int32(int(X.shape[0])), _p(Y), _p(order if m else X), C.c_int64(m), C.c_int32(batch),
