@@ -90,11 +90,12 @@ EXPORTS = ('tkr_version', 'tkr_plan_team', 'tkr_plan_max_blocks', 'tkr_sample_pl
            'tkr_matrix_tokens_host', 'tkr_group_count_dev', 'tkr_group_emit_dev', 'tkr_last_line_of_user_dev', 'tkr_compact_rows_count_dev',
            'tkr_compact_rows_emit_dev', 'tkr_fusion_features', 'tkr_fusion_sgd', 'tkr_fusion_user_weights', 'tkr_fusion_svm_sums',
            'tkr_mmr_select', 'tkr_list_pair_sums', 'tkr_line_metrics', 'tkr_bootstrap_sums', 'tkr_nearest_anchors', 'tkr_als_gram',
-           'tkr_als_solve_rows', 'tkr_als_solve_rows_prior', 'tkr_mlp_forward', 'tkr_mlp_fit', 'tkr_als_cg_rows', 'tkr_als_gram_wide')
+           'tkr_als_solve_rows', 'tkr_als_solve_rows_prior', 'tkr_mlp_forward', 'tkr_mlp_fit', 'tkr_als_cg_rows', 'tkr_als_gram_wide',
+           'tkr_lmf_dense_rows', 'tkr_lmf_step_rows')
 EXPORTS_I64 = ('tkr_vbpr_workspace_floats', 'tkr_vbpr_colplan_lds_bytes', 'tkr_topk_workspace_bytes_for', 'tkr_topk_workspace_bytes', 'tkr_plan_workspace_bytes', 'tkr_like_ranks_workspace_bytes',
                'tkr_parse_dev_workspace_bytes', 'tkr_idtable_slots', 'tkr_scan_dev_workspace_bytes', 'tkr_als_workspace_bytes',
                'tkr_als_prior_workspace_bytes', 'tkr_mlp_workspace_bytes', 'tkr_fusion_svm_partial_bytes', 'tkr_als_cg_workspace_bytes',
-               'tkr_als_gram_wide_workspace_bytes')
+               'tkr_als_gram_wide_workspace_bytes', 'tkr_lmf_workspace_bytes')
 
 
 def lib():
@@ -1542,8 +1543,84 @@ def als_cg_rows(Y, G, like_ptr, like_cols, X, *, w_like, w_rhs, ridge, steps=ALS
     return _als_done(what, loss, status, check, AlsCgRefused)
 
 
+# ---- K25: the two halves of a logistic-MF half-step (csrc/lmf.hip) --------------------------------------------------------------------------
+LMF_MAX_K = 128              # TKR_LMF_MAX_K of include/tkr.h: the tables hold k + 2 columns
+LMF_SLAB = 4096              # TKR_LMF_SLAB: the rows of Y one workgroup of lmf_dense_rows walks
+LMF_LIKE_SLAB = 256          # TKR_LMF_LIKE_SLAB: the likes of a heavy row one wave sums as one chain
+LMF_HEAVY_WAVES = 16         # TKR_LMF_HEAVY_WAVES
+LMF_HEAVY_FROM = 2048        # a row with more likes than this is summed by a whole workgroup
+LMF_NO_HEAVY = 1 << 62       # heavy_from: no row is heavy
+
+
+class LmfRefused(AlsRefused):
+    """a status word of K25 that is not -1 (the kinds 1 and 3 of K20)"""
+    messages = (None, _ALS_REFUSED[1], None, _ALS_REFUSED[3])
+
+
+def lmf_workspace_bytes(n_x, k, n_y):
+    return _als_bytes('tkr_lmf_workspace_bytes', (C.c_int64, C.c_int32, C.c_int64), (n_x, k, n_y))
+
+
+def _lmf_tables(what, pairs):
+    """pairs: (name, tensor), all fp32 [., k + 2] on one GPU -> k"""
+    k = None
+    for name, t in pairs:
+        _, K = _als_table(what, name, t, LMF_MAX_K + 2, None if k is None else k + 2)
+        if K < 3:
+            raise ValueError('%s: %s has %d columns; a table holds k + 2 of them, k >= 1' % (what, name, K))
+        k = K - 2
+        if t.device != pairs[0][1].device:
+            raise TkrError('%s: %s must be on one GPU' % (what, ', '.join(n for n, _ in pairs)))
+    return k
+
+
+def lmf_dense_rows(X, Y, want_loss=False, workspace=None, out=None):
+    """K25 -> D fp32 [n_x, K] on the device: D[r] = sum over ALL rows c of Y of sigma(X[r] . Y[c]) Y[c], the score matrix never stored
+    (include/tkr.h tkr_lmf_dense_rows).  X fp32 [n_x, K], Y fp32 [n_y, K], K = k + 2 <= LMF_MAX_K + 2.  want_loss: -> (D, sp), sp
+    float64 [n_x] = sum_c softplus(X[r] . Y[c]).  Nothing is read back"""
+    what = 'lmf_dense_rows'
+    k = _lmf_tables(what, [('X', X), ('Y', Y)])
+    n_x, n_y = int(X.shape[0]), int(Y.shape[0])
+    workspace = workspace_room(workspace, lmf_workspace_bytes(n_x, k, n_y), X.device)
+    D = torch.empty((n_x, k + 2), dtype=torch.float32, device=X.device) if out is None else out
+    if D.shape != X.shape or D.dtype != torch.float32 or D.device != X.device or not D.is_contiguous():
+        raise TkrError('%s: out must be a contiguous float32 tensor of the shape of X on its device' % what)
+    sp = torch.empty(n_x, dtype=torch.float64, device=X.device) if want_loss else None
+    _call('tkr_lmf_dense_rows', X, _p(X), C.c_int64(n_x), _p(Y), C.c_int64(n_y), C.c_int32(k), _p(D), _p(sp), _p(workspace),
+          C.c_int64(workspace.numel() * workspace.element_size()))
+    return (D, sp) if want_loss else D
+
+
+def lmf_step_rows(Y, D, like_ptr, like_cols, X, H, *, fixed, alpha, lam, lr, heavy_from=None, want_loss=False, workspace=None, check=True):
+    """K25, in place on X and its AdaGrad slot H (both fp32 [n_x, K]): for every row r the sum over its likes, rows of Y, of
+    (1 - sigma(s)) y, the gradient g = alpha L - D[r] - lam x, h += g^2, x += lr g / sqrt(h); column `fixed` keeps its bits
+    (include/tkr.h tkr_lmf_step_rows).  D: lmf_dense_rows(X, Y).  -> row_loss float64 [n_x] with want_loss, else None.  heavy_from:
+    None = LMF_HEAVY_FROM.  A refusal raises LmfRefused naming row and kind; check=False returns (row_loss, status tensor) instead
+    and reads nothing back"""
+    what = 'lmf_step_rows'
+    k = _lmf_tables(what, [('Y', Y), ('X', X), ('D', D), ('H', H)])
+    n_y, n_x = int(Y.shape[0]), int(X.shape[0])
+    if D.shape != X.shape or H.shape != X.shape:
+        raise TkrError('%s: D and H must have the shape of X, %s' % (what, tuple(X.shape)))
+    _group_tensor(what, 'like_ptr', like_ptr, torch.int64, Y.device)
+    _group_tensor(what, 'like_cols', like_cols, torch.int32, Y.device)
+    if like_ptr.numel() != n_x + 1:
+        raise ValueError('%s: like_ptr must hold n_x + 1 = %d entries, not %d' % (what, n_x + 1, like_ptr.numel()))
+    if not isinstance(fixed, (int,)) or isinstance(fixed, bool) or not 0 <= fixed < k + 2:
+        raise ValueError('%s: fixed = %r must be a column, 0 <= fixed < %d' % (what, fixed, k + 2))
+    n_likes = int(like_cols.numel())
+    heavy_from = LMF_HEAVY_FROM if heavy_from is None else int(heavy_from)
+    workspace = workspace_room(workspace, lmf_workspace_bytes(n_x, k, 1) if heavy_from < n_likes else 0, Y.device)
+    loss = torch.empty(n_x, dtype=torch.float64, device=Y.device) if want_loss else None
+    status = torch.empty(1, dtype=torch.int64, device=Y.device)
+    _call('tkr_lmf_step_rows', Y, _p(Y), C.c_int32(n_y), C.c_int32(k), _p(D), _p(like_ptr), _p(like_cols) if n_likes else C.c_void_p(0),
+          C.c_int64(n_likes), C.c_int64(n_x), C.c_int32(fixed), C.c_double(alpha), C.c_double(lam), C.c_double(lr), C.c_int64(heavy_from), _p(X),
+          _p(H), _p(loss), _p(workspace), C.c_int64(workspace.numel() * workspace.element_size()), _p(status))
+    return _als_done(what, loss, status, check, LmfRefused)
+
+
 # ---- K22: a dense MLP content encoder, applied and trained (csrc/mlp.hip) ------------------------------------------------------------------
-MLP_MAX_LAYERS = 5           # TKR_MLP_MAX_LAYERS of include/tkr.h
+MLP_MAX_LAYERS = 5          # TKR_MLP_MAX_LAYERS of include/tkr.h
 MLP_MAX_BATCH = 256          # TKR_MLP_MAX_BATCH
 MLP_SLAB = 512               # TKR_MLP_SLAB: the inputs of a layer one workgroup sums
 MLP_FORWARD_CHUNK = 256      # TKR_MLP_FORWARD_CHUNK
