@@ -51,10 +51,17 @@ Stated differences from the reference:
     significance.py); only the [R, columns] sums come down.  ``--compare MODEL_B`` ranks a second model directory on the same lines,
     resamples both together (a paired bootstrap) and adds ``S.vs.m`` (B's values), ``S.diff.m`` (this model - B), ``S.diff.m.lo`` /
     ``.hi`` and ``S.diff.m.p`` (two-sided).  Single process only.
+
+How a scenario is ranked: once per entry of ``-sl``, ``main`` makes the ``Lines`` of this rank's shard (user rows, like CSR and, on first
+use, the rated mask on the device; they depend on the Scenario alone) and a ``Ranker`` of the user table and the model on them, which
+builds the model's ``Items`` (the test ids' rows of final-V.dat and final-B.dat) on first use and offers K4, K8 and K5.  Every
+``*_loaded`` function of ``main`` takes that Ranker; ``--compare``'s model gets a Ranker of its own on the same Lines.
 """
 from __future__ import annotations
 
 import argparse
+import collections
+import functools
 import os
 
 os.environ.setdefault('HSA_ENABLE_IPC_MODE_LEGACY', '0')     # multi-process GPU work on this driver needs dmabuf IPC; must be set before
@@ -86,6 +93,19 @@ def read_matrix(path, ids):
     out = np.zeros((len(ids), every.shape[1]), dtype=np.float32)
     out[rows] = every[rows]
     return out
+
+
+def read_model(model_dir, uids=None, vids=None):
+    """a model directory through the id lists -> (U, V, b): final-U.dat when ``uids`` is given, final-V.dat and final-B.dat ([n, 1];
+    None when the file is absent) when ``vids`` is; None for what was not asked for, whose files are not opened"""
+    U = V = b = None
+    if uids is not None:
+        U = read_matrix(os.path.join(model_dir, 'final-U.dat'), uids)
+    if vids is not None:
+        V = read_matrix(os.path.join(model_dir, 'final-V.dat'), vids)
+        if os.path.exists(os.path.join(model_dir, 'final-B.dat')):
+            b = read_matrix(os.path.join(model_dir, 'final-B.dat'), vids)
+    return U, V, b
 
 
 class Scenario:
@@ -228,32 +248,72 @@ def _take_rows(ptr, cols, rows):
     return out, cols[pos]
 
 
-def _scenario_operands(vmat, bmat, vids, sc, device):
-    """the scenario's test-item rows, bias, user rows and rated mask on the device: the operands of K4 and K8"""
-    te_rows = np.zeros(len(sc.teids), dtype=np.int64)
-    for vid, col in sc.teids.items():
-        te_rows[col] = vids[vid]                                     # evaluate.py:75-77
+class Lines:
+    """The test lines of a Scenario -- whole, or one rank's shard -- on the device.  It depends on the Scenario alone, so every model
+    ranked on these lines shares it.  The rated mask is built on first use and kept: a path that needs none launches none."""
+
+    def __init__(self, sc, device):
+        self.sc, self.device = sc, device
+        users, self.like_ptr, self.like_cols, self.rated_ptr = _on_device(sc, device, 'users', 'like_ptr', 'like_cols', 'rated_ptr')
+        self.user_idx = users.to(torch.int32)
+
+    @functools.cached_property
+    def mask(self):
+        """(the bit mask of every line's train-rated test columns, its pitch)"""
+        return tkr_hip.build_rated_mask(self.rated_ptr, *_on_device(self.sc, self.device, 'rated_cols'), len(self.sc.users), len(self.sc.teids))
+
+
+Items = collections.namedtuple('Items', 'te_rows Vt bias')
+
+
+def scenario_items(vmat, bmat, vids, teids, device):
+    """a model's rows of a scenario's test ids -> Items: ``te_rows`` int64 [n_te], the row of final-V.dat of every test column; those
+    rows of it (``Vt``) and of final-B.dat (``bias``, None without one) on the device"""
+    te_rows = np.zeros(len(teids), dtype=np.int64)
+    for vid, col in teids.items():
+        te_rows[col] = vids[vid]                                     # evaluate.py:75-77 (KeyError: a test id that `vid` lacks)
     Vt = torch.from_numpy(np.ascontiguousarray(vmat[te_rows])).to(device)
-    bias = None
-    if bmat is not None:
-        bias = torch.from_numpy(np.ascontiguousarray(bmat.reshape(-1)[te_rows])).to(device)
-    users, rptr, rcols = _on_device(sc, device, 'users', 'rated_ptr', 'rated_cols')
-    user_idx = users.to(torch.int32)
-    mask, pitch = tkr_hip.build_rated_mask(rptr, rcols, len(sc.users), len(sc.teids))
-    return Vt, bias, user_idx, mask, pitch
+    return Items(te_rows, Vt, None if bmat is None else torch.from_numpy(np.ascontiguousarray(bmat.reshape(-1)[te_rows])).to(device))
+
+
+class Ranker:
+    """A user table on the device, a model (vmat, bmat, vids) and the Lines it is ranked on: the operands of K4 (score_topk), K8
+    (like_ranks) and K5 (count_hits).  The model's Items are built on first use, as the mask is: a shard without lines builds neither."""
+
+    def __init__(self, umat_dev, model, lines):
+        self.umat, self.model, self.lines = umat_dev, model, lines
+
+    @functools.cached_property
+    def items(self):
+        return scenario_items(*self.model, self.lines.sc.teids, self.lines.device)
+
+    def _filter(self):
+        mask, pitch = self.lines.mask
+        return dict(bias=self.items.bias, user_idx=self.lines.user_idx, mask=mask, mask_pitch=pitch)
+
+    def score_topk(self, K, want_scores=False):
+        return tkr_hip.score_topk(self.umat, self.items.Vt, K, want_scores=want_scores, **self._filter())
+
+    def like_ranks(self):
+        return tkr_hip.like_ranks(self.umat, self.items.Vt, self.lines.like_ptr, self.lines.like_cols, **self._filter())
+
+    def count_hits(self, ids, step, interval):
+        return tkr_hip.count_hits(ids, self.lines.like_ptr, self.lines.like_cols, step, interval)
 
 
 def rank_scenario(umat_dev, vmat, bmat, vids, sc, total, device, want_scores=False):
     """filtered top-`total` test columns of every test line -> int32 [n_lines, total] (device)"""
-    Vt, bias, user_idx, mask, pitch = _scenario_operands(vmat, bmat, vids, sc, device)
-    return tkr_hip.score_topk(umat_dev, Vt, total, bias=bias, user_idx=user_idx, mask=mask, mask_pitch=pitch,
-                              want_scores=want_scores)
+    return Ranker(umat_dev, (vmat, bmat, vids), Lines(sc, device)).score_topk(total, want_scores)
+
+
+def _block(n, rank, world):
+    """the lines [lo, hi) of n that rank `rank` of `world` ranks takes"""
+    return rank * n // world, (rank + 1) * n // world
 
 
 def shard_scenario(sc, rank, world):
     """the contiguous block of test lines rank `rank` of `world` ranks scores (users are independent: SURVEY.md §8e)"""
-    n = len(sc.users)
-    lo, hi = rank * n // world, (rank + 1) * n // world
+    lo, hi = _block(len(sc.users), rank, world)
     lp, rp = sc.like_ptr, sc.rated_ptr
     sp = sc.seen_ptr
     seen = (None, None) if sp is None else (sp[lo:hi + 1] - sp[lo], sc.seen_cols[sp[lo]:sp[hi]])
@@ -268,6 +328,21 @@ def _world():
     return 0, 1
 
 
+def _shard(full):
+    """-> (the Scenario this rank ranks -- `full` itself in a single process --, rank, world)"""
+    rank, world = _world()
+    return (shard_scenario(full, rank, world) if world > 1 else full), rank, world
+
+
+def _sum_over_ranks(vec, device):
+    """a host vector summed over the ranks, on every rank (one all-reduce: RCCL reduces device tensors, gloo host tensors)"""
+    import torch.distributed as dist
+    acc = torch.from_numpy(vec)
+    acc = acc.to(device) if dist.get_backend() == 'nccl' else acc
+    dist.all_reduce(acc, op=dist.ReduceOp.SUM)
+    return acc.cpu().numpy()
+
+
 def evaluate_scenario(umat_dev, vmat, bmat, uids, vids, data_dir, fold, scenario, step, total, device, umap=None):
     """accuracy@(step, 2*step, ...) of one scenario (evaluate.py:72-112).  Under torch.distributed every rank ranks its
     block of the scenario's test lines; what the reference accumulates over users -- tresults[k] and tcount, :106-112 --
@@ -278,70 +353,57 @@ def evaluate_scenario(umat_dev, vmat, bmat, uids, vids, data_dir, fold, scenario
 
 def evaluate_loaded(umat_dev, vmat, bmat, vids, full, step, total, device):
     """the ranking + counting half of evaluate_scenario on an already parsed Scenario (the same on every rank)"""
-    rank, world = _world()
-    sc = shard_scenario(full, rank, world) if world > 1 else full
+    return accuracy_loaded(Ranker(umat_dev, (vmat, bmat, vids), Lines(_shard(full)[0], device)), step, total)
+
+
+def accuracy_loaded(ops, step, total):
+    """evaluate_loaded on a Ranker over this rank's shard: K4, K5 and the all-reduce"""
+    sc = ops.lines.sc
     interval = total // step
-    hits = np.zeros(interval, dtype=np.int64)
+    hits, tcount = np.zeros(interval, dtype=np.int64), sc.tcount
     if len(sc.users):
-        ids = rank_scenario(umat_dev, vmat, bmat, vids, sc, total, device)
-        lptr, lcols = _on_device(sc, device, 'like_ptr', 'like_cols')
-        hits = tkr_hip.count_hits(ids, lptr, lcols, step, interval).cpu().numpy()
-    tcount = sc.tcount
-    if world > 1:
-        import torch.distributed as dist
-        on_dev = dist.get_backend() == 'nccl'                        # RCCL reduces device tensors, gloo host tensors
-        acc = torch.from_numpy(np.r_[hits, tcount].astype(np.int64))
-        acc = acc.to(device) if on_dev else acc
-        dist.all_reduce(acc, op=dist.ReduceOp.SUM)
-        acc = acc.cpu().numpy()
+        hits = ops.count_hits(ops.score_topk(total), step, interval).cpu().numpy()
+    if _world()[1] > 1:
+        acc = _sum_over_ranks(np.r_[hits, tcount].astype(np.int64), ops.lines.device)
         hits, tcount = acc[:interval], int(acc[interval])
     return [float(h) / tcount for h in hits]                          # ZeroDivisionError like evaluate.py:112
 
 
 def like_ranks_loaded(umat_dev, vmat, bmat, vids, sc, device):
     """K8 on an already parsed Scenario with at least one line -> the filtered rank of every liked column, int32 [n_likes] (device)"""
-    Vt, bias, user_idx, mask, pitch = _scenario_operands(vmat, bmat, vids, sc, device)
-    lptr, lcols = _on_device(sc, device, 'like_ptr', 'like_cols')
-    return tkr_hip.like_ranks(umat_dev, Vt, lptr, lcols, bias=bias, user_idx=user_idx, mask=mask, mask_pitch=pitch)
+    return Ranker(umat_dev, (vmat, bmat, vids), Lines(sc, device)).like_ranks()
 
 
-def rank_metrics_loaded(umat_dev, vmat, bmat, vids, full, step, total, metrics, device, keep=None):
-    """{metric: list of values} (rankmetrics.py) of an already parsed Scenario from one full-rank pass: K8 gives the filtered rank of
-    every liked column of this rank's block of test lines, the metric sums and counts are all-reduced like the hits of
-    evaluate_loaded (one fp64 vector; the same on every rank afterwards).  keep: a dict that receives K8's output, still on the device,
-    as 'ranks' (None without a test line)."""
-    rank, world = _world()
-    sc = shard_scenario(full, rank, world) if world > 1 else full
+def rank_metrics_loaded(ops, step, total, metrics, keep=None):
+    """{metric: list of values} (rankmetrics.py) from one full-rank pass of a Ranker over this rank's shard: K8 gives the filtered rank
+    of every liked column of the shard's test lines, the metric sums and counts are all-reduced like the hits of accuracy_loaded (one
+    fp64 vector; the same on every rank afterwards).  keep: a dict that receives K8's output, still on the device, as 'ranks' (None
+    without a test line)."""
+    sc = ops.lines.sc
     ranks, ranks_dev = np.zeros(0, dtype=np.int32), None
     if len(sc.users):
-        ranks_dev = like_ranks_loaded(umat_dev, vmat, bmat, vids, sc, device)
+        ranks_dev = ops.like_ranks()
         ranks = ranks_dev.cpu().numpy()
     if keep is not None:
         keep['ranks'] = ranks_dev
     sums = rankmetrics.rank_sums(ranks, sc.like_ptr, sc.rated_ptr, len(sc.teids), step, total)
-    if world > 1:
-        import torch.distributed as dist
-        on_dev = dist.get_backend() == 'nccl'
-        acc = torch.from_numpy(rankmetrics.to_vector(sums))
-        acc = acc.to(device) if on_dev else acc
-        dist.all_reduce(acc, op=dist.ReduceOp.SUM)
-        sums = rankmetrics.from_vector(acc.cpu().numpy(), total // step)
+    if _world()[1] > 1:
+        sums = rankmetrics.from_vector(_sum_over_ranks(rankmetrics.to_vector(sums), ops.lines.device), total // step)
     return rankmetrics.finish(sums, metrics)
 
 
-def significance_loaded(ranks_dev, umat_b, vmat_b, bmat_b, vids, sc, step, total, metrics, boot, device):
-    """the bootstrap figures of an already parsed Scenario (single process) -> significance.report's dict.  ranks_dev: K8's ranks of the
-    model under evaluation (device); umat_b (device) / vmat_b / bmat_b: the model of --compare, or None; boot: dict(R, seed, level).
+def significance_loaded(ranks_dev, lines, other, step, total, metrics, boot):
+    """the bootstrap figures of a scenario's Lines (single process) -> significance.report's dict.  ranks_dev: K8's ranks of the model
+    under evaluation (device); other: the Ranker of --compare's model on the same Lines, or None; boot: dict(R, seed, level).
     The line tables of both models are built, joined and resampled on the device (K18); only the column sums come down"""
     if ranks_dev is None:
         raise ZeroDivisionError('--bootstrap: no test line to resample')
-    lptr, rptr = _on_device(sc, device, 'like_ptr', 'rated_ptr')
-    X = significance.line_table(ranks_dev, lptr, rptr, len(sc.teids), step, total)
-    if umat_b is not None:
-        ranks_b = like_ranks_loaded(umat_b, vmat_b, bmat_b, vids, sc, device)
-        X = torch.cat([X, significance.line_table(ranks_b, lptr, rptr, len(sc.teids), step, total)], dim=1).contiguous()
+    n_cols = len(lines.sc.teids)
+    X = significance.line_table(ranks_dev, lines.like_ptr, lines.rated_ptr, n_cols, step, total)
+    if other is not None:
+        X = torch.cat([X, significance.line_table(other.like_ranks(), lines.like_ptr, lines.rated_ptr, n_cols, step, total)], dim=1).contiguous()
     reps = significance.bootstrap_sums(X, boot['R'], boot['seed']).cpu().numpy()
-    return significance.report(X.sum(dim=0).cpu().numpy(), reps, total // step, metrics, boot['level'], 2 if umat_b is not None else 1)
+    return significance.report(X.sum(dim=0).cpu().numpy(), reps, total // step, metrics, boot['level'], 2 if other is not None else 1)
 
 
 def negative_rows(sc, n_neg, seed):
@@ -358,46 +420,38 @@ def negative_rows(sc, n_neg, seed):
     return np.repeat(np.arange(n, dtype=np.int64), np.diff(lptr)), cand_ptr, cand_cols, like_at
 
 
-def negative_metrics_loaded(umat_dev, vmat, bmat, vids, full, step, total, n_neg, seed, metrics, device):
-    """{metric: list of values} of hr / ndcg / mrr against sampled negatives.  The rows are drawn for the whole scenario on every rank
-    (a host function of the seed: the same rows whatever the number of ranks); a rank scores the rows of its block of test lines --
-    the block shard_scenario gives it -- with K12, and the sums are all-reduced like those of rank_metrics_loaded."""
+def negative_metrics_loaded(ops, full, step, total, n_neg, seed, metrics):
+    """{metric: list of values} of hr / ndcg / mrr of a Ranker's model against sampled negatives.  The rows are drawn for the whole
+    Scenario `full` on every rank (a host function of the seed: the same rows whatever the number of ranks); a rank scores the rows of
+    its block of test lines -- the block shard_scenario gives it -- with K12, and the sums are all-reduced like those of
+    rank_metrics_loaded."""
     rank, world = _world()
+    device = ops.lines.device
     line, cand_ptr, cand_cols, like_at = negative_rows(full, n_neg, seed)
-    n = len(full.users)
-    lo, hi = (rank * n // world, (rank + 1) * n // world) if world > 1 else (0, n)
+    lo, hi = _block(len(full.users), rank, world)
     q0, q1 = int(np.searchsorted(line, lo)), int(np.searchsorted(line, hi))
     like_ranks = np.zeros(0, dtype=np.int32)
     if q1 > q0:
-        te_rows = np.zeros(len(full.teids), dtype=np.int64)
-        for vid, col in full.teids.items():
-            te_rows[col] = vids[vid]
-        Vt = torch.from_numpy(np.ascontiguousarray(vmat[te_rows])).to(device)
-        bias = None if bmat is None else torch.from_numpy(np.ascontiguousarray(bmat.reshape(-1)[te_rows])).to(device)
         user_idx = torch.from_numpy(full.users[line[q0:q1]].astype(np.int32)).to(device)
         ptr = cand_ptr[q0:q1 + 1] - cand_ptr[q0]
         cols = cand_cols[cand_ptr[q0]:cand_ptr[q1]]
-        _, ranks = tkr_hip.rank_candidates(umat_dev, Vt, torch.from_numpy(ptr).to(device), torch.from_numpy(cols).to(device), bias=bias,
-                                           user_idx=user_idx)
+        _, ranks = tkr_hip.rank_candidates(ops.umat, ops.items.Vt, torch.from_numpy(ptr).to(device), torch.from_numpy(cols).to(device),
+                                           bias=ops.items.bias, user_idx=user_idx)
         like_ranks = ranks.cpu().numpy()[like_at[q0:q1] - cand_ptr[q0]]
     sums = rankmetrics.negative_sums(like_ranks, step, total)
     if world > 1:
-        import torch.distributed as dist
-        on_dev = dist.get_backend() == 'nccl'
-        acc = torch.from_numpy(rankmetrics.neg_to_vector(sums))
-        acc = acc.to(device) if on_dev else acc
-        dist.all_reduce(acc, op=dist.ReduceOp.SUM)
-        sums = rankmetrics.neg_from_vector(acc.cpu().numpy(), total // step)
+        sums = rankmetrics.neg_from_vector(_sum_over_ranks(rankmetrics.neg_to_vector(sums), device), total // step)
     return rankmetrics.finish(sums, metrics)
 
 
-def list_metrics_loaded(umat_dev, vmat, bmat, vids, sc, step, total, metrics, div, device, anchors=None):
-    """the list metrics of an already parsed Scenario (single process) -> (plain, mmr): {metric: values at step, 2 step, ...} of the
+def list_metrics_loaded(ops, step, total, metrics, div, anchors=None):
+    """the list metrics of a Ranker over a whole Scenario (single process) -> (plain, mmr): {metric: values at step, 2 step, ...} of the
     ordinary top-`total` lists for the `metrics` of diversity.LIST_METRICS, and -- with div, the arguments of --diversify -- the same of
-    the lists K17 re-ranks out of the div['pool'] best, plus 'acc': K5's hit count on them as evaluate_loaded reports it (else None).
+    the lists K17 re-ranks out of the div['pool'] best, plus 'acc': K5's hit count on them as accuracy_loaded reports it (else None).
     anchors: (ptr, cols) on the device, the training likes of every test line's user in the `vid` numbering -- both dicts then also
     hold 'unexp', the unexpectedness of the lists against them (K19, explain.list_unexpectedness): the similarity table is the whole
     final-V.dat's, and the lists' test columns are mapped to its rows first"""
+    sc, device = ops.lines.sc, ops.lines.device
     interval = total // step
     grid = [step * (q + 1) for q in range(interval)]
     plain = {m: [0.0] * interval for m in list(metrics) + (['unexp'] if anchors is not None else [])}
@@ -406,20 +460,15 @@ def list_metrics_loaded(umat_dev, vmat, bmat, vids, sc, step, total, metrics, di
         return plain, mmr
     unexp = None
     if anchors is not None:
-        te_rows = np.zeros(len(sc.teids), dtype=np.int64)
-        for vid, col in sc.teids.items():
-            te_rows[col] = vids[vid]
-        te_rows = torch.from_numpy(te_rows.astype(np.int32)).to(device)
-        S_full = diversity.similarity_table(torch.from_numpy(vmat).to(device), div['similarity'] if div else 'cosine')
+        te_rows = torch.from_numpy(ops.items.te_rows.astype(np.int32)).to(device)
+        S_full = diversity.similarity_table(torch.from_numpy(ops.model[0]).to(device), div['similarity'] if div else 'cosine')
 
         def unexp(lists):
             as_vid = torch.where(lists >= 0, te_rows[lists.clamp(min=0).long()], torch.full_like(lists, -1)).contiguous()
             return explain.list_unexpectedness(S_full, as_vid, anchors[0], anchors[1], grid)
-    Vt, bias, user_idx, mask, pitch = _scenario_operands(vmat, bmat, vids, sc, device)
-    S = diversity.similarity_table(Vt, div['similarity'] if div else 'cosine')
+    S = diversity.similarity_table(ops.items.Vt, div['similarity'] if div else 'cosine')
     n_cols = len(sc.teids)
-    ids, scores = tkr_hip.score_topk(umat_dev, Vt, div['pool'] if div else total, bias=bias, user_idx=user_idx, mask=mask, mask_pitch=pitch,
-                                     want_scores=True)
+    ids, scores = ops.score_topk(div['pool'] if div else total, want_scores=True)
     if metrics:
         every = diversity.list_metrics(S, ids[:, :total].contiguous(), n_cols, grid)
         plain = {m: every[m] for m in metrics}
@@ -427,8 +476,7 @@ def list_metrics_loaded(umat_dev, vmat, bmat, vids, sc, step, total, metrics, di
         plain['unexp'] = unexp(ids[:, :total])
     if div:
         picked, _ = diversity.rerank(S, diversity.relevance(ids, scores), ids, scores, div['diversify'], total)
-        lptr, lcols = _on_device(sc, device, 'like_ptr', 'like_cols')
-        hits = tkr_hip.count_hits(picked, lptr, lcols, step, interval).cpu().numpy()
+        hits = ops.count_hits(picked, step, interval).cpu().numpy()
         mmr = {'acc': [float(h) / sc.tcount for h in hits]}
         if metrics:
             every = diversity.list_metrics(S, picked, n_cols, grid)
@@ -501,73 +549,67 @@ def main(argv=None):
     device = torch.device('cuda', torch.cuda.current_device())
     uids = read_ids(os.path.join(args.data, 'uid'))
     vids = read_ids(os.path.join(args.data, 'vid'))
-    umat = read_matrix(os.path.join(args.model, 'final-U.dat'), uids)
-    vmat = read_matrix(os.path.join(args.model, 'final-V.dat'), vids)
-    bmat = None
-    if os.path.exists(os.path.join(args.model, 'final-B.dat')):
-        bmat = read_matrix(os.path.join(args.model, 'final-B.dat'), vids)
+    umat, vmat, bmat = read_model(args.model, uids, vids)
     umat_dev = torch.from_numpy(umat).to(device)
     umap = textio.IdMap(uids)
-    umat_b = vmat_b = bmat_b = None
     if args.compare is not None:                                     # model B: the same uid / vid lists
-        umat_b = torch.from_numpy(read_matrix(os.path.join(args.compare, 'final-U.dat'), uids)).to(device)
-        vmat_b = read_matrix(os.path.join(args.compare, 'final-V.dat'), vids)
-        if os.path.exists(os.path.join(args.compare, 'final-B.dat')):
-            bmat_b = read_matrix(os.path.join(args.compare, 'final-B.dat'), vids)
+        umat_b, vmat_b, bmat_b = read_model(args.compare, uids, vids)
+        umat_b = torch.from_numpy(umat_b).to(device)
     results, extra, negs, lists, boots = {}, {}, {}, {}, {}
     liked = textio.parse_ratings(os.path.join(args.data, 'f%dtr.txt' % args.fold), umap, textio.IdMap(vids)) if unexp else None
+
+    def rank_entry(scenario):
+        """the accuracy of one entry of -sl, and its other figures when the scenario is named for the first time.  One set of operands
+        serves all of them; it is released on return, so the next entry is loaded into the device memory this one leaves"""
+        full = load_scenario(args.data, args.fold, scenario, uids, umap)
+        ops = Ranker(umat_dev, (vmat, bmat, vids), Lines(_shard(full)[0], device))
+        acc = accuracy_loaded(ops, args.step, args.total)
+        if (args.metrics or div) and scenario not in extra:          # (a scenario listed twice: its metric lines are not doubled)
+            kept = {} if boot else None
+            extra[scenario] = rank_metrics_loaded(ops, args.step, args.total, full_metrics, kept)
+            if boot:
+                other = Ranker(umat_b, (vmat_b, bmat_b, vids), ops.lines) if args.compare is not None else None
+                boots[scenario] = significance_loaded(kept['ranks'], ops.lines, other, args.step, args.total, full_metrics, boot)
+            if neg_metrics:
+                negs[scenario] = negative_metrics_loaded(ops, full, args.step, args.total, args.negatives, args.neg_seed, neg_metrics)
+            if list_metrics or div or unexp:
+                anchors = explain.anchors_csr([liked], full.users, len(vmat), device) if unexp else None
+                lists[scenario] = list_metrics_loaded(ops, args.step, args.total, list_metrics, div, anchors)
+        return acc
+
     for scenario in args.scenarios:
-        if args.metrics or div:
-            full = load_scenario(args.data, args.fold, scenario, uids, umap)
-            acc = evaluate_loaded(umat_dev, vmat, bmat, vids, full, args.step, args.total, device)
-            if scenario not in extra:                                # (a scenario listed twice: its metric lines are not doubled)
-                kept = {} if boot else None
-                extra[scenario] = rank_metrics_loaded(umat_dev, vmat, bmat, vids, full, args.step, args.total, full_metrics, device, kept)
-                if boot:
-                    boots[scenario] = significance_loaded(kept['ranks'], umat_b, vmat_b, bmat_b, vids, full, args.step, args.total,
-                                                          full_metrics, boot, device)
-                if neg_metrics:
-                    negs[scenario] = negative_metrics_loaded(umat_dev, vmat, bmat, vids, full, args.step, args.total, args.negatives,
-                                                             args.neg_seed, neg_metrics, device)
-                if list_metrics or div or unexp:
-                    anchors = explain.anchors_csr([liked], full.users, len(vmat), device) if unexp else None
-                    lists[scenario] = list_metrics_loaded(umat_dev, vmat, bmat, vids, full, args.step, args.total, list_metrics, div, device,
-                                                          anchors)
-        else:
-            acc = evaluate_scenario(umat_dev, vmat, bmat, uids, vids, args.data, args.fold, scenario, args.step, args.total, device, umap)
+        acc = rank_entry(scenario)
         if scenario not in results:                                  # evaluate.py:109-112 ACCUMULATES per scenario name: a scenario
             results[scenario] = [0.0] * len(acc)                     # listed twice ("-sl im im") prints doubled values, twice
         for k, v in enumerate(acc):
             results[scenario][k] += v
     lines = []
-    for scenario in args.scenarios:
-        lines.append(scenario + ''.join(',%.6f' % v for v in results[scenario]))
-        if rank == 0:                                                # one report, like the single process
+
+    def report(name, values, every_rank=False):
+        lines.append(name + ''.join(',%.6f' % v for v in values))
+        if rank == 0 or every_rank:                                  # one report, like the single process
             print(lines[-1])
+
+    for scenario in args.scenarios:
+        report(scenario, results[scenario])
     for scenario in args.scenarios if args.metrics else ():
         for m in full_metrics:
-            lines.append('%s.%s' % (scenario, m) + ''.join(',%.6f' % v for v in extra[scenario][m]))
-            if rank == 0:
-                print(lines[-1])
+            report('%s.%s' % (scenario, m), extra[scenario][m])
     for scenario in args.scenarios if neg_metrics else ():
         for m in neg_metrics:
-            lines.append('%s.neg%d.%s' % (scenario, args.negatives, m) + ''.join(',%.6f' % v for v in negs[scenario][m]))
-            if rank == 0:
-                print(lines[-1])
-    list_names = list_metrics + (['unexp'] if unexp else [])
+            report('%s.neg%d.%s' % (scenario, args.negatives, m), negs[scenario][m])
+    list_names = list_metrics + (['unexp'] if unexp else [])         # (from here on a single process: refused above otherwise)
     for which, names in ((0, list_names), (1, (['acc'] + list_names) if div else [])):
         for scenario in args.scenarios if names else ():
             for m in names:
-                lines.append('%s.%s%s' % (scenario, 'mmr.' if which else '', m) + ''.join(',%.6f' % v for v in lists[scenario][which][m]))
-                print(lines[-1])                                     # (single process: refused above otherwise)
+                report('%s.%s%s' % (scenario, 'mmr.' if which else '', m), lists[scenario][which][m], every_rank=True)
     named = [('%s.lo', 'lo'), ('%s.hi', 'hi')]                       # (the line's name after 'S.', significance.report's key)
     if args.compare is not None:
         named += [('vs.%s', 'vs'), ('diff.%s', 'diff'), ('diff.%s.lo', 'diff.lo'), ('diff.%s.hi', 'diff.hi'), ('diff.%s.p', 'diff.p')]
     for scenario in args.scenarios if boot else ():
         for m in full_metrics:
             for name, key in named:
-                lines.append('%s.%s' % (scenario, name % m) + ''.join(',%.6f' % v for v in boots[scenario][m][key]))
-                print(lines[-1])                                     # (single process: refused above otherwise)
+                report('%s.%s' % (scenario, name % m), boots[scenario][m][key], every_rank=True)
     if started_group:
         import torch.distributed as dist
         dist.destroy_process_group()

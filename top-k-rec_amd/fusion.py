@@ -39,17 +39,14 @@ METHODS = ('a', 'p', 'b', 'e', 'w')
 def load_models(data_dir, model_dirs):
     """-> [(U fp32 [n_users, k_m], V fp32 [n_items, k_m], b fp32 [n_items] | None)] from every directory's final-U.dat, final-V.dat and
     optional final-B.dat, rows addressed through DATA/uid and DATA/vid as evaluate.py addresses them (textio.read_matrix)."""
-    from evaluate import read_ids, read_matrix
+    from evaluate import read_ids, read_model
     uids, vids = read_ids(os.path.join(data_dir, 'uid')), read_ids(os.path.join(data_dir, 'vid'))
     models = []
     for d in model_dirs:
-        U = read_matrix(os.path.join(d, 'final-U.dat'), uids)
-        V = read_matrix(os.path.join(d, 'final-V.dat'), vids)
-        bpath = os.path.join(d, 'final-B.dat')
-        b = read_matrix(bpath, vids).reshape(-1) if os.path.exists(bpath) else None
+        U, V, b = read_model(d, uids, vids)
         if U.shape[1] != V.shape[1]:
             raise ValueError('%s: final-U.dat has %d columns, final-V.dat %d' % (d, U.shape[1], V.shape[1]))
-        models.append((U, V, b))
+        models.append((U, V, None if b is None else b.reshape(-1)))
     return models
 
 

@@ -66,7 +66,7 @@ import explain as expl
 import foldin
 import textio
 import tkr_hip
-from evaluate import _group, read_ids, read_matrix
+from evaluate import _group, read_ids, read_matrix, read_model     # noqa: F401  (read_matrix: tests/test_gpu_item_foldin.py reads through it)
 from textio import format_lines      # noqa: F401  (the host formatter of the output lines; textio.write_lists writes them)
 
 
@@ -210,13 +210,12 @@ def rank(U_dev, user_rows, V_dev, bias_dev, R, total, also_rated=None, candidate
     return ids.cpu().numpy(), scores.cpu().numpy()
 
 
-def fold_in_new_items(args, uids, vids, new_vids, vmat, bmat, device):
+def fold_in_new_items(args, uids, vids, new_vids, umat, vmat, bmat, device):
     """-> (vmat, bmat, vids) grown by the items of `new_vids` in file order, their rows folded in (K10) from the model users' likes in
-    args.new_ratings against final-U.dat and the users' positives in the fold's train file, and that ratings file parsed over the
-    grown catalogue"""
+    args.new_ratings against final-U.dat (`umat`) and the users' positives in the fold's train file, and that ratings file parsed over
+    the grown catalogue"""
     n_users, n_items, m = len(uids), len(vmat), max(new_vids.values()) + 1
     umap = textio.IdMap(uids)
-    umat = read_matrix(os.path.join(args.model, 'final-U.dat'), uids)
     user_pos = foldin.liked_csr(textio.parse_ratings(os.path.join(args.data, 'f%dtr.txt' % args.fold), umap, textio.IdMap(vids)), n_users, n_items)
     likers = foldin.liked_csr(textio.parse_ratings(args.new_ratings, umap, textio.IdMap(new_vids)), m, n_users, by='item')
     V_new, b_new = foldin.fold_in_items(umat, vmat, bmat, user_pos, likers, li=args.fold_li, lj=args.fold_lj, lb=args.fold_lb, lr=args.fold_lr,
@@ -288,13 +287,12 @@ def main(argv=None):
         raise tkr_hip.TkrError('recommend.py scores on the GPU through libtkr_hip.so; no MI355X is visible')
     device = torch.device('cuda', torch.cuda.current_device())
 
-    vmat = read_matrix(os.path.join(args.model, 'final-V.dat'), vids)
-    bmat = None
-    if os.path.exists(os.path.join(args.model, 'final-B.dat')):
-        bmat = read_matrix(os.path.join(args.model, 'final-B.dat'), vids).reshape(-1)
-    R_new_items = None
+    _, vmat, bmat = read_model(args.model, vids=vids)
+    bmat = None if bmat is None else bmat.reshape(-1)
+    umat = R_new_items = None                                       # final-U.dat is read once, and only when something needs it
     if new_vids:
-        vmat, bmat, vids, R_new_items = fold_in_new_items(args, uids, vids, new_vids, vmat, bmat, device)
+        umat = read_model(args.model, uids=uids)[0]
+        vmat, bmat, vids, R_new_items = fold_in_new_items(args, uids, vids, new_vids, umat, vmat, bmat, device)
     V_dev = torch.from_numpy(vmat).to(device)
     bias_dev = None if bmat is None else torch.from_numpy(np.ascontiguousarray(bmat)).to(device)
     vmap = textio.IdMap(vids)
@@ -312,7 +310,7 @@ def main(argv=None):
         tok = {idx: t for t, idx in uids.items()}
         users = [tok[int(x)] for x in cand_model[1]]
     if users:
-        umat = read_matrix(os.path.join(args.model, 'final-U.dat'), uids)
+        umat = read_model(args.model, uids=uids)[0] if umat is None else umat
         R = textio.parse_ratings(os.path.join(args.data, 'f%dtr.txt' % args.fold), textio.IdMap(uids), vmap)
         ids, scores, *why = rank(torch.from_numpy(umat).to(device), [uids[u] for u in users], V_dev, bias_dev, R, args.total, also_rated=R_new_items,
                                  candidates=cand_model[2:] if cand_model else None, on_device=True, where=args.group, **div)
