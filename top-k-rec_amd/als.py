@@ -130,9 +130,8 @@ def half_step(X, Y, like_ptr, like_cols, rated_y, *, w=None, ridge_in_G, ridge, 
 def check_status(words, what):
     """words: the status words of half-steps, as integers, (gram, solve) pairs in call order; raises for the first that is not -1"""
     for i, word in enumerate(words):
-        word = int(word)
-        if word != -1:
-            raise tkr_hip.AlsRefused('%s, %s' % (what[i // 2], 'als_solve_rows' if i & 1 else 'als_gram (row = position in the rated list)'), word)
+        tkr_hip.status_check('%s, %s' % (what[i // 2], 'als_solve_rows' if i & 1 else 'als_gram (row = position in the rated list)'),
+                             tkr_hip._ALS_REFUSED, tkr_hip.AlsRefused, int(word))
 
 
 SOLVERS = ('cholesky', 'cg')
@@ -570,7 +569,7 @@ class MLP:
         down = torch.cat([loss.sum().reshape(1), status.double()]).cpu().numpy()
         if int(down[1]) != -1:
             self.epochs_done -= 1                                  # (nothing was written: the epoch did not happen)
-            raise tkr_hip.MlpRefused('MLP.fit', int(down[1]))
+            tkr_hip.status_check('MLP.fit', tkr_hip._MLP_REFUSED, tkr_hip.MlpRefused, int(down[1]))
         if not np.isfinite(down[0]):
             raise FloatingPointError('MLP.fit: the objective of epoch %d is %r' % (self.epochs_done - 1, float(down[0])))
         return float(down[0])
@@ -650,8 +649,7 @@ class DPM(WMF):
         return fit.sum(), [se]
 
     def _check_iteration(self, who, it, loss, words):
-        if int(words[0]) != -1:
-            raise tkr_hip.MlpRefused('the encoder step of iteration %d' % it, int(words[0]))
+        tkr_hip.status_check('the encoder step of iteration %d' % it, tkr_hip._MLP_REFUSED, tkr_hip.MlpRefused, int(words[0]))
         if not np.isfinite(loss):
             raise FloatingPointError('%s: the loss of iteration %d is %r' % (who, it, loss))
 

@@ -127,7 +127,7 @@ __global__ __launch_bounds__(kAlsBlock) void als_wide_slab_kernel(const float* _
                 const long long t = first + base + tid;
                 c = list ? list[t] : (int)t;
                 if ((uint32_t)c >= (uint32_t)n) {
-                    atomicMin(status, (unsigned long long)t * 4ull + 1ull);    // kind 1: skipped
+                    status_refuse(status, t, kAlsSkipped);
                     c = -1;
                 }
             }
@@ -279,13 +279,13 @@ __global__ __launch_bounds__(kAlsBlock) void als_solve_kernel(const float* __res
     int* fail_s = cols_s + 33;
     const int tid = threadIdx.x;
     const long long r = blockIdx.x;
-    const unsigned long long word = (unsigned long long)r * 4ull;
+    const unsigned long long word = (unsigned long long)r * 4ull;  // status_refuse's packing by hand: the two exits share the word
 
     // the row's likes: the same two words in every thread, so every exit below is taken by the whole workgroup
     const long long lo = MODE == kAlsFactor ? 0 : like_ptr[r], hi = MODE == kAlsFactor ? 0 : like_ptr[r + 1];
     if (!als_ptr_ok(lo, hi, n_likes, r)) {
         if (tid == 0) {
-            atomicMin(status, word + 3ull);                       // kind 3: the row is left as it is
+            atomicMin(status, word + kAlsBadPtr);                 // the row is left as it is
             if (row_loss) row_loss[r] = 0.0;
         }
         return;
@@ -458,9 +458,9 @@ __global__ __launch_bounds__(kAlsBlock) void als_solve_kernel(const float* __res
         }
     }
     __syncthreads();
-    if (!ok || *fail_s) {                                         // (uniform) kind 2: not positive definite in fp32; nothing is written
+    if (!ok || *fail_s) {                                         // (uniform) not positive definite in fp32; nothing is written
         if (tid == 0) {
-            atomicMin(status, word + 2ull);
+            atomicMin(status, word + kAlsNotSolved);
             if (row_loss) row_loss[r] = 0.0;
         }
         return;
@@ -565,8 +565,8 @@ __global__ __launch_bounds__(kAlsBlock) void als_cold_kernel(const float* __rest
         cold = lo == hi && als_ptr_ok(lo, hi, n_likes, r);         // (a row like_ptr is wrong at: kind 3, the per-row kernel's)
     }
     if (*reinterpret_cast<const int*>(factor + (size_t)k * k) == 0) {      // (the same word in every thread of the grid)
-        if (cold) {                                               // kind 2 on the shared factor: every cold row refused, none touched
-            atomicMin(status, (unsigned long long)r * 4ull + 2ull);
+        if (cold) {                                               // on the shared factor: every cold row refused, none touched
+            status_refuse(status, r, kAlsNotSolved);
             if (row_loss) row_loss[r] = 0.0;
         }
         return;
@@ -641,7 +641,7 @@ __global__ __launch_bounds__(kAlsBlock) void als_cold_kernel(const float* __rest
     }
     const bool write = cold && finite;
     if (cold) {
-        if (!finite) atomicMin(status, (unsigned long long)r * 4ull + 2ull);   // kind 2 on this row's own solution: left as it is
+        if (!finite) status_refuse(status, r, kAlsNotSolved);     // on this row's own solution: left as it is
         if (row_loss) row_loss[r] = finite ? 0.5 * w_prior * q : 0.0;
     }
     const unsigned long long wmask = __ballot(write);

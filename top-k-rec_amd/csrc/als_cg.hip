@@ -157,7 +157,7 @@ __device__ __forceinline__ void cg_likes(const float* __restrict__ Y, int n_y, i
             if (base + lane < m) {
                 mine = like_cols[lo + base + lane];
                 if ((uint32_t)mine >= (uint32_t)n_y) {
-                    if (MODE == kCgFirst) atomicMin(status, (unsigned long long)row * 4ull + 1ull);      // kind 1: skipped
+                    if (MODE == kCgFirst) status_refuse(status, row, kAlsSkipped);
                     mine = -1;
                 }
             }
@@ -257,7 +257,7 @@ __global__ __launch_bounds__(kCgBlock) void als_cg_kernel(const float* __restric
         if (row < n_x) {
             const long long a = like_ptr[row], b = like_ptr[row + 1];
             if (!als_ptr_ok(a, b, n_likes, row)) {
-                atomicMin(status, (unsigned long long)row * 4ull + 3ull);      // kind 3: the row is left as it is
+                status_refuse(status, row, kAlsBadPtr);            // the row is left as it is
                 state = kCgRefused;
             } else {
                 lo = a;
@@ -321,9 +321,9 @@ __global__ __launch_bounds__(kCgBlock) void als_cg_kernel(const float* __restric
                 q[c] = col < k ? Q[lr * PP + col] : 0.f;
             }
             const float pq = cg_dot<KC>(p, q);
-            if (!(pq > 0.f) || !(pq < INFINITY)) {                // kind 2: not positive definite (or not finite) along p
+            if (!(pq > 0.f) || !(pq < INFINITY)) {                // not positive definite (or not finite) along p
                 if (lane == 0) {
-                    atomicMin(status, (unsigned long long)(row0 + lr) * 4ull + 2ull);
+                    status_refuse(status, row0 + lr, kAlsNotSolved);
                     state_s[lr] = kCgRefused;
                 }
                 continue;
@@ -347,14 +347,14 @@ __global__ __launch_bounds__(kCgBlock) void als_cg_kernel(const float* __restric
     }
 
 #pragma unroll
-    for (int i = 0; i < kCgRows; ++i) {                           // kind 2: a solution that is not finite is not stored
+    for (int i = 0; i < kCgRows; ++i) {                           // a solution that is not finite is not stored
         const int lr = wave * kCgRows + i;
         if (__builtin_amdgcn_readfirstlane(state_s[lr]) >= kCgSkip) continue;
         bool finite = true;
 #pragma unroll
         for (int c = 0; c < KC; ++c) finite = finite && fabsf(x[i][c]) < INFINITY;       // (false for a NaN)
         if (__ballot(!finite) != 0ull && lane == 0) {
-            atomicMin(status, (unsigned long long)(row0 + lr) * 4ull + 2ull);
+            status_refuse(status, row0 + lr, kAlsNotSolved);
             state_s[lr] = kCgRefused;
         }
     }

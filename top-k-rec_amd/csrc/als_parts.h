@@ -21,6 +21,10 @@ constexpr int kAlsTile = 32;                                      // rows of Y s
 constexpr int kAlsSlab = TKR_ALS_GRAM_SLAB;
 static_assert(kAlsSlab % kAlsTile == 0 && kAlsSlab < (1 << 24), "whole tiles; a slab's count is exact in fp32");
 
+// the kinds of K20, K21, K24 and K25 (no kind 0): an index outside the table was skipped; the row's system cannot be solved (K20: not
+// positive definite in fp32, K24: p . q or the solution not finite); like_ptr is wrong at the row.  The last two leave the row as it is
+enum { kAlsSkipped = 1, kAlsNotSolved = 2, kAlsBadPtr = 3 };
+
 __host__ __device__ constexpr int als_tiles(int KT) { return KT * (KT + 1) / 2; }
 __host__ __device__ constexpr int als_tiles_per_wave(int KT) { return (als_tiles(KT) + kAlsWaves - 1) / kAlsWaves; }
 // floats between two staged rows (and two rows of K24's panel of G): the two rows an MFMA reads at once (lanes 0-31, lanes 32-63)
@@ -72,7 +76,7 @@ __device__ __forceinline__ void slab_sum(const float* __restrict__ Y, int n, int
                 const long long t = first + base + tid;
                 c = list ? list[t] : (int)t;
                 if ((uint32_t)c >= (uint32_t)n) {
-                    atomicMin(status, (unsigned long long)(word_row < 0 ? t : word_row) * 4ull + 1ull);      // kind 1: skipped
+                    status_refuse(status, word_row < 0 ? t : word_row, kAlsSkipped);
                     c = -1;
                 }
             }

@@ -33,6 +33,7 @@ constexpr int kDivMaxWaves = kDivMaxPool / TKR_WAVE;
 constexpr int kDivHeadBytes = 2 * kDivMaxWaves * 8 + kDivMaxWaves * 4;       // the waves' argmax words (two parities), their prefix ends
 constexpr size_t kDivLdsBudget = 160 * 1024;                     // what one CU holds
 static_assert(kDivMaxPool % TKR_WAVE == 0 && kDivHeadBytes % 16 == 0, "whole waves, an aligned image");
+enum { kDivBadId = 1 };                                          // the one kind of K17's status word: an id outside the table ends row `where`
 
 // floats between the staged rows: lane l reads row l, so the rows of 16 (b128) resp. 32 (b32) consecutive lanes must start in
 // different 16-byte slots resp. banks
@@ -58,7 +59,7 @@ __device__ __forceinline__ uint64_t wave_max_key(uint64_t key) {
 }
 
 // the valid prefix of a row's ids (thread e holds entry e, -1 behind the row's end): its length, the same in every thread.  The entry
-// that ends it, when it is an id >= n_items, is reported (K15's status word: the smallest 4 * row + 1).  One barrier.
+// that ends it, when it is an id >= n_items, is reported (status_refuse, tkr_common.h).  One barrier.
 __device__ __forceinline__ int valid_prefix(int id, int n, int n_items, int row, int* ends, unsigned long long* status) {
     const int tid = threadIdx.x, wave = tid >> 6, n_waves = blockDim.x >> 6;
     const bool bad = tid < n && (uint32_t)id >= (uint32_t)n_items;
@@ -67,7 +68,7 @@ __device__ __forceinline__ int valid_prefix(int id, int n, int n_items, int row,
     __syncthreads();
     int n_valid = n;
     for (int w = 0; w < n_waves; ++w) n_valid = min(n_valid, ends[w]);
-    if (tid == n_valid && bad && id >= 0) atomicMin(status, (unsigned long long)row * 4ull + 1ull);
+    if (tid == n_valid && bad && id >= 0) status_refuse(status, row, kDivBadId);
     return n_valid;
 }
 

@@ -40,6 +40,8 @@ constexpr int kAncChains = 4;                                    // chains a thr
 constexpr int kAncHeadBytes = kAncMaxWaves * 4 + kAncTile * 4;   // the waves' prefix ends, the tile's checked columns
 constexpr size_t kAncLdsBudget = 160 * 1024;                     // what one CU holds
 static_assert(kAncMaxT % TKR_WAVE == 0 && kAncHeadBytes % 16 == 0 && kAncMaxT == TKR_MMR_MAX_POOL, "whole waves, an aligned image");
+// K19's kinds (no kind 2): a list id outside the table ends the row; an anchor outside it was skipped; a bad anchor_ptr, padding only
+enum { kAncBadId = 0, kAncSkipped = 1, kAncBadPtr = 3 };
 
 // floats between two staged rows: K17's pitch (csrc/diversity.hip div_pitch) -- the rows of 16 (b128) resp. 32 (b32) consecutive
 // lanes start in different 16-byte slots resp. banks
@@ -120,7 +122,7 @@ __global__ __launch_bounds__(BLOCK) void nearest_anchors_kernel(const float* __r
     constexpr int NC = BLOCK <= 256 ? kAncChains : kAncChains / 2;
     const int tid = threadIdx.x, wave = tid >> 6;
     const int row = blockIdx.x;
-    const unsigned long long word = (unsigned long long)row * 4ull;
+    const unsigned long long word = (unsigned long long)row * 4ull;  // status_refuse's packing by hand: the three sites share the word
 
     // the valid prefix (thread p < t holds entry p)
     const int id = tid < t ? ids[(size_t)row * t + tid] : -1;
@@ -131,12 +133,12 @@ __global__ __launch_bounds__(BLOCK) void nearest_anchors_kernel(const float* __r
     __syncthreads();
     int n_valid = t;
     for (int w = 0; w < BLOCK / TKR_WAVE; ++w) n_valid = min(n_valid, ends[w]);
-    if (tid == n_valid && bad && id >= 0) atomicMin(status, word);                             // kind 0
+    if (tid == n_valid && bad && id >= 0) atomicMin(status, word + kAncBadId);
 
     // the row's anchors: the same two words in every thread
     const long long lo = anchor_ptr[row], hi = anchor_ptr[row + 1];
     const bool ptr_ok = lo >= 0 && lo <= hi && hi <= n_anchors && (row != 0 || lo == 0) && hi - lo <= (long long)INT_MAX;
-    if (!ptr_ok && tid == 0) atomicMin(status, word + 3ull);                                   // kind 3: padding only
+    if (!ptr_ok && tid == 0) atomicMin(status, word + kAncBadPtr);
     const int n_anc = ptr_ok ? (int)(hi - lo) : 0;
 
     const int G = min(BLOCK / t, tile);
@@ -155,7 +157,7 @@ __global__ __launch_bounds__(BLOCK) void nearest_anchors_kernel(const float* __r
             const int c = anchor_cols[lo + base + tid];
             const bool ok = (uint32_t)c < (uint32_t)n_items;
             if (!ok && !told) {
-                atomicMin(status, word + 1ull);                   // kind 1: skipped
+                atomicMin(status, word + kAncSkipped);
                 told = true;
             }
             acol_s[tid] = ok ? c : -1;

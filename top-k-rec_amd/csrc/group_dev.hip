@@ -41,10 +41,6 @@ struct GroupArgs {
     int64_t n_rows;
 };
 
-__device__ __forceinline__ void refuse(unsigned long long* status, int64_t where, int kind) {
-    atomicMin(status, (unsigned long long)where * 4ull + (unsigned long long)kind);
-}
-
 // T lanes work on one row: T = 64, a wave of a kGroupWaveBlock workgroup, or T = kGroupWgBlock, the workgroup
 template <int T>
 struct Team {
@@ -97,12 +93,12 @@ __device__ __forceinline__ void build_bitmap(const GroupArgs& a, int64_t r, bool
             const int64_t seg = src.seg_of_row ? src.seg_of_row[r] : r;
             if (seg == -1) continue;
             if (seg < -1 || seg >= src.n_seg) {
-                if (tl == 0) refuse(status, r, kBadSegOfRow);
+                if (tl == 0) status_refuse(status, r, kBadSegOfRow);
                 continue;
             }
             const int64_t lo = src.seg_ptr[seg], hi = src.seg_ptr[seg + 1];
             if (lo < 0 || hi < lo || hi > src.n_entries) {
-                if (tl == 0) refuse(status, r, kBadSegPtr);
+                if (tl == 0) status_refuse(status, r, kBadSegPtr);
                 continue;
             }
             bool bad = false;
@@ -115,7 +111,7 @@ __device__ __forceinline__ void build_bitmap(const GroupArgs& a, int64_t r, bool
                 }
                 atomicOr(&bm[it >> 5], 1u << (it & 31));
             }
-            if (bad) refuse(status, r, kBadItem);
+            if (bad) status_refuse(status, r, kBadItem);
         }
     }
     __syncthreads();
@@ -133,7 +129,7 @@ __global__ __launch_bounds__(Team<T>::block) void group_count_kernel(GroupArgs a
         const tkr_group_source& src = a.src[s];
         for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < src.n_seg; i += (int64_t)gridDim.x * blockDim.x) {
             const int64_t lo = src.seg_ptr[i], hi = src.seg_ptr[i + 1];
-            if (lo < 0 || hi < lo || hi > src.n_entries) refuse(status, i, kBadSegPtr);
+            if (lo < 0 || hi < lo || hi > src.n_entries) status_refuse(status, i, kBadSegPtr);
         }
     }
     for (int64_t base = (int64_t)blockIdx.x * Team<T>::rows; base < a.n_rows; base += (int64_t)gridDim.x * Team<T>::rows) {      // uniform over the workgroup
@@ -170,7 +166,7 @@ __global__ __launch_bounds__(Team<T>::block) void group_emit_kernel(GroupArgs a,
         if (active) {
             const int64_t p0 = ptr[r], p1 = ptr[r + 1];
             if (p0 < 0 || p1 < p0 || p1 > n_out || p1 - p0 != (int64_t)total) {      // not the ptr of these sources: nothing is written
-                if (tl == 0) refuse(status, r, kBadPtr);
+                if (tl == 0) status_refuse(status, r, kBadPtr);
             } else {
                 int64_t o = p0 + before;                               // o + n <= p1 <= n_out
                 for (int w = w0; w < w1; ++w) {
@@ -232,7 +228,7 @@ __global__ __launch_bounds__(kGroupLaneBlock) void compact_emit_kernel(const int
         if (ptr[r + 1] <= ptr[r]) continue;
         const int64_t k = pos[r];
         if (k < 0 || k >= n_kept) {                                    // not the pos of this ptr
-            refuse(status, r, kBadPtr);
+            status_refuse(status, r, kBadPtr);
             continue;
         }
         rows[k] = r;

@@ -35,10 +35,6 @@ static_assert((size_t)TKR_LINE_MAX_COLS / 8 <= kLineLdsBudget, "one line's bitma
 
 enum { kBadRankLow = 0, kBadRankHigh = 1, kBadRankTwice = 2, kBadLinePtr = 3 };
 
-__device__ __forceinline__ void line_refuse(unsigned long long* status, int64_t line, int kind) {
-    atomicMin(status, (unsigned long long)line * 4ull + (unsigned long long)kind);
-}
-
 __global__ __launch_bounds__(kLineRows * TKR_WAVE) void line_metrics_kernel(const int32_t* __restrict__ ranks, int64_t n_likes,
                                                                           const int64_t* __restrict__ like_ptr,
                                                                           const int64_t* __restrict__ rated_ptr, int64_t n_lines, int n_cols,
@@ -50,7 +46,7 @@ __global__ __launch_bounds__(kLineRows * TKR_WAVE) void line_metrics_kernel(cons
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, rows = blockDim.x >> 6;
     uint32_t* bm = line_lds + (size_t)wave * W;                    // W words: max(n_cols, total) bits
     const int C = 3 * interval + 5;
-    if (blockIdx.x == 0 && threadIdx.x == 0 && (like_ptr[0] != 0 || rated_ptr[0] != 0)) line_refuse(status, 0, kBadLinePtr);
+    if (blockIdx.x == 0 && threadIdx.x == 0 && (like_ptr[0] != 0 || rated_ptr[0] != 0)) status_refuse(status, 0, kBadLinePtr);
     for (int w = lane; w < W; w += TKR_WAVE) bm[w] = 0u;
     __syncthreads();
     for (int64_t base = (int64_t)blockIdx.x * rows; base < n_lines; base += (int64_t)gridDim.x * rows) {     // uniform over the workgroup
@@ -64,7 +60,7 @@ __global__ __launch_bounds__(kLineRows * TKR_WAVE) void line_metrics_kernel(cons
             hi = like_ptr[r + 1];
             const int64_t rlo = rated_ptr[r], rhi = rated_ptr[r + 1];
             ok = lo >= 0 && hi >= lo && hi <= n_likes && rlo >= 0 && rhi >= rlo && rhi - rlo <= (int64_t)n_cols;
-            if (!ok && lane == 0) line_refuse(status, r, kBadLinePtr);
+            if (!ok && lane == 0) status_refuse(status, r, kBadLinePtr);
             cap = ok ? n_cols - (int)(rhi - rlo) : 0;
         }
         int P = 0, first = INT_MAX, bad = 4;                      // the smallest kind this lane met
@@ -85,7 +81,7 @@ __global__ __launch_bounds__(kLineRows * TKR_WAVE) void line_metrics_kernel(cons
                 }
             }
         }
-        if (bad < 4) line_refuse(status, r, bad);
+        if (bad < 4) status_refuse(status, r, bad);
         const bool good = ok && __ballot(bad < 4) == 0ull;        // uniform over the wave
         for (int d = 32; d; d >>= 1) {
             P += __shfl_xor(P, d);

@@ -253,7 +253,7 @@ __global__ __launch_bounds__(kLmfBlock) void lmf_step_kernel(const float* __rest
     const long long lo = like_ptr[r], hi = like_ptr[r + 1];
     if (!als_ptr_ok(lo, hi, n_likes, r)) {
         if (lane == 0) {
-            atomicMin(status, (unsigned long long)r * 4ull + 3ull);      // kind 3: the row is left as it is
+            status_refuse(status, r, kAlsBadPtr);                 // the row is left as it is
             if (row_loss) row_loss[r] = 0.0;
         }
         return;
@@ -266,7 +266,7 @@ __global__ __launch_bounds__(kLmfBlock) void lmf_step_kernel(const float* __rest
     lmf_load_row<NR>(X + (size_t)r * K, K, x);
     LmfSum<NR> sum;
     if (lmf_like_chain<NR>(Y, n_y, K, like_cols, lo, (int)(hi - lo), x, sum) && lane == 0)
-        atomicMin(status, (unsigned long long)r * 4ull + 1ull);    // kind 1: skipped
+        status_refuse(status, r, kAlsSkipped);
     lmf_update_row<NR>(r, K, fixed, x, sum, D, alpha, lam, lr, X, H, row_loss);
 }
 
@@ -298,7 +298,7 @@ __global__ __launch_bounds__(kLmfHeavyBlock) void lmf_heavy_kernel(const float* 
         sp += sum.sp;
         ss += sum.ss;
     }
-    if (skipped && lane == 0) atomicMin(status, (unsigned long long)r * 4ull + 1ull);
+    if (skipped && lane == 0) status_refuse(status, r, kAlsSkipped);
 #pragma unroll
     for (int j = 0; j < NR; ++j) part[wave][lane + 64 * j] = L[j];
     if (lane == 0) {

@@ -46,6 +46,7 @@ constexpr unsigned long long kMlpClean = ~0ull;
 static_assert(kMlpSlab % kMlpStep == 0 && kMlpChunk % kMlpTile == 0, "whole steps, whole tiles");
 
 enum { kMlpLinear = 0, kMlpSigmoid = 1, kMlpDelta = 2 };
+enum { kMlpBadIndex = 1 };                                        // the one kind of K22's status word: entry `where` of rows / order is outside [0, n)
 
 // row of the 32 x 32 block that register `reg` of lane half h holds (the column is the lane & 31)
 __device__ __forceinline__ int mlp_acc_row(int reg, int h) { return (reg & 3) + 8 * (reg >> 2) + 4 * h; }
@@ -53,7 +54,7 @@ __device__ __forceinline__ int mlp_acc_row(int reg, int h) { return (reg & 3) + 
 __global__ __launch_bounds__(kMlpBlock) void mlp_check_kernel(const int32_t* __restrict__ idx, long long m, int n,
                                                               unsigned long long* __restrict__ status) {
     for (long long t = (long long)blockIdx.x * kMlpBlock + threadIdx.x; t < m; t += (long long)gridDim.x * kMlpBlock)
-        if ((uint32_t)idx[t] >= (uint32_t)n) atomicMin(status, (unsigned long long)t * 4ull + 1ull);
+        if ((uint32_t)idx[t] >= (uint32_t)n) status_refuse(status, t, kMlpBadIndex);
 }
 
 template <bool TRANS>

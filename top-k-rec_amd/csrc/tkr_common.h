@@ -114,4 +114,11 @@ __device__ __forceinline__ float pair_softplus_neg(float ea, float eb, float x) 
 
 __device__ __forceinline__ float sgn(float v) { return (v > 0.f) ? 1.f : ((v < 0.f) ? -1.f : 0.f); }
 
+// The status word of K15 and every family after it: the host sets it to -1 (clean); a kernel that refuses something of its input
+// lowers it to 4 * where + kind -- `where` the row, line, segment or list position, `kind` one of the family's at most four reasons --
+// with an atomic minimum on the unsigned word, so the smallest refusal of a call is what the host reads, whatever the order.
+__device__ __forceinline__ void status_refuse(unsigned long long* status, int64_t where, int kind) {
+    atomicMin(status, (unsigned long long)where * 4ull + (unsigned long long)kind);
+}
+
 }  // namespace tkr

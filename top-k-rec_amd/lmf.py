@@ -166,8 +166,7 @@ class LMF(REC):
             total = part + 0.5 * self.lam * Xa[:, :k + 1].double().square().sum()
             down = torch.cat([total.reshape(1), su.double(), sv.double()]).cpu().numpy()      # one copy: the loss, the status words behind it
             for word, what in zip(down[1:], ('the user step of iteration %d', 'the item step of iteration %d')):
-                if int(word) != -1:
-                    raise tkr_hip.LmfRefused('LMF.train, %s' % (what % it), int(word))
+                tkr_hip.status_check('LMF.train, %s' % (what % it), tkr_hip._LMF_REFUSED, tkr_hip.LmfRefused, int(word))
             loss = float(down[0])
             if not np.isfinite(loss):
                 raise tkr_hip.TkrError('LMF.train: the loss of iteration %d is %r; lower lr (%g)' % (it, loss, self.lr))
@@ -204,8 +203,7 @@ class LMF(REC):
             words.append(half_step(X, H, Ya, ptr, cols, fixed=k + 1, alpha=self.alpha_, lam=self.lam, lr=self.lr, heavy_from=heavy_from, work=work)[1])
         X = X.cpu().numpy()
         for word in (torch.cat(words).cpu().numpy() if words else ()):
-            if int(word) != -1:
-                raise tkr_hip.LmfRefused('LMF.fold_in', int(word))
+            tkr_hip.status_check('LMF.fold_in', tkr_hip._LMF_REFUSED, tkr_hip.LmfRefused, int(word))
         return np.ascontiguousarray(X[:, :k]), np.ascontiguousarray(X[:, k])
 
     # ------------------------------------------------------------------ lmf.npz

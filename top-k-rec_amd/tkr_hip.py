@@ -564,6 +564,78 @@ def like_ranks(U, Vt, like_ptr, like_cols, bias=None, user_idx=None, mask=None, 
     return out
 
 
+# ---- what the bindings of K12 and every family after it share: one operand check, one reader of the status word, one size call ------
+_STD = (TypeError, ValueError)     # what an operand check raises in K12 / K15 style: (not a tensor or a wrong dtype, the rest)
+_TKR = (TkrError, TkrError)        # ... and in every other family
+_LATER = object()                  # on=_LATER: the entry point has rules of its own to check first and calls _on_gpu itself
+
+
+def _on_gpu(what, name, t, on=None, raises=_TKR):
+    """the last check of an operand: on a GPU, and on the GPU `on` where the entry point has an anchor"""
+    if not t.is_cuda or (on is not None and t.device != on):
+        raise raises[1]('%s: %s must live on the GPU, one GPU for every operand of the call, not on %s' % (what, name, t.device))
+
+
+def _operand(what, name, t, dtype, dim=None, numel=None, at_least=None, on=None, optional=False, raises=_TKR):
+    """refuse the tensor operand `name` of the entry point `what` by its properties alone (no device access), always in this order:
+    a tensor, the dtype, contiguous, `dim` dimensions, `numel` values (or `at_least` that many), on the GPU (_on_gpu)"""
+    if t is None and optional:
+        return
+    if not isinstance(t, torch.Tensor):
+        raise raises[0]('%s: %s must be a tensor' % (what, name))
+    if t.dtype != dtype:
+        raise raises[0]('%s: %s must be %s, not %s' % (what, name, dtype, t.dtype))
+    if not t.is_contiguous():
+        raise raises[1]('%s: %s must be contiguous' % (what, name))
+    if dim is not None and t.dim() != dim:
+        raise raises[1]('%s: %s must have %d dimensions, not %d' % (what, name, dim, t.dim()))
+    if numel is not None and t.numel() != numel:
+        raise raises[1]('%s: %s must hold %d values, not %d' % (what, name, numel, t.numel()))
+    if at_least is not None and t.numel() < at_least:
+        raise raises[1]('%s: %s must hold at least %d values, not %d' % (what, name, at_least, t.numel()))
+    if on is not _LATER:
+        _on_gpu(what, name, t, on, raises)
+
+
+def status_check(what, messages, raises, word):
+    """the one reader of a status word in the convention of K15 (include/tkr.h): -1 is clean; anything else is 4 * row + kind and
+    raises `raises` (a class, or one class per kind) with messages[kind] about the row, and .word, .row and .kind set.  A kind the
+    family does not write is a TkrError that names the word."""
+    if word == -1:
+        return
+    row, kind = word >> 2, word & 3
+    if kind >= len(messages) or messages[kind] is None:
+        raise TkrError('%s: status word %d (row %d, kind %d) is none of the refusals this entry point knows' % (what, word, row, kind))
+    error = (raises[kind] if isinstance(raises, tuple) else raises)('%s: %s' % (what, messages[kind] % row))
+    error.word, error.row, error.kind = word, row, kind
+    raise error
+
+
+def _done(what, result, status, check, messages, raises):
+    """the tail of every wrapper with a check= argument: check=False hands the status word on unread, else it is read and a refusal
+    raised"""
+    if not check:
+        return result, status
+    status_check(what, messages, raises, int(status.item()))
+    return result
+
+
+def _size(entry, types, values, shown=None):
+    """a *_workspace_bytes / *_partial_bytes export called with `values` (`shown`: how the message writes them) -> bytes"""
+    need = int(getattr(lib(), entry)(*(t(v) for t, v in zip(types, values))))
+    if need < 0:
+        raise TkrError('%s(%s) failed: tkr error %d' % (entry, ', '.join('%d' % v for v in values) if shown is None else shown, need))
+    return need
+
+
+def _chunked_size(entry, what, n_bytes, chunk_bytes):
+    try:
+        return _size(entry, (C.c_int64, C.c_int64), (n_bytes, chunk_bytes))
+    except TkrError:
+        raise ValueError('%s on the device: chunk_bytes must be a power of two in [%d, %d], got %r'
+                         % (what, PARSE_CHUNK_MIN, PARSE_CHUNK_MAX, chunk_bytes)) from None
+
+
 # ---- K12: per-user candidate lists (csrc/candidates.hip) ----------------------------------------------------------------------------
 CANDIDATES_RESIDENT = 2048   # TKR_CANDIDATES_RESIDENT of include/tkr.h: a longer row is ranked by the slow whole-workgroup form
 
@@ -571,20 +643,14 @@ CANDIDATES_RESIDENT = 2048   # TKR_CANDIDATES_RESIDENT of include/tkr.h: a longe
 def _cand_args(U, Vt, cand_ptr, cand_cols, bias, user_idx, mask, mask_pitch):
     """refuse what tkr_rank_candidates cannot take, the tensors' properties first (no device access), then the row pointer
     -> (n_rows, n_cols, k, nnz)"""
-    named = dict(U=(U, torch.float32), Vt=(Vt, torch.float32), cand_ptr=(cand_ptr, torch.int64), cand_cols=(cand_cols, torch.int32),
-                 bias=(bias, torch.float32), user_idx=(user_idx, torch.int32), mask=(mask, torch.int32))
-    for name, (t, dtype) in named.items():
-        if t is None and name in ('bias', 'user_idx', 'mask'):
-            continue
-        if not isinstance(t, torch.Tensor):
-            raise TypeError('rank_candidates: %s must be a tensor' % name)
-        if t.dtype != dtype:
-            raise TypeError('rank_candidates: %s must be %s, not %s' % (name, dtype, t.dtype))
-        if not t.is_contiguous():
-            raise ValueError('rank_candidates: %s must be contiguous' % name)
-    for name, (t, _) in named.items():
-        if t is not None and (not t.is_cuda or t.device != U.device):
-            raise ValueError('rank_candidates: %s must live on the GPU that holds U, not on %s' % (name, t.device))
+    what = 'rank_candidates'
+    named = (('U', U, torch.float32), ('Vt', Vt, torch.float32), ('cand_ptr', cand_ptr, torch.int64), ('cand_cols', cand_cols, torch.int32),
+             ('bias', bias, torch.float32), ('user_idx', user_idx, torch.int32), ('mask', mask, torch.int32))
+    for name, t, dtype in named:
+        _operand(what, name, t, dtype, on=_LATER, optional=name in ('bias', 'user_idx', 'mask'), raises=_STD)
+    for name, t, _ in named:
+        if t is not None:
+            _on_gpu(what, name, t, U.device, _STD)
     if U.dim() != 2 or Vt.dim() != 2 or U.shape[1] != Vt.shape[1] or U.shape[1] < 1 or Vt.shape[0] < 1:
         raise ValueError('rank_candidates: U [*, k] and Vt [n_cols, k] must share k >= 1')
     n_rows = int(user_idx.numel()) if user_idx is not None else int(U.shape[0])
@@ -739,10 +805,7 @@ def idtable_build(blob, index):
 
 
 def parse_dev_workspace_bytes(n_bytes, chunk_bytes):
-    need = int(lib().tkr_parse_dev_workspace_bytes(C.c_int64(n_bytes), C.c_int64(chunk_bytes)))
-    if need < 0:
-        raise ValueError('parse on the device: chunk_bytes must be a power of two in [%d, %d], got %r' % (PARSE_CHUNK_MIN, PARSE_CHUNK_MAX, chunk_bytes))
-    return need
+    return _chunked_size('tkr_parse_dev_workspace_bytes', 'parse', n_bytes, chunk_bytes)
 
 
 def ratings_count_dev(text, chunk_bytes, workspace, totals):
@@ -837,10 +900,7 @@ def matrix_format_emit(data, line_ptr, first_row, n_rows, out):
 
 # ---- K14: the matrix reader on the device (csrc/scan_dev.hip) --------------------------------------------------------------------
 def scan_dev_workspace_bytes(n_bytes, chunk_bytes):
-    need = int(lib().tkr_scan_dev_workspace_bytes(C.c_int64(n_bytes), C.c_int64(chunk_bytes)))
-    if need < 0:
-        raise ValueError('read on the device: chunk_bytes must be a power of two in [%d, %d], got %r' % (PARSE_CHUNK_MIN, PARSE_CHUNK_MAX, chunk_bytes))
-    return need
+    return _chunked_size('tkr_scan_dev_workspace_bytes', 'read', n_bytes, chunk_bytes)
 
 
 def matrix_count_dev(text, chunk_bytes, workspace, totals):
@@ -900,24 +960,6 @@ class GroupSource(C.Structure):
                 ('n_entries', C.c_int64)]
 
 
-def _group_tensor(what, name, t, dtype, device, optional=False):
-    if t is None and optional:
-        return
-    if not isinstance(t, torch.Tensor):
-        raise TypeError('%s: %s must be a tensor' % (what, name))
-    if t.dtype != dtype:
-        raise TypeError('%s: %s must be %s, not %s' % (what, name, dtype, t.dtype))
-    if t.dim() != 1 or not t.is_contiguous():
-        raise ValueError('%s: %s must be contiguous and one-dimensional' % (what, name))
-    if not t.is_cuda or (device is not None and t.device != device):
-        raise ValueError('%s: %s must live on the GPU%s, not on %s' % (what, name, '' if device is None else ' that holds seg_ptr', t.device))
-
-
-def _group_status(word, what):
-    if word != -1:
-        raise ValueError('%s: %s' % (what, _GROUP_REFUSED[word & 3] % (word >> 2)))
-
-
 def group_segments(sources, n_rows, n_cols, like_only=False):
     """K15 -> (ptr int64 [n_rows + 1], cols int32 [ptr[-1]]) on the device: row r is the ascending, duplicate-free union of the counted
     items of its segments.  sources: one or two tuples (seg_ptr int64 [n_seg + 1], item int32, like int32 | None, seg_of_row int64
@@ -937,14 +979,12 @@ def group_segments(sources, n_rows, n_cols, like_only=False):
         if not isinstance(source, (tuple, list)) or len(source) != 4:
             raise TypeError('%s: a source is (seg_ptr, item, like | None, seg_of_row | None)' % what)
         seg_ptr, item, like, seg_of_row = source
-        _group_tensor(what, 'seg_ptr', seg_ptr, torch.int64, device)
+        _operand(what, 'seg_ptr', seg_ptr, torch.int64, 1, at_least=1, on=device, raises=_STD)      # n_seg + 1 entries
         device = seg_ptr.device
-        _group_tensor(what, 'item', item, torch.int32, device)
-        _group_tensor(what, 'like', like, torch.int32, device, optional=True)
-        _group_tensor(what, 'seg_of_row', seg_of_row, torch.int64, device, optional=True)
+        _operand(what, 'item', item, torch.int32, 1, on=device, raises=_STD)
+        _operand(what, 'like', like, torch.int32, 1, on=device, optional=True, raises=_STD)
+        _operand(what, 'seg_of_row', seg_of_row, torch.int64, 1, on=device, optional=True, raises=_STD)
         n_seg, n_entries = int(seg_ptr.numel()) - 1, int(item.numel())
-        if n_seg < 0:
-            raise ValueError('%s: seg_ptr must hold n_seg + 1 >= 1 entries' % what)
         if like is None and like_only:
             raise ValueError('%s: like_only needs the like array of every source' % what)
         if like is not None and like.numel() != n_entries:
@@ -964,18 +1004,18 @@ def group_segments(sources, n_rows, n_cols, like_only=False):
     args = (C.byref(structs), C.c_int32(len(sources)), C.c_int64(n_rows), C.c_int32(n_cols), C.c_int32(1 if like_only else 0))
     _call('tkr_group_count_dev', ptr, *args, _p(ptr), _p(totals))
     total, word = totals.tolist()                                   # the one round trip: cols is sized by it
-    _group_status(word, what)
+    status_check(what, _GROUP_REFUSED, ValueError, word)
     cols = torch.empty(total, dtype=torch.int32, device=device)
     status = torch.empty(1, dtype=torch.int64, device=device)
     _call('tkr_group_emit_dev', ptr, *args, _p(ptr), _p(cols) if total else C.c_void_p(0), C.c_int64(total), _p(status))
-    _group_status(int(status.item()), what)
+    status_check(what, _GROUP_REFUSED, ValueError, int(status.item()))
     return ptr, cols
 
 
 def last_line_of_user(line_user, n_users):
     """-> int64 [n_users] on the device: the last line of every user in line_user (int32 [n_lines], -1 = unknown user), -1 = no line"""
     what = 'last_line_of_user'
-    _group_tensor(what, 'line_user', line_user, torch.int32, None)
+    _operand(what, 'line_user', line_user, torch.int32, 1, raises=_STD)
     n_users = int(n_users)
     if n_users < 0:
         raise ValueError('%s: n_users >= 0 required' % what)
@@ -989,10 +1029,8 @@ def scenario_lines(ptr):
     """the rows of the CSR `ptr` (device int64 [n_rows + 1]) with at least one element -> (rows int64 [n_kept], ascending; the ptr
     int64 [n_kept + 1] of the CSR that keeps only them -- its cols are the same array)"""
     what = 'scenario_lines'
-    _group_tensor(what, 'ptr', ptr, torch.int64, None)
+    _operand(what, 'ptr', ptr, torch.int64, 1, at_least=1, raises=_STD)      # n_rows + 1 entries
     n_rows = int(ptr.numel()) - 1
-    if n_rows < 0:
-        raise ValueError('%s: ptr must hold n_rows + 1 >= 1 entries' % what)
     dev = ptr.device
     if n_rows == 0:
         return torch.empty(0, dtype=torch.int64, device=dev), ptr.clone()
@@ -1004,7 +1042,7 @@ def scenario_lines(ptr):
     status = torch.empty(1, dtype=torch.int64, device=dev)
     _call('tkr_compact_rows_emit_dev', ptr, _p(ptr), _p(pos), C.c_int64(n_rows), C.c_int64(n_kept), _p(rows) if n_kept else C.c_void_p(0),
           _p(out_ptr), _p(status))
-    _group_status(int(status.item()), what)
+    status_check(what, _GROUP_REFUSED, ValueError, int(status.item()))
     return rows, out_ptr
 
 
@@ -1023,24 +1061,6 @@ class FusionModels(C.Structure):
                 ('reserved', C.c_int32)]
 
 
-def _fusion_table(what, name, t, dim):
-    if not isinstance(t, torch.Tensor):
-        raise TkrError('%s: %s must be a tensor' % (what, name))
-    if t.dtype != torch.float32:
-        raise TkrError('%s: %s must be torch.float32, not %s' % (what, name, t.dtype))
-    if not t.is_contiguous():
-        raise TkrError('%s: %s must be contiguous' % (what, name))
-    if dim is not None and t.dim() != dim:
-        raise TkrError('%s: %s must have %d dimensions' % (what, name, dim))
-
-
-def _fusion_int(what, name, t, dtype, device):
-    if not isinstance(t, torch.Tensor) or t.dtype != dtype or t.dim() != 1 or not t.is_contiguous():
-        raise TkrError('%s: %s must be a contiguous one-dimensional %s tensor' % (what, name, dtype))
-    if not t.is_cuda or t.device != device:
-        raise TkrError('%s: %s must live on the GPU that holds the models, not on %s' % (what, name, t.device))
-
-
 def fusion_models(what, models):
     """a list of (U [n_users, k_m], V [n_items, k_m], bias [n_items] | [n_items, 1] | None) -> (FusionModels, n_users, n_items, device).
     Refuses with TkrError, the tensors' properties first (no device access): more than FUSION_MAX_MODELS models, a table that is not
@@ -1054,10 +1074,9 @@ def fusion_models(what, models):
         if not isinstance(model, (tuple, list)) or len(model) != 3:
             raise TkrError('%s: a model is (U, V, bias | None)' % what)
         U, V, b = model
-        _fusion_table(what, 'U of model %d' % m, U, 2)
-        _fusion_table(what, 'V of model %d' % m, V, 2)
-        if b is not None:
-            _fusion_table(what, 'bias of model %d' % m, b, None)
+        _operand(what, 'U of model %d' % m, U, torch.float32, 2, on=_LATER)
+        _operand(what, 'V of model %d' % m, V, torch.float32, 2, on=_LATER)
+        _operand(what, 'bias of model %d' % m, b, torch.float32, on=_LATER, optional=True)
         if U.shape[1] != V.shape[1] or U.shape[1] < 1:
             raise TkrError('%s: U and V of model %d must share k >= 1 (%d, %d)' % (what, m, U.shape[1], V.shape[1]))
         if n_users is None:
@@ -1067,11 +1086,10 @@ def fusion_models(what, models):
         if b is not None and b.numel() != n_items:
             raise TkrError('%s: the bias of model %d must hold one value per item' % (what, m))
     device = models[0][0].device
-    for m, model in enumerate(models):
-        for t in model:
-            if t is not None and (not t.is_cuda or t.device != device):
-                raise TkrError('%s: the tables of model %d must live on one GPU, not on %s' % (what, m, t.device))
-        U, V, b = model
+    for m, (U, V, b) in enumerate(models):
+        for name, t in (('U', U), ('V', V), ('bias', b)):
+            if t is not None:
+                _on_gpu(what, '%s of model %d' % (name, m), t, device)
         st.m[m] = FusionModel(U.data_ptr(), V.data_ptr(), b.data_ptr() if b is not None else None, int(U.shape[1]), 0)
     st.n_models, st.n_users, st.n_items = len(models), n_users, n_items
     return st, n_users, n_items, device
@@ -1089,7 +1107,7 @@ def fusion_features(models, csr, n_items, seed, first_triplet, count, want_tripl
     if count < 1:
         raise TkrError('%s: count >= 1 required' % what)
     for name in ('tr_users', 'row_ptr', 'pos_cols', 'cols_sorted'):
-        _fusion_int(what, name, getattr(csr, name), torch.int32, device)
+        _operand(what, name, getattr(csr, name), torch.int32, 1, on=device)
     if csr.row_ptr.numel() != n_users + 1 or csr.tr_users.numel() < 1:
         raise TkrError('%s: the CSR must describe the models\' %d users and hold at least one row' % (what, n_users))
     M = st.n_models
@@ -1106,8 +1124,8 @@ def fusion_sgd(D, batch, n_batches, lr, lambda_w, W, want_loss=False):
     updated in place -> W (with want_loss: (W, loss fp32 [n_batches])).  One workgroup, bitwise repeatable, and the same bits whether
     the batches run in one call or in several with W carried across (include/tkr.h tkr_fusion_sgd)"""
     what = 'fusion_sgd'
-    _fusion_table(what, 'D', D, 2)
-    _fusion_table(what, 'W', W, 1)
+    _operand(what, 'D', D, torch.float32, 2, on=_LATER)
+    _operand(what, 'W', W, torch.float32, 1, on=_LATER)
     n_rows, M = int(D.shape[0]), int(D.shape[1])
     batch, n_batches = int(batch), int(n_batches)
     if not 1 <= M <= FUSION_MAX_MODELS:
@@ -1118,9 +1136,9 @@ def fusion_sgd(D, batch, n_batches, lr, lambda_w, W, want_loss=False):
         raise TkrError('%s: W must hold one weight per column of D (%d, %d)' % (what, W.numel(), M))
     if n_batches < 0 or n_batches * batch > n_rows:
         raise TkrError('%s: %d batches of %d rows do not fit the %d rows of D' % (what, n_batches, batch, n_rows))
-    if not D.is_cuda or W.device != D.device:
-        raise TkrError('%s: D and W must live on one GPU' % what)
-    loss = torch.empty(n_batches, dtype=torch.float32, device=D.device) if want_loss else None
+    _on_gpu(what, 'D', D)
+    _on_gpu(what, 'W', W, D.device)
+    loss =torch.empty(n_batches, dtype=torch.float32, device=D.device) if want_loss else None
     if n_batches:
         _call('tkr_fusion_sgd', D, _p(D), C.c_int64(n_rows), C.c_int32(M), C.c_int32(batch), C.c_int64(n_batches), C.c_float(lr),
               C.c_float(lambda_w), _p(W), _p(loss))
@@ -1132,8 +1150,8 @@ def fusion_user_weights(models, like_ptr, like_cols):
     (like_ptr int64 [n_users + 1] from 0, like_cols int32, a set per row: foldin.liked_csr) -- include/tkr.h tkr_fusion_user_weights"""
     what = 'fusion_user_weights'
     st, n_users, n_items, device = fusion_models(what, models)
-    _fusion_int(what, 'like_ptr', like_ptr, torch.int64, device)
-    _fusion_int(what, 'like_cols', like_cols, torch.int32, device)
+    _operand(what, 'like_ptr', like_ptr, torch.int64, 1, on=device)
+    _operand(what, 'like_cols', like_cols, torch.int32, 1, on=device)
     if like_ptr.numel() != n_users + 1:
         raise TkrError('%s: like_ptr must hold n_users + 1 = %d entries' % (what, n_users + 1))
     nnz = int(like_cols.numel())
@@ -1163,23 +1181,7 @@ def fusion_svm_slabs(n_rows, first_row=0):
 
 
 def fusion_svm_partial_bytes(n_rows, M, first_row=0):
-    need = int(lib().tkr_fusion_svm_partial_bytes(C.c_int64(n_rows), C.c_int32(M), C.c_int64(first_row)))
-    if need < 0:
-        raise TkrError('tkr_fusion_svm_partial_bytes(%d, %d, %d) failed: tkr error %d' % (n_rows, M, first_row, need))
-    return need
-
-
-def _fusion_svm_f64(what, name, t, numel, device, at_least=False):
-    if not isinstance(t, torch.Tensor):
-        raise TkrError('%s: %s must be a tensor' % (what, name))
-    if t.dtype != torch.float64:
-        raise TkrError('%s: %s must be torch.float64, not %s' % (what, name, t.dtype))
-    if not t.is_contiguous():
-        raise TkrError('%s: %s must be contiguous' % (what, name))
-    if t.numel() < numel if at_least else t.numel() != numel:
-        raise TkrError('%s: %s must hold %s%d values, not %d' % (what, name, 'at least ' if at_least else '', numel, t.numel()))
-    if t.device != device:
-        raise TkrError('%s: D and %s must live on one GPU' % (what, name))
+    return _size('tkr_fusion_svm_partial_bytes', (C.c_int64, C.c_int32, C.c_int64), (n_rows, M, first_row))
 
 
 def fusion_svm_unpack(out, M):
@@ -1203,7 +1205,7 @@ def fusion_svm_sums(D, W, first_row=0, *, partial=None, slab_offset=0, reduce=Tr
     call with slab_offset 0.  A row that is not finite raises TkrError naming it and leaves ``out`` as it is; check=False reads
     nothing back (the caller reads ``status``: -1 or the row)."""
     what = 'fusion_svm_sums'
-    _fusion_table(what, 'D', D, 2)
+    _operand(what, 'D', D, torch.float32, 2, on=_LATER)
     n_rows, M = int(D.shape[0]), int(D.shape[1])
     first_row, slab_offset = int(first_row), int(slab_offset)
     if not 1 <= M <= FUSION_MAX_MODELS:
@@ -1212,18 +1214,17 @@ def fusion_svm_sums(D, W, first_row=0, *, partial=None, slab_offset=0, reduce=Tr
         raise TkrError('%s: D must hold at least one row' % what)
     if first_row < 0 or slab_offset < 0:
         raise TkrError('%s: first_row and slab_offset must not be negative (%d, %d)' % (what, first_row, slab_offset))
-    if not D.is_cuda:
-        raise TkrError('%s: D must live on the GPU, not on %s' % (what, D.device))
+    _on_gpu(what, 'D', D)
     words = fusion_svm_words(M)
-    _fusion_svm_f64(what, 'W', W, M + 1, D.device)
+    _operand(what, 'W', W, torch.float64, numel=M + 1, on=D.device)
     need = (slab_offset + fusion_svm_slabs(n_rows, first_row)) * words
     if partial is None:
         partial = torch.empty(need, dtype=torch.float64, device=D.device)
-    _fusion_svm_f64(what, 'partial', partial, need, D.device, at_least=True)
+    _operand(what, 'partial', partial, torch.float64, at_least=need, on=D.device)
     if reduce:
         if out is None:
             out = torch.empty(words, dtype=torch.float64, device=D.device)
-        _fusion_svm_f64(what, 'out', out, words, D.device)
+        _operand(what, 'out', out, torch.float64, numel=words, on=D.device)
     else:
         out = None
     if status is None:
@@ -1246,21 +1247,16 @@ def fusion_svm_check(word):
 
 # ---- K17: diversify a pool into a list, the pair sums of list diversity (csrc/diversity.hip) -------------------------------------------
 MMR_MAX_POOL = 1024          # TKR_MMR_MAX_POOL of include/tkr.h: a thread per pool entry
+_DIV_REFUSED = (None, 'row %d holds an id outside [0, n_items) in front of its padding')
 
 
 def _div_args(what, S, ids, rel=None):
     """refuse what the K17 entry points cannot take, the tensors' properties only (no device access) -> (n_items, k, n_rows, width)"""
-    named = dict(S=(S, torch.float32, 2), ids=(ids, torch.int32, 2))
-    if rel is not None:
-        named['rel'] = (rel, torch.float32, 2)
-    for name, (t, dtype, dim) in named.items():
-        if not isinstance(t, torch.Tensor):
-            raise TkrError('%s: %s must be a tensor' % (what, name))
-        if t.dtype != dtype or t.dim() != dim or not t.is_contiguous():
-            raise TkrError('%s: %s must be a contiguous %d-dimensional %s tensor' % (what, name, dim, dtype))
-    for name, (t, _, _) in named.items():
-        if not t.is_cuda or t.device != S.device:
-            raise TkrError('%s: %s must live on the GPU that holds S, not on %s' % (what, name, t.device))
+    named = [('S', S, torch.float32), ('ids', ids, torch.int32)] + ([] if rel is None else [('rel', rel, torch.float32)])
+    for name, t, dtype in named:
+        _operand(what, name, t, dtype, 2, on=_LATER)
+    for name, t, _ in named:
+        _on_gpu(what, name, t, S.device)
     if S.shape[0] < 1 or S.shape[1] < 1:
         raise TkrError('%s: S [n_items, k] needs n_items >= 1 and k >= 1' % what)
     if rel is not None and rel.shape != ids.shape:
@@ -1268,12 +1264,6 @@ def _div_args(what, S, ids, rel=None):
     if ids.shape[1] > MMR_MAX_POOL:
         raise TkrError('%s: %d entries per row, at most %d are supported' % (what, ids.shape[1], MMR_MAX_POOL))
     return int(S.shape[0]), int(S.shape[1]), int(ids.shape[0]), int(ids.shape[1])
-
-
-def _div_status(status, what, n_items):
-    word = int(status.item())
-    if word != -1:
-        raise TkrError('%s: row %d holds an id outside [0, %d) in front of its padding' % (what, word >> 2, n_items))
 
 
 def mmr_select(S, ids, rel, lam, t):
@@ -1293,7 +1283,7 @@ def mmr_select(S, ids, rel, lam, t):
     status = torch.empty(1, dtype=torch.int64, device=S.device)
     _call('tkr_mmr_select', S, _p(S), C.c_int32(n_items), C.c_int32(k), _p(ids), _p(rel), C.c_int32(n_rows), C.c_int32(N), C.c_double(lam),
           C.c_int32(t), _p(sel), _p(status))
-    _div_status(status, what, n_items)
+    status_check(what, _DIV_REFUSED, TkrError, int(status.item()))
     return sel
 
 
@@ -1307,15 +1297,16 @@ def list_pair_sums(S, ids):
         return out
     status = torch.empty(1, dtype=torch.int64, device=S.device)
     _call('tkr_list_pair_sums', S, _p(S), C.c_int32(n_items), C.c_int32(k), _p(ids), C.c_int32(n_rows), C.c_int32(t), _p(out), _p(status))
-    _div_status(status, what, n_items)
+    status_check(what, _DIV_REFUSED, TkrError, int(status.item()))
     return out
 
 
 # ---- K19: the nearest anchors of every list entry (csrc/explain.hip) ---------------------------------------------------------------------
 ANCHOR_MAX_E = 8             # TKR_ANCHOR_MAX_E of include/tkr.h: the best anchors kept per entry
-ANCHOR_MAX_T = 1024          # TKR_ANCHOR_MAX_T (= MMR_MAX_POOL)
+ANCHOR_MAX_T = MMR_MAX_POOL  # TKR_ANCHOR_MAX_T
 _ANCHOR_REFUSED = ('row %d holds an id outside [0, n_items) in front of its padding', 'row %d holds an anchor outside [0, n_items)', None,
                    'anchor_ptr does not start at 0, decreases or leaves [0, len(anchor_cols)] at row %d')
+_ANCHOR_RAISES = (TkrError, TkrError, None, ValueError)          # by kind: a bad row pointer is a ValueError, as a bad argument is
 
 
 def nearest_anchors(S, ids, anchor_ptr, anchor_cols, e):
@@ -1331,8 +1322,8 @@ def nearest_anchors(S, ids, anchor_ptr, anchor_cols, e):
         raise TkrError('%s: 1 <= e <= %d required, got %d' % (what, ANCHOR_MAX_E, e))
     if t < 1:
         raise TkrError('%s: ids [n_rows, t] needs t >= 1' % what)
-    _group_tensor(what, 'anchor_ptr', anchor_ptr, torch.int64, S.device)
-    _group_tensor(what, 'anchor_cols', anchor_cols, torch.int32, S.device)
+    _operand(what, 'anchor_ptr', anchor_ptr, torch.int64, 1, on=S.device, raises=_STD)
+    _operand(what, 'anchor_cols', anchor_cols, torch.int32, 1, on=S.device, raises=_STD)
     if anchor_ptr.numel() != n_rows + 1:
         raise ValueError('%s: anchor_ptr must hold n_rows + 1 = %d entries, not %d' % (what, n_rows + 1, anchor_ptr.numel()))
     pos = torch.empty((n_rows, t, e), dtype=torch.int32, device=S.device)
@@ -1343,9 +1334,7 @@ def nearest_anchors(S, ids, anchor_ptr, anchor_cols, e):
     status = torch.empty(1, dtype=torch.int64, device=S.device)
     _call('tkr_nearest_anchors', S, _p(S), C.c_int32(n_items), C.c_int32(k), _p(ids), C.c_int32(n_rows), C.c_int32(t), _p(anchor_ptr),
           _p(anchor_cols) if n_anchors else C.c_void_p(0), C.c_int64(n_anchors), C.c_int32(e), _p(pos), _p(sim), _p(status))
-    word = int(status.item())
-    if word != -1:
-        raise (ValueError if word & 3 == 3 else TkrError)('%s: %s' % (what, _ANCHOR_REFUSED[word & 3] % (word >> 2)))
+    status_check(what, _ANCHOR_REFUSED, _ANCHOR_RAISES, int(status.item()))
     return pos, sim
 
 
@@ -1353,22 +1342,17 @@ def nearest_anchors(S, ids, anchor_ptr, anchor_cols, e):
 ALS_MAX_K = 128              # TKR_ALS_MAX_K of include/tkr.h: A (k x k) lives in the LDS of one workgroup
 ALS_GRAM_SLAB = 1024         # TKR_ALS_GRAM_SLAB: the listed rows one workgroup sums
 ALS_NO_HEAVY = 1 << 62       # heavy_from: no row is heavy
-_ALS_REFUSED = (None, 'row %d holds a like outside [0, n_y)', 'the system of row %d is not positive definite in fp32',
-                'like_ptr does not start at 0, decreases or leaves [0, len(like_cols)] at row %d')
+_ALS_REFUSED = (None, 'row %d holds a like outside [0, n_y) (kind 1)', 'the system of row %d is not positive definite in fp32 (kind 2)',
+                'like_ptr does not start at 0, decreases or leaves [0, len(like_cols)] at row %d (kind 3)')
 
 
 class AlsRefused(TkrError):
-    """a status word of K20 that is not -1; .row and .kind say what it holds (include/tkr.h)"""
-    messages = _ALS_REFUSED
-
-    def __init__(self, what, word):
-        self.word, self.row, self.kind = word, word >> 2, word & 3
-        super().__init__('%s: %s (kind %d)' % (what, self.messages[self.kind] % self.row, self.kind))
+    """a status word of K20 that is not -1; .word, .row and .kind say what it holds (include/tkr.h; raised by status_check)"""
 
 
 def _als_table(what, name, t, k_max, k=None):
-    if not isinstance(t, torch.Tensor) or t.dtype != torch.float32 or t.dim() != 2 or not t.is_contiguous() or not t.is_cuda:
-        raise TkrError('%s: %s must be a contiguous two-dimensional float32 tensor on the GPU' % (what, name))
+    """the shape rules of a factor table of the ALS family -> (rows, k)"""
+    _operand(what, name, t, torch.float32, 2)
     if t.shape[0] < 1 or (k is not None and t.shape[1] != k):
         raise TkrError('%s: %s has shape %s' % (what, name, tuple(t.shape)))
     if not 1 <= t.shape[1] <= k_max:
@@ -1376,15 +1360,8 @@ def _als_table(what, name, t, k_max, k=None):
     return int(t.shape[0]), int(t.shape[1])
 
 
-def _als_bytes(entry, types, values):
-    need = int(getattr(lib(), entry)(*(t(v) for t, v in zip(types, values))))
-    if need < 0:
-        raise TkrError('%s(%s) failed: tkr error %d' % (entry, ', '.join('%d' % v for v in values), need))
-    return need
-
-
 def als_workspace_bytes(n_x, k, n_slabs):
-    return _als_bytes('tkr_als_workspace_bytes', (C.c_int64, C.c_int32, C.c_int64), (n_x, k, n_slabs))
+    return _size('tkr_als_workspace_bytes', (C.c_int64, C.c_int32, C.c_int64), (n_x, k, n_slabs))
 
 
 def als_heavy_slabs(like_ptr, heavy_from):
@@ -1403,20 +1380,10 @@ def workspace_room(workspace, need, device):
     return torch.empty((max(need, 16) + 7) // 8, dtype=torch.int64, device=device)
 
 
-def _als_done(what, result, status, check, refused=AlsRefused):
-    """the tail of every ALS wrapper: check=False hands the status word on unread, else it is read and a refusal raised"""
-    if not check:
-        return result, status
-    word = int(status.item())
-    if word != -1:
-        raise refused(what, word)
-    return result
-
-
 def _als_gram(what, entry, k_max, sizer, Y, rows, scale, ridge, workspace, out, check):
     n, k = _als_table(what, 'Y', Y, k_max)
     if rows is not None:
-        _group_tensor(what, 'rows', rows, torch.int32, Y.device)
+        _operand(what, 'rows', rows, torch.int32, 1, on=Y.device, raises=_STD)
     n_listed = n if rows is None else int(rows.numel())
     workspace = workspace_room(workspace, sizer(k, (n_listed + ALS_GRAM_SLAB - 1) // ALS_GRAM_SLAB), Y.device)
     G = torch.empty((k, k), dtype=torch.float32, device=Y.device) if out is None else out
@@ -1425,7 +1392,7 @@ def _als_gram(what, entry, k_max, sizer, Y, rows, scale, ridge, workspace, out, 
     rows_p = C.c_void_p(0) if rows is None else _p(rows if n_listed else Y)
     _call(entry, Y, _p(Y), C.c_int32(n), C.c_int32(k), rows_p, C.c_int64(n_listed), C.c_double(scale), C.c_double(ridge), _p(G), _p(workspace),
           C.c_int64(workspace.numel() * workspace.element_size()), _p(status))
-    return _als_done(what, G, status, check)
+    return _done(what, G, status, check, _ALS_REFUSED, AlsRefused)
 
 
 def als_gram(Y, rows=None, scale=1.0, ridge=0.0, workspace=None, out=None, check=True):
@@ -1446,8 +1413,8 @@ def _als_rows(what, k_max, Y, G, like_ptr, like_cols, X, priors=None):
         _als_table(what, 'prior', prior, k_max, k)
     if G.shape[0] != k or X.device != Y.device or G.device != Y.device or any(p.device != Y.device or p.shape[0] != n_x for p in priors or ()):
         raise TkrError('%s: G must be [k, k], %s on one GPU' % (what, 'and Y, G and X' if priors is None else 'prior [n_x, k], and Y, G, X and prior'))
-    _group_tensor(what, 'like_ptr', like_ptr, torch.int64, Y.device)
-    _group_tensor(what, 'like_cols', like_cols, torch.int32, Y.device)
+    _operand(what, 'like_ptr', like_ptr, torch.int64, 1, on=Y.device, raises=_STD)
+    _operand(what, 'like_cols', like_cols, torch.int32, 1, on=Y.device, raises=_STD)
     if like_ptr.numel() != n_x + 1:
         raise ValueError('%s: like_ptr must hold n_x + 1 = %d entries, not %d' % (what, n_x + 1, like_ptr.numel()))
     return n_y, k, n_x, int(like_cols.numel())
@@ -1471,11 +1438,11 @@ def als_solve_rows(Y, G, like_ptr, like_cols, X, *, w_like, w_rhs, ridge, heavy_
     _call('tkr_als_solve_rows', Y, _p(Y), C.c_int32(n_y), C.c_int32(k), _p(G), _p(like_ptr), _p(like_cols) if n_likes else C.c_void_p(0),
           C.c_int64(n_likes), C.c_int64(n_x), C.c_double(w_like), C.c_double(w_rhs), C.c_double(ridge), C.c_int64(heavy_from), _p(X), _p(loss),
           _p(workspace), C.c_int64(workspace.numel() * workspace.element_size()), _p(status))
-    return _als_done(what, loss, status, check)
+    return _done(what, loss, status, check, _ALS_REFUSED, AlsRefused)
 
 
 def als_prior_workspace_bytes(n_x, k, n_slabs):
-    return _als_bytes('tkr_als_prior_workspace_bytes', (C.c_int64, C.c_int32, C.c_int64), (n_x, k, n_slabs))
+    return _size('tkr_als_prior_workspace_bytes', (C.c_int64, C.c_int32, C.c_int64), (n_x, k, n_slabs))
 
 
 def als_solve_rows_prior(Y, G, like_ptr, like_cols, X, prior, *, w_like, w_rhs, w_prior, ridge, heavy_from=None, want_loss=False, workspace=None,
@@ -1497,7 +1464,7 @@ def als_solve_rows_prior(Y, G, like_ptr, like_cols, X, prior, *, w_like, w_rhs, 
     _call('tkr_als_solve_rows_prior', Y, _p(Y), C.c_int32(n_y), C.c_int32(k), _p(G), _p(like_ptr), _p(like_cols) if n_likes else C.c_void_p(0),
           C.c_int64(n_likes), C.c_int64(n_x), C.c_double(w_like), C.c_double(w_rhs), C.c_double(ridge), C.c_int64(heavy_from), _p(X), _p(loss),
           _p(prior), C.c_double(w_prior), _p(workspace), C.c_int64(workspace.numel() * workspace.element_size()), _p(status))
-    return _als_done(what, loss, status, check)
+    return _done(what, loss, status, check, _ALS_REFUSED, AlsRefused)
 
 
 ALS_HEAVY_FROM = 4 * ALS_GRAM_SLAB       # a row with this many likes is shared by several workgroups (scripts/time_als.py)
@@ -1510,15 +1477,17 @@ ALS_CG_STEPS = 3             # the steps per half-step als.py takes by default
 
 class AlsCgRefused(AlsRefused):
     """a status word of K24 that is not -1 (the kinds of K20; kind 2 is conjugate gradients' own)"""
-    messages = (None, _ALS_REFUSED[1], 'p.q of row %d is not positive and finite, or its solution is not finite', _ALS_REFUSED[3])
+
+
+_ALS_CG_REFUSED = (None, _ALS_REFUSED[1], 'p.q of row %d is not positive and finite, or its solution is not finite (kind 2)', _ALS_REFUSED[3])
 
 
 def als_cg_workspace_bytes(n_x, k):
-    return _als_bytes('tkr_als_cg_workspace_bytes', (C.c_int64, C.c_int32), (n_x, k))
+    return _size('tkr_als_cg_workspace_bytes', (C.c_int64, C.c_int32), (n_x, k))
 
 
 def als_gram_wide_workspace_bytes(k, n_slabs):
-    return _als_bytes('tkr_als_gram_wide_workspace_bytes', (C.c_int32, C.c_int64), (k, n_slabs))
+    return _size('tkr_als_gram_wide_workspace_bytes', (C.c_int32, C.c_int64), (k, n_slabs))
 
 
 def als_gram_wide(Y, rows=None, scale=1.0, ridge=0.0, workspace=None, out=None, check=True):
@@ -1540,7 +1509,7 @@ def als_cg_rows(Y, G, like_ptr, like_cols, X, *, w_like, w_rhs, ridge, steps=ALS
     _call('tkr_als_cg_rows', Y, _p(Y), C.c_int32(n_y), C.c_int32(k), _p(G), _p(like_ptr), _p(like_cols) if n_likes else C.c_void_p(0),
           C.c_int64(n_likes), C.c_int64(n_x), C.c_double(w_like), C.c_double(w_rhs), C.c_double(ridge), C.c_int32(steps), _p(X), _p(loss),
           _p(prior), C.c_double(w_prior), C.c_void_p(0), C.c_int64(0), _p(status))
-    return _als_done(what, loss, status, check, AlsCgRefused)
+    return _done(what, loss, status, check, _ALS_CG_REFUSED, AlsCgRefused)
 
 
 # ---- K25: the two halves of a logistic-MF half-step (csrc/lmf.hip) --------------------------------------------------------------------------
@@ -1554,11 +1523,13 @@ LMF_NO_HEAVY = 1 << 62       # heavy_from: no row is heavy
 
 class LmfRefused(AlsRefused):
     """a status word of K25 that is not -1 (the kinds 1 and 3 of K20)"""
-    messages = (None, _ALS_REFUSED[1], None, _ALS_REFUSED[3])
+
+
+_LMF_REFUSED = (None, _ALS_REFUSED[1], None, _ALS_REFUSED[3])
 
 
 def lmf_workspace_bytes(n_x, k, n_y):
-    return _als_bytes('tkr_lmf_workspace_bytes', (C.c_int64, C.c_int32, C.c_int64), (n_x, k, n_y))
+    return _size('tkr_lmf_workspace_bytes', (C.c_int64, C.c_int32, C.c_int64), (n_x, k, n_y))
 
 
 def _lmf_tables(what, pairs):
@@ -1569,8 +1540,7 @@ def _lmf_tables(what, pairs):
         if K < 3:
             raise ValueError('%s: %s has %d columns; a table holds k + 2 of them, k >= 1' % (what, name, K))
         k = K - 2
-        if t.device != pairs[0][1].device:
-            raise TkrError('%s: %s must be on one GPU' % (what, ', '.join(n for n, _ in pairs)))
+        _on_gpu(what, name, t, pairs[0][1].device)
     return k
 
 
@@ -1583,8 +1553,9 @@ def lmf_dense_rows(X, Y, want_loss=False, workspace=None, out=None):
     n_x, n_y = int(X.shape[0]), int(Y.shape[0])
     workspace = workspace_room(workspace, lmf_workspace_bytes(n_x, k, n_y), X.device)
     D = torch.empty((n_x, k + 2), dtype=torch.float32, device=X.device) if out is None else out
-    if D.shape != X.shape or D.dtype != torch.float32 or D.device != X.device or not D.is_contiguous():
-        raise TkrError('%s: out must be a contiguous float32 tensor of the shape of X on its device' % what)
+    _operand(what, 'out', D, torch.float32, 2, on=X.device)
+    if D.shape != X.shape:
+        raise TkrError('%s: out must have the shape of X, %s' % (what, tuple(X.shape)))
     sp = torch.empty(n_x, dtype=torch.float64, device=X.device) if want_loss else None
     _call('tkr_lmf_dense_rows', X, _p(X), C.c_int64(n_x), _p(Y), C.c_int64(n_y), C.c_int32(k), _p(D), _p(sp), _p(workspace),
           C.c_int64(workspace.numel() * workspace.element_size()))
@@ -1602,8 +1573,8 @@ def lmf_step_rows(Y, D, like_ptr, like_cols, X, H, *, fixed, alpha, lam, lr, hea
     n_y, n_x = int(Y.shape[0]), int(X.shape[0])
     if D.shape != X.shape or H.shape != X.shape:
         raise TkrError('%s: D and H must have the shape of X, %s' % (what, tuple(X.shape)))
-    _group_tensor(what, 'like_ptr', like_ptr, torch.int64, Y.device)
-    _group_tensor(what, 'like_cols', like_cols, torch.int32, Y.device)
+    _operand(what, 'like_ptr', like_ptr, torch.int64, 1, on=Y.device, raises=_STD)
+    _operand(what, 'like_cols', like_cols, torch.int32, 1, on=Y.device, raises=_STD)
     if like_ptr.numel() != n_x + 1:
         raise ValueError('%s: like_ptr must hold n_x + 1 = %d entries, not %d' % (what, n_x + 1, like_ptr.numel()))
     if not isinstance(fixed, (int,)) or isinstance(fixed, bool) or not 0 <= fixed < k + 2:
@@ -1616,7 +1587,7 @@ def lmf_step_rows(Y, D, like_ptr, like_cols, X, H, *, fixed, alpha, lam, lr, hea
     _call('tkr_lmf_step_rows', Y, _p(Y), C.c_int32(n_y), C.c_int32(k), _p(D), _p(like_ptr), _p(like_cols) if n_likes else C.c_void_p(0),
           C.c_int64(n_likes), C.c_int64(n_x), C.c_int32(fixed), C.c_double(alpha), C.c_double(lam), C.c_double(lr), C.c_int64(heavy_from), _p(X),
           _p(H), _p(loss), _p(workspace), C.c_int64(workspace.numel() * workspace.element_size()), _p(status))
-    return _als_done(what, loss, status, check, LmfRefused)
+    return _done(what, loss, status, check, _LMF_REFUSED, LmfRefused)
 
 
 # ---- K22: a dense MLP content encoder, applied and trained (csrc/mlp.hip) ------------------------------------------------------------------
@@ -1633,11 +1604,11 @@ class MlpNet(C.Structure):
 
 
 class MlpRefused(TkrError):
-    """a status word of K22 that is not -1: .position is the entry of rows / order that lies outside [0, n)"""
+    """a status word of K22 that is not -1: .position (= .row) is the entry of rows / order that lies outside [0, n)"""
+    position = property(lambda self: self.row)
 
-    def __init__(self, what, word):
-        self.word, self.position = word, word >> 2
-        super().__init__('%s: entry %d of the row list lies outside [0, n)' % (what, self.position))
+
+_MLP_REFUSED = (None, 'entry %d of the row list lies outside [0, n)')
 
 
 def mlp_net(layers):
@@ -1651,17 +1622,20 @@ def mlp_net(layers):
     device = layers[0]['W'].device
     for l, layer in enumerate(layers):
         W = layer['W']
-        if not isinstance(W, torch.Tensor) or W.dtype != torch.float32 or W.dim() != 2 or W.shape[0] < 1 or W.shape[1] < 1:
-            raise TkrError('%s: W of layer %d must be a two-dimensional float32 tensor' % (what, l))
+        _operand(what, 'W of layer %d' % l, W, torch.float32, 2, on=device)
+        if W.shape[0] < 1 or W.shape[1] < 1:
+            raise TkrError('%s: W of layer %d has shape %s' % (what, l, tuple(W.shape)))
         if l and W.shape[0] != layers[l - 1]['W'].shape[1]:
             raise ValueError('%s: layer %d takes %d inputs, layer %d gives %d' % (what, l, W.shape[0], l - 1, layers[l - 1]['W'].shape[1]))
         net.width[l], net.width[l + 1] = int(W.shape[0]), int(W.shape[1])
-        for name, shape in (('W', W.shape), ('bias', W.shape[1:]), ('msW', W.shape), ('msb', W.shape[1:])):
+        net.W[l] = W.data_ptr()
+        for name, shape in (('bias', W.shape[1:]), ('msW', W.shape), ('msb', W.shape[1:])):
             t = layer.get(name)
             if t is None and name in ('msW', 'msb'):
                 continue
-            if not isinstance(t, torch.Tensor) or t.dtype != torch.float32 or t.shape != shape or not t.is_contiguous() or t.device != device or not t.is_cuda:
-                raise TkrError('%s: %s of layer %d must be a contiguous float32 tensor of shape %s on the GPU of layer 0' % (what, name, l, tuple(shape)))
+            _operand(what, '%s of layer %d' % (name, l), t, torch.float32, len(shape), on=device)
+            if t.shape != shape:
+                raise TkrError('%s: %s of layer %d must have shape %s, not %s' % (what, name, l, tuple(shape), tuple(t.shape)))
             getattr(net, name)[l] = t.data_ptr()
     net.keep = layers
     net.device = device
@@ -1669,15 +1643,14 @@ def mlp_net(layers):
 
 
 def mlp_workspace_bytes(net, m, batch=0):
-    need = int(lib().tkr_mlp_workspace_bytes(C.byref(net), C.c_int64(m), C.c_int32(batch)))
-    if need < 0:
-        raise TkrError('tkr_mlp_workspace_bytes(m = %d, batch = %d) failed: tkr error %d' % (m, batch, need))
-    return need
+    return _size('tkr_mlp_workspace_bytes', (C.byref, C.c_int64, C.c_int32), (net, m, batch), 'm = %d, batch = %d' % (m, batch))
 
 
-def _mlp_rows(what, name, t, device):
-    if not isinstance(t, torch.Tensor) or t.dtype != torch.int32 or t.dim() != 1 or not t.is_contiguous() or t.device != device:
-        raise TkrError('%s: %s must be a contiguous one-dimensional int32 tensor on the GPU of the parameters' % (what, name))
+def _mlp_table(what, name, t, n, width, device):
+    """X or Y of the K22 entry points: fp32 [n, width] (n None: any, at least one row) on the GPU of the parameters"""
+    _operand(what, name, t, torch.float32, 2, on=device)
+    if t.shape[1] != width or t.shape[0] < 1 or (n is not None and t.shape[0] != n):
+        raise TkrError('%s: %s must be [n, %d], not %s' % (what, name, width, tuple(t.shape)))
 
 
 def mlp_forward(net, X, rows=None, workspace=None, out=None, check=True):
@@ -1685,28 +1658,21 @@ def mlp_forward(net, X, rows=None, workspace=None, out=None, check=True):
     tkr_mlp_forward.  A row outside [0, n) raises MlpRefused and nothing is written; check=False returns (out, status tensor) and
     reads nothing back"""
     what = 'mlp_forward'
-    if not isinstance(X, torch.Tensor) or X.dtype != torch.float32 or X.dim() != 2 or not X.is_contiguous() or X.device != net.device or \
-            X.shape[1] != net.width[0] or X.shape[0] < 1:
-        raise TkrError('%s: X must be a contiguous float32 [n, %d] tensor on the GPU of the parameters' % (what, net.width[0]))
+    _mlp_table(what, 'X', X, None, net.width[0], net.device)
     n = int(X.shape[0])
-    if rows is not None:
-        _mlp_rows(what, 'rows', rows, X.device)
+    _operand(what, 'rows', rows, torch.int32, 1, on=X.device, optional=True)
     m = n if rows is None else int(rows.numel())
     k = net.width[net.n_layers]
     workspace = workspace_room(workspace, mlp_workspace_bytes(net, m), X.device)
     if out is None:
         out = torch.empty((m, k), dtype=torch.float32, device=X.device)
-    elif not isinstance(out, torch.Tensor) or out.dtype != torch.float32 or tuple(out.shape) != (m, k) or not out.is_contiguous() or out.device != X.device:
-        raise TkrError('%s: out must be a contiguous float32 [%d, %d] tensor on the GPU of X' % (what, m, k))
+    _operand(what, 'out', out, torch.float32, 2, on=X.device)
+    if tuple(out.shape) != (m, k):
+        raise TkrError('%s: out must be [%d, %d], not %s' % (what, m, k, tuple(out.shape)))
     status = torch.empty(1, dtype=torch.int64, device=X.device)
     _call('tkr_mlp_forward', X, C.byref(net), _p(X), C.c_int32(n), C.c_void_p(0) if rows is None else _p(rows if m else X), C.c_int64(m),
           _p(out if m else X), _p(workspace), C.c_int64(workspace.numel() * workspace.element_size()), _p(status))
-    if not check:
-        return out, status
-    word = int(status.item())
-    if word != -1:
-        raise MlpRefused(what, word)
-    return out
+    return _done(what, out, status, check, _MLP_REFUSED, MlpRefused)
 
 
 def mlp_fit(net, X, Y, order, batch, lr, workspace=None, check=True):
@@ -1716,11 +1682,9 @@ def mlp_fit(net, X, Y, order, batch, lr, workspace=None, check=True):
     back"""
     what = 'mlp_fit'
     k = net.width[net.n_layers]
-    for name, t, width in (('X', X, net.width[0]), ('Y', Y, k)):
-        if not isinstance(t, torch.Tensor) or t.dtype != torch.float32 or t.dim() != 2 or not t.is_contiguous() or t.device != net.device or \
-                t.shape[1] != width or t.shape[0] != X.shape[0] or t.shape[0] < 1:
-            raise TkrError('%s: %s must be a contiguous float32 [n, %d] tensor on the GPU of the parameters' % (what, name, width))
-    _mlp_rows(what, 'order', order, X.device)
+    _mlp_table(what, 'X', X, None, net.width[0], net.device)
+    _mlp_table(what, 'Y', Y, int(X.shape[0]), k, net.device)
+    _operand(what, 'order', order, torch.int32, 1, on=X.device)
     batch = int(batch)
     if not 1 <= batch <= MLP_MAX_BATCH:
         raise ValueError('%s: batch = %d, 1 <= batch <= %d is supported' % (what, batch, MLP_MAX_BATCH))
@@ -1730,30 +1694,16 @@ def mlp_fit(net, X, Y, order, batch, lr, workspace=None, check=True):
     status = torch.empty(1, dtype=torch.int64, device=X.device)
     _call('tkr_mlp_fit', X, C.byref(net), _p(X), C.c_int32(int(X.shape[0])), _p(Y), _p(order if m else X), C.c_int64(m), C.c_int32(batch),
           C.c_float(lr), _p(loss if m else X), _p(workspace), C.c_int64(workspace.numel() * workspace.element_size()), _p(status))
-    if not check:
-        return loss, status
-    word = int(status.item())
-    if word != -1:
-        raise MlpRefused(what, word)
-    return loss
+    return _done(what, loss, status, check, _MLP_REFUSED, MlpRefused)
 
 
 # ---- K18: the metric values of every test line, their sums over resampled lines (csrc/line_metrics.hip) -------------------------------
 LINE_MAX_TOTAL = 1024        # TKR_LINE_MAX_TOTAL of include/tkr.h
-LINE_MAX_COLS = 1308672      # TKR_LINE_MAX_COLS: the bitmap of one line must fit the LDS of one workgroup
+LINE_MAX_COLS = GROUP_MAX_COLS   # TKR_LINE_MAX_COLS: the bitmap of one line must fit the LDS of one workgroup, as K15's of one row
 BOOT_MAX_COLUMNS = 64        # TKR_BOOT_MAX_COLUMNS: a lane per column of a row
 BOOT_CHUNK = 8192            # TKR_BOOT_CHUNK: the draws one wave sums
 _LINE_REFUSED = ('line %d holds a rank below -1', 'line %d holds a rank that is not below its number of unrated columns',
                  'line %d names a rank twice', 'like_ptr / rated_ptr do not ascend from 0 inside their arrays at line %d')
-
-
-def _sig_tensor(what, name, t, dtype, dim, device=None):
-    if not isinstance(t, torch.Tensor):
-        raise TkrError('%s: %s must be a tensor' % (what, name))
-    if t.dtype != dtype or t.dim() != dim or not t.is_contiguous():
-        raise TkrError('%s: %s must be a contiguous %d-dimensional %s tensor' % (what, name, dim, dtype))
-    if not t.is_cuda or (device is not None and t.device != device):
-        raise TkrError('%s: %s must live on the GPU%s, not on %s' % (what, name, '' if device is None else ' that holds ranks', t.device))
 
 
 def line_metrics(ranks, like_ptr, rated_ptr, n_cols, step, total, gain, ideal):
@@ -1762,10 +1712,10 @@ def line_metrics(ranks, like_ptr, rated_ptr, n_cols, step, total, gain, ideal):
     significance.columns).  ranks int32 [n_likes] as tkr_hip.like_ranks returns them, like_ptr / rated_ptr int64 [n_lines + 1], gain
     float64 [total], ideal float64 [total + 1], all on one GPU.  Ranks or pointers that cannot come from K8 raise TkrError"""
     what = 'line_metrics'
-    _sig_tensor(what, 'ranks', ranks, torch.int32, 1)
+    _operand(what, 'ranks', ranks, torch.int32, 1)
     for name, t, dtype in (('like_ptr', like_ptr, torch.int64), ('rated_ptr', rated_ptr, torch.int64), ('gain', gain, torch.float64),
                            ('ideal', ideal, torch.float64)):
-        _sig_tensor(what, name, t, dtype, 1, ranks.device)
+        _operand(what, name, t, dtype, 1, on=ranks.device)
     n_cols, step, total = int(n_cols), int(step), int(total)
     n_lines = int(like_ptr.numel()) - 1
     if n_lines < 0 or rated_ptr.numel() != n_lines + 1:
@@ -1782,9 +1732,7 @@ def line_metrics(ranks, like_ptr, rated_ptr, n_cols, step, total, gain, ideal):
     status = torch.empty(1, dtype=torch.int64, device=ranks.device)
     _call('tkr_line_metrics', ranks, _p(ranks) if ranks.numel() else C.c_void_p(0), C.c_int64(ranks.numel()), _p(like_ptr), _p(rated_ptr),
           C.c_int64(n_lines), C.c_int32(n_cols), C.c_int32(step), C.c_int32(total), _p(gain), _p(ideal), _p(X), _p(status))
-    word = int(status.item())
-    if word != -1:
-        raise TkrError('%s: %s' % (what, _LINE_REFUSED[word & 3] % (word >> 2)))
+    status_check(what, _LINE_REFUSED, TkrError, int(status.item()))
     return X
 
 
@@ -1798,7 +1746,7 @@ def bootstrap_sums(X, R, seed, pad=True):
     replacement, the draw a function of (seed, r, n) alone (include/tkr.h tkr_bootstrap_sums).  Bitwise repeatable.  pad: gather from
     a copy of X at a row pitch of whole cache lines (boot_pitch: faster, the same bits; one more table in memory)"""
     what = 'bootstrap_sums'
-    _sig_tensor(what, 'X', X, torch.float64, 2)
+    _operand(what, 'X', X, torch.float64, 2)
     n, width = int(X.shape[0]), int(X.shape[1])
     R, seed = int(R), int(seed)
     if not 1 <= width <= BOOT_MAX_COLUMNS:
