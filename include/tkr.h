@@ -1157,6 +1157,63 @@ int tkr_lmf_step_rows(const float* Y, int32_t n_y, int32_t k, const float* D, co
                       int64_t n_x, int32_t fixed, double alpha, double lam, double lr, int64_t heavy_from, float* X, float* H, double* row_loss,
                       void* workspace, int64_t workspace_bytes, int64_t* status, void* stream);
 
+/* ---- K26: a sparse x dense product, and CER's E-step by conjugate gradients on it (csrc/sparse.hip) ------------------------------------------
+ * The opt-in estep='cg' of top-k-rec_amd/als.py: the content features stay a CSR on the device, nothing of size
+ * d x d or n_items x d is formed.  1 <= k <= TKR_ALS_CG_MAX_K (wider: TKR_E_UNSUPPORTED).
+ *
+ *   tkr_csr_spmm        A: a CSR of n_rows x n_cols, ptr int64 [n_rows + 1] from 0, col int32 [nnz], val fp32 [nnz]; X fp32 [n_cols, k];
+ *                       Z fp32 [n_rows, k] or NULL; out fp32 [n_rows, k], overlapping neither X nor Z.
+ *                         out[r][c] = fp32(alpha * s + beta * Z[r][c]),  s = sum over the row's nonzeros e of val[e] * X[col[e]][c]
+ *                       (without Z: fp32(alpha * s)); the products and the sum in float64, rounded ONCE.  A row of at most heavy_from
+ *                       nonzeros (>= 1): s is ONE fp32 chain per component, s = fma(val[e], X[col[e]][c], s) over its nonzeros in stored
+ *                       order from +0.0.  A longer row goes to one workgroup in a second launch: it is cut into slabs of TKR_SPMM_SLAB
+ *                       nonzeros in stored order, each slab is that chain, and s is the slab sums added in ascending slab order in
+ *                       float64.  A row's bits depend on its own nonzeros, the rows of X they name, Z[r], alpha, beta and heavy_from:
+ *                       not on n_rows, on the other rows or on the run.  A row is owned by 8, 16, 32 or 64 lanes (k <= 8, 16, 32, more),
+ *                       so narrow tables put several rows on a wave; the rows of X are gathered 16 at a time (8 at k <= 8 and above
+ *                       k = 128, 4 above k = 256) ahead of
+ *                       the chain, which takes them one by one.  A column named twice counts twice.
+ *                       status: -1, or the smallest 4 * r + kind: 0 -- row r holds a column outside [0, n_cols) (never used as an index);
+ *                       1 -- it holds a value that is not finite; 3 -- ptr does not start at 0, descends at row r, leaves [0, nnz] or
+ *                       gives the row 2^31 nonzeros or more.  A refused row of out is NOT written; the other rows are.
+ *                       workspace: 16-byte aligned, tkr_csr_spmm_workspace_bytes(n_rows) bytes; may be NULL when heavy_from >= nnz.
+ *   tkr_estep_cg        F: the CSR (f_ptr, f_col, f_val) of n_items x d; its transpose (t_ptr, t_col, t_val) of d x n_items, the same nnz;
+ *                       both canonical (ascending columns, no duplicates -- not checked: the result is what the stored order gives).
+ *                       V fp32 [n_items, k]; E fp32 [d, k], in and out.  `steps` (>= 1) steps of conjugate gradients on
+ *                       (lv F^T F + le I) E = lv F^T V from the E given, lv, le > 0, the k columns side by side:
+ *                         B = lv F^T V;  R = B - (lv F^T (F E) + le E);  P = R;  rho_c = R_c . R_c
+ *                         `steps` times, in the columns with rho_c >= 1e-20:  T = F P;  Q = lv F^T T + le P;  alpha_c = rho_c / (P_c . Q_c);
+ *                           E_c = fma(alpha_c, P_c, E_c);  R_c = fma(-alpha_c, Q_c, R_c);  rho'_c = R_c . R_c;
+ *                           P_c = fma(rho'_c / rho_c, P_c, R_c);  rho_c = rho'_c
+ *                       Every product is tkr_csr_spmm (lv F^T T + le P is one: alpha = lv, beta = le, Z = P); R = B - W is an fp32
+ *                       subtraction; the divisions are IEEE fp32.  A dot product of column c is ONE tree: the d rows are cut into slabs
+ *                       of TKR_ESTEP_SLAB rows, a slab into 16 runs of 64 rows; a run is an fma chain from +0.0 over its rows in ascending
+ *                       order, the 16 run sums are added in ascending order in fp32 (a run past d is +0.0), and the slabs' partials are
+ *                       added in ascending slab order in float64 and rounded once.  alpha, beta and rho stay on the device.
+ *                       status: -1, or the smallest 4 * where + kind.  Of the input: kinds 0, 1, 3 of tkr_csr_spmm with where = the row
+ *                       of F, or n_items + the row of F^T; kind 1 also for row `where` of V holding a value that is not finite.  Any of
+ *                       these: E is left as it came in, all of it.  Of the recurrence: 4 * c + 2 -- P_c . Q_c is not positive and
+ *                       finite at some step: column c of E is left as it came in, the other columns are solved.
+ *                       workspace: 16-byte aligned, tkr_estep_cg_workspace_bytes(n_items, d, k) bytes: T, five tables of E's shape
+ *                       (B, R, P, Q and the E being built), two [slabs, k] tables of partials, the list of heavy rows.
+ * The input is not trusted: nothing refused is ever used as an index.  Arguments are checked before any device access and before any
+ * launch (TKR_E_INVAL): a null or misaligned pointer (floats and col 4, ptr / status 8, workspace 16), a null col or val with nnz > 0,
+ * n_rows / n_cols / n_items / d < 1 or >= 2^31, nnz < 0, heavy_from < 1, steps < 1, lv or le not positive and finite, alpha or beta
+ * not finite, a workspace too small.  tkr_estep_cg and its size call: n_items * k or d * k above (2^31 - 1) * 256 - 255 elements (a table
+ * of 2 TB: the one-thread-per-element launches would leave the grid) is TKR_E_UNSUPPORTED.  No float atomics: the atomics are the
+ * status word's minimum and the integer counter of the list of heavy rows, whose order changes no result. */
+#define TKR_SPMM_SLAB 256        /* nonzeros of a heavy row one group of lanes sums as one chain */
+#define TKR_SPMM_HEAVY_FROM 2048 /* what the bindings pass for heavy_from by default */
+#define TKR_ESTEP_SLAB 1024      /* rows of E whose part of a dot product is one fp32 partial */
+int64_t tkr_csr_spmm_workspace_bytes(int64_t n_rows);
+int tkr_csr_spmm(const int64_t* ptr, const int32_t* col, const float* val, int64_t nnz, int64_t n_rows, int32_t n_cols, const float* X, int32_t k,
+                 double alpha, const float* Z, double beta, float* out, int64_t heavy_from, void* workspace, int64_t workspace_bytes,
+                 int64_t* status, void* stream);
+int64_t tkr_estep_cg_workspace_bytes(int64_t n_items, int64_t d, int32_t k);
+int tkr_estep_cg(const int64_t* f_ptr, const int32_t* f_col, const float* f_val, const int64_t* t_ptr, const int32_t* t_col, const float* t_val,
+                 int64_t nnz, int64_t n_items, int64_t d, const float* V, int32_t k, float* E, double lv, double le, int32_t steps,
+                 int64_t heavy_from, void* workspace, int64_t workspace_bytes, int64_t* status, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

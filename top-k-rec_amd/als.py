@@ -36,6 +36,11 @@ regression for E behind it:
     every item j:  (G_U + (a - b) sum_{u in L_j} u u^T + lv I) v = a sum_{u in L_j} u + lv Fe_j,  Fe = F E;  an item without likes too
     E = (lv F^T F + le I)^-1 (lv F^T V)
 
+``CER(k, d, ..., estep='cg', e_steps=8)`` (K26, csrc/sparse.hip) keeps the features sparse from the pickle to the device: feat is a
+canonical fp32 scipy.sparse.csr_matrix, F and F^T are CSRs on the GPU, Fe = F E is one sparse x dense product and the E-step takes
+e_steps steps of conjugate gradients on (lv F^T F + le I) E = lv F^T V from the E of the iteration before.  Nothing of size d x d or
+n_items x d exists, so d = 200,000 trains (cer_sparse_train_bytes).  The default, 'cholesky', is the dense path above with its bits.
+
 ``DPM`` (single/dpm.py:10-76) puts ``MLP`` (single/mlp.py), a dense network d -> 2000 -> 1000 -> k with sigmoid hidden layers, where CER
 has E: the prior of item j is encoder(f_j), and after every alternation the encoder takes one epoch of mini-batch RMSProp towards the
 item table:
@@ -307,6 +312,31 @@ def cer_train_bytes(n_users, n_items, k, d):
     return 8 * (d * d + n_items * d), 4 * k * (n_users + 2 * n_items + d)
 
 
+def cer_sparse_train_bytes(n_users, n_items, k, d, nnz):
+    """device bytes CER.train allocates under estep='cg' -> (sparse, tables, workspace): sparse = 16 nnz + 8 (n_items + d + 2), the CSR
+    of the features and of their transpose (int64 ptr, int32 col, fp32 val each); tables = 4 k (n_users + 2 n_items + d), U, V, Fe and E
+    in fp32; workspace = tkr_hip.estep_cg_workspace_bytes(n_items, d, k), the E-step's: T = F P [n_items, k], five tables of E's shape
+    (B, R, P, Q and the E being built), two [ceil(d / 1024), k] tables of dot-product partials and the list of heavy rows.  Nothing
+    grows with d^2 or n_items d"""
+    n_users, n_items, k, d, nnz = int(n_users), int(n_items), int(k), int(d), int(nnz)
+    return 16 * nnz + 8 * (n_items + d + 2), 4 * k * (n_users + 2 * n_items + d), tkr_hip.estep_cg_workspace_bytes(n_items, d, k)
+
+
+ESTEPS = ('cholesky', 'cg')
+ESTEP_HEAVY_FROM = 512      # the E-step's heavy_from: a row of F^T with more nonzeros gets a workgroup (scripts/time_cer_sparse.py; tkr_hip's default is 2,048)
+
+
+def canonical_csr(feat):
+    """a scipy.sparse matrix or a dense array -> the canonical fp32 scipy.sparse.csr_matrix of it: ascending columns, no duplicates, no
+    stored zeros (a copy: the argument is left as it is)"""
+    import scipy.sparse as ss
+    m = ss.csr_matrix(feat, dtype=np.float32, copy=True) if ss.issparse(feat) else ss.csr_matrix(np.asarray(feat, dtype=np.float32))
+    m.sum_duplicates()
+    m.eliminate_zeros()
+    m.sort_indices()
+    return m
+
+
 def _need_content(model, who):
     if model.feat is None:
         raise ValueError('%s: load_content_data() first' % who)
@@ -319,8 +349,14 @@ class CER(WMF):
     draws E standard normal fp32 [d, k] in train() when no final-E.dat was imported -- one seed fixes all three."""
 
     def __init__(self, k: int, d: int, lu: float = 0.01, lv: float = 10, le: float = 10e3, a: float = 1, b: float = 0.01, *,
-                 solver: str = 'cholesky', cg_steps: int = tkr_hip.ALS_CG_STEPS) -> None:
+                 solver: str = 'cholesky', cg_steps: int = tkr_hip.ALS_CG_STEPS, estep: str = 'cholesky', e_steps: int = tkr_hip.ESTEP_STEPS) -> None:
         super().__init__(k, lu, lv, a, b, solver=solver, cg_steps=cg_steps)
+        if estep not in ESTEPS:
+            raise ValueError("CER: estep = %r, 'cholesky' (a dense d x d factor, K21) and 'cg' (conjugate gradients on the sparse features, "
+                             'K26) are the ones there are' % (estep,))
+        if not isinstance(e_steps, (int, np.integer)) or isinstance(e_steps, bool) or e_steps < 1:
+            raise ValueError('CER: e_steps = %r must be an integer, at least 1' % (e_steps,))
+        self.estep, self.e_steps = estep, int(e_steps)
         if not isinstance(d, (int, np.integer)) or d < 1:
             raise ValueError('CER: d = %r, the width of the content features, must be a positive integer' % (d,))
         if not lv > 0:
@@ -339,6 +375,26 @@ class CER(WMF):
         self._rng.random((self.n_users, self.k), dtype=np.float32)
         self._rng.random((self.n_items, self.k), dtype=np.float32)
 
+    def load_content_data(self, content_file: str, iid_file: str) -> None:
+        """estep='cg': the features stay sparse -- self.feat is the canonical fp32 scipy.sparse.csr_matrix [n_items, d] with the rows
+        placed at the model's item indices as the dense loader places them (a dense pickle is converted; for a sparse one nothing of
+        size n_items x d is allocated).  estep='cholesky': REC's dense loader, as it is"""
+        if self.estep != 'cg':
+            return super().load_content_data(content_file, iid_file)
+        import pickle
+        import scipy.sparse as ss
+        tprint('Load content data from %s' % (content_file))
+        feature_ids = get_id_dict_from_file(iid_file)
+        with open(content_file, 'rb') as fh:
+            raw = pickle.load(fh, encoding='latin1')
+        dst = np.asarray([idx for iid, idx in self.iids.items() if iid in feature_ids], dtype=np.int64)
+        src = [feature_ids[iid] for iid in self.iids if iid in feature_ids]
+        sub = (raw.tocsr()[src, :] if ss.issparse(raw) else ss.csr_matrix(np.asarray(raw)[src, :])).tocoo()
+        if sub.shape[1] != self.d:
+            raise ValueError('CER.load_content_data: %s holds features of width %d, the model needs d = %d' % (content_file, sub.shape[1], self.d))
+        self.feat = canonical_csr(ss.coo_matrix((sub.data, (dst[sub.row], sub.col)), shape=(self.n_items, self.d)))
+        tprint('Loading finished!')
+
     def _check_E(self, where):
         if np.shape(self.E) != (self.d, self.k):
             raise ValueError('%s: E has shape %s, the model needs (d, k) = (%d, %d)' % (where, np.shape(self.E), self.d, self.k))
@@ -354,6 +410,8 @@ class CER(WMF):
             self.E = self._rng.standard_normal((self.d, self.k), dtype=np.float32)
         self._check_E(who)
         device = foldin._device(device, who)
+        if self.estep == 'cg':
+            return self._prepare_sparse(who, device)
         dense, tables = cer_train_bytes(self.n_users, self.n_items, self.k, self.d)
         free = torch.cuda.mem_get_info(device)[0]
         if dense + tables > free:
@@ -365,25 +423,64 @@ class CER(WMF):
         FF = torch.addmm(torch.eye(self.d, dtype=torch.float64, device=device), F.t(), F, beta=self.le, alpha=self.lv)
         return types.SimpleNamespace(device=device, E=E, F=F, FF=torch.linalg.cholesky(FF))
 
+    def _prepare_sparse(self, who, device):
+        """estep='cg' (K26): F and F^T as CSRs on the device, the transpose taken once on the host; nothing of size d^2 or n_items d"""
+        feat = canonical_csr(self.feat)
+        sparse, tables, ws = cer_sparse_train_bytes(self.n_users, self.n_items, self.k, self.d, feat.nnz)
+        free = torch.cuda.mem_get_info(device)[0]
+        if sparse + tables + ws > free:
+            raise ValueError('%s: the two CSRs of the features need %d bytes (nnz = %d), the tables %d and the E-step %d; %d are free on %s'
+                             % (who, sparse, feat.nnz, tables, ws, free, device))
+        E = foldin._upload(np.ascontiguousarray(self.E, dtype=np.float32), device, np.float32)
+        return types.SimpleNamespace(device=device, E=E, F=tkr_hip.csr_upload(feat, device), Ft=tkr_hip.csr_upload(canonical_csr(feat.T), device),
+                                     ws=tkr_hip.workspace_room(None, ws, device))
+
+    def _fe(self, run, check):
+        return tkr_hip.csr_spmm(run.F, run.E, workspace=run.ws, check=check)
+
     def _prior(self, run):
+        if self.estep == 'cg':
+            Fe, run.fe_status = self._fe(run, False)
+            return dict(prior=Fe, w_prior=self.lv)
         return dict(prior=(run.F @ run.E.double()).float(), w_prior=self.lv)
 
     def _after_steps(self, run):
+        if self.estep == 'cg':                                     # warm-started: run.E is the E of the iteration before
+            _, status = tkr_hip.estep_cg(run.F, run.Ft, run.V, run.E, lv=self.lv, le=self.le, steps=self.e_steps, heavy_from=ESTEP_HEAVY_FROM, workspace=run.ws,
+                                         check=False)
+            return 0.5 * self.le * run.E.double().square().sum(), [run.fe_status, status]
         run.E = torch.cholesky_solve(self.lv * (run.F.t() @ run.V.double()), run.FF).float()
         return 0.5 * self.le * run.E.double().square().sum(), []      # cer.py:63-65: the new E beside the Fe that entered the solve
 
     LOGS_CONVERGE = False
 
+    def _check_iteration(self, who, it, loss, words):
+        if self.estep == 'cg':
+            tkr_hip.status_check('the prior F E of iteration %d' % it, tkr_hip._SPMM_REFUSED, tkr_hip.EstepRefused, int(words[0]))
+            tkr_hip.status_check('the E-step of iteration %d' % it, tkr_hip._ESTEP_REFUSED, tkr_hip.EstepRefused, int(words[1]))
+
     def _cold_rows(self, run):                                     # cer.py:70-73: an item without a training like gets its content's row
         self.E = run.E.cpu().numpy()
+        if self.estep == 'cg':
+            return self._fe(run, True)
         return (run.F @ run.E.double()).float()
 
-    def embed_items(self, feat):
+    def embed_items(self, feat, device=None):
         """fp32 [m, d] content features -> fp32 [m, k] = feat E, the fp64 product rounded once: the row of an item that was no line of
-        vid, by the rule train() gives an item without a training like"""
+        vid, by the rule train() gives an item without a training like.  A scipy.sparse matrix stays sparse: feat E is one
+        tkr_hip.csr_spmm on the GPU (`device`: None = the current one), a row the fp32 chain over its nonzeros in column order"""
         if self.E is None:
             raise ValueError('CER.embed_items: train() or import_embeddings() first')
         self._check_E('CER.embed_items')
+        import scipy.sparse as ss
+        if ss.issparse(feat):
+            if feat.shape[1] != self.d:
+                raise ValueError('CER.embed_items: feat has shape %s, the model needs (m, %d)' % (feat.shape, self.d))
+            if feat.shape[0] == 0:
+                return np.zeros((0, self.k), dtype=np.float32)
+            device = foldin._device(device, 'CER.embed_items')
+            E = foldin._upload(np.ascontiguousarray(self.E, dtype=np.float32), device, np.float32)
+            return tkr_hip.csr_spmm(tkr_hip.csr_upload(canonical_csr(feat), device), E).cpu().numpy()
         feat = np.asarray(feat, dtype=np.float32)
         if feat.ndim != 2 or feat.shape[1] != self.d:
             raise ValueError('CER.embed_items: feat has shape %s, the model needs (m, %d)' % (feat.shape, self.d))

@@ -91,11 +91,11 @@ EXPORTS = ('tkr_version', 'tkr_plan_team', 'tkr_plan_max_blocks', 'tkr_sample_pl
            'tkr_compact_rows_emit_dev', 'tkr_fusion_features', 'tkr_fusion_sgd', 'tkr_fusion_user_weights', 'tkr_fusion_svm_sums',
            'tkr_mmr_select', 'tkr_list_pair_sums', 'tkr_line_metrics', 'tkr_bootstrap_sums', 'tkr_nearest_anchors', 'tkr_als_gram',
            'tkr_als_solve_rows', 'tkr_als_solve_rows_prior', 'tkr_mlp_forward', 'tkr_mlp_fit', 'tkr_als_cg_rows', 'tkr_als_gram_wide',
-           'tkr_lmf_dense_rows', 'tkr_lmf_step_rows')
+           'tkr_lmf_dense_rows', 'tkr_lmf_step_rows', 'tkr_csr_spmm', 'tkr_estep_cg')
 EXPORTS_I64 = ('tkr_vbpr_workspace_floats', 'tkr_vbpr_colplan_lds_bytes', 'tkr_topk_workspace_bytes_for', 'tkr_topk_workspace_bytes', 'tkr_plan_workspace_bytes', 'tkr_like_ranks_workspace_bytes',
                'tkr_parse_dev_workspace_bytes', 'tkr_idtable_slots', 'tkr_scan_dev_workspace_bytes', 'tkr_als_workspace_bytes',
                'tkr_als_prior_workspace_bytes', 'tkr_mlp_workspace_bytes', 'tkr_fusion_svm_partial_bytes', 'tkr_als_cg_workspace_bytes',
-               'tkr_als_gram_wide_workspace_bytes', 'tkr_lmf_workspace_bytes')
+               'tkr_als_gram_wide_workspace_bytes', 'tkr_lmf_workspace_bytes', 'tkr_csr_spmm_workspace_bytes', 'tkr_estep_cg_workspace_bytes')
 
 
 def lib():
@@ -1588,6 +1588,138 @@ def lmf_step_rows(Y, D, like_ptr, like_cols, X, H, *, fixed, alpha, lam, lr, hea
           C.c_int64(n_likes), C.c_int64(n_x), C.c_int32(fixed), C.c_double(alpha), C.c_double(lam), C.c_double(lr), C.c_int64(heavy_from), _p(X),
           _p(H), _p(loss), _p(workspace), C.c_int64(workspace.numel() * workspace.element_size()), _p(status))
     return _done(what, loss, status, check, _LMF_REFUSED, LmfRefused)
+
+
+# ---- K26: a sparse x dense product and CER's E-step by conjugate gradients (csrc/sparse.hip) ------------------------------------------------
+SPMM_SLAB = 256              # TKR_SPMM_SLAB of include/tkr.h: the nonzeros of a heavy row summed as one chain
+SPMM_HEAVY_FROM = 2048       # TKR_SPMM_HEAVY_FROM: a row with more nonzeros than this is summed by a whole workgroup
+SPMM_NO_HEAVY = 1 << 62      # heavy_from: no row is heavy
+ESTEP_SLAB = 1024            # TKR_ESTEP_SLAB: the rows of E whose part of a dot product is one fp32 partial
+ESTEP_STEPS = 8              # the steps per E-step als.py takes by default
+_SPMM_REFUSED = ('row %d holds a column outside [0, n_cols) (kind 0)', 'row %d holds a value that is not finite (kind 1)', None,
+                 'ptr does not start at 0, decreases or leaves [0, nnz] at row %d (kind 3)')
+_ESTEP_REFUSED = ('row %d of F (from n_items on: row - n_items of F^T) holds a column outside the matrix (kind 0)',
+                  'row %d of F (from n_items on: row - n_items of F^T), or that row of V, holds a value that is not finite (kind 1)',
+                  'p.q of column %d of E is not positive and finite: the column keeps the value it came in with (kind 2)',
+                  'ptr does not start at 0, decreases or leaves [0, nnz] at row %d of F (from n_items on: row - n_items of F^T) (kind 3)')
+
+
+class EstepRefused(TkrError):
+    """a status word of K26 that is not -1; .word, .row and .kind say what it holds (include/tkr.h; raised by status_check)"""
+
+
+class Csr:
+    """a CSR matrix on one GPU: ptr int64 [n_rows + 1], col int32 [nnz], val fp32 [nnz], shape (n_rows, n_cols)"""
+    __slots__ = ('ptr', 'col', 'val', 'shape')
+
+    def __init__(self, ptr, col, val, shape):
+        self.ptr, self.col, self.val, self.shape = ptr, col, val, (int(shape[0]), int(shape[1]))
+
+    @property
+    def nnz(self):
+        return int(self.col.numel())
+
+    @property
+    def device(self):
+        return self.ptr.device
+
+
+def csr_upload(matrix, device):
+    """a scipy.sparse matrix (any format, any dtype) -> Csr on `device`, as the matrix stores it once it is a CSR"""
+    import numpy as np
+    m = matrix.tocsr()
+    up = lambda a, dt: torch.from_numpy(np.ascontiguousarray(a, dtype=dt)).to(device)
+    return Csr(up(m.indptr, np.int64), up(m.indices, np.int32), up(m.data, np.float32), m.shape)
+
+
+def _csr(what, name, A):
+    if not isinstance(A, Csr):
+        raise TypeError('%s: %s must be a tkr_hip.Csr (csr_upload makes one of a scipy matrix)' % (what, name))
+    n_rows, n_cols = A.shape
+    if n_rows < 1 or n_cols < 1:
+        raise ValueError('%s: %s has shape %s' % (what, name, A.shape))
+    _operand(what, name + '.ptr', A.ptr, torch.int64, 1, numel=n_rows + 1, raises=_STD)
+    _operand(what, name + '.col', A.col, torch.int32, 1, on=A.ptr.device, raises=_STD)
+    _operand(what, name + '.val', A.val, torch.float32, 1, numel=A.nnz, on=A.ptr.device, raises=_STD)
+    return n_rows, n_cols
+
+
+def _spmm_table(what, name, t, rows, k, device):
+    _operand(what, name, t, torch.float32, 2, on=device)
+    if tuple(t.shape) != (rows, k):
+        raise TkrError('%s: %s has shape %s, the call needs (%d, %d)' % (what, name, tuple(t.shape), rows, k))
+
+
+def _heavy_from(what, heavy_from):
+    heavy_from = SPMM_HEAVY_FROM if heavy_from is None else heavy_from
+    if not isinstance(heavy_from, int) or isinstance(heavy_from, bool) or heavy_from < 1:
+        raise ValueError('%s: heavy_from = %r must be an integer, at least 1' % (what, heavy_from))
+    return heavy_from
+
+
+def csr_spmm_workspace_bytes(n_rows):
+    return _size('tkr_csr_spmm_workspace_bytes', (C.c_int64,), (n_rows,))
+
+
+def csr_spmm(A, X, *, alpha=1.0, Z=None, beta=0.0, heavy_from=None, workspace=None, out=None, check=True):
+    """K26 -> out fp32 [n_rows, k] on the device: out[r] = alpha * sum over row r's nonzeros of val * X[col] (+ beta * Z[r]), one fma
+    chain per component in stored order, rounded once (include/tkr.h tkr_csr_spmm).  A: a Csr; X fp32 [n_cols, k], 1 <= k <=
+    ALS_CG_MAX_K; Z fp32 [n_rows, k] or None.  heavy_from: None = SPMM_HEAVY_FROM.  A refusal raises EstepRefused naming row and kind
+    (the refused row of out is not written); check=False returns (out, status tensor) instead and reads nothing back"""
+    what = 'csr_spmm'
+    n_rows, n_cols = _csr(what, 'A', A)
+    _operand(what, 'X', X, torch.float32, 2, on=A.device)
+    k = int(X.shape[1])
+    if X.shape[0] != n_cols:
+        raise TkrError('%s: X has shape %s, A has %d columns' % (what, tuple(X.shape), n_cols))
+    if not 1 <= k <= ALS_CG_MAX_K:
+        raise ValueError('%s: k = %d, 1 <= k <= %d is supported' % (what, k, ALS_CG_MAX_K))
+    if Z is not None:
+        _spmm_table(what, 'Z', Z, n_rows, k, A.device)
+    if out is None:
+        out = torch.empty((n_rows, k), dtype=torch.float32, device=A.device)
+    _spmm_table(what, 'out', out, n_rows, k, A.device)
+    heavy_from = _heavy_from(what, heavy_from)
+    workspace = workspace_room(workspace, csr_spmm_workspace_bytes(n_rows) if heavy_from < A.nnz else 0, A.device)
+    status = torch.empty(1, dtype=torch.int64, device=A.device)
+    _call('tkr_csr_spmm', X, _p(A.ptr), _p(A.col) if A.nnz else C.c_void_p(0), _p(A.val) if A.nnz else C.c_void_p(0), C.c_int64(A.nnz),
+          C.c_int64(n_rows), C.c_int32(n_cols), _p(X), C.c_int32(k), C.c_double(alpha), _p(Z), C.c_double(beta), _p(out), C.c_int64(heavy_from),
+          _p(workspace), C.c_int64(workspace.numel() * workspace.element_size()), _p(status))
+    return _done(what, out, status, check, _SPMM_REFUSED, EstepRefused)
+
+
+def estep_cg_workspace_bytes(n_items, d, k):
+    return _size('tkr_estep_cg_workspace_bytes', (C.c_int64, C.c_int64, C.c_int32), (n_items, d, k))
+
+
+def estep_cg(F, Ft, V, E, *, lv, le, steps=ESTEP_STEPS, heavy_from=None, workspace=None, check=True):
+    """K26, in place on E fp32 [d, k]: `steps` steps of conjugate gradients on (lv F^T F + le I) E = lv F^T V from the value E holds
+    (include/tkr.h tkr_estep_cg).  F: the Csr of the features [n_items, d]; Ft: the Csr of its transpose; both canonical.  V fp32
+    [n_items, k].  -> E.  A refusal raises EstepRefused naming what and where (of the input: E is untouched; of a column: that column
+    is); check=False returns (E, status tensor) instead and reads nothing back"""
+    what = 'estep_cg'
+    n_items, d = _csr(what, 'F', F)
+    if _csr(what, 'Ft', Ft) != (d, n_items) or Ft.nnz != F.nnz or Ft.device != F.device:
+        raise TkrError('%s: Ft must be the transpose of F, %d x %d with %d nonzeros, on the same GPU' % (what, d, n_items, F.nnz))
+    _operand(what, 'V', V, torch.float32, 2, on=F.device)
+    k = int(V.shape[1])
+    if V.shape[0] != n_items:
+        raise TkrError('%s: V has shape %s, F has %d rows' % (what, tuple(V.shape), n_items))
+    if not 1 <= k <= ALS_CG_MAX_K:
+        raise ValueError('%s: k = %d, 1 <= k <= %d is supported' % (what, k, ALS_CG_MAX_K))
+    _spmm_table(what, 'E', E, d, k, F.device)
+    if not isinstance(steps, int) or isinstance(steps, bool) or steps < 1:
+        raise ValueError('%s: steps = %r must be an integer, at least 1' % (what, steps))
+    if not (0 < lv < float('inf') and 0 < le < float('inf')):
+        raise ValueError('%s: lv = %r and le = %r must be positive and finite' % (what, lv, le))
+    heavy_from = _heavy_from(what, heavy_from)
+    workspace = workspace_room(workspace, estep_cg_workspace_bytes(n_items, d, k), F.device)
+    status = torch.empty(1, dtype=torch.int64, device=F.device)
+    nil = C.c_void_p(0)
+    _call('tkr_estep_cg', V, _p(F.ptr), _p(F.col) if F.nnz else nil, _p(F.val) if F.nnz else nil, _p(Ft.ptr), _p(Ft.col) if F.nnz else nil,
+          _p(Ft.val) if F.nnz else nil, C.c_int64(F.nnz), C.c_int64(n_items), C.c_int64(d), _p(V), C.c_int32(k), _p(E), C.c_double(lv),
+          C.c_double(le), C.c_int32(steps), C.c_int64(heavy_from), _p(workspace), C.c_int64(workspace.numel() * workspace.element_size()), _p(status))
+    return _done(what, E, status, check, _ESTEP_REFUSED, EstepRefused)
 
 
 # ---- K22: a dense MLP content encoder, applied and trained (csrc/mlp.hip) ------------------------------------------------------------------

@@ -3,6 +3,7 @@
     cd top-k-rec_amd && python train_als.py -d data -o embed/wmf -k 50 --iters 200 --tol 1e-4
     cd top-k-rec_amd && python train_als.py -d data -o embed/wmf256 -k 256 --solver cg --cg-steps 3
     cd top-k-rec_amd && python train_als.py --model cer --content data/meta.pkl --dim 20000 -d data -o embed/cer -k 50
+    cd top-k-rec_amd && python train_als.py --model cer --estep cg --e-steps 8 --content data/meta.pkl --dim 200000 -d data -o embed/cer -k 50
     cd top-k-rec_amd && python train_als.py --model dpm --content data/meta.pkl --dim 20000 -d data -o embed/dpm -k 50 --hidden 2000 1000
 
 reads DATA/uid, DATA/vid and DATA/f<FOLD>tr.txt, trains als.WMF (or als.CER / als.DPM, with the pickled content features of --content,
@@ -31,6 +32,9 @@ def main(argv=None):
     ap.add_argument('--content', default=None, metavar='FILE', help='cer, dpm: the pickled [n, d] content features (dense or scipy sparse)')
     ap.add_argument('--dim', type=int, default=None, metavar='D', help='cer, dpm: the width d of the content features')
     ap.add_argument('--le', type=float, default=10e3, help='cer: the ridge of the content projection E')
+    ap.add_argument('--estep', choices=('cholesky', 'cg'), default=None,
+                    help='cer: the E-step: a dense d x d Cholesky factor (K21, the default), or conjugate gradients on the sparse features (K26)')
+    ap.add_argument('--e-steps', type=int, default=None, metavar='N', help='cer, --estep cg: steps of conjugate gradients per E-step (default 8)')
     ap.add_argument('--hidden', type=int, nargs='*', default=None, metavar='H', help="dpm: the encoder's hidden widths (default 2000 1000)")
     ap.add_argument('--mlp-lr', type=float, default=None, help="dpm: the encoder's RMSProp learning rate (default 1e-4)")
     ap.add_argument('--batch', type=int, default=None, help="dpm: the encoder's mini-batch, at most 256 (default 64)")
@@ -47,6 +51,10 @@ def main(argv=None):
         ap.error('--model %s needs --dim D, the width of the content features' % args.model)
     if not dpm and (args.hidden is not None or args.mlp_lr is not None or args.batch is not None or args.mlp_seed is not None):
         ap.error('--hidden, --mlp-lr, --batch and --mlp-seed go with --model dpm')
+    if not cer and (args.estep is not None or args.e_steps is not None):
+        ap.error('--estep and --e-steps go with --model cer: the E-step is the ridge regression of its content projection')
+    if args.e_steps is not None and args.estep != 'cg':
+        ap.error('--e-steps N goes with --estep cg')
     lv = args.lv if args.lv is not None else (10.0 if cer or dpm else 0.01)
     encoder, batch = None, 64 if args.batch is None else args.batch
     how = dict(solver=args.solver, cg_steps=args.cg_steps)
@@ -58,6 +66,10 @@ def main(argv=None):
             encoder = MLP(args.k, args.dim, lr=1e-4 if args.mlp_lr is None else args.mlp_lr, hidden_layers=(2000, 1000) if args.hidden is None else args.hidden,
                           seed=args.seed if args.mlp_seed is None else args.mlp_seed)
         elif cer:
+            if args.estep is not None:
+                how['estep'] = args.estep
+            if args.e_steps is not None:
+                how['e_steps'] = args.e_steps
             model = CER(k=args.k, d=args.dim, lu=args.lu, lv=lv, le=args.le, a=args.a, b=args.b, **how)
         else:
             model = WMF(k=args.k, lu=args.lu, lv=lv, a=args.a, b=args.b, **how)
