@@ -31,7 +31,7 @@
 extern "C" {
 #endif
 
-#define TKR_VERSION 120 /* (additions that change no existing entry point keep the number: K10 tkr_bpr_foldin_items, K11 tkr_ratings_*_dev, K12 tkr_rank_candidates, K13 tkr_lists_format_* / tkr_matrix_format_*, K15 tkr_group_*_dev / tkr_last_line_of_user_dev / tkr_compact_rows_*_dev, K16 tkr_fusion_*, K17 tkr_mmr_select / tkr_list_pair_sums, K21 tkr_als_solve_rows_prior / tkr_als_prior_workspace_bytes, K22 tkr_mlp_forward / tkr_mlp_fit / tkr_mlp_workspace_bytes.) 0.1.20: K9 tkr_bpr_foldin (user vectors for new histories against frozen item factors; csrc/foldin.hip). 0.1.19: K8 tkr_like_ranks + tkr_like_ranks_workspace_bytes (filtered rank of every liked test column; csrc/like_ranks.hip). 0.1.18: K4 second form of bound-and-refine (csrc/topk_refine.hip; tkr_topk_workspace_bytes_for grows by the pieces' packed lists), any k (bpr_wide_kernel, score_topk_wide_kernel), tkr_lab_build; tkr_topk_set_finish is gone, tkr_topk_set_math(0) and tkr_vbpr_set_pairs(1 | 2) need the lab library. 0.1.17: tkr_vbpr_set_pairs (tkr_vbpr_workspace_floats + 64). 0.1.16: tkr_topk_set_finish (larger tkr_topk_workspace_bytes), tkr_bpr_own_plan_run plans inside the step's launch. 0.1.15: tkr_bpr_own_owners_shared; tkr_bpr_run takes `rec` non-const. 0.1.14: per-task loss sums instead of atomics on loss_out (larger tkr_vbpr_workspace_floats; K2 writes word 15 of its records). 0.1.13: tkr_bpr_own_plan_run, K4 to k = 768. 0.1.12: tkr_bpr_own_run_between. 0.1.11: K2o (tkr_sample_plan_owned, tkr_bpr_own_run: item rows owned by one workgroup each, resident in its LDS); prec[5] = last batch of the call that updated the row. 0.1.10: tkr_topk_workspace_bytes_for (K4 stages pre-converted fp16 tiles). 0.1.9: tkr_vbpr_colplan + tkr_vbpr_run_cols (VBPR in three launches per batch). 0.1.8: tkr_sync_flow_* (exchange of the granule tables). 0.1.7: K4 bound-and-refine arithmetic (tkr_topk_set_math(2), the default; larger tkr_topk_workspace_bytes); K2f leaves its ticket words zero. 0.1.6: K2f persistent dataflow step, tkr_plan_rollback, batches above 8192 */
+#define TKR_VERSION 120 /* (additions that change no existing entry point keep the number: K10 tkr_bpr_foldin_items, K11 tkr_ratings_*_dev, K12 tkr_rank_candidates, K13 tkr_lists_format_* / tkr_matrix_format_*, K15 tkr_group_*_dev / tkr_last_line_of_user_dev / tkr_compact_rows_*_dev, K16 tkr_fusion_*, K17 tkr_mmr_select / tkr_list_pair_sums, K21 tkr_als_solve_rows_prior / tkr_als_prior_workspace_bytes, K22 tkr_mlp_forward / tkr_mlp_fit / tkr_mlp_workspace_bytes, K27 tkr_smf_lse_rows / tkr_smf_dense_rows / tkr_smf_step_rows / tkr_smf_workspace_bytes.) 0.1.20: K9 tkr_bpr_foldin (user vectors for new histories against frozen item factors; csrc/foldin.hip). 0.1.19: K8 tkr_like_ranks + tkr_like_ranks_workspace_bytes (filtered rank of every liked test column; csrc/like_ranks.hip). 0.1.18: K4 second form of bound-and-refine (csrc/topk_refine.hip; tkr_topk_workspace_bytes_for grows by the pieces' packed lists), any k (bpr_wide_kernel, score_topk_wide_kernel), tkr_lab_build; tkr_topk_set_finish is gone, tkr_topk_set_math(0) and tkr_vbpr_set_pairs(1 | 2) need the lab library. 0.1.17: tkr_vbpr_set_pairs (tkr_vbpr_workspace_floats + 64). 0.1.16: tkr_topk_set_finish (larger tkr_topk_workspace_bytes), tkr_bpr_own_plan_run plans inside the step's launch. 0.1.15: tkr_bpr_own_owners_shared; tkr_bpr_run takes `rec` non-const. 0.1.14: per-task loss sums instead of atomics on loss_out (larger tkr_vbpr_workspace_floats; K2 writes word 15 of its records). 0.1.13: tkr_bpr_own_plan_run, K4 to k = 768. 0.1.12: tkr_bpr_own_run_between. 0.1.11: K2o (tkr_sample_plan_owned, tkr_bpr_own_run: item rows owned by one workgroup each, resident in its LDS); prec[5] = last batch of the call that updated the row. 0.1.10: tkr_topk_workspace_bytes_for (K4 stages pre-converted fp16 tiles). 0.1.9: tkr_vbpr_colplan + tkr_vbpr_run_cols (VBPR in three launches per batch). 0.1.8: tkr_sync_flow_* (exchange of the granule tables). 0.1.7: K4 bound-and-refine arithmetic (tkr_topk_set_math(2), the default; larger tkr_topk_workspace_bytes); K2f leaves its ticket words zero. 0.1.6: K2f persistent dataflow step, tkr_plan_rollback, batches above 8192 */
 #define TKR_OK 0
 #define TKR_E_INVAL (-1)
 #define TKR_E_UNSUPPORTED (-2)
@@ -1213,6 +1213,58 @@ int64_t tkr_estep_cg_workspace_bytes(int64_t n_items, int64_t d, int32_t k);
 int tkr_estep_cg(const int64_t* f_ptr, const int32_t* f_col, const float* f_val, const int64_t* t_ptr, const int32_t* t_col, const float* t_val,
                  int64_t nnz, int64_t n_items, int64_t d, const float* V, int32_t k, float* E, double lv, double le, int32_t steps,
                  int64_t heavy_from, void* workspace, int64_t workspace_bytes, int64_t* status, void* stream);
+
+/* ---- K27: the three parts of a softmax-matrix-factorisation half-step (csrc/smf.hip) --------------------------------------------------------
+ * Softmax MF (the multinomial likelihood of Mult-DAE / Mult-VAE; top-k-rec_amd/smf.py): p(i | u) =
+ * softmax_i(x_u . y_i + beta_i) over the WHOLE catalogue.  Tables are augmented to K = k + 1 columns -- a user row is [x, 1], an item row
+ * [y, beta_i] -- so a score is s_rc = X[r] . Y[c] over all K columns, one fp32 chain from +0.0 in column order;
+ * 1 <= k <= TKR_SMF_MAX_K (wider: TKR_E_UNSUPPORTED).  Y fp32 [n_y, K] is the table held fixed in a half-step, X fp32 [n_x, K] the one
+ * that moves.  No multiple-of-anything requirement on k.
+ *
+ *   tkr_smf_lse_rows    lse fp32 [n_x]: lse[r] = log sum over c = 0 .. n_y - 1 of exp(s_rc); finite at any finite scores (|s| = 1e4
+ *                       included).  K25's shape: a workgroup owns 128 rows of X (32 per wave, in registers) and one slab of TKR_SMF_SLAB
+ *                       rows of Y, walked in tiles of 32 rows in ascending order, S from v_mfma_f32_32x32x2_f32.  Per (row, slab) a pair
+ *                       (m, l = sum exp(s - m)): the rows c mod 8 < 4 of every tile and the others are followed apart, each by a running
+ *                       maximum -- a tile that raises it scales l by exp(m - m') first, then adds its scores' terms in ascending row
+ *                       order -- and joined at the slab's end: M = max(m0, m1), l = l0 exp(m0 - M) + l1 exp(m1 - M), all in fp32.  The
+ *                       slabs are joined in ascending order in fp64: M = max m, sum l exp(m - M), lse = fp32(M + log sum).
+ *                       workspace: 16-byte aligned, tkr_smf_workspace_bytes(n_x, k, n_y) bytes; may be NULL for n_y <= TKR_SMF_SLAB.
+ *   tkr_smf_dense_rows  row_off fp32 [n_x] or NULL, col_off fp32 [n_y] or NULL (a NULL offset is 0).  D fp32 [n_x, K]:
+ *                         D[r] = sum over c = 0 .. n_y - 1 of P_rc Y[c],   P_rc = exp(fl(fl(s_rc - row_off[r]) - col_off[c]))
+ *                       K25's dense kernel with this P in place of sigma: P goes from the accumulators into LDS in the A-operand layout,
+ *                       D += P Ytile runs on the same MFMA; a slab's partial of D[r][j] is ONE fp32 chain from +0.0 over the slab's rows
+ *                       in row order; the slabs are added in ascending order in fp64 and rounded once.  exp(+0.0) is exactly 1.0f,
+ *                       exp(-inf) exactly +0: an offset of +inf is legal and gives P = +0, whatever finite values that row of Y holds.
+ *                       s_rc has the bits tkr_smf_lse_rows formed for the same X and Y.  No status word: nothing here is an index.
+ *                       workspace: as above.
+ *   tkr_smf_step_rows   like_ptr, like_cols, heavy_from, the status word, the refusals (kinds 1 and 3) and the heavy rows are
+ *                       tkr_lmf_step_rows's: the same code (csrc/lmf_rows.h).  For EVERY row r, in place on X and its AdaGrad slot H:
+ *                         L = sum over the likes c of Y[c]                 (one fp32 chain per column from +0.0 in stored order)
+ *                         g = fp32(L - w * D[r] - lam * X[r])              (the three terms in fp64, rounded once;
+ *                                                                           w: the likes row r stores where scale_by_likes = 1, else 1)
+ *                         h' = fma(g, g, h);  x' = x + (lr * g) / sqrt(h')  (fp32, every operation rounded on its own)
+ *                         column `fixed` (-1 <= fixed < K; -1: none) is left out: X[r][fixed] and H[r][fixed] keep their bits
+ *                         row_loss[r] = -sum_likes s_rc + 1/2 lam * sum_{j != fixed} X[r][j]^2
+ *                                       (float64 [n_x], or NULL; at the X the call found; fp32 values added in fp64)
+ *                       A refused row (kind 3) keeps X and H, and its row_loss is 0.
+ *   tkr_smf_workspace_bytes  what any of the three calls needs at most (a multiple of 16), TKR_E_INVAL or TKR_E_UNSUPPORTED.
+ * A user half-step is lse, dense with row_off = lse, step with fixed = k and scale_by_likes = 1; an item half-step is dense with
+ * col_off[u] = lse_u - log n_u (+inf for a user without likes) and step with fixed = -1 and scale_by_likes = 0.
+ * Arguments are checked before any device access and before any launch (TKR_E_INVAL), the same things as K25: a null or misaligned
+ * pointer (floats 4, like_ptr / row_loss / status 8, workspace 16), a null like_cols with n_likes > 0, n_x / n_y < 1, n_x >= 2^31,
+ * n_likes < 0, heavy_from < 1, fixed outside [-1, K), scale_by_likes not 0 or 1, lam < 0, lam or lr not finite, a workspace too small.
+ * n_y above 65535 slabs: TKR_E_UNSUPPORTED.  No float atomics.  Bits are the same run to run, and the bits of row r depend on X[r], Y,
+ * the offsets and heavy_from only: not on n_x or on the other rows. */
+#define TKR_SMF_MAX_K 128
+#define TKR_SMF_SLAB 4096        /* rows of Y one workgroup of tkr_smf_lse_rows / tkr_smf_dense_rows walks */
+int64_t tkr_smf_workspace_bytes(int64_t n_x, int32_t k, int64_t n_y);
+int tkr_smf_lse_rows(const float* X, int64_t n_x, const float* Y, int64_t n_y, int32_t k, float* lse, void* workspace, int64_t workspace_bytes,
+                     void* stream);
+int tkr_smf_dense_rows(const float* X, int64_t n_x, const float* Y, int64_t n_y, int32_t k, const float* row_off, const float* col_off, float* D,
+                       void* workspace, int64_t workspace_bytes, void* stream);
+int tkr_smf_step_rows(const float* Y, int32_t n_y, int32_t k, const float* D, const int64_t* like_ptr, const int32_t* like_cols, int64_t n_likes,
+                      int64_t n_x, int32_t fixed, int32_t scale_by_likes, double lam, double lr, int64_t heavy_from, float* X, float* H,
+                      double* row_loss, void* workspace, int64_t workspace_bytes, int64_t* status, void* stream);
 
 #ifdef __cplusplus
 }

@@ -19,6 +19,7 @@
 //                           order; the two lanes of a row are added at the end.
 //   lmf_reduce_kernel       more than one slab: the partials are added in ascending slab order in fp64 and rounded once (K20's Gram
 //                           rule).  One slab: the dense kernel writes D and sp itself -- fp32 -> fp64 -> fp32 is the identity.
+// The two kernels of the step are csrc/lmf_rows.h's, in its mode kLmfLogistic (K27's step is the same code in another mode):
 //   lmf_step_kernel<NR>     one wave per row: the row, its slot and the gradient in registers (element j of the row in lane j & 63,
 //                           register j >> 6).  Whole rows of Y are gathered through L2, 64 like columns read at a time; per like the
 //                           score is one fixed tree (lane chains by fma from +0.0 over its registers, then the DPP tree of wave_sum),
@@ -28,7 +29,7 @@
 //                           summed by wave j mod 16 as the step kernel sums a row (an fp32 chain from +0.0), a wave adds its slabs in
 //                           ascending order in fp64, wave 0 adds the 16 waves in ascending order in fp64 and rounds once.
 // No float atomics; the atomics are the status word's minimum and the list's counter.  Nothing refused is used as an index.
-#include "lmf_parts.h"
+#include "lmf_rows.h"
 
 #include <math.h>
 
@@ -155,191 +156,7 @@ static int launch_dense(hipStream_t stream, dim3 grid, const float* X, long long
     return TKR_OK;
 }
 
-// ---- the per-row step ------------------------------------------------------------------------------------------------------------------
-// what a wave holds of a sum over likes: L (element j in lane j & 63, register j >> 6) and the two sums of the loss (the same in every lane)
-template <int NR>
-struct LmfSum {
-    float L[NR];
-    double sp, ss;
-};
-
-template <int NR>
-__device__ __forceinline__ void lmf_load_row(const float* __restrict__ row, int K, float (&v)[NR]) {
-    const int lane = threadIdx.x & 63;
-#pragma unroll
-    for (int j = 0; j < NR; ++j) v[j] = lane + 64 * j < K ? row[lane + 64 * j] : 0.f;
-}
-
-// the likes cols[first .. first + count) against the row x: an fp32 chain per component from +0.0 in stored order.  A column outside
-// [0, n_y) is skipped; -> whether one was.  Called by a whole wave with the same arguments.
-template <int NR>
-__device__ __forceinline__ bool lmf_like_chain(const float* __restrict__ Y, int n_y, int K, const int32_t* __restrict__ cols, long long first, int count,
-                                               const float (&x)[NR], LmfSum<NR>& sum) {
-    const int lane = threadIdx.x & 63;
-#pragma unroll
-    for (int j = 0; j < NR; ++j) sum.L[j] = 0.f;
-    sum.sp = sum.ss = 0.0;
-    bool skipped = false;
-    for (int base = 0; base < count; base += TKR_WAVE) {          // wave-uniform
-        const int n_here = min(TKR_WAVE, count - base);
-        int mine = -1;
-        if (lane < n_here) {
-            mine = cols[first + base + lane];
-            if ((uint32_t)mine >= (uint32_t)n_y) {
-                mine = -1;
-                skipped = true;
-            }
-        }
-        for (int i = 0; i < n_here; ++i) {
-            const int c = bcast_i(mine, i);
-            if (c < 0) continue;                                  // (uniform)
-            float y[NR];
-            lmf_load_row<NR>(Y + (size_t)c * K, K, y);
-            float d = 0.f;
-#pragma unroll
-            for (int j = 0; j < NR; ++j) d = fmaf(x[j], y[j], d);
-            const float s = wave_sum(d);
-            const float w = lmf_sigmoid(-s);                      // 1 - sigma(s)
-#pragma unroll
-            for (int j = 0; j < NR; ++j) sum.L[j] = fmaf(w, y[j], sum.L[j]);
-            sum.sp += (double)lmf_softplus(s);
-            sum.ss += (double)s;
-        }
-    }
-    return __ballot(skipped) != 0ull;
-}
-
-__device__ __forceinline__ double lmf_wave_sum_f64(double v) {    // a fixed tree: v += v(lane ^ 32), ^ 16, .. ^ 1
-#pragma unroll
-    for (int d = 32; d >= 1; d >>= 1) v += __shfl_xor(v, d);
-    return v;
-}
-
-// the gradient, AdaGrad in place and the row's loss terms; x: the row as it came in, sum: over its likes.  One wave.
-template <int NR>
-__device__ __forceinline__ void lmf_update_row(long long r, int K, int fixed, const float (&x)[NR], const LmfSum<NR>& sum, const float* __restrict__ D,
-                                               double alpha, double lam, float lr, float* __restrict__ X, float* __restrict__ H,
-                                               double* __restrict__ row_loss) {
-    const int lane = threadIdx.x & 63;
-    double sq = 0.0;
-#pragma unroll
-    for (int j = 0; j < NR; ++j) {
-        const int col = lane + 64 * j;
-        if (col < K && col != fixed) {
-            const size_t at = (size_t)r * K + col;
-            const float g = (float)(alpha * (double)sum.L[j] - (double)D[at] - lam * (double)x[j]);      // three terms in fp64, rounded once
-            const float hn = fmaf(g, g, H[at]);
-            H[at] = hn;
-            X[at] = x[j] + (lr * g) / sqrtf(hn);
-            sq += (double)x[j] * (double)x[j];
-        }
-    }
-    if (row_loss) {
-        sq = lmf_wave_sum_f64(sq);
-        if (lane == 0) row_loss[r] = alpha * sum.sp - alpha * sum.ss + 0.5 * lam * sq;
-    }
-}
-
-template <int NR>
-__global__ __launch_bounds__(kLmfBlock) void lmf_step_kernel(const float* __restrict__ Y, int n_y, int K, const float* __restrict__ D,
-                                                             const int64_t* __restrict__ like_ptr, const int32_t* __restrict__ like_cols,
-                                                             long long n_likes, long long n_x, int fixed, double alpha, double lam, float lr,
-                                                             long long heavy_from, float* __restrict__ X, float* __restrict__ H,
-                                                             double* __restrict__ row_loss, unsigned long long* __restrict__ status,
-                                                             int32_t* __restrict__ heavy_count, int32_t* __restrict__ heavy_list) {
-    const int lane = threadIdx.x & 63;
-    const long long r = (long long)blockIdx.x * kLmfWaves + (threadIdx.x >> 6);
-    if (r >= n_x) return;                                         // (wave-uniform, as every exit below: no barrier in this kernel)
-    const long long lo = like_ptr[r], hi = like_ptr[r + 1];
-    if (!als_ptr_ok(lo, hi, n_likes, r)) {
-        if (lane == 0) {
-            status_refuse(status, r, kAlsBadPtr);                 // the row is left as it is
-            if (row_loss) row_loss[r] = 0.0;
-        }
-        return;
-    }
-    if (hi - lo > heavy_from && heavy_list) {
-        if (lane == 0) heavy_list[atomicAdd(heavy_count, 1)] = (int32_t)r;
-        return;
-    }
-    float x[NR];
-    lmf_load_row<NR>(X + (size_t)r * K, K, x);
-    LmfSum<NR> sum;
-    if (lmf_like_chain<NR>(Y, n_y, K, like_cols, lo, (int)(hi - lo), x, sum) && lane == 0)
-        status_refuse(status, r, kAlsSkipped);
-    lmf_update_row<NR>(r, K, fixed, x, sum, D, alpha, lam, lr, X, H, row_loss);
-}
-
-template <int NR>
-__global__ __launch_bounds__(kLmfHeavyBlock) void lmf_heavy_kernel(const float* __restrict__ Y, int n_y, int K, const float* __restrict__ D,
-                                                                   const int64_t* __restrict__ like_ptr, const int32_t* __restrict__ like_cols,
-                                                                   int fixed, double alpha, double lam, float lr, float* __restrict__ X,
-                                                                   float* __restrict__ H, double* __restrict__ row_loss,
-                                                                   unsigned long long* __restrict__ status, const int32_t* __restrict__ heavy_count,
-                                                                   const int32_t* __restrict__ heavy_list) {
-    __shared__ double part[kLmfHeavyWaves][NR * TKR_WAVE + 2];
-    if ((int)blockIdx.x >= *heavy_count) return;                  // (the same word in every thread)
-    const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
-    const long long r = heavy_list[blockIdx.x];
-    const long long lo = like_ptr[r], hi = like_ptr[r + 1];       // checked by the step kernel, which listed the row
-    const long long n_slabs = (hi - lo + kLmfLikeSlab - 1) / kLmfLikeSlab;
-    float x[NR];
-    lmf_load_row<NR>(X + (size_t)r * K, K, x);
-    double L[NR], sp = 0.0, ss = 0.0;
-#pragma unroll
-    for (int j = 0; j < NR; ++j) L[j] = 0.0;
-    bool skipped = false;
-    for (long long b = wave; b < n_slabs; b += kLmfHeavyWaves) {  // wave-uniform
-        const long long first = lo + b * kLmfLikeSlab;
-        LmfSum<NR> sum;
-        skipped |= lmf_like_chain<NR>(Y, n_y, K, like_cols, first, (int)min((long long)kLmfLikeSlab, hi - first), x, sum);
-#pragma unroll
-        for (int j = 0; j < NR; ++j) L[j] += (double)sum.L[j];
-        sp += sum.sp;
-        ss += sum.ss;
-    }
-    if (skipped && lane == 0) status_refuse(status, r, kAlsSkipped);
-#pragma unroll
-    for (int j = 0; j < NR; ++j) part[wave][lane + 64 * j] = L[j];
-    if (lane == 0) {
-        part[wave][NR * TKR_WAVE] = sp;
-        part[wave][NR * TKR_WAVE + 1] = ss;
-    }
-    __syncthreads();                                              // every thread of the workgroup is here: the exit above is uniform
-    if (wave != 0) return;
-    LmfSum<NR> sum;
-    sum.sp = sum.ss = 0.0;
-#pragma unroll
-    for (int j = 0; j < NR; ++j) L[j] = 0.0;
-    for (int w = 0; w < kLmfHeavyWaves; ++w) {
-#pragma unroll
-        for (int j = 0; j < NR; ++j) L[j] += part[w][lane + 64 * j];
-        sum.sp += part[w][NR * TKR_WAVE];
-        sum.ss += part[w][NR * TKR_WAVE + 1];
-    }
-#pragma unroll
-    for (int j = 0; j < NR; ++j) sum.L[j] = (float)L[j];
-    lmf_update_row<NR>(r, K, fixed, x, sum, D, alpha, lam, lr, X, H, row_loss);
-}
-
-template <int NR>
-static int launch_step(hipStream_t stream, const float* Y, int n_y, int K, const float* D, const int64_t* like_ptr, const int32_t* like_cols,
-                       long long n_likes, long long n_x, int fixed, double alpha, double lam, float lr, long long heavy_from, float* X, float* H,
-                       double* row_loss, unsigned long long* st, int32_t* heavy_count, int32_t* heavy_list, long long cap) {
-    hipLaunchKernelGGL(lmf_step_kernel<NR>, dim3((unsigned)((n_x + kLmfWaves - 1) / kLmfWaves)), dim3(kLmfBlock), 0, stream, Y, n_y, K, D, like_ptr,
-                       like_cols, n_likes, n_x, fixed, alpha, lam, lr, heavy_from, X, H, row_loss, st, heavy_count, heavy_list);
-    TKR_LAUNCH_CHECK();
-    if (cap > 0) {
-        hipLaunchKernelGGL(lmf_heavy_kernel<NR>, dim3((unsigned)cap), dim3(kLmfHeavyBlock), 0, stream, Y, n_y, K, D, like_ptr, like_cols, fixed, alpha,
-                           lam, lr, X, H, row_loss, st, heavy_count, heavy_list);
-        TKR_LAUNCH_CHECK();
-    }
-    return TKR_OK;
-}
-
-static int64_t lmf_align(int64_t bytes) { return (bytes + 15) / 16 * 16; }
 static int64_t lmf_slabs(int64_t n_y) { return (n_y + kLmfSlab - 1) / kLmfSlab; }
-static int64_t lmf_list_bytes(int64_t n_x) { return lmf_align(16 + n_x * 4); }       // the counter, then the rows
 
 }  // namespace tkr
 
@@ -418,7 +235,7 @@ extern "C" int tkr_lmf_step_rows(const float* Y, int32_t n_y, int32_t k, const f
     }
     const int NR = (K + TKR_WAVE - 1) / TKR_WAVE;
 #define TKR_LMF_STEP(N)                                                                                                                       \
-    return launch_step<N>(stream, Y, n_y, K, D, like_ptr, like_cols, (long long)n_likes, (long long)n_x, fixed, alpha, lam, (float)lr,        \
+    return lmf_launch_step<N, kLmfLogistic>(stream, Y, n_y, K, D, like_ptr, like_cols, (long long)n_likes, (long long)n_x, fixed, alpha, lam, (float)lr,        \
                           (long long)heavy_from, X, H, row_loss, st, heavy_count, heavy_list, (long long)cap)
     switch (NR) {
         case 1: TKR_LMF_STEP(1);

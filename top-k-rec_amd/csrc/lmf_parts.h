@@ -1,4 +1,5 @@
-// The pieces of K25 (csrc/lmf.hip): its constants, and sigma and softplus, written ONCE for both kernels.
+// The pieces of K25 (csrc/lmf.hip): its constants, and sigma and softplus, written ONCE for both kernels.  K27 (csrc/smf.hip) has the
+// same tiles, pitches and heavy rows.
 #pragma once
 #include "als_parts.h"
 
@@ -20,6 +21,10 @@ static_assert(kLmfSlab % kLmfTile == 0 && kLmfHeavyBlock <= 1024, "whole tiles; 
 // floats between two staged rows of Y: odd, so the first product (a lane per staged row, two columns apart by lane half) and the second
 // (a lane per column, ds_read_b32 banks by 32-lane half) both read without a conflict
 __host__ __device__ constexpr int lmf_stage_pitch(int KT) { return KT * 32 + 1; }
+
+// the workspace of K25 and K27: pieces of whole 16 bytes; the list of heavy rows is a counter, then the rows
+static inline int64_t lmf_align(int64_t bytes) { return (bytes + 15) / 16 * 16; }
+static inline int64_t lmf_list_bytes(int64_t n_x) { return lmf_align(16 + n_x * 4); }
 
 // Finite at every finite s.  exp(-s) is +0 from s = 104 on and 1 + e is 1.0f from s = 17 on: sigma(s) == 1.0f for s >= 40.  exp(-s) is
 // +inf below s = -88.8, and 1 / inf = +0: sigma(s) == +0 for s <= -110.  The division is IEEE: sigma(0) == 0.5f.

@@ -91,11 +91,12 @@ EXPORTS = ('tkr_version', 'tkr_plan_team', 'tkr_plan_max_blocks', 'tkr_sample_pl
            'tkr_compact_rows_emit_dev', 'tkr_fusion_features', 'tkr_fusion_sgd', 'tkr_fusion_user_weights', 'tkr_fusion_svm_sums',
            'tkr_mmr_select', 'tkr_list_pair_sums', 'tkr_line_metrics', 'tkr_bootstrap_sums', 'tkr_nearest_anchors', 'tkr_als_gram',
            'tkr_als_solve_rows', 'tkr_als_solve_rows_prior', 'tkr_mlp_forward', 'tkr_mlp_fit', 'tkr_als_cg_rows', 'tkr_als_gram_wide',
-           'tkr_lmf_dense_rows', 'tkr_lmf_step_rows', 'tkr_csr_spmm', 'tkr_estep_cg')
+           'tkr_lmf_dense_rows', 'tkr_lmf_step_rows', 'tkr_csr_spmm', 'tkr_estep_cg', 'tkr_smf_lse_rows', 'tkr_smf_dense_rows', 'tkr_smf_step_rows')
 EXPORTS_I64 = ('tkr_vbpr_workspace_floats', 'tkr_vbpr_colplan_lds_bytes', 'tkr_topk_workspace_bytes_for', 'tkr_topk_workspace_bytes', 'tkr_plan_workspace_bytes', 'tkr_like_ranks_workspace_bytes',
                'tkr_parse_dev_workspace_bytes', 'tkr_idtable_slots', 'tkr_scan_dev_workspace_bytes', 'tkr_als_workspace_bytes',
                'tkr_als_prior_workspace_bytes', 'tkr_mlp_workspace_bytes', 'tkr_fusion_svm_partial_bytes', 'tkr_als_cg_workspace_bytes',
-               'tkr_als_gram_wide_workspace_bytes', 'tkr_lmf_workspace_bytes', 'tkr_csr_spmm_workspace_bytes', 'tkr_estep_cg_workspace_bytes')
+               'tkr_als_gram_wide_workspace_bytes', 'tkr_lmf_workspace_bytes', 'tkr_csr_spmm_workspace_bytes', 'tkr_estep_cg_workspace_bytes',
+               'tkr_smf_workspace_bytes')
 
 
 def lib():
@@ -1588,6 +1589,100 @@ def lmf_step_rows(Y, D, like_ptr, like_cols, X, H, *, fixed, alpha, lam, lr, hea
           C.c_int64(n_likes), C.c_int64(n_x), C.c_int32(fixed), C.c_double(alpha), C.c_double(lam), C.c_double(lr), C.c_int64(heavy_from), _p(X),
           _p(H), _p(loss), _p(workspace), C.c_int64(workspace.numel() * workspace.element_size()), _p(status))
     return _done(what, loss, status, check, _LMF_REFUSED, LmfRefused)
+
+
+# ---- K27: the three parts of a softmax-MF half-step (csrc/smf.hip) ---------------------------------------------------------------------------
+SMF_MAX_K = 128              # TKR_SMF_MAX_K of include/tkr.h: the tables hold k + 1 columns
+SMF_SLAB = 4096              # TKR_SMF_SLAB: the rows of Y one workgroup of smf_lse_rows / smf_dense_rows walks
+SMF_HEAVY_FROM = LMF_HEAVY_FROM      # the heavy rows are K25's: slabs of LMF_LIKE_SLAB likes, LMF_HEAVY_WAVES waves
+SMF_NO_HEAVY = 1 << 62       # heavy_from: no row is heavy
+
+
+class SmfRefused(AlsRefused):
+    """a status word of K27 that is not -1 (the kinds 1 and 3 of K20)"""
+
+
+_SMF_REFUSED = _LMF_REFUSED
+
+
+def smf_workspace_bytes(n_x, k, n_y):
+    return _size('tkr_smf_workspace_bytes', (C.c_int64, C.c_int32, C.c_int64), (n_x, k, n_y))
+
+
+def _smf_tables(what, pairs):
+    """pairs: (name, tensor), all fp32 [., k + 1] on one GPU -> k"""
+    k = None
+    for name, t in pairs:
+        _, K = _als_table(what, name, t, SMF_MAX_K + 1, None if k is None else k + 1)
+        if K < 2:
+            raise ValueError('%s: %s has %d columns; a table holds k + 1 of them, k >= 1' % (what, name, K))
+        k = K - 1
+        _on_gpu(what, name, t, pairs[0][1].device)
+    return k
+
+
+def _ws_bytes(workspace):
+    return C.c_int64(workspace.numel() * workspace.element_size())
+
+
+def smf_lse_rows(X, Y, workspace=None, out=None):
+    """K27 -> lse fp32 [n_x] on the device: lse[r] = log sum over ALL rows c of Y of exp(X[r] . Y[c]), finite at any finite scores
+    (include/tkr.h tkr_smf_lse_rows).  X fp32 [n_x, K], Y fp32 [n_y, K], K = k + 1 <= SMF_MAX_K + 1.  Nothing is read back"""
+    what = 'smf_lse_rows'
+    k = _smf_tables(what, [('X', X), ('Y', Y)])
+    n_x, n_y = int(X.shape[0]), int(Y.shape[0])
+    workspace = workspace_room(workspace, smf_workspace_bytes(n_x, k, n_y), X.device)
+    lse = torch.empty(n_x, dtype=torch.float32, device=X.device) if out is None else out
+    _operand(what, 'out', lse, torch.float32, 1, numel=n_x, on=X.device)
+    _call('tkr_smf_lse_rows', X, _p(X), C.c_int64(n_x), _p(Y), C.c_int64(n_y), C.c_int32(k), _p(lse), _p(workspace), _ws_bytes(workspace))
+    return lse
+
+
+def smf_dense_rows(X, Y, row_off=None, col_off=None, workspace=None, out=None):
+    """K27 -> D fp32 [n_x, K] on the device: D[r] = sum over ALL rows c of Y of exp((X[r] . Y[c] - row_off[r]) - col_off[c]) Y[c], the
+    score matrix never stored (include/tkr.h tkr_smf_dense_rows).  row_off fp32 [n_x], col_off fp32 [n_y]; None is 0, +inf is legal
+    and makes the term +0.  Nothing is read back"""
+    what = 'smf_dense_rows'
+    k = _smf_tables(what, [('X', X), ('Y', Y)])
+    n_x, n_y = int(X.shape[0]), int(Y.shape[0])
+    _operand(what, 'row_off', row_off, torch.float32, 1, numel=n_x, on=X.device, optional=True)
+    _operand(what, 'col_off', col_off, torch.float32, 1, numel=n_y, on=X.device, optional=True)
+    workspace = workspace_room(workspace, smf_workspace_bytes(n_x, k, n_y), X.device)
+    D = torch.empty((n_x, k + 1), dtype=torch.float32, device=X.device) if out is None else out
+    _operand(what, 'out', D, torch.float32, 2, on=X.device)
+    if D.shape != X.shape:
+        raise TkrError('%s: out must have the shape of X, %s' % (what, tuple(X.shape)))
+    _call('tkr_smf_dense_rows', X, _p(X), C.c_int64(n_x), _p(Y), C.c_int64(n_y), C.c_int32(k), _p(row_off), _p(col_off), _p(D), _p(workspace),
+          _ws_bytes(workspace))
+    return D
+
+
+def smf_step_rows(Y, D, like_ptr, like_cols, X, H, *, fixed, scale_by_likes, lam, lr, heavy_from=None, want_loss=False, workspace=None, check=True):
+    """K27, in place on X and its AdaGrad slot H (both fp32 [n_x, K]): for every row r the sum L over its likes, rows of Y, the gradient
+    g = L - w D[r] - lam x (w: the row's like count with scale_by_likes, else 1), h += g^2, x += lr g / sqrt(h); column `fixed` keeps
+    its bits, -1 fixes none (include/tkr.h tkr_smf_step_rows).  D: smf_dense_rows(X, Y, ...).  -> row_loss float64 [n_x] with
+    want_loss, else None.  heavy_from: None = SMF_HEAVY_FROM.  A refusal raises SmfRefused naming row and kind; check=False returns
+    (row_loss, status tensor) instead and reads nothing back"""
+    what = 'smf_step_rows'
+    k = _smf_tables(what, [('Y', Y), ('X', X), ('D', D), ('H', H)])
+    n_y, n_x = int(Y.shape[0]), int(X.shape[0])
+    if D.shape != X.shape or H.shape != X.shape:
+        raise TkrError('%s: D and H must have the shape of X, %s' % (what, tuple(X.shape)))
+    _operand(what, 'like_ptr', like_ptr, torch.int64, 1, on=Y.device, raises=_STD)
+    _operand(what, 'like_cols', like_cols, torch.int32, 1, on=Y.device, raises=_STD)
+    if like_ptr.numel() != n_x + 1:
+        raise ValueError('%s: like_ptr must hold n_x + 1 = %d entries, not %d' % (what, n_x + 1, like_ptr.numel()))
+    if not isinstance(fixed, (int,)) or isinstance(fixed, bool) or not -1 <= fixed < k + 1:
+        raise ValueError('%s: fixed = %r must be a column, 0 <= fixed < %d, or -1 for none' % (what, fixed, k + 1))
+    n_likes = int(like_cols.numel())
+    heavy_from = SMF_HEAVY_FROM if heavy_from is None else int(heavy_from)
+    workspace = workspace_room(workspace, smf_workspace_bytes(n_x, k, 1) if heavy_from < n_likes else 0, Y.device)
+    loss = torch.empty(n_x, dtype=torch.float64, device=Y.device) if want_loss else None
+    status = torch.empty(1, dtype=torch.int64, device=Y.device)
+    _call('tkr_smf_step_rows', Y, _p(Y), C.c_int32(n_y), C.c_int32(k), _p(D), _p(like_ptr), _p(like_cols) if n_likes else C.c_void_p(0),
+          C.c_int64(n_likes), C.c_int64(n_x), C.c_int32(fixed), C.c_int32(1 if scale_by_likes else 0), C.c_double(lam), C.c_double(lr),
+          C.c_int64(heavy_from), _p(X), _p(H), _p(loss), _p(workspace), _ws_bytes(workspace), _p(status))
+    return _done(what, loss, status, check, _SMF_REFUSED, SmfRefused)
 
 
 # ---- K26: a sparse x dense product and CER's E-step by conjugate gradients (csrc/sparse.hip) ------------------------------------------------
