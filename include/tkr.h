@@ -1266,6 +1266,71 @@ int tkr_smf_step_rows(const float* Y, int32_t n_y, int32_t k, const float* D, co
                       int64_t n_x, int32_t fixed, int32_t scale_by_likes, double lam, double lr, int64_t heavy_from, float* X, float* H,
                       double* row_loss, void* workspace, int64_t workspace_bytes, int64_t* status, void* stream);
 
+/* ---- K28 / K29: the item-neighbourhood model, built from the likes and served from histories (csrc/knn.hip) ----------------------------------
+ * ItemKNN (top-k-rec_amd/knn.py): no factors, no iteration, no seed.  The n_items x n_items matrix of
+ * co-occurrence counts is never in memory.
+ *
+ *   tkr_knn_build       The training likes as sets, twice: the CSR over users (u_ptr int64 [n_users + 1] from 0, u_cols int32, the columns
+ *                       of a row ascending and unique) and its transpose over items (i_ptr int64 [n_items + 1], i_rows int32);
+ *                       n_u_entries / n_i_entries: the lengths of u_cols / i_rows (at least u_ptr[n_users] / i_ptr[n_items]).
+ *                       norm float64 [n_items], finite and positive; shrink >= 0, finite; 1 <= N <= TKR_KNN_MAX_N.
+ *                         c_ij     = the number of users who like both i and j                                   (an exact integer)
+ *                         sim(i,j) = fp32( (double)c_ij / ( fl64(norm[i] * norm[j]) + shrink ) )
+ *                       in IEEE fp64, the product rounded first, then the sum, ONE division, rounded once to fp32 -- no fma.  Only a
+ *                       multiply, an add and a divide run on the device, so NumPy restates every bit.  The candidates of row i are the
+ *                       j != i with c_ij > 0.  nbr_ids int32 [n_items, N]: the N best candidates in K4's canonical order (sim
+ *                       descending, ties -> the higher column first); nbr_w fp32 [n_items, N]: their sim; a row with fewer than N
+ *                       candidates is padded with -1 / +0.0.
+ *                       heavy_from (0: TKR_KNN_HEAVY_FROM): a row's work is the sum of n_u over its likers u; a row whose work is above
+ *                       heavy_from is cut over its likers into up to 64 workgroups, whose partial counters are added as integers in a
+ *                       row of the workspace.  slab_cols (0: TKR_KNN_MAX_SLAB, the most one workgroup's LDS holds): a wider catalogue is
+ *                       walked once per slab of that many columns, and the slabs' winners are merged.  The result depends on neither.
+ *                       status: -1, or the smallest 4 * where + kind, found by a pre-pass before anything is written -- a refused call
+ *                       leaves nbr_ids and nbr_w untouched:
+ *                         0  u_ptr (where = the row) or i_ptr (where = n_users + 1 + the row) does not start at 0, decreases or leaves
+ *                            [0, its array's length]
+ *                         1  u_cols[where] is outside [0, n_items), or i_rows[where - n_u_entries] outside [0, n_users)
+ *                         2  u_ptr[n_users] != i_ptr[n_items], both inside their arrays: the two CSRs hold different numbers of entries (where = 0)
+ *                         3  norm[where] is not finite and positive
+ *                       workspace: 16-byte aligned, tkr_knn_build_workspace_bytes(n_items) bytes.
+ *   tkr_knn_score       n_rows lines.  hist_ptr int64 [n_rows + 1] from 0, hist_cols int32 (n_hist of them): the liked catalogue items
+ *                       of every line, ascending and unique.  The table of tkr_knn_build: nbr_ids, nbr_w [n_items, N].  col_of_item
+ *                       int32 [n_items] or NULL: the scenario column of a catalogue item, or -1; NULL is the identity and needs
+ *                       n_cols == n_items.  mask / mask_pitch: K4's (nullable).  For line r and column c, with j the item mapped to c:
+ *                         s(r,c) = the fp32 chain acc = fl(acc + nbr_w[i][p]) from +0.0 over the history items i of the line in stored
+ *                                  order, item i contributing when nbr_ids[i][p] == j for some p (j is among the N nearest of i)
+ *                       A column nobody contributes to scores +0.0; an entry that maps to -1 is dropped.  out_ids [n_rows, K] and
+ *                       out_scores (nullable) are tkr_score_topk's with this s: the K best unmasked columns in the canonical order,
+ *                       padded -1 / -inf, 1 <= K <= TKR_KNN_MAX_K (out_ids NULL: no lists, K is ignored).  like_ptr int64
+ *                       [n_rows + 1], like_cols int32 (n_likes of them), rank_out int32 [n_likes], all three or none: tkr_like_ranks's
+ *                       definition with this s (-1 for a masked or out-of-range like; a like at position p of the list has rank p).
+ *                       slab_cols as above (the history is walked once per slab; the result does not depend on it).
+ *                       status: -1, or the smallest 4 * where + kind of the pre-pass; a refused call writes nothing:
+ *                         0  hist_ptr does not start at 0, decreases or leaves [0, n_hist] at row `where`
+ *                         1  hist_cols[where] is outside [0, n_items)
+ *                         2  like_ptr does not start at 0, decreases or leaves [0, n_likes] at row `where`
+ *                       A neighbour id outside [0, n_items) (the -1 padding included) names nothing and is never used as an index, a
+ *                       mapped column outside [0, n_cols) neither.  Weights must be finite (knn.py import_model checks); on a table
+ *                       that breaks the rule nothing is indexed out of range and nothing more is promised.
+ * One workgroup owns a line from the first add to the last rank, and its first wave alone walks the history, so a column's chain is in
+ * history order; no atomics but LDS histogram counters whose order changes no result: two runs
+ * give the same bits, and a block of lines ranked alone gives what it gives inside a larger call.  Arguments are checked before any launch
+ * (TKR_E_INVAL): a null or misaligned pointer, a negative length, n_users / n_items / n_rows / n_cols < 1 or >= 2^31, shrink negative or
+ * not finite, heavy_from or slab_cols < 0, a workspace too small, mask_pitch < n_rows, likes given in part.  N, K or slab_cols above their
+ * limits: TKR_E_UNSUPPORTED. */
+#define TKR_KNN_MAX_N 512        /* neighbours kept per item */
+#define TKR_KNN_MAX_K 32         /* columns one launch of tkr_knn_score lists per line */
+#define TKR_KNN_MAX_SLAB 36864   /* columns whose counters (K28) or accumulators (K29) one workgroup keeps in LDS */
+#define TKR_KNN_HEAVY_FROM 262144 /* what heavy_from = 0 means */
+int64_t tkr_knn_build_workspace_bytes(int64_t n_items);
+int tkr_knn_build(const int64_t* u_ptr, const int32_t* u_cols, int64_t n_u_entries, const int64_t* i_ptr, const int32_t* i_rows,
+                  int64_t n_i_entries, int64_t n_users, int64_t n_items, const double* norm, double shrink, int32_t N, int64_t heavy_from,
+                  int32_t slab_cols, int32_t* nbr_ids, float* nbr_w, void* workspace, int64_t workspace_bytes, int64_t* status, void* stream);
+int tkr_knn_score(const int64_t* hist_ptr, const int32_t* hist_cols, int64_t n_hist, int64_t n_rows, const int32_t* nbr_ids,
+                  const float* nbr_w, int32_t n_items, int32_t N, const int32_t* col_of_item, int32_t n_cols, const uint32_t* mask,
+                  int32_t mask_pitch, int32_t K, int32_t* out_ids, float* out_scores, const int64_t* like_ptr, const int32_t* like_cols,
+                  int64_t n_likes, int32_t* rank_out, int32_t slab_cols, int64_t* status, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -52,6 +52,13 @@ Stated differences from the reference:
     resamples both together (a paired bootstrap) and adds ``S.vs.m`` (B's values), ``S.diff.m`` (this model - B), ``S.diff.m.lo`` /
     ``.hi`` and ``S.diff.m.p`` (two-sided).  Single process only.
 
+  * ``-m DIR`` (or ``--compare DIR``) where DIR holds ``knn.npz`` is a neighbourhood model (knn.ItemKNN, K28): it has no
+    ``final-*.dat``.  A test line's history is its user's like == 1 entries of ``f{fold}tr.txt`` in the ``vid`` numbering, the mask is
+    the scenario's rated mask as for any model, and K29 (tkr_hip.knn_score) gives the lists and the ranks (``KnnRanker``).  The accuracy
+    lines, ``-M acc auc mrr ndcg map``, ``--bootstrap`` and ``--compare`` in both directions work; ``--negatives``, ``--diversify``,
+    ``-M ild cov gini unexp`` and a multi-process launch end in a parser error: there are no item factors to sample against, to
+    measure similarity in or to replicate.
+
 How a scenario is ranked: once per entry of ``-sl``, ``main`` makes the ``Lines`` of this rank's shard (user rows, like CSR and, on first
 use, the rated mask on the device; they depend on the Scenario alone) and a ``Ranker`` of the user table and the model on them, which
 builds the model's ``Items`` (the test ids' rows of final-V.dat and final-B.dat) on first use and offers K4, K8 and K5.  Every
@@ -71,6 +78,8 @@ import torch
 
 import diversity
 import explain
+import foldin
+import knn
 import rankmetrics
 import significance
 import textio
@@ -301,6 +310,58 @@ class Ranker:
         return tkr_hip.count_hits(ids, self.lines.like_ptr, self.lines.like_cols, step, interval)
 
 
+class KnnRanker:
+    """Ranker's three methods for a neighbourhood model (knn.ItemKNN, a directory with knn.npz): K29 (tkr_hip.knn_score) in place of K4
+    and K8.  liked: the (ptr, cols) CSR over the uid indices of the like == 1 entries of the fold's train file in the `vid` numbering --
+    a line's history is its user's row.  The test columns are a subset of `vid`: col_of_item maps a catalogue item to its column or -1"""
+
+    def __init__(self, model, liked, vids, lines):
+        if model.n_items != max(vids.values()) + 1:
+            raise ValueError('the neighbourhood model holds %d items, the vid list %d' % (model.n_items, max(vids.values()) + 1))
+        self.model, self.liked, self.vids, self.lines = model, liked, vids, lines
+
+    @functools.cached_property
+    def items(self):
+        """(history ptr, history cols, col_of_item) of the lines on the device"""
+        sc, device = self.lines.sc, self.lines.device
+        col_of_item = np.full(self.model.n_items, -1, dtype=np.int32)
+        for vid, col in sc.teids.items():
+            col_of_item[self.vids[vid]] = col                        # (KeyError: a test id that `vid` lacks, as scenario_items)
+        ptr, cols = _take_rows(self.liked[0], self.liked[1], np.asarray(sc.users, dtype=np.int64))
+        return tuple(torch.from_numpy(np.ascontiguousarray(a)).to(device) for a in (ptr, cols, col_of_item))
+
+    def _call(self, K, **kw):
+        mask, pitch = self.lines.mask
+        ptr, cols, col_of_item = self.items
+        return tkr_hip.knn_score(ptr, cols, *self.model.table(self.lines.device), K, col_of_item=col_of_item, n_cols=len(self.lines.sc.teids),
+                                 mask=mask, mask_pitch=pitch, **kw)
+
+    def score_topk(self, K, want_scores=False):
+        return self._call(K, want_scores=want_scores)
+
+    def like_ranks(self):
+        return self._call(0, like_ptr=self.lines.like_ptr, like_cols=self.lines.like_cols)
+
+    def count_hits(self, ids, step, interval):
+        return tkr_hip.count_hits(ids, self.lines.like_ptr, self.lines.like_cols, step, interval)
+
+
+def knn_refusals(parser, args, what='the model'):
+    """the flags a neighbourhood model (a directory with knn.npz) cannot serve: it has no factors to sample against, to measure
+    similarity in or to shard"""
+    tail = 'is not available for a neighbourhood model (%s holds knn.npz): it has no item factors' % what
+    if args.negatives is not None:
+        parser.error('--negatives ' + tail)
+    if args.diversify is not None:
+        parser.error('--diversify ' + tail)
+    listy = [m for m in args.metrics or () if m in diversity.LIST_METRICS + explain.METRICS]
+    if listy:
+        parser.error('-M %s %s' % (' '.join(listy), tail))
+    if int(os.environ.get('WORLD_SIZE', '1')) > 1:
+        parser.error('a multi-process launch (WORLD_SIZE > 1) is not available for a neighbourhood model (%s holds knn.npz): run it in a '
+                     'single process' % what)
+
+
 def rank_scenario(umat_dev, vmat, bmat, vids, sc, total, device, want_scores=False):
     """filtered top-`total` test columns of every test line -> int32 [n_lines, total] (device)"""
     return Ranker(umat_dev, (vmat, bmat, vids), Lines(sc, device)).score_topk(total, want_scores)
@@ -511,6 +572,9 @@ def main(argv=None):
                         help="With --bootstrap: a second model directory, resampled on the same lines; prints S.vs.metric, S.diff.metric, "
                              "its interval and its two-sided p")
     args = parser.parse_args(argv)
+    is_knn = {path: knn.is_model_dir(path) for path in (args.model, args.compare)}
+    for path in (p for p in (args.model, args.compare) if is_knn[p]):
+        knn_refusals(parser, args, path)
     div = diversity.check_arguments(parser, args)
     list_metrics = [m for m in args.metrics or () if m in diversity.LIST_METRICS]
     if (div or list_metrics) and int(os.environ.get('WORLD_SIZE', '1')) > 1:
@@ -549,12 +613,24 @@ def main(argv=None):
     device = torch.device('cuda', torch.cuda.current_device())
     uids = read_ids(os.path.join(args.data, 'uid'))
     vids = read_ids(os.path.join(args.data, 'vid'))
-    umat, vmat, bmat = read_model(args.model, uids, vids)
-    umat_dev = torch.from_numpy(umat).to(device)
     umap = textio.IdMap(uids)
-    if args.compare is not None:                                     # model B: the same uid / vid lists
-        umat_b, vmat_b, bmat_b = read_model(args.compare, uids, vids)
-        umat_b = torch.from_numpy(umat_b).to(device)
+    liked_csr = None
+    if any(is_knn.values()):                                         # a line's history: its user's like == 1 entries of the train file
+        n_users = max(int(max(uids.values())) + 1 if uids else 0, 1)
+        liked_csr = foldin.liked_csr(textio.parse_ratings(os.path.join(args.data, 'f%dtr.txt' % args.fold), umap, textio.IdMap(vids)),
+                                     n_users, max(vids.values()) + 1)
+
+    def ranker_of(path):
+        """lines -> the Ranker of a model directory: a neighbourhood model where it holds knn.npz, else final-U.dat / final-V.dat"""
+        if is_knn[path]:
+            model = knn.load(path)
+            return lambda lines: KnnRanker(model, liked_csr, vids, lines)
+        umat, vmat, bmat = read_model(path, uids, vids)
+        umat_dev = torch.from_numpy(umat).to(device)
+        return lambda lines: Ranker(umat_dev, (vmat, bmat, vids), lines)
+
+    ranker_a = ranker_of(args.model)
+    ranker_b = ranker_of(args.compare) if args.compare is not None else None      # model B: the same uid / vid lists
     results, extra, negs, lists, boots = {}, {}, {}, {}, {}
     liked = textio.parse_ratings(os.path.join(args.data, 'f%dtr.txt' % args.fold), umap, textio.IdMap(vids)) if unexp else None
 
@@ -562,18 +638,18 @@ def main(argv=None):
         """the accuracy of one entry of -sl, and its other figures when the scenario is named for the first time.  One set of operands
         serves all of them; it is released on return, so the next entry is loaded into the device memory this one leaves"""
         full = load_scenario(args.data, args.fold, scenario, uids, umap)
-        ops = Ranker(umat_dev, (vmat, bmat, vids), Lines(_shard(full)[0], device))
+        ops = ranker_a(Lines(_shard(full)[0], device))
         acc = accuracy_loaded(ops, args.step, args.total)
         if (args.metrics or div) and scenario not in extra:          # (a scenario listed twice: its metric lines are not doubled)
             kept = {} if boot else None
             extra[scenario] = rank_metrics_loaded(ops, args.step, args.total, full_metrics, kept)
             if boot:
-                other = Ranker(umat_b, (vmat_b, bmat_b, vids), ops.lines) if args.compare is not None else None
+                other = ranker_b(ops.lines) if ranker_b is not None else None
                 boots[scenario] = significance_loaded(kept['ranks'], ops.lines, other, args.step, args.total, full_metrics, boot)
             if neg_metrics:
                 negs[scenario] = negative_metrics_loaded(ops, full, args.step, args.total, args.negatives, args.neg_seed, neg_metrics)
             if list_metrics or div or unexp:
-                anchors = explain.anchors_csr([liked], full.users, len(vmat), device) if unexp else None
+                anchors = explain.anchors_csr([liked], full.users, len(ops.model[0]), device) if unexp else None
                 lists[scenario] = list_metrics_loaded(ops, args.step, args.total, list_metrics, div, anchors)
         return acc
 

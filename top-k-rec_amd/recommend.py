@@ -51,6 +51,11 @@ line excludes: the user's last line of ``f{fold}tr.txt``, with ``--new-vid`` als
 ``--new-history``.  An item never explains itself; an item without an anchor is its bare token.  With ``--diversify`` the final lists
 are explained.  The main output is byte for byte what it is without the two flags.
 
+A MODEL that holds ``knn.npz`` is a neighbourhood model (knn.ItemKNN, K28 / K29): model users are ranked from their like == 1 entries
+of ``f{fold}tr.txt``, ``--new-uid`` users from those of ``--new-history`` with no fold-in step (the ``--fold-*`` flags mean nothing
+there); the excluded items, the output format and the writers are the same.  ``--candidates``, ``--new-vid``, ``--diversify`` and
+``--explain`` need item factors and end in a parser error.
+
 The scores, the filter and the selection run on the GPU (tkr_hip.build_rated_mask, tkr_hip.score_topk); single process.
 """
 from __future__ import annotations
@@ -64,9 +69,10 @@ import torch
 import diversity
 import explain as expl
 import foldin
+import knn
 import textio
 import tkr_hip
-from evaluate import _group, read_ids, read_matrix, read_model     # noqa: F401  (read_matrix: tests/test_gpu_item_foldin.py reads through it)
+from evaluate import _group, _take_rows, read_ids, read_matrix, read_model     # noqa: F401  (read_matrix: tests/test_gpu_item_foldin.py reads through it)
 from textio import format_lines      # noqa: F401  (the host formatter of the output lines; textio.write_lists writes them)
 
 
@@ -229,6 +235,51 @@ def fold_in_new_items(args, uids, vids, new_vids, umat, vmat, bmat, device):
     return vmat, bmat, grown, textio.parse_ratings(args.new_ratings, umap, textio.IdMap(grown))
 
 
+def rank_knn(model, liked, user_rows, R, total, device):
+    """rank() for a neighbourhood model (knn.ItemKNN): the history of a ranked row is its user's row of `liked`, the (ptr, cols) CSR of
+    the like == 1 entries of R by user index; every known item on the user's last line of R is excluded, as rank() excludes it
+    -> (ids int32 [n, total], scores fp32 [n, total]) on the device (K29, tkr_hip.knn_score)"""
+    n = len(user_rows)
+    rows_of_user = {}
+    for row, user in enumerate(user_rows):
+        rows_of_user.setdefault(int(user), []).append(row)
+    ptr, cols = rated_csr(textio.ratings_to_host(R), rows_of_user, n, model.n_items)
+    mask, pitch = tkr_hip.build_rated_mask(torch.from_numpy(ptr).to(device), torch.from_numpy(cols).to(device), n, model.n_items)
+    hptr, hcols = _take_rows(liked[0], liked[1], np.asarray(user_rows, dtype=np.int64))
+    return tkr_hip.knn_score(torch.from_numpy(hptr).to(device), torch.from_numpy(np.ascontiguousarray(hcols)).to(device), *model.table(device),
+                             total, mask=mask, mask_pitch=pitch, want_scores=True)
+
+
+def main_knn(parser, args, uids, vids, users, new_uids):
+    """main() for a model directory that holds knn.npz: model users are ranked from their like == 1 entries of the train file, the
+    --new-uid users from those of --new-history, with no fold-in step (the --fold-* flags mean nothing here).  Same output, same writers"""
+    for flag, given in (('--candidates', args.candidates), ('--new-vid', args.new_vid), ('--diversify', args.diversify), ('--explain', args.explain)):
+        if given is not None:
+            parser.error('%s is not available for a neighbourhood model (%s holds knn.npz): it has no item factors' % (flag, args.model))
+    if not torch.cuda.is_available():
+        raise tkr_hip.TkrError('recommend.py scores on the GPU through libtkr_hip.so; no MI355X is visible')
+    device = torch.device('cuda', torch.cuda.current_device())
+    model = knn.load(args.model)
+    n_items = max(vids.values()) + 1
+    if model.n_items != n_items:
+        raise ValueError('%s holds %d items, the vid list %d' % (args.model, model.n_items, n_items))
+    vmap = textio.IdMap(vids)
+    wrote = False
+    for tokens_of, table, path in ((users, uids, os.path.join(args.data, 'f%dtr.txt' % args.fold)), (list(new_uids), new_uids, args.new_history)):
+        if not tokens_of:
+            continue
+        R = textio.parse_ratings(path, textio.IdMap(table), vmap)
+        liked = foldin.liked_csr(R, max(table.values()) + 1, n_items)
+        ids, scores = rank_knn(model, liked, [table[u] for u in tokens_of], R, args.total, device)
+        tokens, rows = row_tokens(tokens_of)
+        textio.write_lists(args.output, tokens, ids, scores, rows, vmap, where=args.format, append=wrote)
+        wrote = True
+    if not wrote:
+        open(args.output, 'wb').close()
+    with open(args.output, 'rb') as fh:
+        return fh.read().decode().split('\n')[:-1]
+
+
 def main(argv=None):
     parser = argparse.ArgumentParser(description="Write the top-k items of every user, scored on the GPU.")
     parser.add_argument('-d', '--data', required=True, help="The data path (uid, vid, f{fold}tr.txt)")
@@ -283,6 +334,8 @@ def main(argv=None):
         clash = [v for v in new_vids if v in vids]
         if clash:
             raise KeyError('%s: item %r is in the model already' % (args.new_vid, clash[0]))
+    if knn.is_model_dir(args.model):
+        return main_knn(parser, args, uids, vids, users, new_uids)
     if not torch.cuda.is_available():
         raise tkr_hip.TkrError('recommend.py scores on the GPU through libtkr_hip.so; no MI355X is visible')
     device = torch.device('cuda', torch.cuda.current_device())

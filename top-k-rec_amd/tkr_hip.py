@@ -91,12 +91,13 @@ EXPORTS = ('tkr_version', 'tkr_plan_team', 'tkr_plan_max_blocks', 'tkr_sample_pl
            'tkr_compact_rows_emit_dev', 'tkr_fusion_features', 'tkr_fusion_sgd', 'tkr_fusion_user_weights', 'tkr_fusion_svm_sums',
            'tkr_mmr_select', 'tkr_list_pair_sums', 'tkr_line_metrics', 'tkr_bootstrap_sums', 'tkr_nearest_anchors', 'tkr_als_gram',
            'tkr_als_solve_rows', 'tkr_als_solve_rows_prior', 'tkr_mlp_forward', 'tkr_mlp_fit', 'tkr_als_cg_rows', 'tkr_als_gram_wide',
-           'tkr_lmf_dense_rows', 'tkr_lmf_step_rows', 'tkr_csr_spmm', 'tkr_estep_cg', 'tkr_smf_lse_rows', 'tkr_smf_dense_rows', 'tkr_smf_step_rows')
+           'tkr_lmf_dense_rows', 'tkr_lmf_step_rows', 'tkr_csr_spmm', 'tkr_estep_cg', 'tkr_smf_lse_rows', 'tkr_smf_dense_rows', 'tkr_smf_step_rows',
+           'tkr_knn_build', 'tkr_knn_score')
 EXPORTS_I64 = ('tkr_vbpr_workspace_floats', 'tkr_vbpr_colplan_lds_bytes', 'tkr_topk_workspace_bytes_for', 'tkr_topk_workspace_bytes', 'tkr_plan_workspace_bytes', 'tkr_like_ranks_workspace_bytes',
                'tkr_parse_dev_workspace_bytes', 'tkr_idtable_slots', 'tkr_scan_dev_workspace_bytes', 'tkr_als_workspace_bytes',
                'tkr_als_prior_workspace_bytes', 'tkr_mlp_workspace_bytes', 'tkr_fusion_svm_partial_bytes', 'tkr_als_cg_workspace_bytes',
                'tkr_als_gram_wide_workspace_bytes', 'tkr_lmf_workspace_bytes', 'tkr_csr_spmm_workspace_bytes', 'tkr_estep_cg_workspace_bytes',
-               'tkr_smf_workspace_bytes')
+               'tkr_smf_workspace_bytes', 'tkr_knn_build_workspace_bytes')
 
 
 def lib():
@@ -1817,7 +1818,152 @@ def estep_cg(F, Ft, V, E, *, lv, le, steps=ESTEP_STEPS, heavy_from=None, workspa
     return _done(what, E, status, check, _ESTEP_REFUSED, EstepRefused)
 
 
-# ---- K22: a dense MLP content encoder, applied and trained (csrc/mlp.hip) ------------------------------------------------------------------
+# ---- K28 / K29: the item-neighbourhood model, built and served (csrc/knn.hip) -----------------------------------------------------------------
+KNN_MAX_N = 512              # TKR_KNN_MAX_N of include/tkr.h: neighbours kept per item
+KNN_MAX_K = 32               # TKR_KNN_MAX_K: columns one launch of K29 lists per line
+KNN_MAX_SLAB = 36864         # TKR_KNN_MAX_SLAB: columns one workgroup keeps in LDS
+KNN_HEAVY_FROM = 262144      # TKR_KNN_HEAVY_FROM: a row with more work than this is shared by several workgroups
+_KNN_BUILD_REFUSED = ('u_ptr does not start at 0, decreases or leaves its array at row %d (from n_users + 1 on: row - n_users - 1 of i_ptr) (kind 0)',
+                      'entry %d of u_cols (from len(u_cols) on: entry - len(u_cols) of i_rows) is outside the matrix (kind 1)',
+                      'the two CSRs hold different numbers of entries (kind 2, word %d)', 'norm[%d] is not finite and positive (kind 3)')
+_KNN_SCORE_REFUSED = ('hist_ptr does not start at 0, decreases or leaves [0, len(hist_cols)] at row %d (kind 0)',
+                      'entry %d of hist_cols is outside [0, n_items) (kind 1)',
+                      'like_ptr does not start at 0, decreases or leaves [0, len(like_cols)] at row %d (kind 2)')
+
+
+class KnnRefused(TkrError):
+    """a status word of K28 or K29 that is not -1; .word, .row and .kind say what it holds (include/tkr.h; raised by status_check)"""
+
+
+def _knn_slab(what, slab_cols):
+    slab_cols = 0 if slab_cols is None else slab_cols
+    if not isinstance(slab_cols, int) or isinstance(slab_cols, bool) or not 0 <= slab_cols <= KNN_MAX_SLAB:
+        raise ValueError('%s: slab_cols = %r must be an integer in [1, %d], or None for the widest slab' % (what, slab_cols, KNN_MAX_SLAB))
+    return slab_cols
+
+
+def _knn_ptr(what, name, ptr, cols, on=None):
+    _operand(what, name + '_ptr', ptr, torch.int64, 1, at_least=2, on=on)
+    _operand(what, name + ' entries', cols, torch.int32, 1, on=ptr.device)
+    return int(ptr.numel()) - 1
+
+
+def knn_build_workspace_bytes(n_items):
+    return _size('tkr_knn_build_workspace_bytes', (C.c_int64,), (n_items,))
+
+
+def knn_build(u_ptr, u_cols, i_ptr, i_rows, norm, N, *, shrink=0.0, heavy_from=None, slab_cols=None, workspace=None, out=None, check=True):
+    """K28 -> (nbr_ids int32 [n_items, N], nbr_w fp32 [n_items, N]) on the device: for every item the N items with the largest
+    sim(i, j) = fp32(c_ij / (fl64(norm[i] * norm[j]) + shrink)), c_ij the number of users who like both, in the canonical order (ties ->
+    the higher column first), padded -1 / +0.0 (include/tkr.h tkr_knn_build).  u_ptr / u_cols: the likes as a CSR over users (int64 /
+    int32, ascending and unique in a row); i_ptr / i_rows: its transpose over items; norm float64 [n_items].  heavy_from: None =
+    KNN_HEAVY_FROM; slab_cols: None = KNN_MAX_SLAB; the result depends on neither.  out: a pair of tensors to write.  A refusal raises
+    KnnRefused and leaves the outputs untouched; check=False returns ((nbr_ids, nbr_w), status tensor) instead and reads nothing back"""
+    what = 'knn_build'
+    n_users = _knn_ptr(what, 'u', u_ptr, u_cols)
+    n_items = _knn_ptr(what, 'i', i_ptr, i_rows, on=u_ptr.device)
+    dev = u_ptr.device
+    _operand(what, 'norm', norm, torch.float64, 1, numel=n_items, on=dev)
+    if not isinstance(N, int) or isinstance(N, bool) or not 1 <= N <= KNN_MAX_N:
+        raise ValueError('%s: N = %r, 1 <= N <= %d neighbours are supported' % (what, N, KNN_MAX_N))
+    if not (0.0 <= shrink < float('inf')):
+        raise ValueError('%s: shrink = %r must be finite and not negative' % (what, shrink))
+    heavy_from = KNN_HEAVY_FROM if heavy_from is None else heavy_from
+    if not isinstance(heavy_from, int) or isinstance(heavy_from, bool) or heavy_from < 1:
+        raise ValueError('%s: heavy_from = %r must be an integer, at least 1' % (what, heavy_from))
+    slab_cols = _knn_slab(what, slab_cols)
+    if out is None:
+        out = (torch.empty((n_items, N), dtype=torch.int32, device=dev), torch.empty((n_items, N), dtype=torch.float32, device=dev))
+    _operand(what, 'nbr_ids', out[0], torch.int32, 2, numel=n_items * N, on=dev)
+    _operand(what, 'nbr_w', out[1], torch.float32, 2, numel=n_items * N, on=dev)
+    workspace = workspace_room(workspace, knn_build_workspace_bytes(n_items), dev)
+    status = torch.empty(1, dtype=torch.int64, device=dev)
+    nil = C.c_void_p(0)
+    _call('tkr_knn_build', u_ptr, _p(u_ptr), _p(u_cols) if u_cols.numel() else nil, C.c_int64(u_cols.numel()), _p(i_ptr),
+          _p(i_rows) if i_rows.numel() else nil, C.c_int64(i_rows.numel()), C.c_int64(n_users), C.c_int64(n_items), _p(norm), C.c_double(shrink),
+          C.c_int32(N), C.c_int64(heavy_from), C.c_int32(slab_cols), _p(out[0]), _p(out[1]), _p(workspace),
+          C.c_int64(workspace.numel() * workspace.element_size()), _p(status))
+    return _done(what, out, status, check, _KNN_BUILD_REFUSED, KnnRefused)
+
+
+def _knn_score_once(args, n_rows, K, mask, mask_pitch, want_scores, likes, slab_cols, dev):
+    hist_ptr, hist_cols, nbr_ids, nbr_w, n_items, N, col_of_item, n_cols = args
+    nil = C.c_void_p(0)
+    ids = torch.empty((n_rows, K), dtype=torch.int32, device=dev) if K else None
+    scores = torch.empty((n_rows, K), dtype=torch.float32, device=dev) if K and want_scores else None
+    ranks = torch.empty(int(likes[1].numel()), dtype=torch.int32, device=dev) if likes is not None else None
+    status = torch.empty(1, dtype=torch.int64, device=dev)
+    _call('tkr_knn_score', hist_ptr, _p(hist_ptr), _p(hist_cols) if hist_cols.numel() else nil, C.c_int64(hist_cols.numel()), C.c_int64(n_rows),
+          _p(nbr_ids), _p(nbr_w), C.c_int32(n_items), C.c_int32(N), _p(col_of_item), C.c_int32(n_cols), _p(mask), C.c_int32(mask_pitch),
+          C.c_int32(K), _p(ids), _p(scores), _p(likes[0]) if likes is not None else nil,
+          _p(likes[1]) if likes is not None and likes[1].numel() else nil, C.c_int64(likes[1].numel() if likes is not None else 0), _p(ranks),
+          C.c_int32(slab_cols), _p(status))
+    status_check('knn_score', _KNN_SCORE_REFUSED, KnnRefused, int(status.item()))
+    return ids, scores, ranks
+
+
+def knn_score(hist_ptr, hist_cols, nbr_ids, nbr_w, K, *, col_of_item=None, n_cols=None, mask=None, mask_pitch=0, want_scores=False,
+              like_ptr=None, like_cols=None, slab_cols=None):
+    """K29 -> ids int32 [n_rows, K] (with want_scores: (ids, scores fp32 [n_rows, K]); with like_ptr / like_cols the ranks int32
+    [n_likes] come last; K = 0 with likes: the ranks alone).  hist_ptr / hist_cols: the liked catalogue items of every line (int64 /
+    int32, ascending and unique); nbr_ids / nbr_w: K28's table; col_of_item int32 [n_items] or None: the column of a catalogue item or
+    -1, with n_cols columns (None: the identity).  The score of a column is the fp32 chain over the history, in stored order, of the
+    weights with which its item is among the N nearest of a history item; lists and ranks are score_topk's and like_ranks's with that
+    score (include/tkr.h tkr_knn_score).  K above KNN_MAX_K is served as score_topk serves it: the best KNN_MAX_K, then the best of what
+    is left with the found columns added to a copy of the mask, and so on.  A refusal raises KnnRefused"""
+    what = 'knn_score'
+    n_rows = _knn_ptr(what, 'hist', hist_ptr, hist_cols)
+    dev = hist_ptr.device
+    _operand(what, 'nbr_ids', nbr_ids, torch.int32, 2, on=dev)
+    _operand(what, 'nbr_w', nbr_w, torch.float32, 2, numel=nbr_ids.numel(), on=dev)
+    n_items, N = int(nbr_ids.shape[0]), int(nbr_ids.shape[1])
+    if tuple(nbr_w.shape) != (n_items, N) or n_items < 1 or not 1 <= N <= KNN_MAX_N:
+        raise TkrError('%s: the table has shapes %s and %s; both must be (n_items, N), 1 <= N <= %d' % (what, tuple(nbr_ids.shape), tuple(nbr_w.shape),
+                                                                                                     KNN_MAX_N))
+    _operand(what, 'col_of_item', col_of_item, torch.int32, 1, numel=n_items, on=dev, optional=True)
+    n_cols = n_items if col_of_item is None and n_cols is None else n_cols
+    if not isinstance(n_cols, int) or isinstance(n_cols, bool) or n_cols < 1 or (col_of_item is None and n_cols != n_items):
+        raise ValueError('%s: n_cols = %r must be a positive integer, and the number of items without col_of_item' % (what, n_cols))
+    if (like_ptr is None) != (like_cols is None):
+        raise ValueError('%s: like_ptr and like_cols go together' % what)
+    if not isinstance(K, int) or isinstance(K, bool) or K < 0 or (K == 0 and like_ptr is None):
+        raise ValueError('%s: K = %r must be a positive integer (0 with likes: the ranks alone)' % (what, K))
+    likes = None
+    if like_ptr is not None:
+        if _knn_ptr(what, 'like', like_ptr, like_cols, on=dev) != n_rows:
+            raise TkrError('%s: like_ptr holds %d rows, hist_ptr %d' % (what, like_ptr.numel() - 1, n_rows))
+        likes = (like_ptr, like_cols)
+    if mask is not None:
+        _operand(what, 'mask', mask, torch.int32, at_least=((n_cols + 31) // 32) * mask_pitch, on=dev)
+        if mask_pitch < n_rows:
+            raise ValueError('%s: mask_pitch = %d is below the %d rows' % (what, mask_pitch, n_rows))
+    slab_cols = _knn_slab(what, slab_cols)
+    args = (hist_ptr, hist_cols, nbr_ids, nbr_w, n_items, N, col_of_item, n_cols)
+    if K <= KNN_MAX_K:
+        ids, scores, ranks = _knn_score_once(args, n_rows, K, mask, mask_pitch, want_scores, likes, slab_cols, dev)
+    else:
+        pitch = mask_pitch if mask is not None else (n_rows + 31) // 32 * 32
+        work = mask.clone() if mask is not None else torch.zeros(((n_cols + 31) // 32) * pitch, dtype=torch.int32, device=dev)
+        ptr = torch.arange(0, (n_rows + 1) * KNN_MAX_K, KNN_MAX_K, dtype=torch.int64, device=dev)
+        parts_i, parts_s, left, ranks = [], [], K, None
+        while left > 0:
+            first = not parts_i                       # the ranks are counted under the caller's mask: by the first launch
+            ids, scores, r = _knn_score_once(args, n_rows, KNN_MAX_K, work, pitch, want_scores, likes if first else None, slab_cols, dev)
+            ranks = r if first else ranks
+            take = min(left, KNN_MAX_K)
+            parts_i.append(ids[:, :take])
+            if want_scores:
+                parts_s.append(scores[:, :take])
+            left -= take
+            if left > 0:                              # found columns join the mask (negative ids = padding are skipped by the kernel)
+                _call('tkr_build_rated_mask', work, _p(ptr), _p(ids.reshape(-1)), C.c_int32(n_rows), C.c_int32(n_cols), _p(work), C.c_int32(pitch))
+        ids = torch.cat(parts_i, dim=1).contiguous()
+        scores = torch.cat(parts_s, dim=1).contiguous() if want_scores else None
+    result = tuple(x for x in (ids, scores if want_scores else None, ranks) if x is not None)
+    return result[0] if len(result) == 1 else result
+
+
+# ---- K22: a dense MLP content encoder, applied and trained (csrc/mlp.hip)------------------------------------------------------------------
 MLP_MAX_LAYERS = 5          # TKR_MLP_MAX_LAYERS of include/tkr.h
 MLP_MAX_BATCH = 256          # TKR_MLP_MAX_BATCH
 MLP_SLAB = 512               # TKR_MLP_SLAB: the inputs of a layer one workgroup sums
