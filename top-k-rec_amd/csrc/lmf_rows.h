@@ -5,8 +5,13 @@
 //   kLmfLogistic   L = sum_likes (1 - sigma(s)) y,  g = weight * L - D - lam x        (weight: alpha, the weight of a like)
 //   kSmfUnit       L = sum_likes y,                 g = L - D - lam x
 //   kSmfByLikes    L = sum_likes y,                 g = L - n D - lam x               (n: the likes the row stores, hi - lo)
+// Behind the kernels, lmf_step_entry: the host side of both step calls.
 #pragma once
 #include "lmf_parts.h"
+
+#include <math.h>
+
+#include <algorithm>
 
 namespace tkr {
 
@@ -205,6 +210,48 @@ static int lmf_launch_step(hipStream_t stream, const float* Y, int n_y, int K, c
         TKR_LAUNCH_CHECK();
     }
     return TKR_OK;
+}
+
+// The checked entry behind tkr_lmf_step_rows and tkr_smf_step_rows: the argument checks, the status word, the list of heavy rows and
+// the NR ladder.  The tables hold K = k + extra columns, k <= k_max; fixed_min: 0, or -1 where `fixed` may name no column.
+template <int MODE>
+static int lmf_step_entry(const float* Y, int32_t n_y, int32_t k, int32_t k_max, int extra, const float* D, const int64_t* like_ptr,
+                          const int32_t* like_cols, int64_t n_likes, int64_t n_x, int32_t fixed, int32_t fixed_min, double weight, double lam, double lr,
+                          int64_t heavy_from, float* X, float* H, double* row_loss, void* workspace, int64_t workspace_bytes, int64_t* status,
+                          void* stream_) {
+    if (!Y || !D || !like_ptr || !X || !H || !status || ((uintptr_t)Y & 3) || ((uintptr_t)D & 3) || ((uintptr_t)X & 3) || ((uintptr_t)H & 3) ||
+        ((uintptr_t)like_ptr & 7) || ((uintptr_t)like_cols & 3) || ((uintptr_t)status & 7) || ((uintptr_t)row_loss & 7) || ((uintptr_t)workspace & 15))
+        return TKR_EINVAL;
+    if (n_likes < 0 || (n_likes > 0 && !like_cols) || n_y < 1 || n_x < 1 || n_x > (int64_t)INT_MAX || heavy_from < 1 || workspace_bytes < 0)
+        return TKR_EINVAL;
+    if (!std::isfinite(weight) || !std::isfinite(lam) || !std::isfinite(lr) || lam < 0.0) return TKR_EINVAL;
+    TKR_CHECK_RC(als_check_k(k, k_max));
+    const int K = k + extra;
+    if (fixed < fixed_min || fixed >= K) return TKR_EINVAL;
+    int64_t cap = 0;                                              // listed rows, at most: each has more than heavy_from likes
+    if (heavy_from < n_likes) {
+        cap = std::min<int64_t>(n_x, n_likes / (heavy_from + 1));
+        if (!workspace || workspace_bytes < lmf_list_bytes(n_x)) return TKR_EINVAL;
+    }
+    hipStream_t stream = (hipStream_t)stream_;
+    unsigned long long* st = reinterpret_cast<unsigned long long*>(status);
+    TKR_CHECK(hipMemsetAsync(st, 0xff, sizeof(unsigned long long), stream));          // -1: nothing refused
+    int32_t* heavy_count = nullptr;
+    int32_t* heavy_list = nullptr;
+    if (cap > 0) {
+        heavy_count = reinterpret_cast<int32_t*>(workspace);
+        heavy_list = heavy_count + 4;
+        TKR_CHECK(hipMemsetAsync(heavy_count, 0, 16, stream));
+    }
+#define TKR_LMF_STEP(N)                                                                                                                      \
+    return lmf_launch_step<N, MODE>(stream, Y, n_y, K, D, like_ptr, like_cols, (long long)n_likes, (long long)n_x, fixed, weight, lam, (float)lr, \
+                                    (long long)heavy_from, X, H, row_loss, st, heavy_count, heavy_list, (long long)cap)
+    switch ((K + TKR_WAVE - 1) / TKR_WAVE) {
+        case 1: TKR_LMF_STEP(1);
+        case 2: TKR_LMF_STEP(2);
+        default: TKR_LMF_STEP(3);
+    }
+#undef TKR_LMF_STEP
 }
 
 }  // namespace tkr

@@ -26,39 +26,18 @@ slots, lam, lr, the seed and the iteration count are kept in smf.npz, so that a 
 """
 from __future__ import annotations
 
-import os
-import time
-
 import numpy as np
 import torch
 
-import foldin
-import textio
 import tkr_hip
-from single.rec import REC
-from utils import get_id_dict_from_file, tprint
+from adagrad_mf import AdagradMF, dense_room
 
 MAX_K = tkr_hip.SMF_MAX_K
 
 
-def _check_hyper(k, lam, lr):
-    if not isinstance(k, (int, np.integer)) or isinstance(k, bool) or not 1 <= k <= MAX_K:
-        raise ValueError('SMF: k = %r, 1 <= k <= %d is supported (TKR_SMF_MAX_K: a row block of the gradient lives in the registers of '
-                         'one workgroup)' % (k, MAX_K))
-    if not (np.isfinite(lam) and lam >= 0):
-        raise ValueError('SMF: lam = %r must be finite and not negative' % (lam,))
-    if not (np.isfinite(lr) and lr > 0):
-        raise ValueError('SMF: lr = %r must be positive and finite' % (lr,))
-
-
 def _work(work, X, Y):
-    """the workspace and the D and lse of X's shape, kept in the dict `work` between calls"""
-    k = int(X.shape[1]) - 1
-    ws = work['ws'] = tkr_hip.workspace_room(work.get('ws'), tkr_hip.smf_workspace_bytes(int(X.shape[0]), k, int(Y.shape[0])), X.device)
-    D = work.get(('D', X.shape))
-    if D is None or D.device != X.device:
-        D = work[('D', X.shape)] = torch.empty_like(X)
-    return ws, D
+    """the workspace and the D of X's shape, kept in the dict `work` between calls"""
+    return dense_room(work, X, Y, int(X.shape[1]) - 1, tkr_hip.smf_workspace_bytes)
 
 
 def user_step(X, H, Y, like_ptr, like_cols, *, lam, lr, heavy_from=None, want_loss=False, work=None):
@@ -85,58 +64,18 @@ def item_step(Y, H, X, log_n, like_ptr, like_cols, *, lam, lr, heavy_from=None, 
                                  workspace=ws, check=False)[1]
 
 
-class SMF(REC):
+class SMF(AdagradMF):
+    EXTRA, MAX_K = 1, MAX_K
+    REFUSED, RAISES = tkr_hip._SMF_REFUSED, tkr_hip.SmfRefused
+
     def __init__(self, k: int = 30, lam: float = 0.01, lr: float = 0.1) -> None:
-        _check_hyper(k, lam, lr)
-        self.__sn = 'smf'
-        self.k = int(k)
-        self.lam, self.lr = float(lam), float(lr)
-        self.uids = self.iids = None
-        self.n_users = self.n_items = self.n_likes = None
-        self.fue = self.fie = self.fib = None                         # factors [n, k], item biases [n_items, 1]
-        self.hu = self.hi = None                                      # the AdaGrad slots, [n_users, k + 1] and [n_items, k + 1]
-        self.seed = None
-        self.iters_done = 0
-        self.losses = []
-        self._csr = None                                              # host CSRs: (user ptr, user cols, item ptr, item cols)
-
-    # ------------------------------------------------------------------ data
-    def load_training_data(self, uid_file: str, iid_file: str, tr_file: str, seed=None) -> None:
-        tprint('Load training data from %s' % (tr_file))
-        self.uids = get_id_dict_from_file(uid_file)
-        self.iids = get_id_dict_from_file(iid_file)
-        self.n_users, self.n_items = len(self.uids), len(self.iids)
-        if self.n_users < 1 or self.n_items < 1:
-            raise ValueError('SMF: %s / %s list no users or no items' % (uid_file, iid_file))
-        R = textio.parse_ratings(tr_file, self.uids, self.iids)
-        up, uc = foldin.liked_csr(R, self.n_users, self.n_items, by='user')
-        ip, ic = foldin.liked_csr(R, self.n_items, self.n_users, by='item')
-        self._csr = (up, uc, ip, ic)
-        self.n_likes = int(len(uc))
-        rng = np.random.Generator(np.random.PCG64(seed))
-        self.seed = seed
-        self.fue = rng.standard_normal((self.n_users, self.k), dtype=np.float32) * np.float32(0.01)
-        self.fie = rng.standard_normal((self.n_items, self.k), dtype=np.float32) * np.float32(0.01)
-        self.fib = np.zeros((self.n_items, 1), dtype=np.float32)
-        self.hu = np.ones((self.n_users, self.k + 1), dtype=np.float32)
-        self.hi = np.ones((self.n_items, self.k + 1), dtype=np.float32)
-        self.iters_done = 0
-        tprint('Loading finished!')
-
-    def build_graph(self) -> None:
-        tprint('%s does not require build_graph method!' % self.__sn)
+        super().__init__(k, lam, lr)
 
     # ------------------------------------------------------------------ the augmented tables
     def _tables(self):
         """-> (users [n_users, k + 1] = [x, 1], items [n_items, k + 1] = [y, beta_i]), fp32 host arrays"""
         k = self.k
-        if self.fib is not None and np.size(self.fib) == self.n_items:
-            self.fib = np.asarray(self.fib, dtype=np.float32).reshape(-1, 1)
-        shapes = (('fue', self.fue, (self.n_users, k)), ('fie', self.fie, (self.n_items, k)), ('fib', self.fib, (self.n_items, 1)),
-                  ('hu', self.hu, (self.n_users, k + 1)), ('hi', self.hi, (self.n_items, k + 1)))
-        for name, table, shape in shapes:
-            if np.shape(table) != shape:
-                raise ValueError('SMF: %s has shape %s, the model needs %s' % (name, np.shape(table), shape))
+        self._check_shapes()
         Xa = np.ones((self.n_users, k + 1), dtype=np.float32)
         Ya = np.empty((self.n_items, k + 1), dtype=np.float32)
         Xa[:, :k] = self.fue
@@ -150,85 +89,27 @@ class SMF(REC):
         self.fie, self.fib = np.ascontiguousarray(Ya[:, :k]), np.ascontiguousarray(Ya[:, k:k + 1])
         self.hu, self.hi = Hx.cpu().numpy(), Hy.cpu().numpy()
 
-    # ------------------------------------------------------------------ train
-    def train(self, max_iter: int = 30, tol: float = None, model_path: str = None, verbose: bool = True, device=None, heavy_from=None) -> None:
-        if self._csr is None:
-            raise ValueError('SMF.train: load_training_data() first')
-        if model_path is not None and os.path.isdir(model_path):
-            self.import_embeddings(model_path)
-        device = foldin._device(device, 'SMF.train')
-        Xa, Ya = (foldin._upload(t, device, np.float32) for t in self._tables())
-        Hx, Hy = foldin._upload(self.hu, device, np.float32), foldin._upload(self.hi, device, np.float32)
-        up, uc, ip, ic = (foldin._upload(x, device) for x in self._csr)
-        n_u = (up[1:] - up[:-1]).double()                             # the users' like counts, and their logarithms: -inf for none
-        log_n = torch.log(n_u.float())
-        hyper = dict(lam=self.lam, lr=self.lr, heavy_from=heavy_from, work={})
-        loss, self.losses = np.exp(50), []
-        for it in range(max_iter):
-            t1 = time.time()
-            loss_old = loss
-            reg = 0.5 * self.lam * Ya.double().square().sum()         # F at the tables entering the iteration
-            lse, rows, su = user_step(Xa, Hx, Ya, up, uc, want_loss=True, **hyper)
-            total = (n_u * lse.double()).sum() + rows.sum() + reg
-            sv = item_step(Ya, Hy, Xa, log_n, ip, ic, **hyper)
-            down = torch.cat([total.reshape(1), su.double(), sv.double()]).cpu().numpy()      # one copy: the loss, the status words behind it
-            for word, what in zip(down[1:], ('the user step of iteration %d', 'the item step of iteration %d')):
-                tkr_hip.status_check('SMF.train, %s' % (what % it), tkr_hip._SMF_REFUSED, tkr_hip.SmfRefused, int(word))
-            loss = float(down[0])
-            if not np.isfinite(loss):
-                raise tkr_hip.TkrError('SMF.train: the loss of iteration %d is %r; lower lr (%g)' % (it, loss, self.lr))
-            self.losses.append(loss)
-            self.iters_done += 1
-            cond = abs(loss_old - loss) / loss_old
-            if verbose:
-                tprint('Iter %3d, loss %.6f, converge %.6f, time %.2fs' % (it, loss, cond, time.time() - t1))
-            if tol is not None and cond < tol:
-                break
-        self._take(Xa, Ya, Hx, Hy)
+    # ------------------------------------------------------------------ one iteration: F at the tables entering it, then the two steps
+    def _prepare(self, run, heavy_from):
+        run.n_u = (run.up[1:] - run.up[:-1]).double()                 # the users' like counts, and their logarithms: -inf for none
+        run.log_n = torch.log(run.n_u.float())
+        run.hyper = dict(lam=self.lam, lr=self.lr, heavy_from=heavy_from, work={})
+
+    def _iteration(self, run):
+        reg = 0.5 * self.lam * run.Ya.double().square().sum()         # F at the tables entering the iteration
+        lse, rows, su = user_step(run.Xa, run.Hx, run.Ya, run.up, run.uc, want_loss=True, **run.hyper)
+        total = (run.n_u * lse.double()).sum() + rows.sum() + reg
+        return total, su, item_step(run.Ya, run.Hy, run.Xa, run.log_n, run.ip, run.ic, **run.hyper)
 
     # ------------------------------------------------------------------ fold-in
     def fold_in(self, histories, steps: int = 30, device=None, heavy_from=None):
         """rows for users the model was not trained on, from the items they like: `steps` user half-steps (lse, dense, step) from zero
         rows (slots 1.0) against the frozen item table.  histories: a list of item-index sequences, one per user, or the (ptr, cols)
         pair of foldin.group_history.  -> rows fp32 [n_new, k].  A user without likes only shrinks: its row stays zero"""
-        if self.fie is None:
-            raise ValueError('SMF.fold_in: load_training_data() and train() first')
-        if not isinstance(steps, (int, np.integer)) or isinstance(steps, bool) or steps < 0:
-            raise ValueError('SMF.fold_in: steps = %r must be an integer, at least 0' % (steps,))
-        device = foldin._device(device, 'SMF.fold_in')
-        k = self.k
-        ptr, cols = histories if isinstance(histories, tuple) else foldin.history_csr(histories, self.n_items)
-        X = torch.zeros((len(ptr) - 1, k + 1), dtype=torch.float32, device=device)
-        if len(ptr) == 1:
-            return X[:, :k].cpu().numpy()
-        X[:, k] = 1
-        H = torch.ones_like(X)
-        Ya = foldin._upload(self._tables()[1], device, np.float32)
-        ptr, cols = foldin._upload(ptr, device), foldin._upload(cols, device)
-        work, words = {}, []
-        for _ in range(int(steps)):
-            words.append(user_step(X, H, Ya, ptr, cols, lam=self.lam, lr=self.lr, heavy_from=heavy_from, work=work)[2])
-        X = X.cpu().numpy()
-        for word in (torch.cat(words).cpu().numpy() if words else ()):
-            tkr_hip.status_check('SMF.fold_in', tkr_hip._SMF_REFUSED, tkr_hip.SmfRefused, int(word))
-        return np.ascontiguousarray(X[:, :k])
+        return np.ascontiguousarray(self._fold_in(histories, steps, device, heavy_from)[:, :self.k])
 
-    # ------------------------------------------------------------------ smf.npz
-    def export_model(self, model_path: str) -> None:
-        target = os.path.join(model_path, 'smf.npz')
-        tprint('Saving AdaGrad slots and hyper-parameters to %s' % target)
-        np.savez(target, hu=np.asarray(self.hu, dtype=np.float32), hi=np.asarray(self.hi, dtype=np.float32), lam=np.float64(self.lam),
-                 lr=np.float64(self.lr), seed=np.int64(-1 if self.seed is None else self.seed), iters=np.int64(self.iters_done))
+    def _fold_start(self, X):
+        X[:, self.k] = 1
 
-    def import_model(self, model_path: str) -> None:
-        source = os.path.join(model_path, 'smf.npz')
-        if not os.path.exists(source):
-            return
-        tprint('Loading AdaGrad slots from %s' % source)
-        with np.load(source) as z:
-            hu, hi = z['hu'].astype(np.float32), z['hi'].astype(np.float32)
-            want = ((self.n_users, self.k + 1), (self.n_items, self.k + 1))
-            if self.n_users is not None and (hu.shape, hi.shape) != want:
-                raise ValueError('SMF: %s holds arrays of shapes %s, the model needs %s' % (source, (hu.shape, hi.shape), want))
-            self.hu, self.hi = hu, hi
-            self.iters_done = int(z['iters'])
+    def _fold_step(self, X, H, Ya, ptr, cols, heavy_from, work):
+        return user_step(X, H, Ya, ptr, cols, lam=self.lam, lr=self.lr, heavy_from=heavy_from, work=work)[2]

@@ -1514,6 +1514,58 @@ def als_cg_rows(Y, G, like_ptr, like_cols, X, *, w_like, w_rhs, ridge, steps=ALS
     return _done(what, loss, status, check, _ALS_CG_REFUSED, AlsCgRefused)
 
 
+# ---- what K25 and K27 share: tables augmented by a few columns, D of X's shape beside a workspace, the step over a like CSR -------------------
+def _ws_bytes(workspace):
+    return C.c_int64(workspace.numel() * workspace.element_size())
+
+
+def _aug_tables(what, pairs, extra, max_k):
+    """pairs: (name, tensor), all fp32 [., k + extra] on one GPU -> k"""
+    k = None
+    for name, t in pairs:
+        _, K = _als_table(what, name, t, max_k + extra, None if k is None else k + extra)
+        if K < extra + 1:
+            raise ValueError('%s: %s has %d columns; a table holds k + %d of them, k >= 1' % (what, name, K, extra))
+        k = K - extra
+        _on_gpu(what, name, t, pairs[0][1].device)
+    return k
+
+
+def _aug_dense_out(what, X, Y, k, sizer, workspace, out):
+    """behind the operand checks of a *_dense_rows call -> (workspace, D): room for sizer(n_x, k, n_y) bytes; D of X's shape, `out` or new"""
+    workspace = workspace_room(workspace, sizer(int(X.shape[0]), k, int(Y.shape[0])), X.device)
+    D = torch.empty(tuple(X.shape), dtype=torch.float32, device=X.device) if out is None else out
+    _operand(what, 'out', D, torch.float32, 2, on=X.device)
+    if D.shape != X.shape:
+        raise TkrError('%s: out must have the shape of X, %s' % (what, tuple(X.shape)))
+    return workspace, D
+
+
+def _aug_step_rows(what, family, Y, D, like_ptr, like_cols, X, H, fixed, weight, lam, lr, heavy_from, want_loss, workspace, check):
+    """the body of lmf_step_rows and smf_step_rows, which call tkr_<what>.  family: (extra columns, max k, lowest `fixed`, the C type
+    of `weight`, the scalar between fixed and lam, the workspace's size call, heavy_from's default, the refusals' messages, their class)"""
+    extra, max_k, fixed_min, weight_type, sizer, heavy_default, messages, raises = family
+    k = _aug_tables(what, [('Y', Y), ('X', X), ('D', D), ('H', H)], extra, max_k)
+    n_y, n_x = int(Y.shape[0]), int(X.shape[0])
+    if D.shape != X.shape or H.shape != X.shape:
+        raise TkrError('%s: D and H must have the shape of X, %s' % (what, tuple(X.shape)))
+    _operand(what, 'like_ptr', like_ptr, torch.int64, 1, on=Y.device, raises=_STD)
+    _operand(what, 'like_cols', like_cols, torch.int32, 1, on=Y.device, raises=_STD)
+    if like_ptr.numel() != n_x + 1:
+        raise ValueError('%s: like_ptr must hold n_x + 1 = %d entries, not %d' % (what, n_x + 1, like_ptr.numel()))
+    if not isinstance(fixed, (int,)) or isinstance(fixed, bool) or not fixed_min <= fixed < k + extra:
+        raise ValueError('%s: fixed = %r must be a column, 0 <= fixed < %d%s' % (what, fixed, k + extra, ', or -1 for none' if fixed_min < 0 else ''))
+    n_likes = int(like_cols.numel())
+    heavy_from = heavy_default if heavy_from is None else int(heavy_from)
+    workspace = workspace_room(workspace, sizer(n_x, k, 1) if heavy_from < n_likes else 0, Y.device)
+    loss = torch.empty(n_x, dtype=torch.float64, device=Y.device) if want_loss else None
+    status = torch.empty(1, dtype=torch.int64, device=Y.device)
+    _call('tkr_' + what, Y, _p(Y), C.c_int32(n_y), C.c_int32(k), _p(D), _p(like_ptr), _p(like_cols) if n_likes else C.c_void_p(0),
+          C.c_int64(n_likes), C.c_int64(n_x), C.c_int32(fixed), weight_type(weight), C.c_double(lam), C.c_double(lr), C.c_int64(heavy_from), _p(X), _p(H),
+          _p(loss), _p(workspace), _ws_bytes(workspace), _p(status))
+    return _done(what, loss, status, check, messages, raises)
+
+
 # ---- K25: the two halves of a logistic-MF half-step (csrc/lmf.hip) --------------------------------------------------------------------------
 LMF_MAX_K = 128              # TKR_LMF_MAX_K of include/tkr.h: the tables hold k + 2 columns
 LMF_SLAB = 4096              # TKR_LMF_SLAB: the rows of Y one workgroup of lmf_dense_rows walks
@@ -1534,16 +1586,7 @@ def lmf_workspace_bytes(n_x, k, n_y):
     return _size('tkr_lmf_workspace_bytes', (C.c_int64, C.c_int32, C.c_int64), (n_x, k, n_y))
 
 
-def _lmf_tables(what, pairs):
-    """pairs: (name, tensor), all fp32 [., k + 2] on one GPU -> k"""
-    k = None
-    for name, t in pairs:
-        _, K = _als_table(what, name, t, LMF_MAX_K + 2, None if k is None else k + 2)
-        if K < 3:
-            raise ValueError('%s: %s has %d columns; a table holds k + 2 of them, k >= 1' % (what, name, K))
-        k = K - 2
-        _on_gpu(what, name, t, pairs[0][1].device)
-    return k
+_LMF_FAMILY = (2, LMF_MAX_K, 0, C.c_double, lmf_workspace_bytes, LMF_HEAVY_FROM, _LMF_REFUSED, LmfRefused)
 
 
 def lmf_dense_rows(X, Y, want_loss=False, workspace=None, out=None):
@@ -1551,16 +1594,11 @@ def lmf_dense_rows(X, Y, want_loss=False, workspace=None, out=None):
     (include/tkr.h tkr_lmf_dense_rows).  X fp32 [n_x, K], Y fp32 [n_y, K], K = k + 2 <= LMF_MAX_K + 2.  want_loss: -> (D, sp), sp
     float64 [n_x] = sum_c softplus(X[r] . Y[c]).  Nothing is read back"""
     what = 'lmf_dense_rows'
-    k = _lmf_tables(what, [('X', X), ('Y', Y)])
+    k = _aug_tables(what, [('X', X), ('Y', Y)], 2, LMF_MAX_K)
     n_x, n_y = int(X.shape[0]), int(Y.shape[0])
-    workspace = workspace_room(workspace, lmf_workspace_bytes(n_x, k, n_y), X.device)
-    D = torch.empty((n_x, k + 2), dtype=torch.float32, device=X.device) if out is None else out
-    _operand(what, 'out', D, torch.float32, 2, on=X.device)
-    if D.shape != X.shape:
-        raise TkrError('%s: out must have the shape of X, %s' % (what, tuple(X.shape)))
+    workspace, D = _aug_dense_out(what, X, Y, k, lmf_workspace_bytes, workspace, out)
     sp = torch.empty(n_x, dtype=torch.float64, device=X.device) if want_loss else None
-    _call('tkr_lmf_dense_rows', X, _p(X), C.c_int64(n_x), _p(Y), C.c_int64(n_y), C.c_int32(k), _p(D), _p(sp), _p(workspace),
-          C.c_int64(workspace.numel() * workspace.element_size()))
+    _call('tkr_lmf_dense_rows', X, _p(X), C.c_int64(n_x), _p(Y), C.c_int64(n_y), C.c_int32(k), _p(D), _p(sp), _p(workspace), _ws_bytes(workspace))
     return (D, sp) if want_loss else D
 
 
@@ -1570,26 +1608,7 @@ def lmf_step_rows(Y, D, like_ptr, like_cols, X, H, *, fixed, alpha, lam, lr, hea
     (include/tkr.h tkr_lmf_step_rows).  D: lmf_dense_rows(X, Y).  -> row_loss float64 [n_x] with want_loss, else None.  heavy_from:
     None = LMF_HEAVY_FROM.  A refusal raises LmfRefused naming row and kind; check=False returns (row_loss, status tensor) instead
     and reads nothing back"""
-    what = 'lmf_step_rows'
-    k = _lmf_tables(what, [('Y', Y), ('X', X), ('D', D), ('H', H)])
-    n_y, n_x = int(Y.shape[0]), int(X.shape[0])
-    if D.shape != X.shape or H.shape != X.shape:
-        raise TkrError('%s: D and H must have the shape of X, %s' % (what, tuple(X.shape)))
-    _operand(what, 'like_ptr', like_ptr, torch.int64, 1, on=Y.device, raises=_STD)
-    _operand(what, 'like_cols', like_cols, torch.int32, 1, on=Y.device, raises=_STD)
-    if like_ptr.numel() != n_x + 1:
-        raise ValueError('%s: like_ptr must hold n_x + 1 = %d entries, not %d' % (what, n_x + 1, like_ptr.numel()))
-    if not isinstance(fixed, (int,)) or isinstance(fixed, bool) or not 0 <= fixed < k + 2:
-        raise ValueError('%s: fixed = %r must be a column, 0 <= fixed < %d' % (what, fixed, k + 2))
-    n_likes = int(like_cols.numel())
-    heavy_from = LMF_HEAVY_FROM if heavy_from is None else int(heavy_from)
-    workspace = workspace_room(workspace, lmf_workspace_bytes(n_x, k, 1) if heavy_from < n_likes else 0, Y.device)
-    loss = torch.empty(n_x, dtype=torch.float64, device=Y.device) if want_loss else None
-    status = torch.empty(1, dtype=torch.int64, device=Y.device)
-    _call('tkr_lmf_step_rows', Y, _p(Y), C.c_int32(n_y), C.c_int32(k), _p(D), _p(like_ptr), _p(like_cols) if n_likes else C.c_void_p(0),
-          C.c_int64(n_likes), C.c_int64(n_x), C.c_int32(fixed), C.c_double(alpha), C.c_double(lam), C.c_double(lr), C.c_int64(heavy_from), _p(X),
-          _p(H), _p(loss), _p(workspace), C.c_int64(workspace.numel() * workspace.element_size()), _p(status))
-    return _done(what, loss, status, check, _LMF_REFUSED, LmfRefused)
+    return _aug_step_rows('lmf_step_rows', _LMF_FAMILY, Y, D, like_ptr, like_cols, X, H, fixed, alpha, lam, lr, heavy_from, want_loss, workspace, check)
 
 
 # ---- K27: the three parts of a softmax-MF half-step (csrc/smf.hip) ---------------------------------------------------------------------------
@@ -1610,27 +1629,14 @@ def smf_workspace_bytes(n_x, k, n_y):
     return _size('tkr_smf_workspace_bytes', (C.c_int64, C.c_int32, C.c_int64), (n_x, k, n_y))
 
 
-def _smf_tables(what, pairs):
-    """pairs: (name, tensor), all fp32 [., k + 1] on one GPU -> k"""
-    k = None
-    for name, t in pairs:
-        _, K = _als_table(what, name, t, SMF_MAX_K + 1, None if k is None else k + 1)
-        if K < 2:
-            raise ValueError('%s: %s has %d columns; a table holds k + 1 of them, k >= 1' % (what, name, K))
-        k = K - 1
-        _on_gpu(what, name, t, pairs[0][1].device)
-    return k
-
-
-def _ws_bytes(workspace):
-    return C.c_int64(workspace.numel() * workspace.element_size())
+_SMF_FAMILY = (1, SMF_MAX_K, -1, C.c_int32, smf_workspace_bytes, SMF_HEAVY_FROM, _SMF_REFUSED, SmfRefused)
 
 
 def smf_lse_rows(X, Y, workspace=None, out=None):
     """K27 -> lse fp32 [n_x] on the device: lse[r] = log sum over ALL rows c of Y of exp(X[r] . Y[c]), finite at any finite scores
     (include/tkr.h tkr_smf_lse_rows).  X fp32 [n_x, K], Y fp32 [n_y, K], K = k + 1 <= SMF_MAX_K + 1.  Nothing is read back"""
     what = 'smf_lse_rows'
-    k = _smf_tables(what, [('X', X), ('Y', Y)])
+    k = _aug_tables(what, [('X', X), ('Y', Y)], 1, SMF_MAX_K)
     n_x, n_y = int(X.shape[0]), int(Y.shape[0])
     workspace = workspace_room(workspace, smf_workspace_bytes(n_x, k, n_y), X.device)
     lse = torch.empty(n_x, dtype=torch.float32, device=X.device) if out is None else out
@@ -1644,15 +1650,11 @@ def smf_dense_rows(X, Y, row_off=None, col_off=None, workspace=None, out=None):
     score matrix never stored (include/tkr.h tkr_smf_dense_rows).  row_off fp32 [n_x], col_off fp32 [n_y]; None is 0, +inf is legal
     and makes the term +0.  Nothing is read back"""
     what = 'smf_dense_rows'
-    k = _smf_tables(what, [('X', X), ('Y', Y)])
+    k = _aug_tables(what, [('X', X), ('Y', Y)], 1, SMF_MAX_K)
     n_x, n_y = int(X.shape[0]), int(Y.shape[0])
     _operand(what, 'row_off', row_off, torch.float32, 1, numel=n_x, on=X.device, optional=True)
     _operand(what, 'col_off', col_off, torch.float32, 1, numel=n_y, on=X.device, optional=True)
-    workspace = workspace_room(workspace, smf_workspace_bytes(n_x, k, n_y), X.device)
-    D = torch.empty((n_x, k + 1), dtype=torch.float32, device=X.device) if out is None else out
-    _operand(what, 'out', D, torch.float32, 2, on=X.device)
-    if D.shape != X.shape:
-        raise TkrError('%s: out must have the shape of X, %s' % (what, tuple(X.shape)))
+    workspace, D = _aug_dense_out(what, X, Y, k, smf_workspace_bytes, workspace, out)
     _call('tkr_smf_dense_rows', X, _p(X), C.c_int64(n_x), _p(Y), C.c_int64(n_y), C.c_int32(k), _p(row_off), _p(col_off), _p(D), _p(workspace),
           _ws_bytes(workspace))
     return D
@@ -1664,26 +1666,8 @@ def smf_step_rows(Y, D, like_ptr, like_cols, X, H, *, fixed, scale_by_likes, lam
     its bits, -1 fixes none (include/tkr.h tkr_smf_step_rows).  D: smf_dense_rows(X, Y, ...).  -> row_loss float64 [n_x] with
     want_loss, else None.  heavy_from: None = SMF_HEAVY_FROM.  A refusal raises SmfRefused naming row and kind; check=False returns
     (row_loss, status tensor) instead and reads nothing back"""
-    what = 'smf_step_rows'
-    k = _smf_tables(what, [('Y', Y), ('X', X), ('D', D), ('H', H)])
-    n_y, n_x = int(Y.shape[0]), int(X.shape[0])
-    if D.shape != X.shape or H.shape != X.shape:
-        raise TkrError('%s: D and H must have the shape of X, %s' % (what, tuple(X.shape)))
-    _operand(what, 'like_ptr', like_ptr, torch.int64, 1, on=Y.device, raises=_STD)
-    _operand(what, 'like_cols', like_cols, torch.int32, 1, on=Y.device, raises=_STD)
-    if like_ptr.numel() != n_x + 1:
-        raise ValueError('%s: like_ptr must hold n_x + 1 = %d entries, not %d' % (what, n_x + 1, like_ptr.numel()))
-    if not isinstance(fixed, (int,)) or isinstance(fixed, bool) or not -1 <= fixed < k + 1:
-        raise ValueError('%s: fixed = %r must be a column, 0 <= fixed < %d, or -1 for none' % (what, fixed, k + 1))
-    n_likes = int(like_cols.numel())
-    heavy_from = SMF_HEAVY_FROM if heavy_from is None else int(heavy_from)
-    workspace = workspace_room(workspace, smf_workspace_bytes(n_x, k, 1) if heavy_from < n_likes else 0, Y.device)
-    loss = torch.empty(n_x, dtype=torch.float64, device=Y.device) if want_loss else None
-    status = torch.empty(1, dtype=torch.int64, device=Y.device)
-    _call('tkr_smf_step_rows', Y, _p(Y), C.c_int32(n_y), C.c_int32(k), _p(D), _p(like_ptr), _p(like_cols) if n_likes else C.c_void_p(0),
-          C.c_int64(n_likes), C.c_int64(n_x), C.c_int32(fixed), C.c_int32(1 if scale_by_likes else 0), C.c_double(lam), C.c_double(lr),
-          C.c_int64(heavy_from), _p(X), _p(H), _p(loss), _p(workspace), _ws_bytes(workspace), _p(status))
-    return _done(what, loss, status, check, _SMF_REFUSED, SmfRefused)
+    return _aug_step_rows('smf_step_rows', _SMF_FAMILY, Y, D, like_ptr, like_cols, X, H, fixed, 1 if scale_by_likes else 0, lam, lr, heavy_from, want_loss,
+                          workspace, check)
 
 
 # ---- K26: a sparse x dense product and CER's E-step by conjugate gradients (csrc/sparse.hip) ------------------------------------------------
