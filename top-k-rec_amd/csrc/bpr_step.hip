@@ -28,7 +28,6 @@
 #include "tkr_common.h"
 #include "../../include/tkr.h"
 
-extern "C" int tkr_plan_team(int32_t batch_size);
 
 namespace tkr {
 
@@ -562,7 +561,6 @@ __global__ __launch_bounds__(256) void step_loss_kernel(const int32_t* __restric
 }
 }  // namespace tkr
 
-extern "C" int tkr_plan_max_blocks(int32_t batch_size);
 
 static int check_state(const tkr_bpr_state* st) {
     if (!st || !st->U || !st->V || !st->b) return TKR_EINVAL;

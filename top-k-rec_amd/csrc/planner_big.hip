@@ -20,6 +20,7 @@
 
 #include "tkr_common.h"
 #include "sampler_draw.h"
+#include "plan_units.h"
 
 namespace tkr {
 
@@ -254,14 +255,10 @@ static BigLayout big_layout(char* base, size_t nB) {
 
 }  // namespace tkr
 
-extern "C" int tkr_plan_team(int32_t batch_size);
-extern "C" int tkr_plan_max_blocks(int32_t batch_size);
-
-extern "C" __attribute__((visibility("hidden"))) int64_t tkr_plan_workspace_bytes_for(int32_t batch_size, int32_t n_batches) {      // (a helper between translation units, not an entry point)
+TKR_UNIT int64_t tkr_plan_workspace_bytes_for(int32_t batch_size, int32_t n_batches) {
     if (batch_size <= 0 || n_batches <= 0) return 0;
     return (int64_t)tkr::big_layout(nullptr, (size_t)batch_size * n_batches).total_bytes;
 }
-extern "C" __attribute__((visibility("hidden"))) int64_t tkr_plan_mid_workspace_bytes(int32_t batch_size, int32_t n_batches);     // csrc/planner_mid.hip
 extern "C" int64_t tkr_plan_workspace_bytes(int32_t batch_size, int32_t n_batches) {
     static const int big_from = [] { const char* e = getenv("TKR_PLAN_BIG_FROM"); const int v = e ? atoi(e) : 0; return v > 0 ? v : 4096; }();
     const int64_t big = batch_size >= big_from ? tkr_plan_workspace_bytes_for(batch_size, n_batches) : 0;
@@ -270,7 +267,7 @@ extern "C" int64_t tkr_plan_workspace_bytes(int32_t batch_size, int32_t n_batche
 }
 
 // called by tkr_sample_plan for batch_size > 8192
-extern "C" __attribute__((visibility("hidden"))) int tkr_sample_plan_big(const int32_t* tr_users, int32_t n_tr, const int32_t* row_ptr, const int32_t* pos_cols,
+TKR_UNIT int tkr_sample_plan_big(const int32_t* tr_users, int32_t n_tr, const int32_t* row_ptr, const int32_t* pos_cols,
                                    const int32_t* cols_sorted, int32_t n_users, int32_t n_items, uint64_t seed,
                                    uint64_t first_triplet, const int64_t* ctl, int32_t n_batches, int32_t B, int32_t* ucnt,
                                    int32_t* icnt, uint32_t* touch_u, uint32_t* touch_i, int32_t* out_u, int32_t* out_i,

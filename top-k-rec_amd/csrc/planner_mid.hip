@@ -34,6 +34,7 @@
 #include "tkr_common.h"
 #include "sampler_draw.h"
 #include "plan_parts.h"
+#include "plan_units.h"
 
 namespace tkr {
 
@@ -885,13 +886,8 @@ extern "C" int tkr_debug_mid_prof(unsigned long long* out /*[32] host*/) {
     return hipMemcpyFromSymbol(out, HIP_SYMBOL(tkr::mid_prof), sizeof(unsigned long long) * 32) == hipSuccess ? 0 : -100;
 }
 #endif
-extern "C" int tkr_plan_team(int32_t batch_size);
-extern "C" int tkr_plan_max_blocks(int32_t batch_size);
-extern "C" __attribute__((visibility("hidden"))) int tkr_plan_commit(int32_t n_users, int32_t n_items, int32_t* ucnt, int32_t* icnt, uint32_t* touch_u,
-                                                                     uint32_t* touch_i, void* stream);       // csrc/sampler.hip: K1c
 
-// (helpers between translation units, not entry points)
-extern "C" __attribute__((visibility("hidden"))) int tkr_plan_mid_ok(int32_t n_users, int32_t n_items, int32_t B) {
+TKR_UNIT int tkr_plan_mid_ok(int32_t n_users, int32_t n_items, int32_t B) {
     static const int from = [] { const char* e = getenv("TKR_PLAN_MID_FROM"); const int v = e ? atoi(e) : 0; return v > 0 ? v : 1025; }();
     static const int upto = [] { const char* e = getenv("TKR_PLAN_MID_UPTO"); const int v = e ? atoi(e) : 0; return v > 0 ? v : tkr::kMidWideMaxB; }();
     if (B < from || B > upto || B > tkr::kMidWideMaxB) return 0;
@@ -901,13 +897,13 @@ extern "C" __attribute__((visibility("hidden"))) int tkr_plan_mid_ok(int32_t n_u
     const int G = g.gu + g.gi, worth = B / 128 > 16 ? B / 128 : 16;
     return G <= tkr::kMidMaxRanges && G <= worth;
 }
-extern "C" __attribute__((visibility("hidden"))) int64_t tkr_plan_mid_workspace_bytes(int32_t batch_size, int32_t n_batches) {
+TKR_UNIT int64_t tkr_plan_mid_workspace_bytes(int32_t batch_size, int32_t n_batches) {
     if (batch_size <= 1024 || batch_size > tkr::kMidWideMaxB || n_batches <= 0) return 0;
     const int64_t sums = (int64_t)n_batches * tkr::kMidMaxRanges * (int64_t)sizeof(int4);
     return tkr::mid_wide(batch_size) ? sums + (int64_t)n_batches * 3 * batch_size * 4 : sums;         // the wide form's occurrence lists
 }
 
-extern "C" __attribute__((visibility("hidden"))) int tkr_sample_plan_mid(
+TKR_UNIT int tkr_sample_plan_mid(
     const int32_t* tr_users, int32_t n_tr, const int32_t* row_ptr, const int32_t* pos_cols, const int32_t* cols_sorted, int32_t n_users,
     int32_t n_items, uint64_t seed, uint64_t first_triplet, const int64_t* ctl, int32_t n_batches, int32_t B, int32_t* ucnt, int32_t* icnt,
     uint32_t* touch_u, uint32_t* touch_i, int32_t* out_u, int32_t* out_i, int32_t* out_j, int32_t* task, int32_t* occ, int32_t* rec,

@@ -28,6 +28,7 @@
 namespace tkr { __device__ unsigned long long k1_prof[32]; }
 #define K1_STAMP(i) do { if (blockIdx.x == 0 && threadIdx.x == 0) tkr::k1_prof[i] = __builtin_amdgcn_s_memrealtime(); } while (0)
 #endif
+#include "plan_units.h"
 #include "plan_parts.h"      // the sorts, task heads, versions and record assembly: shared with the prologue of csrc/bpr_own.hip
 
 namespace tkr {
@@ -361,8 +362,7 @@ __global__ void rollback_kernel(const int4* __restrict__ task, size_t n_slots, i
 
 extern "C" int tkr_plan_team(int32_t batch_size) { return tkr::team_for(batch_size); }
 
-extern "C" __attribute__((visibility("hidden"))) int tkr_plan_commit(int32_t n_users, int32_t n_items, int32_t* ucnt, int32_t* icnt, uint32_t* touch_u,
-                                                                     uint32_t* touch_i, void* stream) {      // (for csrc/planner_mid.hip)
+TKR_UNIT int tkr_plan_commit(int32_t n_users, int32_t n_items, int32_t* ucnt, int32_t* icnt, uint32_t* touch_u, uint32_t* touch_i, void* stream) {
     const int rows = n_users + n_items;
     hipLaunchKernelGGL(tkr::commit_kernel, dim3((rows + 255) / 256), dim3(256), 0, (hipStream_t)stream, n_users, n_items, ucnt, icnt, touch_u, touch_i);
     TKR_LAUNCH_CHECK();
@@ -373,21 +373,6 @@ extern "C" int tkr_plan_max_blocks(int32_t batch_size) {
     const int lpb = tkr::light_per_block(batch_size);
     return (3 * batch_size + lpb - 1) / lpb + (3 * batch_size) / (tkr::light_max(batch_size) + 1);
 }
-
-extern "C" __attribute__((visibility("hidden"))) int64_t tkr_plan_workspace_bytes_for(int32_t batch_size, int32_t n_batches);       // csrc/planner_big.hip, any batch size
-extern "C" __attribute__((visibility("hidden"))) int tkr_plan_mid_ok(int32_t n_users, int32_t n_items, int32_t B);                  // csrc/planner_mid.hip
-extern "C" __attribute__((visibility("hidden"))) int64_t tkr_plan_mid_workspace_bytes(int32_t batch_size, int32_t n_batches);
-extern "C" __attribute__((visibility("hidden"))) int tkr_sample_plan_mid(
-    const int32_t* tr_users, int32_t n_tr, const int32_t* row_ptr, const int32_t* pos_cols, const int32_t* cols_sorted, int32_t n_users,
-    int32_t n_items, uint64_t seed, uint64_t first_triplet, const int64_t* ctl, int32_t n_batches, int32_t B, int32_t* ucnt, int32_t* icnt,
-    uint32_t* touch_u, uint32_t* touch_i, int32_t* out_u, int32_t* out_i, int32_t* out_j, int32_t* task, int32_t* occ, int32_t* rec,
-    int32_t* hdr, int32_t* occt, int32_t* tpar, void* workspace, int64_t workspace_bytes, void* stream);
-extern "C" __attribute__((visibility("hidden"))) int tkr_sample_plan_big(const int32_t* tr_users, int32_t n_tr, const int32_t* row_ptr, const int32_t* pos_cols,
-                                   const int32_t* cols_sorted, int32_t n_users, int32_t n_items, uint64_t seed,
-                                   uint64_t first_triplet, const int64_t* ctl, int32_t n_batches, int32_t B, int32_t* ucnt,
-                                   int32_t* icnt, uint32_t* touch_u, uint32_t* touch_i, int32_t* out_u, int32_t* out_i,
-                                   int32_t* out_j, int32_t* task, int32_t* occ, int32_t* rec, int32_t* hdr, int32_t* occt,
-                                   int32_t* tpar, void* workspace, int64_t workspace_bytes, void* stream);      // csrc/planner_big.hip
 
 static int sample_plan_impl(const int32_t* tr_users, int32_t n_tr, const int32_t* row_ptr,
                                const int32_t* pos_cols, const int32_t* cols_sorted, int32_t n_users,

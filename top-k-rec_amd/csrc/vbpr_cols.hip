@@ -41,24 +41,9 @@
 // hits: cem is 5 MB at d = 20,000); bench.py quotes the fraction on those bytes.
 #include <stdlib.h>
 
-#include "tkr_common.h"
-#include "../../include/tkr.h"
-#include "vbpr_rows.h"
-
-extern "C" int tkr_plan_team(int32_t batch_size);
-extern "C" int tkr_plan_max_blocks(int32_t batch_size);
-extern "C" int64_t tkr_vbpr_workspace_floats(int32_t batch_size, int32_t kh, int32_t d);
-extern "C" __attribute__((visibility("hidden"))) int64_t tkr_vbpr_workspace_core_floats(int32_t batch_size, int32_t kh, int32_t d);
+#include "vbpr_host.h"
 
 namespace tkr {
-// the generic form for any kh (csrc/vbpr_wide.hip)
-__attribute__((visibility("hidden"))) void vbpr_wide_project(const tkr_vbpr_state& st, const int32_t* ti, const int32_t* tj, const int32_t* tu, const int32_t* tp,
-                                                             const int32_t* tc, const int2* te, int tcap, int B, float* P, float* ab2, float* Wm,
-                                                             float* loss, hipStream_t s);
-__attribute__((visibility("hidden"))) int vbpr_wide_col_blocks(int d);
-__attribute__((visibility("hidden"))) void vbpr_wide_update(const tkr_vbpr_state& st, const int32_t* rec, const int2* occ2, const int32_t* occt, const int4* hdr4,
-                                                            const float* s_buf, const float* t_buf, const float* P, const float* Wm, const int4* colh,
-                                                            const int2* cent, int B, float* loss, hipStream_t s);
 
 // ------------------------------------------------------------------------------------------------------------------------------
 // K1-side: one workgroup per batch, wave w OWNS the columns [w*RW, (w+1)*RW) and their counters in LDS.  Every wave reads every
@@ -203,16 +188,15 @@ __global__ __launch_bounds__(W * 64) void vbpr_tproject_kernel(tkr_vbpr_state st
                                                            const int32_t* __restrict__ tpar, const int32_t* __restrict__ tcnt,
                                                            const int2* __restrict__ tent, int tcap, int B, float* __restrict__ P,
                                                            float* __restrict__ ab_out, float* __restrict__ Wraw,
-                                                           float* __restrict__ loss_out, int tune) {
+                                                           float* __restrict__ loss_out) {
     __shared__ float red[W][NH * 64 + 1];
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, t = blockIdx.x;
     const int kh = st.kh;
     const int2* list = tent + (size_t)t * tcap;
-    int n = tcnt[t];                                                   // same level as the speculative first round of entries
-    if (tune & 1) n = 0;                                               // (TKR_VBPR_TUNE: timing experiments, scripts/probe_vbpr.py)
+    const int n = tcnt[t];                                             // same level as the speculative first round of entries
     int2 ent = list[min(W * lane + wave, tcap - 1)];
     float ure[NH], uce[NH], vi[NH], vj[NH], bi = 0.f, bj = 0.f;
-    if (wave == 0 && !(tune & 2)) {
+    if (wave == 0) {
         const int pr = tpar[t], k2 = 2 * kh;
         const int u = tu[t], i = ti[t], j = tj[t];
         const float* urow = st.U + ((size_t)(pr & 1) * st.n_users + u) * k2;
@@ -386,7 +370,7 @@ __device__ __forceinline__ void col_accumulate(const int2* __restrict__ cent, in
 template <int LPC, class PS, int UNL = 4>
 __device__ __forceinline__ void col_block(const tkr_vbpr_state& st, const PS& ps, const float* __restrict__ Wraw,
                                           const int4* __restrict__ colh, const int2* __restrict__ cent, int cb, int cpb,
-                                          float* __restrict__ loss_out, int tune, float* shm) {
+                                          float* __restrict__ loss_out, float* shm) {
     constexpr int G = 256 / LPC;
     const int tid = threadIdx.x, grp = tid / LPC, gl = tid % LPC, lane = tid & 63;
     const int kh = st.kh, d = st.d;
@@ -408,7 +392,7 @@ __device__ __forceinline__ void col_block(const tkr_vbpr_state& st, const PS& ps
         bv0 = st.icb[c];
         bms0 = st.msicb[c];
     }
-    const int n = (tune & 4) ? 0 : h0.x, beg = h0.y;
+    const int n = h0.x, beg = h0.y;
     float4 g = make_float4(0.f, 0.f, 0.f, 0.f);
     float gi = 0.f;
     // ---- light runs: the group alone; entries 0..2 came with the header, the others four in flight
@@ -486,7 +470,7 @@ __device__ __forceinline__ void col_block(const tkr_vbpr_state& st, const PS& ps
     // ---- TF's dense ApplyRMSProp on cem[c][.] and icb[c] (vbpr.py:65,67,73), exactly as V3 / S3 of csrc/vbpr_step.hip
     const bool l2 = st.mode == 0;
     float lpart = 0.f;
-    if (own && live && !(tune & 16)) {
+    if (own && live) {
         float gv[4] = {g.x, g.y, g.z, g.w}, v[4] = {pv.x, pv.y, pv.z, pv.w}, ms[4] = {pms.x, pms.y, pms.z, pms.w};
 #pragma unroll
         for (int x = 0; x < 4; ++x) {
@@ -526,7 +510,7 @@ __global__ __launch_bounds__(256) void vbpr_update_kernel(
     const int4* __restrict__ hdr, const float* __restrict__ s_in, const float* __restrict__ t_in, const float* __restrict__ P,
     const float* __restrict__ Wraw /*[B][kh]: uce_u(t)*/, const int4* __restrict__ colh, const int2* __restrict__ cent,
     int n_row_blocks, int n_col_blocks, int cpb, float* __restrict__ loss_out /*the batch's loss words: [B] projection | [B] pair sums | [column blocks]*/,
-    int ps_B /*batch size*/, int tune) {
+    int ps_B /*batch size*/) {
     constexpr int G = 256 / LPC;
     constexpr int ROWS_LDS = 2 * 4 * (NE * TKR_WAVE + 1);
     constexpr int COLS_LDS = G * (4 * LPC + 1) + 2 * G;
@@ -534,33 +518,30 @@ __global__ __launch_bounds__(256) void vbpr_update_kernel(
     typedef float (*red_t)[NE * TKR_WAVE + 1];
     const PairSumArrays ps{s_in, t_in};
     if ((int)blockIdx.x < n_row_blocks) {
-        if (tune & 8) return;
         vbpr_rows_body<NE, 4>(st, rec_all, occ, occt, hdr, ps, P, nullptr, nullptr, nullptr, reinterpret_cast<red_t>(shm),
                               reinterpret_cast<red_t>(shm + 4 * (NE * TKR_WAVE + 1)), blockIdx.x, n_row_blocks);
         return;
     }
-    col_block<LPC, PairSumArrays, UNL>(st, ps, Wraw, colh, cent, (int)blockIdx.x - n_row_blocks, cpb, loss_out ? loss_out + 2 * ps_B : nullptr, tune, shm);
+    col_block<LPC, PairSumArrays, UNL>(st, ps, Wraw, colh, cent, (int)blockIdx.x - n_row_blocks, cpb, loss_out ? loss_out + 2 * ps_B : nullptr, shm);
 }
 
+template <int NH, int W>
+static void launch_tproject(const tkr_vbpr_state& st, const VbprBatch& bt, const VbprCarve& c, float* loss, hipStream_t stream) {
+    hipLaunchKernelGGL((vbpr_tproject_kernel<NH, W>), dim3(bt.B), dim3(W * 64), 0, stream, st, bt.ti, bt.tj, bt.tu, bt.tp, bt.tcnt, bt.tent, bt.tcap, bt.B,
+                       c.P, c.ab2, c.Wm, loss);
+}
+
+// cpb of the 256 / LPC column groups of a block own a column
 template <int NE, int LPC>
-static void launch_update(const tkr_vbpr_state& st, const int32_t* rec, const int2* occ2, const int32_t* occt, const int4* hdr4,
-                          const float* s_buf, const float* t_buf, const float* P, const float* Wm, const int4* colh, const int2* cent,
-                          int B, int cpb, float* loss, hipStream_t stream, int tune, bool long_runs) {
-    constexpr int G = 256 / LPC;
-    if (cpb <= 0 || cpb > G) cpb = G;
-    const int n_row_blocks = vbpr_grid(B, 4);
+static void launch_update(const tkr_vbpr_state& st, const VbprBatch& bt, const VbprCarve& c, float* loss, hipStream_t stream, int cpb, bool long_runs) {
+    const int n_row_blocks = vbpr_grid(bt.B, 4);
     const int n_col_blocks = (st.d + cpb - 1) / cpb;
-    if (long_runs)           // a narrow dense feat: every column's run is split over the block's groups, 16 entries in flight (168 registers; 32: slower, 21.5 vs 19.7 us)
-        hipLaunchKernelGGL((vbpr_update_kernel<NE, LPC, 16>), dim3(n_row_blocks + n_col_blocks), dim3(256), 0, stream, st, rec, occ2, occt, hdr4,
-                           s_buf, t_buf, P, Wm, colh, cent, n_row_blocks, n_col_blocks, cpb, loss, B, tune);
-    else
-        hipLaunchKernelGGL((vbpr_update_kernel<NE, LPC>), dim3(n_row_blocks + n_col_blocks), dim3(256), 0, stream, st, rec, occ2, occt, hdr4,
-                           s_buf, t_buf, P, Wm, colh, cent, n_row_blocks, n_col_blocks, cpb, loss, B, tune);
+    // long runs (a narrow dense feat): every column's run is split over the block's groups, 16 entries in flight (168 registers; 32: slower, 21.5 vs 19.7 us)
+    auto kernel = long_runs ? vbpr_update_kernel<NE, LPC, 16> : vbpr_update_kernel<NE, LPC>;
+    hipLaunchKernelGGL(kernel, dim3(n_row_blocks + n_col_blocks), dim3(256), 0, stream, st, bt.rec, bt.occ2, bt.occt, bt.hdr4, c.s_buf, c.t_buf, c.P, c.Wm,
+                       bt.colh, bt.cent, n_row_blocks, n_col_blocks, cpb, loss, bt.B);
 }
 
-}  // namespace tkr
-
-namespace tkr {
 // loss_out[b] += the `count` loss words of batch b: one per triplet from the projection, one per triplet from the pair sums, one per
 // column block of the update -- plain stores of their tasks (64 spread atomic slots cost the step 2.9 of 25.7 us: ~5,500 atomics per
 // batch, each a memory operation its wave's next load waits behind).  Fixed order: thread t adds words t, t + 256, ..., then the
@@ -626,83 +607,58 @@ extern "C" int tkr_vbpr_run_cols(const tkr_vbpr_state* st, const int32_t* tri_i,
                                  const int32_t* colh, const int32_t* cent, const int32_t* tcnt, const int32_t* tent, int32_t row_cap,
                                  int32_t cols_per_block, int32_t batch_size, int32_t n_batches, float* workspace, float* loss_out,
                                  void* stream) {
-    if (!st || !st->U || !st->msU || !st->I || !st->msI || !st->irb || !st->msirb || !st->cem || !st->mscem || !st->icb || !st->msicb)
-        return TKR_EINVAL;
-    if (st->n_users <= 0 || st->n_items <= 0 || st->kh <= 0 || st->d <= 0) return TKR_EINVAL;
+    using namespace tkr;
+    TKR_CHECK_RC(vbpr_state_check(st));
     if (!tri_i || !tri_j || !rec || !occ || !hdr || !occt || !tri_u || !tpar || !colh || !cent || !tcnt || !tent || !workspace ||
         batch_size <= 0 || n_batches < 0 || row_cap <= 0)
         return TKR_EINVAL;
     if (batch_size > 1024) return TKR_EUNSUPPORTED;
     const bool wide = st->kh > 128 || (st->kh & 3);               // the generic form (csrc/vbpr_wide.hip): any kh
-    const int B = batch_size, kh = st->kh, tcap = 2 * row_cap;
-    const size_t stride_r = (size_t)tkr_plan_max_blocks(B) * tkr_plan_team(B) * 16;
-    const size_t stride_o = (size_t)3 * B;
-    if (tkr_vbpr_workspace_core_floats(B, kh, st->d) < (int64_t)B * (6 + 2 * kh)) return TKR_EINVAL;
-    float* s_buf = workspace;                                        // S_t [B] | T_t [B] | alpha, beta, e^alpha, e^beta [4B] | P [B][kh] | uce rows [B][kh]
-    float* t_buf = s_buf + B;
-    float* ab2 = t_buf + B;
-    float* P = ab2 + 4 * (size_t)B;
-    float* Wm = P + (size_t)B * kh;
+    const int B = batch_size, kh = st->kh;
+    const VbprPlan plan{tri_i, tri_j, rec, occ, hdr, occt, tri_u, tpar, colh, cent, tcnt, tent, row_cap};
+    const VbprCarve c = vbpr_carve(workspace, B, kh, st->d, true);
+    const int64_t core = tkr_vbpr_workspace_core_floats(B, kh, st->d);
+    if (core < c.floats) return TKR_EINVAL;
     const int NH = (kh + 63) / 64, NE = (2 * kh + 63) / 64;
     hipStream_t s = (hipStream_t)stream;
-    static const int tune = getenv("TKR_VBPR_TUNE") ? atoi(getenv("TKR_VBPR_TUNE")) : 0;      // timing experiments only (results invalid)
     static const int pw_env = getenv("TKR_VBPR_PWAVES") ? atoi(getenv("TKR_VBPR_PWAVES")) : 0;
     // waves per triplet of the projection: enough that a triplet's gather list (2 rows of feat) is one round of <= 32 gathers per wave
     if (pw_env && pw_env != 4 && pw_env != 8 && pw_env != 16) return TKR_EINVAL;       // the instantiated team sizes
     int pw = pw_env ? pw_env : (row_cap <= 64 ? 4 : (row_cap <= 128 || B > 256 ? 8 : 16));
     if (NH == 2 && pw > 8) pw = 8;          // kh > 64: two registers per gathered row and wave -- the 16-wave team is not instantiated there:
                                             // two rounds of gathers per wave instead of one (was a silent fall-through)
+    // a column group is LPC lanes of a float4 each; cpb of a block's 256 / LPC groups own a column
+    const int lpc = kh <= 16 ? 4 : (kh <= 32 ? 8 : (kh <= 64 ? 16 : 32));
+    const int cpb = (cols_per_block <= 0 || cols_per_block > 256 / lpc) ? 256 / lpc : cols_per_block;
     // the loss words of the call's batches: behind the step's own scratch, every word written by its task (nothing to zero)
-    const int lpc_ = kh <= 16 ? 4 : (kh <= 32 ? 8 : (kh <= 64 ? 16 : 32));
-    const int cpb_ = (cols_per_block <= 0 || cols_per_block > 256 / lpc_) ? 256 / lpc_ : cols_per_block;
-    const int n_col_blocks = wide ? tkr::vbpr_wide_col_blocks(st->d) : (st->d + cpb_ - 1) / cpb_;
+    const int n_col_blocks = wide ? vbpr_wide_col_blocks(st->d) : (st->d + cpb - 1) / cpb;
     const size_t loss_stride = (size_t)2 * B + n_col_blocks;
-    float* slots = loss_out ? workspace + tkr_vbpr_workspace_core_floats(B, kh, st->d) : nullptr;
-    if (slots && (n_batches > 512 || (int64_t)n_batches * (int64_t)loss_stride > tkr_vbpr_workspace_floats(B, kh, st->d) - tkr_vbpr_workspace_core_floats(B, kh, st->d)))
-        return TKR_EUNSUPPORTED;
-    const bool long_runs = 2.0 * B * (double)row_cap / st->d > (double)tkr::kLightRun;      // (row_cap: the longest row of feat)
+    float* slots = loss_out ? workspace + core : nullptr;
+    if (slots && (n_batches > 512 || (int64_t)n_batches * (int64_t)loss_stride > tkr_vbpr_workspace_floats(B, kh, st->d) - core)) return TKR_EUNSUPPORTED;
+    const bool long_runs = 2.0 * B * (double)row_cap / st->d > (double)kLightRun;      // (row_cap: the longest row of feat)
     for (int b = 0; b < n_batches; ++b) {
-        const int32_t* ti = tri_i + (size_t)b * B;
-        const int32_t* tj = tri_j + (size_t)b * B;
-        const int32_t* tu = tri_u + (size_t)b * B;
-        const int32_t* tp = tpar + (size_t)b * B;
-        const int32_t* r = rec + b * stride_r;
-        const int2* o2 = reinterpret_cast<const int2*>(occ + b * stride_o * 2);
-        const int4* h4 = reinterpret_cast<const int4*>(hdr + (size_t)b * 4);
-        const int32_t* ot = occt + b * stride_o;
-        const int4* ch = reinterpret_cast<const int4*>(colh) + (size_t)b * st->d * 2;
-        const int2* ce = reinterpret_cast<const int2*>(cent) + (size_t)b * B * tcap;
-        const int32_t* tc = tcnt + (size_t)b * B;
-        const int2* te = reinterpret_cast<const int2*>(tent) + (size_t)b * B * tcap;
+        const VbprBatch bt = vbpr_batch(plan, st->d, b, B);
         float* l = slots ? slots + (size_t)b * loss_stride : nullptr;
-        if (wide) {
-            tkr::vbpr_wide_project(*st, ti, tj, tu, tp, tc, te, tcap, B, P, ab2, Wm, l, s);
-            hipLaunchKernelGGL(tkr::vbpr_pairsum_kernel, dim3((B + 3) / 4), dim3(256), 0, s, ab2, B, s_buf, t_buf, l);
-            tkr::vbpr_wide_update(*st, r, o2, ot, h4, s_buf, t_buf, P, Wm, ch, ce, B, l, s);
-            TKR_LAUNCH_CHECK();
-            continue;
+        if (wide) vbpr_wide_project(*st, bt, c, l, s);
+        else if (NH == 1 && pw == 4) launch_tproject<1, 4>(*st, bt, c, l, s);
+        else if (NH == 1 && pw == 8) launch_tproject<1, 8>(*st, bt, c, l, s);
+        else if (NH == 1) launch_tproject<1, 16>(*st, bt, c, l, s);
+        else if (pw == 4) launch_tproject<2, 4>(*st, bt, c, l, s);
+        else launch_tproject<2, 8>(*st, bt, c, l, s);
+        hipLaunchKernelGGL(vbpr_pairsum_kernel, dim3((B + 3) / 4), dim3(256), 0, s, c.ab2, B, c.s_buf, c.t_buf, l);
+        if (wide) vbpr_wide_update(*st, bt, c, l, s);
+        else switch (lpc) {                                       // NE = ceil(2 kh / 64) of the row tasks at this LPC's widths
+            case 4: launch_update<1, 4>(*st, bt, c, l, s, cpb, long_runs); break;
+            case 8: launch_update<1, 8>(*st, bt, c, l, s, cpb, long_runs); break;
+            case 16: launch_update<2, 16>(*st, bt, c, l, s, cpb, long_runs); break;
+            default:
+                if (NE <= 3) launch_update<3, 32>(*st, bt, c, l, s, cpb, long_runs);
+                else launch_update<4, 32>(*st, bt, c, l, s, cpb, long_runs);
         }
-        if (tune & 64) {
-        } else if (NH == 1 && pw == 4) hipLaunchKernelGGL((tkr::vbpr_tproject_kernel<1, 4>), dim3(B), dim3(256), 0, s, *st, ti, tj, tu, tp, tc, te, tcap, B, P, ab2, Wm, l, tune);
-        else if (NH == 1 && pw == 8) hipLaunchKernelGGL((tkr::vbpr_tproject_kernel<1, 8>), dim3(B), dim3(512), 0, s, *st, ti, tj, tu, tp, tc, te, tcap, B, P, ab2, Wm, l, tune);
-        else if (NH == 1) hipLaunchKernelGGL((tkr::vbpr_tproject_kernel<1, 16>), dim3(B), dim3(1024), 0, s, *st, ti, tj, tu, tp, tc, te, tcap, B, P, ab2, Wm, l, tune);
-        else if (pw == 4) hipLaunchKernelGGL((tkr::vbpr_tproject_kernel<2, 4>), dim3(B), dim3(256), 0, s, *st, ti, tj, tu, tp, tc, te, tcap, B, P, ab2, Wm, l, tune);
-        else hipLaunchKernelGGL((tkr::vbpr_tproject_kernel<2, 8>), dim3(B), dim3(512), 0, s, *st, ti, tj, tu, tp, tc, te, tcap, B, P, ab2, Wm, l, tune);
-        if (!(tune & 32)) hipLaunchKernelGGL(tkr::vbpr_pairsum_kernel, dim3((B + 3) / 4), dim3(256), 0, s, ab2, B, s_buf, t_buf, l);
-        if (tune & 128) continue;
-        const int lpc = kh <= 16 ? 4 : (kh <= 32 ? 8 : (kh <= 64 ? 16 : 32));
-#define TKR_UPD(NE_, LPC_) tkr::launch_update<NE_, LPC_>(*st, r, o2, ot, h4, s_buf, t_buf, P, Wm, ch, ce, B, cols_per_block, l, s, tune, long_runs)
-        switch (lpc) {
-            case 4: TKR_UPD(1, 4); break;
-            case 8: TKR_UPD(1, 8); break;
-            case 16: if (NE == 1) TKR_UPD(1, 16); else TKR_UPD(2, 16); break;
-            default: if (NE <= 3) TKR_UPD(3, 32); else TKR_UPD(4, 32); break;
-        }
-#undef TKR_UPD
         TKR_LAUNCH_CHECK();
     }
     if (slots && n_batches > 0) {
-        hipLaunchKernelGGL(tkr::vbpr_loss_sum_kernel, dim3(n_batches), dim3(256), 0, s, slots, loss_stride, (int)loss_stride, loss_out);
+        hipLaunchKernelGGL(vbpr_loss_sum_kernel, dim3(n_batches), dim3(256), 0, s, slots, loss_stride, (int)loss_stride, loss_out);
         TKR_LAUNCH_CHECK();
     }
     return TKR_OK;

@@ -41,22 +41,11 @@
 // fp32 MFMA (V1 + V3) against 2*4d B = 160 KB of feature rows per triplet read twice from HBM/MALL
 // and 16*d*kh B = 20 MB of dense optimizer traffic per batch: MFMA and HBM ceilings are within 10 %
 // of each other, both reported by bench.
-#include "tkr_common.h"
-#include "../../include/tkr.h"
-#include "vbpr_rows.h"
-
-extern "C" int tkr_plan_team(int32_t batch_size);
-extern "C" int tkr_plan_max_blocks(int32_t batch_size);
-extern "C" int64_t tkr_vbpr_workspace_floats(int32_t batch_size, int32_t kh, int32_t d);
-extern "C" __attribute__((visibility("hidden"))) int64_t tkr_vbpr_workspace_core_floats(int32_t batch_size, int32_t kh, int32_t d);
+#include "vbpr_host.h"
 
 namespace tkr {
 
 typedef float f32x16 __attribute__((ext_vector_type(16)));
-
-constexpr int kSlice = 128;                      // d-columns per split-K slice of V1 (64 per MFMA k-slot)
-
-__host__ __device__ inline int vbpr_slices(int d) { return (d + kSlice - 1) / kSlice; }
 
 // ------------------------------------------------------------------------------------------------
 // V1: Ppart[s][t][0..kh) = sum_{c in slice s} (f_i[c]-f_j[c]) * cem[c][.],  Ppart[s][t][kh] = same with icb
@@ -632,47 +621,36 @@ __global__ __launch_bounds__(256) void vbpr_sdense_kernel(tkr_vbpr_state st, con
     }
 }
 
-
-template <int NT, int TEAM, bool kBig = false>
-static int launch_vbpr_t(const tkr_vbpr_state& st, const int32_t* ti, const int32_t* tj, const int32_t* rec,
-                         const int32_t* occ, const int32_t* hdr, const int32_t* occt, int B, float* ws, float* loss,
-                         hipStream_t stream, const int32_t* tu, const int32_t* tpar) {
-    const int kh = st.kh, S = vbpr_slices(st.d);
-    float* ppart = ws;
-    float* s_buf = ppart + (size_t)S * B * (kh + 1);
-    float* P = s_buf + B;
-    float* Wm = P + (size_t)B * kh;
-    float* Q = Wm + (size_t)B * kh;
-    float* ab2 = ws + tkr_vbpr_workspace_core_floats(B, kh, st.d) - 5 * (size_t)B;      // alpha, beta, e^alpha, e^beta [B] of the batch
-    float* t_buf = ab2 + 4 * (size_t)B;                                            // T_t (s_buf holds S_t)
-    const int2* occ2 = reinterpret_cast<const int2*>(occ);
-    const int4* hdr4 = reinterpret_cast<const int4*>(hdr);
+// one batch of the five launches, kh <= 128
+template <int NT, int TEAM, bool kBig>
+static int launch_vbpr_t(const tkr_vbpr_state& st, const VbprBatch& bt, const VbprCarve& c, float* loss, hipStream_t stream) {
+    const int B = bt.B, kh = st.kh, S = vbpr_slices(st.d);
     const dim3 rgrid(vbpr_grid(B, TEAM)), rblock(TEAM * 64);
     const int NH = (kh + 63) / 64, NE = (2 * kh + 63) / 64;
     const bool sparse = st.f_ptr != nullptr;
-    float* Aw = nullptr;
-    float* ab = nullptr;
+    float* Aw = sparse ? c.Aw : nullptr;                  // the per-item sums A, a: only S3 reads them
+    float* ab = sparse ? c.ab : nullptr;
     if (sparse) {
-        Aw = Q + B;
-        ab = Aw + (size_t)tkr_plan_max_blocks(B) * TEAM * kh;
         // with the per-triplet parities of K1 the projection also scores the triplet: no per-occurrence launch
-        if (NH == 1) hipLaunchKernelGGL(vbpr_sproject_kernel<1>, dim3(B), dim3(256), 0, stream, st, ti, tj, B, P, Q, tu, tpar, ab2, Wm, loss);
-        else hipLaunchKernelGGL(vbpr_sproject_kernel<2>, dim3(B), dim3(256), 0, stream, st, ti, tj, B, P, Q, tu, tpar, ab2, Wm, loss);
+        if (NH == 1) hipLaunchKernelGGL(vbpr_sproject_kernel<1>, dim3(B), dim3(256), 0, stream, st, bt.ti, bt.tj, B, c.P, c.Q, bt.tu, bt.tp, c.ab2, c.Wm, loss);
+        else hipLaunchKernelGGL(vbpr_sproject_kernel<2>, dim3(B), dim3(256), 0, stream, st, bt.ti, bt.tj, B, c.P, c.Q, bt.tu, bt.tp, c.ab2, c.Wm, loss);
     } else {
-        hipLaunchKernelGGL(vbpr_project_kernel<NT>, dim3(S, (B + 31) / 32), dim3(64), 0, stream, st, ti, tj, B, ppart);
-        hipLaunchKernelGGL(vbpr_reduce_kernel, dim3(B), dim3(1024), 0, stream, ppart, S, B, kh, P, Q);
+        hipLaunchKernelGGL(vbpr_project_kernel<NT>, dim3(S, (B + 31) / 32), dim3(64), 0, stream, st, bt.ti, bt.tj, B, c.ppart);
+        hipLaunchKernelGGL(vbpr_reduce_kernel, dim3(B), dim3(1024), 0, stream, c.ppart, S, B, kh, c.P, c.Q);
     }
-    if (!(sparse && tpar)) {
-        if (NH == 1) hipLaunchKernelGGL((vbpr_occur_kernel<1, TEAM, kBig>), rgrid, rblock, 0, stream, st, rec, occ2, occt, hdr4, B, Q, ab2, P, Wm, loss);
-        else hipLaunchKernelGGL((vbpr_occur_kernel<2, TEAM, kBig>), rgrid, rblock, 0, stream, st, rec, occ2, occt, hdr4, B, Q, ab2, P, Wm, loss);
+    if (!(sparse && bt.tp)) {
+        if (NH == 1) hipLaunchKernelGGL((vbpr_occur_kernel<1, TEAM, kBig>), rgrid, rblock, 0, stream, st, bt.rec, bt.occ2, bt.occt, bt.hdr4, B, c.Q, c.ab2, c.P, c.Wm, loss);
+        else hipLaunchKernelGGL((vbpr_occur_kernel<2, TEAM, kBig>), rgrid, rblock, 0, stream, st, bt.rec, bt.occ2, bt.occt, bt.hdr4, B, c.Q, c.ab2, c.P, c.Wm, loss);
     }
-    hipLaunchKernelGGL(vbpr_pair_kernel, dim3((B + 3) / 4), dim3(256), 0, stream, ab2, B, kh, s_buf, t_buf, Wm, loss);
+    hipLaunchKernelGGL(vbpr_pair_kernel, dim3((B + 3) / 4), dim3(256), 0, stream, c.ab2, B, kh, c.s_buf, c.t_buf, c.Wm, loss);
+#define TKR_ROWS(NE_) hipLaunchKernelGGL((vbpr_rows_kernel<NE_, TEAM, kBig>), rgrid, rblock, 0, stream, st, bt.rec, bt.occ2, bt.occt, bt.hdr4, c.s_buf, c.t_buf, c.P, c.Wm, Aw, ab)
     switch (NE) {
-        case 1: hipLaunchKernelGGL((vbpr_rows_kernel<1, TEAM, kBig>), rgrid, rblock, 0, stream, st, rec, occ2, occt, hdr4, s_buf, t_buf, P, Wm, Aw, ab); break;
-        case 2: hipLaunchKernelGGL((vbpr_rows_kernel<2, TEAM, kBig>), rgrid, rblock, 0, stream, st, rec, occ2, occt, hdr4, s_buf, t_buf, P, Wm, Aw, ab); break;
-        case 3: hipLaunchKernelGGL((vbpr_rows_kernel<3, TEAM, kBig>), rgrid, rblock, 0, stream, st, rec, occ2, occt, hdr4, s_buf, t_buf, P, Wm, Aw, ab); break;
-        default: hipLaunchKernelGGL((vbpr_rows_kernel<4, TEAM, kBig>), rgrid, rblock, 0, stream, st, rec, occ2, occt, hdr4, s_buf, t_buf, P, Wm, Aw, ab); break;
+        case 1: TKR_ROWS(1); break;
+        case 2: TKR_ROWS(2); break;
+        case 3: TKR_ROWS(3); break;
+        default: TKR_ROWS(4); break;
     }
+#undef TKR_ROWS
     if (sparse) {
         if (NH == 1) hipLaunchKernelGGL(vbpr_sdense_kernel<1>, dim3((st.d + 3) / 4), dim3(256), 0, stream, st, Aw, ab, loss);
         else hipLaunchKernelGGL(vbpr_sdense_kernel<2>, dim3((st.d + 3) / 4), dim3(256), 0, stream, st, Aw, ab, loss);
@@ -684,64 +662,30 @@ static int launch_vbpr_t(const tkr_vbpr_state& st, const int32_t* ti, const int3
         hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(dense), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
         if (e != hipSuccess) return (int)e;
     }
-    hipLaunchKernelGGL(dense, dim3((st.d + 63) / 64), dim3(256), lds, stream, st, ti, tj, B, s_buf, Wm, loss);
+    hipLaunchKernelGGL(dense, dim3((st.d + 63) / 64), dim3(256), lds, stream, st, bt.ti, bt.tj, B, c.s_buf, c.Wm, loss);
     return (int)hipGetLastError();
 }
 
 template <int NT>
-static int launch_vbpr(const tkr_vbpr_state& st, const int32_t* ti, const int32_t* tj, const int32_t* rec,
-                       const int32_t* occ, const int32_t* hdr, const int32_t* occt, int B, float* ws, float* loss,
-                       hipStream_t stream, const int32_t* tu, const int32_t* tpar) {
-    // above 65,536 the records' 16-bit triplet halves no longer hold an index: the first four come from occt (vbpr_rows.h read_rec)
-    const bool big = B > 65536;
-#define TKR_LV(T) (big ? launch_vbpr_t<NT, T, true>(st, ti, tj, rec, occ, hdr, occt, B, ws, loss, stream, tu, tpar) \
-                       : launch_vbpr_t<NT, T>(st, ti, tj, rec, occ, hdr, occt, B, ws, loss, stream, tu, tpar))
-    switch (tkr_plan_team(B)) {                    // csrc/plan_parts.h team_for
-        case 4: return TKR_LV(4);
-        case 8: return TKR_LV(8);
-        default: return TKR_LV(16);
-    }
-#undef TKR_LV
+static int launch_vbpr(const tkr_vbpr_state& st, const VbprBatch& bt, const VbprCarve& c, float* loss, hipStream_t stream) {
+    return vbpr_team_dispatch(bt.B, [&](auto team, auto big) {
+        return launch_vbpr_t<NT, decltype(team)::value, decltype(big)::value>(st, bt, c, loss, stream);
+    });
 }
 
-// kh > 128 (csrc/vbpr_wide.hip): the generic form of the sparse view on the same records and the same carve of the workspace
-__attribute__((visibility("hidden"))) void vbpr_gen_front(const tkr_vbpr_state& st, const int32_t* ti, const int32_t* tj, const int32_t* rec,
-                                                          const int2* occ2, const int32_t* occt, const int4* hdr4, int B, int team,
-                                                          const int32_t* tu, const int32_t* tpar, float* P, float* Q, float* ab2, float* Wm,
-                                                          float* loss, hipStream_t s);
-__attribute__((visibility("hidden"))) void vbpr_gen_back(const tkr_vbpr_state& st, const int32_t* rec, const int2* occ2, const int32_t* occt,
-                                                         const int4* hdr4, int B, int team, const float* s_buf, const float* t_buf, const float* P,
-                                                         const float* Wm, float* Aw, float* ab, float* loss, hipStream_t s);
-
-static int launch_vbpr_gen(const tkr_vbpr_state& st, const int32_t* ti, const int32_t* tj, const int32_t* rec, const int32_t* occ,
-                           const int32_t* hdr, const int32_t* occt, int B, float* ws, float* loss, hipStream_t stream, const int32_t* tu,
-                           const int32_t* tpar) {
-    const int kh = st.kh, S = vbpr_slices(st.d), team = tkr_plan_team(B);
-    float* s_buf = ws + (size_t)S * B * (kh + 1);                                   // the carve of launch_vbpr_t
-    float* P = s_buf + B;
-    float* Wm = P + (size_t)B * kh;
-    float* Q = Wm + (size_t)B * kh;
-    float* Aw = Q + B;
-    float* ab = Aw + (size_t)tkr_plan_max_blocks(B) * team * kh;
-    float* ab2 = ws + tkr_vbpr_workspace_core_floats(B, kh, st.d) - 5 * (size_t)B;
-    float* t_buf = ab2 + 4 * (size_t)B;
-    const int2* occ2 = reinterpret_cast<const int2*>(occ);
-    const int4* hdr4 = reinterpret_cast<const int4*>(hdr);
-    vbpr_gen_front(st, ti, tj, rec, occ2, occt, hdr4, B, team, tu, tpar, P, Q, ab2, Wm, loss, stream);
-    hipLaunchKernelGGL(vbpr_pair_kernel, dim3((B + 3) / 4), dim3(256), 0, stream, ab2, B, kh, s_buf, t_buf, Wm, loss);
-    vbpr_gen_back(st, rec, occ2, occt, hdr4, B, team, s_buf, t_buf, P, Wm, Aw, ab, loss, stream);
+// kh > 128 (csrc/vbpr_wide.hip): the generic form of the sparse view on the same records and the same carve
+static int launch_vbpr_gen(const tkr_vbpr_state& st, const VbprBatch& bt, const VbprCarve& c, float* loss, hipStream_t stream) {
+    vbpr_gen_front(st, bt, c, loss, stream);
+    hipLaunchKernelGGL(vbpr_pair_kernel, dim3((bt.B + 3) / 4), dim3(256), 0, stream, c.ab2, bt.B, st.kh, c.s_buf, c.t_buf, c.Wm, loss);
+    vbpr_gen_back(st, bt, c, loss, stream);
     return (int)hipGetLastError();
 }
 
 }  // namespace tkr
 
-extern "C" int tkr_plan_max_blocks(int32_t batch_size);
-
 // the step's own scratch ...
 extern "C" __attribute__((visibility("hidden"))) int64_t tkr_vbpr_workspace_core_floats(int32_t batch_size, int32_t kh, int32_t d) {
-    const int64_t S = tkr::vbpr_slices(d);
-    const int64_t slots = (int64_t)tkr_plan_max_blocks(batch_size) * tkr_plan_team(batch_size);     // sparse view: A, a per item task
-    return S * batch_size * (kh + 1) + 2ll * batch_size + 2ll * batch_size * kh + slots * (kh + 1) + 5ll * batch_size;
+    return tkr::vbpr_carve(nullptr, batch_size, kh, d, false).floats;
 }
 // ... and behind it the loss words of up to 512 batches of a call: 64 spread slots per batch for this file's kernels (tkr_common.h
 // loss_add_spread), one word per triplet (twice) and per column block for the column-plan step (csrc/vbpr_cols.hip: no atomics)
@@ -782,38 +726,29 @@ extern "C" int tkr_vbpr_run(const tkr_vbpr_state* st, const int32_t* tri_i, cons
                             const int32_t* occ, const int32_t* hdr, const int32_t* occt, const int32_t* tri_u,
                             const int32_t* tpar, int32_t batch_size, int32_t n_batches, float* workspace, float* loss_out,
                             void* stream) {
-    if (!st || !st->U || !st->msU || !st->I || !st->msI || !st->irb || !st->msirb || !st->cem || !st->mscem ||
-        !st->icb || !st->msicb || !st->feat)
-        return TKR_EINVAL;
-    if (st->n_users <= 0 || st->n_items <= 0 || st->kh <= 0 || st->d <= 0) return TKR_EINVAL;
+    TKR_CHECK_RC(tkr::vbpr_state_check(st));
+    if (!st->feat) return TKR_EINVAL;
     if (!tri_i || !tri_j || !rec || !occ || !hdr || !occt || !workspace || batch_size <= 0 || n_batches < 0) return TKR_EINVAL;
     // kh > 128: the generic form of the sparse view (csrc/vbpr_wide.hip); the dense MFMA view (f_ptr == NULL) holds at most 128 factors
     // in its tiles and stays unsupported there (single/_engine.py takes the CSR view whenever k // 2 > 128).  Any batch size: above
     // 65,536 the first four triplet indices of a launch record come from occt instead of its 16-bit halves (vbpr_rows.h read_rec)
     if (st->kh > 128 && !st->f_ptr) return TKR_EUNSUPPORTED;
     if (st->f_ptr && (!st->f_col || !st->f_val || !st->c_ptr || !st->c_item || !st->c_val || !st->item_tag)) return TKR_EINVAL;
-    const size_t stride_r = (size_t)tkr_plan_max_blocks(batch_size) * tkr_plan_team(batch_size) * 16;
-    const size_t stride_o = (size_t)3 * batch_size;
+    const tkr::VbprPlan plan{tri_i, tri_j, rec, occ, hdr, occt, tri_u, tpar, nullptr, nullptr, nullptr, nullptr, 0};
+    const tkr::VbprCarve c = tkr::vbpr_carve(workspace, batch_size, st->kh, st->d, false);
+    hipStream_t s = (hipStream_t)stream;
     const int NT = (st->kh + 31) / 32;
     tkr::LossSlots ls;
-    TKR_CHECK_RC(ls.begin(workspace + tkr_vbpr_workspace_core_floats(batch_size, st->kh, st->d), loss_out, n_batches, (hipStream_t)stream));
+    TKR_CHECK_RC(ls.begin(workspace + c.floats, loss_out, n_batches, s));
     for (int b = 0; b < n_batches; ++b) {
-        const int32_t* ti = tri_i + (size_t)b * batch_size;
-        const int32_t* tj = tri_j + (size_t)b * batch_size;
-        const int32_t* r = rec + b * stride_r;
-        const int32_t* o = occ + b * stride_o * 2;
-        const int32_t* h = hdr + (size_t)b * 4;
-        const int32_t* ot = occt + b * stride_o;
-        const int32_t* tu = (tri_u && tpar) ? tri_u + (size_t)b * batch_size : nullptr;
-        const int32_t* tp = (tri_u && tpar) ? tpar + (size_t)b * batch_size : nullptr;
-        float* l = ls.of(b);
+        const tkr::VbprBatch bt = tkr::vbpr_batch(plan, st->d, b, batch_size);
         int rc;
-        if (st->kh > 128) rc = tkr::launch_vbpr_gen(*st, ti, tj, r, o, h, ot, batch_size, workspace, l, (hipStream_t)stream, tu, tp);
+        if (st->kh > 128) rc = tkr::launch_vbpr_gen(*st, bt, c, ls.of(b), s);
         else switch (NT) {
-            case 1: rc = tkr::launch_vbpr<1>(*st, ti, tj, r, o, h, ot, batch_size, workspace, l, (hipStream_t)stream, tu, tp); break;
-            case 2: rc = tkr::launch_vbpr<2>(*st, ti, tj, r, o, h, ot, batch_size, workspace, l, (hipStream_t)stream, tu, tp); break;
-            case 3: rc = tkr::launch_vbpr<3>(*st, ti, tj, r, o, h, ot, batch_size, workspace, l, (hipStream_t)stream, tu, tp); break;
-            default: rc = tkr::launch_vbpr<4>(*st, ti, tj, r, o, h, ot, batch_size, workspace, l, (hipStream_t)stream, tu, tp); break;
+            case 1: rc = tkr::launch_vbpr<1>(*st, bt, c, ls.of(b), s); break;
+            case 2: rc = tkr::launch_vbpr<2>(*st, bt, c, ls.of(b), s); break;
+            case 3: rc = tkr::launch_vbpr<3>(*st, bt, c, ls.of(b), s); break;
+            default: rc = tkr::launch_vbpr<4>(*st, bt, c, ls.of(b), s); break;
         }
         if (rc != 0) return rc;
     }

@@ -12,9 +12,7 @@
 //   L2 vbpr_pairsum_kernel        (csrc/vbpr_cols.hip)
 //   W3 vbpr_wide_update_kernel    row blocks: a wave per launch record (wave 0 of a heavy team walks the whole team), factor by factor;
 //                                 column blocks: a wave per feature column, TF's dense ApplyRMSProp on cem[c][.] and icb[c]
-#include "tkr_common.h"
-#include "../../include/tkr.h"
-#include "vbpr_rows.h"
+#include "vbpr_host.h"
 
 namespace tkr {
 
@@ -194,12 +192,11 @@ __global__ __launch_bounds__(256) void vbpr_wide_update_kernel(tkr_vbpr_state st
 }
 
 // one batch of the generic form; the pair-sum launch between the two is the caller's (csrc/vbpr_cols.hip)
-__attribute__((visibility("hidden"))) void vbpr_wide_project(const tkr_vbpr_state& st, const int32_t* ti, const int32_t* tj, const int32_t* tu, const int32_t* tp,
-                                                             const int32_t* tc, const int2* te, int tcap, int B, float* P, float* ab2, float* Wm,
-                                                             float* loss, hipStream_t s) {
-    hipLaunchKernelGGL(vbpr_wide_project_kernel, dim3(B), dim3(256), (size_t)tcap * sizeof(int2), s, st, ti, tj, tu, tp, tc, te, tcap, B, P, ab2, Wm, loss);
+void vbpr_wide_project(const tkr_vbpr_state& st, const VbprBatch& bt, const VbprCarve& c, float* loss, hipStream_t s) {
+    hipLaunchKernelGGL(vbpr_wide_project_kernel, dim3(bt.B), dim3(256), (size_t)bt.tcap * sizeof(int2), s, st, bt.ti, bt.tj, bt.tu, bt.tp, bt.tcnt, bt.tent,
+                       bt.tcap, bt.B, c.P, c.ab2, c.Wm, loss);
 }
-__attribute__((visibility("hidden"))) int vbpr_wide_col_blocks(int d) { return (d + 3) / 4; }
+int vbpr_wide_col_blocks(int d) { return (d + 3) / 4; }
 
 // ------------------------------------------------------------------------------------------------------------------------------
 // The generic form of the five-launch sparse view (csrc/vbpr_step.hip S1 / V1b / V1p / V2 / S3) for kh > 128: the batches the column
@@ -518,51 +515,28 @@ __global__ __launch_bounds__(256) void vbpr_gen_sdense_kernel(tkr_vbpr_state st,
     }
 }
 
-// one batch of the generic sparse view: G1 (+ G2 without tpar) in front of the pair launch, G3 + G4 behind it (csrc/vbpr_step.hip)
-template <int kVTeam, bool kBig>
-static void gen_front_t(const tkr_vbpr_state& st, const int32_t* rec, const int2* occ2, const int32_t* occt, const int4* hdr4, int B, const float* Q,
-                        float* ab2, const float* P, float* Wm, float* loss, hipStream_t s) {
-    hipLaunchKernelGGL((vbpr_gen_occur_kernel<kVTeam, kBig>), dim3(vbpr_grid(B, kVTeam)), dim3(kVTeam * 64), 0, s, st, rec, occ2, occt, hdr4, B, Q, ab2,
-                       P, Wm, loss);
+// one batch of the generic sparse view: G1 (+ G2 without parities) in front of the pair launch, G3 + G4 behind it (csrc/vbpr_step.hip)
+void vbpr_gen_front(const tkr_vbpr_state& st, const VbprBatch& bt, const VbprCarve& c, float* loss, hipStream_t s) {
+    hipLaunchKernelGGL(vbpr_gen_project_kernel, dim3(bt.B), dim3(256), 0, s, st, bt.ti, bt.tj, bt.B, c.P, c.Q, bt.tu, bt.tp, c.ab2, c.Wm, loss);
+    if (bt.tp) return;                                  // with K1's per-triplet parities the projection also scored the triplet
+    vbpr_team_dispatch(bt.B, [&](auto team, auto big) {
+        constexpr int T = decltype(team)::value;
+        hipLaunchKernelGGL((vbpr_gen_occur_kernel<T, decltype(big)::value>), dim3(vbpr_grid(bt.B, T)), dim3(T * 64), 0, s, st, bt.rec, bt.occ2, bt.occt,
+                           bt.hdr4, bt.B, c.Q, c.ab2, c.P, c.Wm, loss);
+    });
 }
-template <int kVTeam, bool kBig>
-static void gen_rows_t(const tkr_vbpr_state& st, const int32_t* rec, const int2* occ2, const int32_t* occt, const int4* hdr4, int B, const float* s_buf,
-                       const float* t_buf, const float* P, const float* Wm, float* Aw, float* ab, hipStream_t s) {
-    hipLaunchKernelGGL((vbpr_gen_rows_kernel<kVTeam, kBig>), dim3(vbpr_grid(B, kVTeam)), dim3(kVTeam * 64), 0, s, st, rec, occ2, occt, hdr4, s_buf,
-                       t_buf, P, Wm, Aw, ab);
+void vbpr_gen_back(const tkr_vbpr_state& st, const VbprBatch& bt, const VbprCarve& c, float* loss, hipStream_t s) {
+    vbpr_team_dispatch(bt.B, [&](auto team, auto big) {
+        constexpr int T = decltype(team)::value;
+        hipLaunchKernelGGL((vbpr_gen_rows_kernel<T, decltype(big)::value>), dim3(vbpr_grid(bt.B, T)), dim3(T * 64), 0, s, st, bt.rec, bt.occ2, bt.occt,
+                           bt.hdr4, c.s_buf, c.t_buf, c.P, c.Wm, c.Aw, c.ab);
+    });
+    hipLaunchKernelGGL(vbpr_gen_sdense_kernel, dim3((st.d + 3) / 4), dim3(256), 0, s, st, c.Aw, c.ab, loss);
 }
-__attribute__((visibility("hidden"))) void vbpr_gen_front(const tkr_vbpr_state& st, const int32_t* ti, const int32_t* tj, const int32_t* rec,
-                                                          const int2* occ2, const int32_t* occt, const int4* hdr4, int B, int team,
-                                                          const int32_t* tu, const int32_t* tpar, float* P, float* Q, float* ab2, float* Wm,
-                                                          float* loss, hipStream_t s) {
-    hipLaunchKernelGGL(vbpr_gen_project_kernel, dim3(B), dim3(256), 0, s, st, ti, tj, B, P, Q, tu, tpar, ab2, Wm, loss);
-    if (tpar) return;                                   // with K1's per-triplet parities the projection also scored the triplet
-    const bool big = B > 65536;                         // the records' 16-bit triplet halves no longer hold an index: occt (read_rec)
-#define TKR_GEN(T) (big ? gen_front_t<T, true>(st, rec, occ2, occt, hdr4, B, Q, ab2, P, Wm, loss, s) \
-                        : gen_front_t<T, false>(st, rec, occ2, occt, hdr4, B, Q, ab2, P, Wm, loss, s))
-    if (team == 4) TKR_GEN(4);
-    else if (team == 8) TKR_GEN(8);
-    else TKR_GEN(16);
-#undef TKR_GEN
-}
-__attribute__((visibility("hidden"))) void vbpr_gen_back(const tkr_vbpr_state& st, const int32_t* rec, const int2* occ2, const int32_t* occt,
-                                                         const int4* hdr4, int B, int team, const float* s_buf, const float* t_buf, const float* P,
-                                                         const float* Wm, float* Aw, float* ab, float* loss, hipStream_t s) {
-    const bool big = B > 65536;
-#define TKR_GEN(T) (big ? gen_rows_t<T, true>(st, rec, occ2, occt, hdr4, B, s_buf, t_buf, P, Wm, Aw, ab, s) \
-                        : gen_rows_t<T, false>(st, rec, occ2, occt, hdr4, B, s_buf, t_buf, P, Wm, Aw, ab, s))
-    if (team == 4) TKR_GEN(4);
-    else if (team == 8) TKR_GEN(8);
-    else TKR_GEN(16);
-#undef TKR_GEN
-    hipLaunchKernelGGL(vbpr_gen_sdense_kernel, dim3((st.d + 3) / 4), dim3(256), 0, s, st, Aw, ab, loss);
-}
-__attribute__((visibility("hidden"))) void vbpr_wide_update(const tkr_vbpr_state& st, const int32_t* rec, const int2* occ2, const int32_t* occt, const int4* hdr4,
-                                                            const float* s_buf, const float* t_buf, const float* P, const float* Wm, const int4* colh,
-                                                            const int2* cent, int B, float* loss, hipStream_t s) {
-    const int n_row_blocks = vbpr_grid(B, 4), n_col_blocks = vbpr_wide_col_blocks(st.d);
-    hipLaunchKernelGGL(vbpr_wide_update_kernel, dim3(n_row_blocks + n_col_blocks), dim3(256), 0, s, st, rec, occ2, occt, hdr4, s_buf, t_buf, P, Wm, colh, cent,
-                       n_row_blocks, n_col_blocks, loss, B);
+void vbpr_wide_update(const tkr_vbpr_state& st, const VbprBatch& bt, const VbprCarve& c, float* loss, hipStream_t s) {
+    const int n_row_blocks = vbpr_grid(bt.B, 4), n_col_blocks = vbpr_wide_col_blocks(st.d);
+    hipLaunchKernelGGL(vbpr_wide_update_kernel, dim3(n_row_blocks + n_col_blocks), dim3(256), 0, s, st, bt.rec, bt.occ2, bt.occt, bt.hdr4, c.s_buf, c.t_buf, c.P,
+                       c.Wm, bt.colh, bt.cent, n_row_blocks, n_col_blocks, loss, bt.B);
 }
 
 }  // namespace tkr

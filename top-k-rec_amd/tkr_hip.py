@@ -395,12 +395,16 @@ def vbpr_workspace_floats(B, kh, d):
     return int(lib().tkr_vbpr_workspace_floats(C.c_int32(B), C.c_int32(kh), C.c_int32(d)))
 
 
-def vbpr_run(state, plan, B, n_batches, workspace, loss_out=None, first=0):
+def _vbpr_plan_at(plan, B, first):
+    """tri_i, tri_j, rec, occ, hdr, occt, tri_u, tpar of a plan at batch `first` (tpar: NULL for a plan without K1's parities)"""
     rs = plan_max_blocks(B) * plan_team(B) * 16
-    _call('tkr_vbpr_run', plan.rec, C.byref(state), _at(plan.i, first * B), _at(plan.j, first * B), _at(plan.rec, first * rs),
-                              _at(plan.occ, first * 6 * B), _at(plan.hdr, first * 4), _at(plan.occt, first * 3 * B),
-                              _at(plan.u, first * B), _at(getattr(plan, 'tpar', None), first * B), C.c_int32(B),
-                              C.c_int32(n_batches), _p(workspace), _at(loss_out, first))
+    return (_at(plan.i, first * B), _at(plan.j, first * B), _at(plan.rec, first * rs), _at(plan.occ, first * 6 * B), _at(plan.hdr, first * 4),
+            _at(plan.occt, first * 3 * B), _at(plan.u, first * B), _at(getattr(plan, 'tpar', None), first * B))
+
+
+def vbpr_run(state, plan, B, n_batches, workspace, loss_out=None, first=0):
+    _call('tkr_vbpr_run', plan.rec, C.byref(state), *_vbpr_plan_at(plan, B, first), C.c_int32(B), C.c_int32(n_batches), _p(workspace),
+          _at(loss_out, first))
 
 
 def vbpr_colplan_lds_bytes(B, d):
@@ -417,13 +421,10 @@ def vbpr_colplan(sparse, d, plan, B, n_batches, row_cap):
 
 
 def vbpr_run_cols(state, plan, B, n_batches, workspace, d, row_cap, cols_per_block=0, loss_out=None, first=0):
-    rs = plan_max_blocks(B) * plan_team(B) * 16
     ent = B * 2 * row_cap * 2
-    _call('tkr_vbpr_run_cols', plan.rec, C.byref(state), _at(plan.i, first * B), _at(plan.j, first * B), _at(plan.rec, first * rs),
-          _at(plan.occ, first * 6 * B), _at(plan.hdr, first * 4), _at(plan.occt, first * 3 * B), _at(plan.u, first * B),
-          _at(plan.tpar, first * B), _at(plan.colh, first * d * 8), _at(plan.cent, first * ent), _at(plan.tcnt, first * B),
-          _at(plan.tent, first * ent), C.c_int32(row_cap), C.c_int32(cols_per_block), C.c_int32(B), C.c_int32(n_batches), _p(workspace),
-          _at(loss_out, first))
+    _call('tkr_vbpr_run_cols', plan.rec, C.byref(state), *_vbpr_plan_at(plan, B, first), _at(plan.colh, first * d * 8), _at(plan.cent, first * ent),
+          _at(plan.tcnt, first * B), _at(plan.tent, first * ent), C.c_int32(row_cap), C.c_int32(cols_per_block), C.c_int32(B), C.c_int32(n_batches),
+          _p(workspace), _at(loss_out, first))
 
 
 # ---- K4 / K5 -------------------------------------------------------------------------------------
