@@ -1,4 +1,5 @@
-"""NumPy restatement of K28 and K29 (include/tkr.h tkr_knn_build / tkr_knn_score), bit for bit: the oracle of tests/test_gpu_knn.py.
+"""NumPy restatement of K28 and K29 (include/tkr.h tkr_knn_build / tkr_knn_score), bit for bit: the oracle of tests/test_gpu_knn.py and
+tests/test_gpu_knn_wide.py.
 
   C = X^T X in int64; sim = fp32(C / (fl64(norm_i norm_j) + shrink)), every operation rounded on its own; the canonical order is a
   stable argsort read backwards (score descending, ties -> the higher column first); a score is the ascending fp32 chain over the
@@ -58,10 +59,27 @@ def build(u_ptr, u_cols, n_items, norm, shrink, N):
     ids = np.full((n_items, N), -1, np.int32)
     w = np.zeros((n_items, N), np.float32)
     for i in range(n_items):
-        order = [j for j in canonical(sim[i]) if j != i and C[i, j] > 0][:N]
+        order = canonical(sim[i])
+        order = order[(order != i) & (C[i, order] > 0)][:N]
         ids[i, :len(order)] = order
         w[i, :len(order)] = sim[i, order]
     return ids, w, C, sim
+
+
+def build_compact(u_ptr, u_cols, n_items, norm, shrink, N):
+    """build() without the n_items x n_items matrix -> (nbr_ids, nbr_w): the liked columns are mapped to 0 .. m - 1 in ascending order (a
+    monotone map keeps the canonical tie order), build() runs on the compacted CSR with norm[liked], the ids are mapped back, and the row
+    of an item nobody likes is -1 / +0.0"""
+    liked = np.flatnonzero(np.bincount(u_cols, minlength=n_items))
+    to_compact = np.full(n_items, -1, np.int32)
+    to_compact[liked] = np.arange(len(liked), dtype=np.int32)
+    ids = np.full((n_items, N), -1, np.int32)
+    w = np.zeros((n_items, N), np.float32)
+    if len(liked):
+        cids, cw = build(u_ptr, to_compact[u_cols], len(liked), np.asarray(norm, np.float64)[liked], shrink, N)[:2]
+        ids[liked] = np.where(cids >= 0, liked[np.maximum(cids, 0)], -1)
+        w[liked] = cw
+    return ids, w
 
 
 def scores(hist_ptr, hist_cols, nbr_ids, nbr_w, col_of_item, n_cols):
@@ -79,6 +97,21 @@ def scores(hist_ptr, hist_cols, nbr_ids, nbr_w, col_of_item, n_cols):
     return s
 
 
+def scores_by_item(hist_ptr, hist_cols, nbr_ids, nbr_w, col_of_item, n_cols):
+    """scores() with one NumPy statement per history item: the ids of a neighbour list are distinct and so are the columns they map to, so
+    s[r, cols] = fl(s[r, cols] + w) is the same chain on every column (tests/test_knn_cpu.py holds it to scores() bit for bit)"""
+    n_rows = len(hist_ptr) - 1
+    s = np.zeros((n_rows, n_cols), np.float32)
+    for r in range(n_rows):
+        for i in hist_cols[hist_ptr[r]:hist_ptr[r + 1]]:
+            ids, wt = nbr_ids[i], nbr_w[i]
+            ok = ids >= 0
+            cols = ids[ok] if col_of_item is None else col_of_item[ids[ok]]
+            wt = wt[ok]
+            s[r, cols[cols >= 0]] += wt[cols >= 0]                 # fp32 + fp32, rounded once; no column twice
+    return s
+
+
 def masked_columns(rated_ptr, rated_cols, n_rows, n_cols):
     m = np.zeros((n_rows, n_cols), bool)
     if rated_ptr is not None:
@@ -92,7 +125,8 @@ def topk(s, masked, K):
     ids = np.full((n_rows, K), -1, np.int32)
     out = np.full((n_rows, K), -np.inf, np.float32)
     for r in range(n_rows):
-        order = [c for c in canonical(s[r]) if not masked[r, c]][:K]
+        order = canonical(s[r])
+        order = order[~masked[r, order]][:K]
         ids[r, :len(order)] = order
         out[r, :len(order)] = s[r, order]
     return ids, out

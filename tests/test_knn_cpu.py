@@ -2,6 +2,7 @@
 another way, the symbols of include/tkr.h, what knn.ItemKNN stores and refuses, and the flags evaluate.py and recommend.py refuse for a
 neighbourhood model before they look for a GPU."""
 import ctypes
+import functools
 import math
 import os
 import re
@@ -275,3 +276,343 @@ def test_flags_a_neighbourhood_model_refuses(tmp_path, capsys):
         err = capsys.readouterr().err
         assert flag in err and 'neighbourhood model' in err, (flag, err)
     assert not os.path.exists(str(tmp_path / 'out.txt'))
+
+
+# ---- the wide cases of tests/test_gpu_knn_wide.py: their generators, and the conditions each exists for -----------------------------------
+# A case is only worth its GPU time while it still holds what it was built to hold, so every condition is asserted here, without a GPU:
+# a later change of generator or seed cannot quietly empty a case.
+EDGES = (256, 36864, 65536)                                        # the first column of byte 1 of a column id, of the second natural slab, of byte 2
+WIDE_ITEMS = 66000
+CHAIN_AT = {5: 0.25, 7: 0.75, 8: 0.6875, 10: 0.9375, 15: 0.625, 16: 1.0625, 17: 0.0625}     # position of the large term -> the terms in front of it
+CHAIN_LEN = 40
+
+
+def _work(up, ip, ir):
+    """a row's work as knn_plan_kernel counts it: the list lengths of its likers"""
+    n_u = np.diff(up)
+    return np.asarray([n_u[ir[ip[i]:ip[i + 1]]].sum() for i in range(len(ip) - 1)])
+
+
+@functools.lru_cache(maxsize=None)
+def wide_build_case():
+    """case 1: 700 users x 600 items, lists and liker sets long enough for every loop of knn_count_likers to repeat"""
+    up, uc = _zipf(700, 600, 281, mean=80)
+    ip, ir = O.transpose(up, uc, 600)
+    return dict(up=up, uc=uc, ip=ip, ir=ir, n_items=600, work=_work(up, ip, ir))
+
+
+@functools.lru_cache(maxsize=None)
+def wide_build_oracle(similarity, N):
+    c = wide_build_case()
+    return O.build(c['up'], c['uc'], 600, O.norms(np.diff(c['ip']), similarity), 0.0, N)
+
+
+def cut_ties(ids, w, N, tied_with, shift):
+    """the rows whose last kept and first dropped candidate have equal similarity and columns that differ in col >> shift; tied_with: the
+    table of N + 1 neighbours"""
+    full = tied_with[0][:, N] >= 0
+    same = _bits32(tied_with[1][:, N - 1]) == _bits32(tied_with[1][:, N])
+    apart = (tied_with[0][:, N - 1] >> shift) != (tied_with[0][:, N] >> shift)
+    assert (ids == tied_with[0][:, :N]).all() and (_bits32(w) == _bits32(tied_with[1][:, :N])).all()      # a list is a prefix of the longer one
+    return np.flatnonzero(full & same & apart)
+
+
+def _bits32(a):
+    return np.ascontiguousarray(a).view(np.int32)
+
+
+@functools.lru_cache(maxsize=None)
+def band_case():
+    """case 2: 400 users x 66,000 items; the liked items lie in three bands, one at the bottom, one astride the edge of the natural slab
+    and one astride 65,536, with a Zipf-like popularity inside each band"""
+    rng = np.random.Generator(np.random.PCG64(66))
+    bands = [np.arange(0, 300), np.arange(36700, 37000), np.arange(65400, 66000)]
+    cols = np.concatenate(bands)
+    pop = np.concatenate([rng.permutation(np.arange(1, len(b) + 1, dtype=np.float64) ** -0.9) / len(bands) for b in bands])
+    pop /= pop.sum()
+    rows = [cols[rng.choice(len(cols), size=int(rng.integers(10, 61)), replace=False, p=pop)] for _ in range(400)]
+    up, uc = O.csr(rows, 400)
+    ip, ir = O.transpose(up, uc, WIDE_ITEMS)
+    return dict(up=up, uc=uc, ip=ip, ir=ir, n_items=WIDE_ITEMS, work=_work(up, ip, ir), heavy_from=600)
+
+
+@functools.lru_cache(maxsize=None)
+def band_oracle(similarity, N=100):
+    c = band_case()
+    return O.build_compact(c['up'], c['uc'], WIDE_ITEMS, O.norms(np.diff(c['ip']), similarity), 0.0, N)
+
+
+def _csr_as_given(rows):
+    """(ptr int64, cols int32) of rows kept as they are: repeats and any order stay (O.csr sorts and drops them)"""
+    ptr = np.zeros(len(rows) + 1, np.int64)
+    np.cumsum([len(r) for r in rows], out=ptr[1:])
+    return ptr, np.asarray([c for r in rows for c in r], np.int64).astype(np.int32)
+
+
+def _take(ptr, cols, rows):
+    return _csr_as_given([cols[ptr[r]:ptr[r + 1]] for r in rows])
+
+
+@functools.lru_cache(maxsize=None)
+def serve_case(columns):
+    """case 3: 96 lines of case 1 as histories (the longest, the shortest that is not empty, every empty one, the rest evenly spaced by
+    length); columns = 'identity' (600) or 'subset' (400 of the 600 items under a random permutation); a rated mask of 0 to 40 columns per
+    line; 0 to 12 likes per line, but `many` has 300 (repeats, masked and out-of-range columns among them) and `chunk` exactly 256"""
+    c = wide_build_case()
+    rng = np.random.Generator(np.random.PCG64(3 if columns == 'identity' else 4))
+    n_u = np.diff(c['up'])
+    by_length = np.argsort(n_u, kind='stable')
+    must = [int(by_length[-1]), int(by_length[n_u[by_length] > 0][0])] + [int(u) for u in np.flatnonzero(n_u == 0)]
+    rest = [int(u) for u in by_length if u not in must]
+    users = sorted(must + [rest[int(round(x))] for x in np.linspace(0, len(rest) - 1, 96 - len(must))])
+    assert len(set(users)) == 96
+    hist = _take(c['up'], c['uc'], users)
+    n_cols, col_of_item = 600, None
+    if columns == 'subset':
+        n_cols, col_of_item = 400, np.full(600, -1, np.int32)
+        col_of_item[np.sort(rng.permutation(600)[:400])] = rng.permutation(400)
+    rated = O.csr([rng.permutation(n_cols)[:rng.integers(0, 41)] for _ in range(96)], 96)
+    masked = O.masked_columns(rated[0], rated[1], 96, n_cols)
+    likes = [rng.permutation(n_cols)[:rng.integers(0, 13)].tolist() for _ in range(96)]
+    many = users.index(must[0])                                    # the longest history ranks 300 likes
+    chunk = int(np.flatnonzero(masked.sum(1) >= 5)[5])
+    chunk += chunk == many
+    some_masked = np.flatnonzero(masked[many])[:5].tolist()
+    outside = [n_cols, n_cols + 1000, -1, 2 ** 31 - 1]
+    likes[many] = rng.permutation(some_masked + outside + rng.integers(0, n_cols, 300 - len(some_masked) - len(outside)).tolist()).tolist()
+    likes[chunk] = rng.permutation(n_cols)[:256].tolist()
+    return dict(users=users, hist=hist, n_cols=n_cols, col_of_item=col_of_item, rated=rated, masked=masked, likes=_csr_as_given(likes),
+                many=many, chunk=chunk, some_masked=some_masked)
+
+
+@functools.lru_cache(maxsize=None)
+def serve_oracle(columns, N):
+    """-> (nbr_ids, nbr_w, scores, ranks) of case 3 at N neighbours"""
+    c = serve_case(columns)
+    ids, w = wide_build_oracle('cosine', N)[:2]
+    s = O.scores_by_item(*c['hist'], ids, w, c['col_of_item'], c['n_cols'])
+    return ids, w, s, O.ranks(s, c['masked'], *c['likes'])
+
+
+def _tie_row(place, negative, rng):
+    """a neighbour list of 512 with three weights: 16 columns of 3.0 astride the next edge, 32 of 2.0 astride EDGES[place], so that a list
+    of 32 is cut between EDGES[place] and the column below it, and the rest 1.0 astride the third edge.  negative: a 17th column of 3.0 (the
+    caller masks it), the low group below its edge is -1.0 and its highest column is -0.0"""
+    e, e_high, e_low = EDGES[place], EDGES[(place + 1) % 3], EDGES[(place + 2) % 3]
+    high = np.arange(e_high - 8, e_high + 8 + negative)
+    mid = np.arange(e - 16, e + 16)
+    low = np.arange(e_low - 232, e_low + 232 - negative)
+    cols = np.concatenate([high, mid, low])
+    w = np.concatenate([np.full(len(high), 3.0), np.full(len(mid), 2.0), np.full(len(low), 1.0)]).astype(np.float32)
+    if negative:
+        w[len(high) + len(mid):][low < e_low] = -1.0
+        w[-1] = -0.0
+    assert len(cols) == len(set(cols.tolist())) == 512
+    order = rng.permutation(512)                                   # K29 takes any table: the list is in no order
+    return cols[order].astype(np.int32), w[order]
+
+
+LIKED_EDGES = [0, 255, 256, 36863, 36864, 65535, 65536, 65999]
+
+
+@functools.lru_cache(maxsize=None)
+def hand_case():
+    """case 4 at N = 512 over 66,000 identity columns: a table that is -1 / 0 but for six rows, and eight lines
+       0      an empty history, nothing masked: every column scores +0.0
+       1      an empty history, [30,000, 66,000) masked but for 65,536 and 36,864
+       2-4    one history item whose list is _tie_row(place): the cut of a list of 32 falls inside a tie group at each edge in turn
+       5-7    the same with negative weights, a -0.0 and one masked column
+    every line likes the columns of LIKED_EDGES (lines 5-7 also a negative column, the -0.0 one and the masked one)"""
+    rng = np.random.Generator(np.random.PCG64(512))
+    ids = np.full((WIDE_ITEMS, 512), -1, np.int32)
+    w = np.zeros((WIDE_ITEMS, 512), np.float32)
+    hist, rated, likes = [[], []], [[], [c for c in range(30000, WIDE_ITEMS) if c not in (65536, 36864)]], [LIKED_EDGES, LIKED_EDGES]
+    for negative in (0, 1):
+        for place in range(3):
+            item = 1000 * (1 + negative) + 7 * place
+            ids[item], w[item] = _tie_row(place, negative, rng)
+            hist.append([item])
+            hidden = EDGES[(place + 1) % 3] + 8                    # the 17th column of 3.0
+            low_edge = EDGES[(place + 2) % 3]
+            rated.append([hidden] if negative else [])
+            likes.append(LIKED_EDGES + ([low_edge - 1, low_edge - 232, low_edge + 230, hidden] if negative else []))
+    return dict(ids=ids, w=w, hist=O.csr(hist, 8), rated=O.csr(rated, 8), likes=_csr_as_given(likes), n_lines=8)
+
+
+def chain_weights(q, at):
+    """CHAIN_LEN weights whose fp32 sum in this order is one value with the large term at position `at` = q and another at q - 1 or q + 1:
+    CHAIN_AT[q] in front of position q, then 1.0, then 2.0, and 2^24 put in at `at`"""
+    small = [CHAIN_AT[q]] * q + [1.0] + [2.0] * (CHAIN_LEN - q - 2)
+    return np.asarray(small[:at] + [2.0 ** 24] + small[at:], np.float32)
+
+
+def chain_columns(k):
+    """the two columns line k of the chain case sums into: through the first piece of every list, and through the last"""
+    return 36860 + 2 * k, 65530 + 2 * k
+
+
+@functools.lru_cache(maxsize=None)
+def chain_case(N):
+    """case 4, the chains: line k has a history of CHAIN_LEN items of its own; the list of its t-th item holds chain_columns(k)[0] in the
+    first piece of 64 (slot (5 t + 3) % 64) and chain_columns(k)[1] in the last slot of the list, both with chain_weights(q, q)[t], and
+    a filler column of weight 0.5 in every other slot, so that every piece of every list adds something"""
+    ids = np.full((WIDE_ITEMS, N), -1, np.int32)
+    w = np.zeros((WIDE_ITEMS, N), np.float32)
+    hist = []
+    for k, q in enumerate(sorted(CHAIN_AT)):
+        items = 3000 + 100 * k + np.arange(CHAIN_LEN)
+        weights = chain_weights(q, q)
+        for t, item in enumerate(items):
+            ids[item] = 10000 + np.arange(N)
+            w[item] = 0.5
+            first = (5 * t + 3) % 64
+            ids[item, first], ids[item, N - 1] = chain_columns(k)
+            w[item, first] = w[item, N - 1] = weights[t]
+        hist.append(items)
+    n = len(CHAIN_AT)
+    likes = [list(chain_columns(k)) + [10000, 10000 + N // 2, 65999] for k in range(n)]
+    return dict(ids=ids, w=w, hist=O.csr(hist, n), rated=O.csr([[]] * n, n), likes=_csr_as_given(likes), n_lines=n)
+
+
+@functools.lru_cache(maxsize=None)
+def hand_oracle(which, N=512):
+    """-> (scores, masked, ranks, top ids at K = 70, their scores) of hand_case() or chain_case(N); a list of K < 70 is a prefix"""
+    c = hand_case() if which == 'hand' else chain_case(N)
+    s = O.scores(*c['hist'], c['ids'], c['w'], None, WIDE_ITEMS)
+    masked = O.masked_columns(c['rated'][0], c['rated'][1], c['n_lines'], WIDE_ITEMS)
+    return (s, masked, O.ranks(s, masked, *c['likes'])) + O.topk(s, masked, 70)
+
+
+def test_wide_build_case_repeats_every_loop_of_the_count():
+    c = wide_build_case()
+    n_u, n_i = np.diff(c['up']), np.diff(c['ip'])
+    assert len(c['uc']) == 53984
+    assert (n_u > 64).sum() == 398 and (n_u > 128).sum() == 122 and n_u.max() == 159       # the x += 64 loop runs twice and three times
+    assert (n_i > 256).sum() == 37 and (n_i > 512).sum() == 8 and n_i.max() == 658         # the b0 += 256 loop likewise
+    assert n_i.min() > 0 and c['work'].max() == 53674
+    assert (c['work'] > 700).mean() > 0.5 and (np.minimum(n_i, -(-c['work'] // 700)) >= 64).any()      # heavy_from = 700: most rows split, some to the cap
+    C = wide_build_oracle('cooc', 16)[2]
+    assert ((C > 0).sum(1) - 1).min() > 512                        # the radix select runs on every row at every N
+
+
+@pytest.mark.parametrize('similarity,N,rows', [('cooc', 100, 3), ('cooc', 512, 18), ('cosine', 100, 11), ('cosine', 512, 91)])
+def test_wide_build_case_has_ties_that_column_byte_1_decides(similarity, N, rows):
+    c = wide_build_case()
+    norm = O.norms(np.diff(c['ip']), similarity)
+    ids, w = wide_build_oracle(similarity, N)[:2]
+    tied = cut_ties(ids, w, N, O.build(c['up'], c['uc'], 600, norm, 0.0, N + 1)[:2], 8)
+    assert len(tied) == rows
+
+
+def test_build_compact_is_build():
+    """the 700 x 600 case widened to 1,000 columns with empty items between the liked ones, and a hand-made case"""
+    c = wide_build_case()
+    rng = np.random.Generator(np.random.PCG64(1000))
+    where = np.sort(rng.permutation(1000)[:600]).astype(np.int32)
+    wide_cols = where[c['uc']]
+    for similarity, shrink, N in (('cosine', 0.0, 100), ('cooc', 1.5, 512)):
+        norm = O.norms(np.bincount(wide_cols, minlength=1000), similarity)
+        want = O.build(c['up'], wide_cols, 1000, norm, shrink, N)[:2]
+        got = O.build_compact(c['up'], wide_cols, 1000, norm, shrink, N)
+        assert (got[0] == want[0]).all() and (_bits32(got[1]) == _bits32(want[1])).all()
+        unliked = np.setdiff1d(np.arange(1000), where)
+        assert len(unliked) == 400 and (got[0][unliked] == -1).all() and (_bits32(got[1][unliked]) == 0).all()
+    up, uc = O.csr([[2, 9, 11], [2, 9], [9, 11, 14], [], [2, 14], [0]], 6)
+    norm = np.asarray([1.0 + 0.25 * i for i in range(16)])
+    want = O.build(up, uc, 16, norm, 0.5, 3)[:2]
+    got = O.build_compact(up, uc, 16, norm, 0.5, 3)
+    assert (got[0] == want[0]).all() and (_bits32(got[1]) == _bits32(want[1])).all()
+    assert got[0][9].tolist() == [2, 11, 14] and got[0][0].tolist() == [-1] * 3 and got[0][15].tolist() == [-1] * 3
+
+
+def test_band_case_spans_both_slabs_and_byte_2():
+    c = band_case()
+    n_u, n_i = np.diff(c['up']), np.diff(c['ip'])
+    liked = np.flatnonzero(n_i)
+    assert n_u.min() >= 10 and n_u.max() <= 60 and len(liked) > 1000
+    assert set(np.unique(liked // 300 * 300).tolist()) <= {0, 36600, 36900, 65400, 65700}
+    assert (c['work'] > c['heavy_from']).sum() >= 50               # rows that take the partial / finish path
+    for similarity in ('cooc', 'cosine'):
+        ids, w = band_oracle(similarity)
+        kept = ids >= 0
+        assert ((kept & (ids < 36864)).any(1) & (ids >= 36864).any(1)).any()           # a kept list with columns from both natural slabs
+        assert (ids[:, -1] == -1).mean() > 0.5                     # most rows are padded
+        assert (ids[n_i == 0] == -1).all() and (_bits32(w[n_i == 0]) == 0).all()
+        assert (ids[liked, -1] == -1).any() and (ids[liked, -1] >= 0).sum() >= 50       # of the liked rows some are padded and some are cut
+        tied = cut_ties(ids, w, 100, band_oracle(similarity, 101), 16)
+        assert len(tied) >= 1                                      # a tie at the cut that only column byte 2 decides
+
+
+def test_serve_case_holds_the_lines_it_names():
+    b = wide_build_case()
+    for columns in ('identity', 'subset'):
+        c = serve_case(columns)
+        n_h, n_l = np.diff(c['hist'][0]), np.diff(c['likes'][0])
+        assert len(n_h) == 96 and n_h.max() == 159 and (n_h == 0).sum() == (np.diff(b['up']) == 0).sum() == 2 and n_h[n_h > 0].min() == 1
+        assert len(set(n_h.tolist())) > 60                         # evenly spaced by length
+        assert n_l[c['many']] == 300 and n_l[c['chunk']] == 256 and np.delete(n_l, [c['many'], c['chunk']]).max() <= 12 and (n_l == 0).any()
+        mine = c['likes'][1][c['likes'][0][c['many']]:c['likes'][0][c['many'] + 1]]
+        assert len(set(mine.tolist())) < 300 and set(c['some_masked']) <= set(mine.tolist()) and (mine >= c['n_cols']).sum() == 3 and (mine < 0).sum() == 1
+        assert np.diff(c['rated'][0]).max() <= 40 and (np.diff(c['rated'][0]) == 0).any()
+        ranks = serve_oracle(columns, 100)[3]
+        assert (ranks[c['likes'][0][c['many']]:c['likes'][0][c['many'] + 1]] == -1).sum() >= 9 and ranks.max() > 300
+
+
+def test_scores_by_item_is_the_loop():
+    """the vectorised oracle against the scalar one: on g2, and on 40 lines of case 3"""
+    up, uc, ip, _, _, n_items = g2_likes()
+    ids, w = O.build(up, uc, n_items, O.norms(np.diff(ip), 'cosine'), 0.0, 5)[:2]
+    col_of_item = np.full(n_items, -1, np.int32)
+    col_of_item[::2] = np.arange(15)[::-1]
+    for cols, n_cols in ((None, n_items), (col_of_item, 15)):
+        assert O.scores_by_item(up, uc, ids, w, cols, n_cols).tobytes() == O.scores(up, uc, ids, w, cols, n_cols).tobytes()
+    c = serve_case('subset')
+    ids, w, s, _ = serve_oracle('subset', 130)
+    hist = _take(c['hist'][0], c['hist'][1], range(50, 90))
+    assert s[50:90].tobytes() == O.scores(*hist, ids, w, c['col_of_item'], 400).tobytes()
+
+
+def test_hand_case_is_decided_by_construction():
+    c = hand_case()
+    s, masked, ranks, top, top_s = hand_oracle('hand')
+    assert top[0].tolist() == list(range(65999, 65929, -1)) and (_bits32(top_s[0]) == 0).all()         # all of column bytes 2, 1 and 0
+    assert top[1, :5].tolist() == [65536, 36864, 29999, 29998, 29997]
+    lp = c['likes'][0]
+    assert ranks[lp[0]:lp[1]].tolist() == [65999 - col for col in LIKED_EDGES]
+    assert ranks[lp[1]:lp[2]].tolist() == [30001, 29746, 29745, -1, 1, -1, 0, -1]
+    for line in range(2, 8):
+        place, negative = (line - 2) % 3, line >= 5
+        e, e_high = EDGES[place], EDGES[(place + 1) % 3]
+        want = list(range(e_high + 7, e_high - 9, -1)) + list(range(e + 15, e - 1, -1))
+        assert top[line, :32].tolist() == want and top[line, 32] == e - 1 and s[line, e] == s[line, e - 1] == 2      # the cut is inside the tie
+        assert (s[line] != 0).sum() == 512 - negative and masked[line].sum() == negative
+        if negative:
+            mine = ranks[lp[line]:lp[line + 1]][-4:]
+            assert (s[line] < 0).sum() == 232 and mine[3] == -1 and mine[0] > 65000 and mine[1] == WIDE_ITEMS - 2      # behind every +0.0; one column is masked
+            assert _bits32(s[line, EDGES[(place + 2) % 3] + 230]) == 0 and 200 < mine[2] < WIDE_ITEMS - 232         # -0.0 is +0.0: among the untouched columns
+
+
+def _chain(weights, order):
+    acc = np.float32(0)
+    for t in order:
+        acc = np.float32(acc + weights[t])
+    return acc
+
+
+@pytest.mark.parametrize('N', [100, 130])
+def test_chain_case_depends_on_the_position_of_the_large_term(N):
+    """moving 2^24 by one position changes the sum, and so does adding each batch of sixteen list pieces backwards"""
+    c = chain_case(N)
+    s = hand_oracle('chain', N)[0]
+    nch = -(-N // 64)
+    for k, q in enumerate(sorted(CHAIN_AT)):
+        base = _chain(chain_weights(q, q), range(CHAIN_LEN))
+        assert len({float(base), float(_chain(chain_weights(q, q - 1), range(CHAIN_LEN))), float(_chain(chain_weights(q, q + 1), range(CHAIN_LEN)))}) == 3
+        for col, piece in zip(chain_columns(k), (0, nch - 1)):
+            assert _bits32(s[k, col]) == _bits32(base)
+            steps = [t * nch + piece for t in range(CHAIN_LEN)]    # the pieces that add to this column, in order
+            backwards = sorted(steps, key=lambda x: (x // 16, -(x % 16)))
+            assert _chain(chain_weights(q, q), [x // nch for x in backwards]) != base
+        assert (s[k, 10000:10000 + N] != 0).sum() == N - 1 and s[k].max() == base       # every filler but the last slot's, which no list holds
+    straddles = [t for t in range(CHAIN_LEN) if (t * nch) // 16 != (t * nch + nch - 1) // 16]
+    assert (straddles == []) if N == 100 else (5 in straddles and 10 in straddles)     # N = 130: the pieces of items 5 and 10 lie in two batches
