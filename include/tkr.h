@@ -31,7 +31,7 @@
 extern "C" {
 #endif
 
-#define TKR_VERSION 120 /* (additions that change no existing entry point keep the number: K10 tkr_bpr_foldin_items, K11 tkr_ratings_*_dev, K12 tkr_rank_candidates, K13 tkr_lists_format_* / tkr_matrix_format_*, K15 tkr_group_*_dev / tkr_last_line_of_user_dev / tkr_compact_rows_*_dev, K16 tkr_fusion_*, K17 tkr_mmr_select / tkr_list_pair_sums, K21 tkr_als_solve_rows_prior / tkr_als_prior_workspace_bytes, K22 tkr_mlp_forward / tkr_mlp_fit / tkr_mlp_workspace_bytes, K27 tkr_smf_lse_rows / tkr_smf_dense_rows / tkr_smf_step_rows / tkr_smf_workspace_bytes.) 0.1.20: K9 tkr_bpr_foldin (user vectors for new histories against frozen item factors; csrc/foldin.hip). 0.1.19: K8 tkr_like_ranks + tkr_like_ranks_workspace_bytes (filtered rank of every liked test column; csrc/like_ranks.hip). 0.1.18: K4 second form of bound-and-refine (csrc/topk_refine.hip; tkr_topk_workspace_bytes_for grows by the pieces' packed lists), any k (bpr_wide_kernel, score_topk_wide_kernel), tkr_lab_build; tkr_topk_set_finish is gone, tkr_topk_set_math(0) and tkr_vbpr_set_pairs(1 | 2) need the lab library. 0.1.17: tkr_vbpr_set_pairs (tkr_vbpr_workspace_floats + 64). 0.1.16: tkr_topk_set_finish (larger tkr_topk_workspace_bytes), tkr_bpr_own_plan_run plans inside the step's launch. 0.1.15: tkr_bpr_own_owners_shared; tkr_bpr_run takes `rec` non-const. 0.1.14: per-task loss sums instead of atomics on loss_out (larger tkr_vbpr_workspace_floats; K2 writes word 15 of its records). 0.1.13: tkr_bpr_own_plan_run, K4 to k = 768. 0.1.12: tkr_bpr_own_run_between. 0.1.11: K2o (tkr_sample_plan_owned, tkr_bpr_own_run: item rows owned by one workgroup each, resident in its LDS); prec[5] = last batch of the call that updated the row. 0.1.10: tkr_topk_workspace_bytes_for (K4 stages pre-converted fp16 tiles). 0.1.9: tkr_vbpr_colplan + tkr_vbpr_run_cols (VBPR in three launches per batch). 0.1.8: tkr_sync_flow_* (exchange of the granule tables). 0.1.7: K4 bound-and-refine arithmetic (tkr_topk_set_math(2), the default; larger tkr_topk_workspace_bytes); K2f leaves its ticket words zero. 0.1.6: K2f persistent dataflow step, tkr_plan_rollback, batches above 8192 */
+#define TKR_VERSION 120 /* (additions that change no existing entry point keep the number: K10 tkr_bpr_foldin_items, K11 tkr_ratings_*_dev, K12 tkr_rank_candidates, K13 tkr_lists_format_* / tkr_matrix_format_*, K15 tkr_group_*_dev / tkr_last_line_of_user_dev / tkr_compact_rows_*_dev, K16 tkr_fusion_*, K17 tkr_mmr_select / tkr_list_pair_sums, K21 tkr_als_solve_rows_prior / tkr_als_prior_workspace_bytes, K22 tkr_mlp_forward / tkr_mlp_fit / tkr_mlp_workspace_bytes, K27 tkr_smf_lse_rows / tkr_smf_dense_rows / tkr_smf_step_rows / tkr_smf_workspace_bytes, K4 tkr_topk_last_report (a diagnostic).) 0.1.20: K9 tkr_bpr_foldin (user vectors for new histories against frozen item factors; csrc/foldin.hip). 0.1.19: K8 tkr_like_ranks + tkr_like_ranks_workspace_bytes (filtered rank of every liked test column; csrc/like_ranks.hip). 0.1.18: K4 second form of bound-and-refine (csrc/topk_refine.hip; tkr_topk_workspace_bytes_for grows by the pieces' packed lists), any k (bpr_wide_kernel, score_topk_wide_kernel), tkr_lab_build; tkr_topk_set_finish is gone, tkr_topk_set_math(0) and tkr_vbpr_set_pairs(1 | 2) need the lab library. 0.1.17: tkr_vbpr_set_pairs (tkr_vbpr_workspace_floats + 64). 0.1.16: tkr_topk_set_finish (larger tkr_topk_workspace_bytes), tkr_bpr_own_plan_run plans inside the step's launch. 0.1.15: tkr_bpr_own_owners_shared; tkr_bpr_run takes `rec` non-const. 0.1.14: per-task loss sums instead of atomics on loss_out (larger tkr_vbpr_workspace_floats; K2 writes word 15 of its records). 0.1.13: tkr_bpr_own_plan_run, K4 to k = 768. 0.1.12: tkr_bpr_own_run_between. 0.1.11: K2o (tkr_sample_plan_owned, tkr_bpr_own_run: item rows owned by one workgroup each, resident in its LDS); prec[5] = last batch of the call that updated the row. 0.1.10: tkr_topk_workspace_bytes_for (K4 stages pre-converted fp16 tiles). 0.1.9: tkr_vbpr_colplan + tkr_vbpr_run_cols (VBPR in three launches per batch). 0.1.8: tkr_sync_flow_* (exchange of the granule tables). 0.1.7: K4 bound-and-refine arithmetic (tkr_topk_set_math(2), the default; larger tkr_topk_workspace_bytes); K2f leaves its ticket words zero. 0.1.6: K2f persistent dataflow step, tkr_plan_rollback, batches above 8192 */
 #define TKR_OK 0
 #define TKR_E_INVAL (-1)
 #define TKR_E_UNSUPPORTED (-2)
@@ -381,6 +381,18 @@ int64_t tkr_topk_workspace_bytes(int32_t n_rows, int32_t K);
  * its tiles with one direct-to-LDS load per thread instead of converting them again (results are identical either way) */
 int64_t tkr_topk_workspace_bytes_for(int32_t n_rows, int32_t n_cols, int32_t k, int32_t K);
 int tkr_topk_set_math(int32_t mode);
+/* A DIAGNOSTIC, for tests: what the last tkr_score_topk call of the process did under mode 2.  `out` is a HOST array of n >= 6 words:
+ *   out[0] form: 0 = no bound-and-refine pass ran (mode 1, k > 128, no room for the block flags in the workspace, or a refused
+ *          call), 1 = the first form (csrc/topk.hip score_topk_bf16_kernel), 2 = the second (csrc/topk_refine.hip)
+ *   out[1] width of the candidate ids, 16 or 32;  out[2] 1 when the pre-converted tile image was used
+ *   out[3] user blocks;  out[4] workgroups of the plan: (user block, item range) pairs, or the pieces of the work-item table --
+ *          more than out[3] means the catalogue was cut into item ranges
+ *   out[5] FLAGGED user blocks: those the fp16 pass gave up (a list could not hold its margin, or a row's margin means nothing)
+ *          and the mode-1 kernel ranked;  out[6 + b], b < min(out[3], n - 6): 1 when block b is one of them
+ * The last call of the process wins and nothing is locked (the library is not thread-safe).  Valid only while that call's
+ * workspace is alive and before the next tkr_score_topk: the flags live in the workspace.  Unlike every other entry point it
+ * SYNCHRONISES the call's stream (it copies the flag words to the host); with form 0 it touches no device.  Changes no result. */
+int tkr_topk_last_report(int32_t* out, int32_t n);
 int tkr_build_rated_mask(const int64_t* rated_ptr, const int32_t* rated_cols, int32_t n_rows, int32_t n_cols,
                          uint32_t* mask, int32_t mask_pitch, void* stream);
 int tkr_score_topk(const float* U, const int32_t* user_idx, int32_t n_rows, const float* Vt, const float* bias,

@@ -154,6 +154,9 @@ def test_refine_is_the_fp32_arithmetic(n_rows, n_cols, k, bias, wide):
             tkr_hip.set_topk_math(mode)
             ids, sc = _gpu_lists(tkr_hip, U, V, b, rated, K, want_scores=True)
             out[mode] = (ids.cpu().numpy(), sc.cpu().numpy())
+            if mode == 'refine':                              # ... and the fp16 pass ranked every block itself (a flagged block is the fp32 kernel's)
+                report = tkr_hip.topk_last_report()
+                assert report['form'] >= 1 and report['flagged'] == 0, report
     finally:
         tkr_hip.set_topk_math(tkr_hip.TOPK_MATH_DEFAULT)
     np.testing.assert_array_equal(out['refine'][0], out['fp32'][0])

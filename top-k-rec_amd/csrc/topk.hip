@@ -1366,6 +1366,23 @@ static TopkPlan redo_plan(TopkPlan p) {
     return p;
 }
 
+// What the last K4 call of the process did (tkr_topk_last_report, a diagnostic): host-side bookkeeping, reset at the entry of
+// tkr_score_topk and filled where the bound-and-refine pass is launched.  No kernel, kernel argument or launch depends on it.
+struct TopkReport {
+    int form;                 // 0: no bound-and-refine pass, 1: first form (score_topk_bf16_kernel), 2: second (csrc/topk_refine.hip)
+    int id_bits;              // 16 or 32: width of the candidate ids
+    int image;                // the pre-converted tile image was used
+    int n_blocks;             // user blocks
+    int n_pieces;             // workgroups of the plan: (block, item range) pairs or pieces of the item table
+    const uint32_t* flags;    // device: [n_blocks] words, nonzero = the block was given to the fp32 kernel
+    hipStream_t stream;
+};
+static TopkReport g_topk_report = {};
+
+static void note_refine_launch(int form, int id_bits, bool image, int n_blocks, const TopkPlan& p, hipStream_t stream) {
+    g_topk_report = TopkReport{form, id_bits, image ? 1 : 0, n_blocks, p.n_pieces, p.extra + 4, stream};      // (plain stores: no runtime call)
+}
+
 static size_t topk_image_bytes(int n_cols, int k) {               // the fp16 tile image of the bound-and-refine arithmetic (k <= 128)
     const int KS = k <= 16 ? 1 : (k <= 32 ? 2 : (k <= 64 ? 4 : 8));
     return (size_t)((n_cols + 31) / 32) * 32 * KS * 32;
@@ -1423,6 +1440,7 @@ static int launch_topk_bf16(const float* U, const int32_t* uidx, int n_rows, con
             a.out_ids = out_ids; a.out_scores = out_scores;
             rc = launch_refine2(a, stream);
             if (rc != TKR_OK) return rc;
+            note_refine_launch(2, 16, true, n_blocks, p, stream);
             // blocks with an overflowed list: the fp32 kernel on the same work items, merged where a block was cut
             rc = launch_fp32_planned<IdT, topk_waves_bf16<KS, IdT>()>(redo_plan(p), U, uidx, n_rows, Vt, bias, n_cols, k, mask, pitch, K, out_ids, out_scores,
                                                                       p.extra + 4, stream);
@@ -1439,6 +1457,7 @@ static int launch_topk_bf16(const float* U, const int32_t* uidx, int n_rows, con
                        out_ids, out_scores, p.tps, p.part, p.thr_shared, p.items, p.extra, (const unsigned char*)vimg);
     rc = (int)hipGetLastError();
     if (rc != TKR_OK) return rc;
+    note_refine_launch(1, 8 * (int)sizeof(IdT), use_img, n_blocks, p, stream);
     // blocks with an overflowed list: the fp32 kernel, same work items
     rc = launch_fp32_planned<IdT, topk_waves_bf16<KS, IdT>()>(redo_plan(p), U, uidx, n_rows, Vt, bias, n_cols, k, mask, pitch, K, out_ids, out_scores,
                                                               p.extra + 4, stream);
@@ -1611,6 +1630,7 @@ extern "C" int tkr_score_topk(const float* U, const int32_t* user_idx, int32_t n
                               const float* bias, int32_t n_cols, int32_t k, const uint32_t* mask, int32_t mask_pitch,
                               int32_t K, int32_t* out_ids, float* out_scores, void* workspace,
                               int64_t workspace_bytes, void* stream) {
+    tkr::g_topk_report = tkr::TopkReport{};
     if (!U || !Vt || !out_ids || n_rows <= 0 || n_cols <= 0 || k <= 0 || K <= 0) return TKR_EINVAL;
     if (mask && mask_pitch < n_rows) return TKR_EINVAL;
     if (K > tkr::kMaxK) return TKR_EUNSUPPORTED;
@@ -1620,6 +1640,30 @@ extern "C" int tkr_score_topk(const float* U, const int32_t* user_idx, int32_t n
                                             (hipStream_t)stream);
     return tkr::dispatch_topk<uint32_t>(U, user_idx, n_rows, Vt, bias, n_cols, k, mask, mask_pitch, K, out_ids, out_scores,
                                         workspace, (size_t)(workspace_bytes > 0 ? workspace_bytes : 0), (hipStream_t)stream);
+}
+
+extern "C" int tkr_topk_last_report(int32_t* out, int32_t n) {
+    const tkr::TopkReport& rep = tkr::g_topk_report;
+    if (!out || n < 6) return TKR_EINVAL;
+    out[0] = rep.form; out[1] = rep.id_bits; out[2] = rep.image; out[3] = rep.n_blocks; out[4] = rep.n_pieces; out[5] = 0;
+    for (int32_t i = 6; i < n; ++i) out[i] = 0;
+    if (rep.form == 0 || rep.n_blocks <= 0) return TKR_OK;
+    int prev = 0;
+    hipPointerAttribute_t at;                                     // the device of the call is asked of its workspace HERE, not noted on every K4 call
+    TKR_CHECK(hipGetDevice(&prev));
+    TKR_CHECK(hipPointerGetAttributes(&at, rep.flags));
+    if (prev != at.device) TKR_CHECK(hipSetDevice(at.device));
+    std::vector<uint32_t> flags((size_t)rep.n_blocks);
+    hipError_t e = hipMemcpyAsync(flags.data(), rep.flags, flags.size() * sizeof(uint32_t), hipMemcpyDeviceToHost, rep.stream);
+    if (e == hipSuccess) e = hipStreamSynchronize(rep.stream);
+    if (prev != at.device) (void)hipSetDevice(prev);
+    if (e != hipSuccess) return (int)e;
+    for (int b = 0; b < rep.n_blocks; ++b) {
+        const int32_t f = flags[(size_t)b] != 0u;
+        out[5] += f;
+        if (6 + b < n) out[6 + b] = f;
+    }
+    return TKR_OK;
 }
 
 extern "C" int tkr_count_hits(const int32_t* ids, int32_t n_rows, int32_t K, const int64_t* like_ptr,

@@ -92,7 +92,7 @@ EXPORTS = ('tkr_version', 'tkr_plan_team', 'tkr_plan_max_blocks', 'tkr_sample_pl
            'tkr_mmr_select', 'tkr_list_pair_sums', 'tkr_line_metrics', 'tkr_bootstrap_sums', 'tkr_nearest_anchors', 'tkr_als_gram',
            'tkr_als_solve_rows', 'tkr_als_solve_rows_prior', 'tkr_mlp_forward', 'tkr_mlp_fit', 'tkr_als_cg_rows', 'tkr_als_gram_wide',
            'tkr_lmf_dense_rows', 'tkr_lmf_step_rows', 'tkr_csr_spmm', 'tkr_estep_cg', 'tkr_smf_lse_rows', 'tkr_smf_dense_rows', 'tkr_smf_step_rows',
-           'tkr_knn_build', 'tkr_knn_score')
+           'tkr_knn_build', 'tkr_knn_score', 'tkr_topk_last_report')
 EXPORTS_I64 = ('tkr_vbpr_workspace_floats', 'tkr_vbpr_colplan_lds_bytes', 'tkr_topk_workspace_bytes_for', 'tkr_topk_workspace_bytes', 'tkr_plan_workspace_bytes', 'tkr_like_ranks_workspace_bytes',
                'tkr_parse_dev_workspace_bytes', 'tkr_idtable_slots', 'tkr_scan_dev_workspace_bytes', 'tkr_als_workspace_bytes',
                'tkr_als_prior_workspace_bytes', 'tkr_mlp_workspace_bytes', 'tkr_fusion_svm_partial_bytes', 'tkr_als_cg_workspace_bytes',
@@ -473,6 +473,18 @@ def set_topk_math(mode):
     them -- same lists and score bits as 'fp32'; k <= 128) or 'fp32' (fp32 MFMA) -- see include/tkr.h.  'bf16x3' was removed: the
     library refuses it (TKR_E_UNSUPPORTED)"""
     _check(lib().tkr_topk_set_math(C.c_int32({'bf16x3': 0, 'fp32': 1, 'refine': 2}[mode])), 'tkr_topk_set_math')
+
+
+def topk_last_report(max_blocks=4096):
+    """A diagnostic (include/tkr.h tkr_topk_last_report): what the last score_topk launch of the process did -> dict with
+    form (0 no bound-and-refine pass, 1 first form, 2 second), id_bits, image, blocks, pieces, flagged (user blocks the fp32 kernel
+    had to redo) and flags (0 / 1 per block, the first max_blocks).  Synchronises the launch's stream.  Valid until the next
+    score_topk (the workspace _topk_workspace caches per device keeps the flag words alive); for K > TOPK_MAX_K it speaks of the last
+    pass."""
+    out = (C.c_int32 * (6 + max_blocks))()
+    _check(lib().tkr_topk_last_report(out, C.c_int32(len(out))), 'tkr_topk_last_report')
+    return dict(form=out[0], id_bits=out[1], image=bool(out[2]), blocks=out[3], pieces=out[4], flagged=out[5],
+                flags=list(out[6:6 + min(out[3], max_blocks)]))
 
 
 def lab():
